@@ -7,11 +7,22 @@
 
 A "step" is one reference train.trainstep (train.py:22-36: forward(training) + BCE/MSE losses +
 gradients + Adam) on one synthetic batch of B clips of [T=3000, F=64, C=7] per GPU (weak scaling:
-B per GPU is fixed).  Rank 0 prints ONE JSON line (metric of BASELINE.json) that also carries
+B per GPU is fixed).  A plain run sets up, warms up, times exactly --steps steps and rank 0 prints ONE
+JSON line (metric of BASELINE.json, `ms_per_step`) that also carries
   roofline      the dominant kernel's achieved rate, from HIP events recorded by the library on its
                 own stream during the timed region, against the gfx950 peak of its bound
-  cpu_baseline  the CPU oracle's train step (PyTorch-CPU restatement of the reference semantics, NOT
-                the reference's TensorFlow) timed on the host cores, N=1 only, bounded sample.
+
+  --dump-outputs DIR  after the timed steps, what the last timed step computed goes to DIR/<name>.npy
+                      (float32): the predictions and losses trainstep returns, the updated weights and
+                      BatchNorm state, the step's gradients.  Inputs and initial weights are seeded, so
+                      two builds compare output for output.
+  --full              everything else the benchmark measures, in the same run: the level-2 profile pass
+                      (per-kernel rooflines), peaks read on the box, the exposed-communication ablation
+                      (N > 1), the feature and inference legs, the other BASELINE configurations as
+                      sub-records, and cpu_baseline (the CPU oracle's train step: a PyTorch-CPU
+                      restatement of the reference semantics, NOT the reference's TensorFlow, N=1 only,
+                      bounded sample).  The DETAIL record is printed on an earlier line prefixed
+                      BENCH_DETAIL and written to --detail-out.
 """
 import argparse
 import json
@@ -450,12 +461,38 @@ def rooflines(kernels, B, T, steps, opts, traffic_tab, valu_clock_mhz, per_step_
     return per_kernel, breakdown
 
 
+DUMP_LIMIT_BYTES = 64_000_000     # --dump-outputs: all files together
+
+
+def timed_outputs(model, y_p, sl, dl):
+    """What a caller of train.trainstep holds after a step: the predictions and the two losses it returns, the model's updated
+    weights and BatchNorm state, and the gradients of that step (host float32 copies)."""
+    w, st = model.get_weights()
+    host = lambda t: t.detach().float().cpu().numpy()
+    return {"sed": host(y_p[0]), "doa": host(y_p[1]), "sed_loss": host(sl), "doa_loss": host(dl), "weights": w, "bn_state": st,
+            "grads": model.get_grads()}
+
+
+def write_outputs(outdir, arrays, limit=DUMP_LIMIT_BYTES):
+    """DIR/<name>.npy, float32.  Over `limit` bytes in all, each array above an equal share of it is replaced by a fixed sample of that
+    many of its elements (flattened; indices drawn with seed 0, in ascending order)."""
+    os.makedirs(outdir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, np.float32) for k, v in arrays.items()}
+    share = limit // (4 * len(arrays))
+    big = sum(a.nbytes for a in arrays.values()) > limit
+    for k, a in arrays.items():
+        if big and a.size > share:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, share, replace=False))]
+        np.save(os.path.join(outdir, k + ".npy"), a)
+
+
 def run_workload(name, B, T, steps, warmup, world, rank, local, dev, *, opts=(), timing_level=1, with_features=False, profile_level=0,
-                 allreduce_ablation=False, dtype="float32"):
+                 allreduce_ablation=False, dtype="float32", dump=False):
     """One BASELINE workload on this rank's GPU: `warmup` untimed steps, then EXACTLY `steps` steps bracketed by barrier + synchronize
     (max over ranks), with the library's HIP-event timers at `timing_level` inside the timed region.  `profile_level` > timing_level:
     a SECOND pass of `steps` steps with the finer per-kernel scopes (hundreds of event pairs per step for the block models: they cost a few
-    percent, so they never run in the pass that is timed for `value`)."""
+    percent, so they never run in the pass that is timed for `value`).  `dump`: res["outputs"] = timed_outputs of the last timed step,
+    copied before anything else runs on the model."""
     import ctypes as C
     from seld_amd import losses, models, train
     from seld_amd.synthetic import synthetic_batch      # oracle/ is imported by the cpu_baseline leg only
@@ -535,7 +572,8 @@ def run_workload(name, B, T, steps, warmup, world, rank, local, dev, *, opts=(),
         elapsed = float(t.item())
     assert np.isfinite(float(sl.item())), "non-finite loss"
     kernels = read_timers(model)
-    res = {"model": model, "elapsed": elapsed, "kernels": kernels, "comm": None, "profile": None, "dp_backend": dp_backend}
+    res = {"model": model, "elapsed": elapsed, "kernels": kernels, "comm": None, "profile": None, "dp_backend": dp_backend,
+           "outputs": timed_outputs(model, y_p, sl, dl) if dump else None}
     if world > 1 and allreduce_ablation:
         # exposed communication per step and rank: the same steps again without the gradient all-reduce (timing aid only:
         # replicas then drift apart, nothing is reported from them but the time)
@@ -728,8 +766,13 @@ def main():
                          "(configs[3]) or resnet50_gru.json (configs[4]); the FIRST blocks of the latter two are defined by "
                          "spec/XCEPTION_BLOCK.md / spec/RESNET50_BLOCK.md: absent from the reference snapshot")
     ap.add_argument("--detail-out", default=os.path.join(ROOT, "gpurun_out", "bench_detail.json"),
-                    help="where the DETAIL record (per-kernel rooflines, sub-records, peaks read on the box) is written; it is also printed "
-                         "on the line before the compact record, prefixed BENCH_DETAIL")
+                    help="--full: where the DETAIL record (per-kernel rooflines, sub-records, peaks read on the box) is written; it is also "
+                         "printed on the line before the compact record, prefixed BENCH_DETAIL")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: level-2 profile pass, peaks on the box, communication ablation, "
+                         "feature / inference legs, the other BASELINE configurations, cpu_baseline; prints and writes the DETAIL record")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32, at most 64 MB in all)")
     ap.add_argument("--with-features", action="store_true",
                     help="configs[4]'s 'on-device STFT feature_extractor': every timed step first extracts and normalises the features of "
                          "its clips from 60-s FOA waveforms resident in HBM (feature_extractor.py:53-88, data_loader.py:117-149,226-234)")
@@ -779,11 +822,18 @@ def main():
     torch.cuda.set_stream(run_stream)
     timing = 0 if args.no_kernel_timing else args.timing_level
     res = run_workload(args.model, B, T, args.steps, args.warmup, world, rank, local, dev, opts=args.opt, timing_level=timing,
-                       with_features=args.with_features, allreduce_ablation=True,
-                       # N = 1: a SECOND pass of the same steps with every kernel group timed (never the pass timed for `value`): the
-                       # per-kernel rooflines of the detail record and the conv stack's MFMA figure of the compact one
-                       profile_level=2 if (world == 1 and timing == 1) else 0)
-    if rank == 0:
+                       with_features=args.with_features, allreduce_ablation=args.full,
+                       # --full, N = 1: a SECOND pass of the same steps with every kernel group timed (never the pass timed for `value`):
+                       # the per-kernel rooflines of the detail record and the conv stack's MFMA figure of the compact one
+                       profile_level=2 if (args.full and world == 1 and timing == 1) else 0,
+                       dump=args.dump_outputs is not None and rank == 0)
+    if rank == 0 and res["outputs"] is not None:
+        write_outputs(args.dump_outputs, res["outputs"])
+    if rank == 0 and not args.full:
+        # plain run: the headline record of the timed pass (its roofline from the level-1 events of that pass), nothing else
+        out = record(args.model, B, T, args.steps, args.warmup, world, res, args.opt, load_traffic(), None, args.with_features)
+        print(compact_record(out), flush=True)
+    elif rank == 0:
         import ctypes as C
         model = res["model"]
         mhz = C.c_double()

@@ -120,7 +120,8 @@ def test_bench_two_ranks_rehearsal(launcher, model):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
     port = 31500 + os.getpid() % 400 + 400 * ["seldnet", "xception_gru", "resnet50_gru"].index(model)
-    args = [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--batch", "4", "--frames", "300", "--model", model]
+    args = [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--batch", "4", "--frames", "300", "--model", model,
+            "--full"]
     if launcher == "self":
         cmd = [sys.executable] + args
     else:

@@ -302,3 +302,21 @@ def test_stored_traffic_figures_are_dropped_when_their_kernel_source_changes(tmp
     # the committed table is consistent with bench.py's group -> source map
     real = json.load(open(os.path.join(bench.ROOT, "profiles", "traffic.json")))
     assert all(k in bench.TRAFFIC_SOURCE for k in real if not k.startswith("_"))
+
+
+def test_bench_write_outputs_caps_size_with_a_fixed_sample(tmp_path):
+    """bench.py --dump-outputs: float32 .npy per array; over the limit, every array above an equal share of it becomes the same
+    seeded sample of its elements from run to run (two builds then compare output for output)."""
+    import bench
+    rng = np.random.default_rng(3)
+    arrays = {"small": rng.standard_normal(10), "big": rng.standard_normal((100, 50)).astype(np.float32)}
+    bench.write_outputs(str(tmp_path / "a"), arrays, limit=1 << 20)
+    for k, v in arrays.items():
+        got = np.load(tmp_path / "a" / f"{k}.npy")
+        assert got.dtype == np.float32 and np.array_equal(got, v.astype(np.float32))
+    bench.write_outputs(str(tmp_path / "b"), arrays, limit=2000)
+    bench.write_outputs(str(tmp_path / "c"), arrays, limit=2000)
+    big = np.load(tmp_path / "b" / "big.npy")
+    assert big.shape == (250,) and np.array_equal(big, np.load(tmp_path / "c" / "big.npy"))
+    assert np.isin(big, arrays["big"]).all() and np.array_equal(np.load(tmp_path / "b" / "small.npy"), arrays["small"].astype(np.float32))
+    assert sum(os.path.getsize(tmp_path / "b" / f"{k}.npy") - 128 for k in arrays) <= 2000

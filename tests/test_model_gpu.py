@@ -2037,3 +2037,29 @@ def test_injected_decisions_reach_the_backward_pass(seldnet_config, resnet50_con
         model.set_weights(w, st)
         step()
         assert np.abs(model.get_grads() - g).max() > 1e-3 * np.abs(g).max()
+
+
+def test_bench_plain_run_times_steps_and_dumps_outputs(tmp_path):
+    """A plain `bench.py` run prints one JSON line for exactly --steps timed steps, with ms_per_step, and --dump-outputs writes what
+    the last timed step computed: the same, within rounding, for two runs with the same arguments."""
+    import json
+    import subprocess
+    import sys
+    from conftest import ROOT
+    dumps = []
+    for d in ("a", "b"):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "4", "--frames", "300",
+               "--dump-outputs", str(tmp_path / d)]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.strip()]
+        assert not any(l.startswith("BENCH_DETAIL") for l in lines), "the detail record belongs to --full"
+        rec = json.loads(lines[-1])
+        assert rec["steps"] == 3 and rec["warmup"] == 1 and rec["ms_per_step"] > 0 and rec["dtype"] == "f32"
+        assert rec["value"] == pytest.approx(4 * 1e3 / rec["ms_per_step"], rel=1e-2)
+        dumps.append({k: np.load(tmp_path / d / f"{k}.npy") for k in ("sed", "doa", "sed_loss", "doa_loss", "weights", "bn_state", "grads")})
+    a, b = dumps
+    assert a["sed"].shape == (4, 60, 12) and a["doa"].shape == (4, 60, 36) and a["weights"].shape == a["grads"].shape == (513840,)
+    for k in a:
+        assert a[k].dtype == np.float32 and np.isfinite(a[k]).all(), k
+        check(f"bench dump {k} run to run", a[k], b[k])

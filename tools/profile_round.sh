@@ -43,10 +43,10 @@ cp "$root/profiles/traffic.json" "$out/traffic_merged.json"
 cd "$root"
 # bench.py prints the DETAIL record on an earlier line and the compact record LAST: the compact line goes to bench.json, the detail
 # (per-kernel rooflines from the level-2 profile pass, sub-records, peaks read on the box) to bench_detail.json
-timeout -k 10 500 python3 bench.py --detail-out "$out/bench_detail.json" 2> "$out/bench.err" | tail -n 1 > "$out/bench.json"
+timeout -k 10 500 python3 bench.py --full --detail-out "$out/bench_detail.json" 2> "$out/bench.err" | tail -n 1 > "$out/bench.json"
 cd /tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/stats" -o stats -- \
-    python3 "$root/bench.py" --steps 10 --warmup 3 --no-cpu-baseline --no-features --no-inference --no-configs --no-kernel-timing --detail-out "$out/bench_under_rocprof_detail.json" 2> "$out/rocprof_stats.log" | tail -n 1 > "$out/bench_under_rocprof.json"
+    python3 "$root/bench.py" --steps 10 --warmup 3 --no-cpu-baseline --no-features --no-inference --no-configs --no-kernel-timing --full --detail-out "$out/bench_under_rocprof_detail.json" 2> "$out/rocprof_stats.log" | tail -n 1 > "$out/bench_under_rocprof.json"
 find "$out/feat_stats" -name '*kernel_trace.csv' -delete
 # seldnet.json in bf16 single-product mode (BASELINE configs[1]'s literal wording): kernel stats
 cd /tmp
@@ -55,14 +55,14 @@ timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/
 find "$out/bf16_stats" -name '*kernel_trace.csv' -delete
 # BASELINE config 4 (xception_gru.json; FIRST block per spec/XCEPTION_BLOCK.md): bench line + kernel stats
 cd "$root"
-timeout -k 10 200 python3 bench.py --model xception_gru --steps 10 --warmup 3 --no-cpu-baseline --no-features --detail-out "$out/bench_xception_gru_detail.json" 2>> "$out/bench.err" | tail -n 1 > "$out/bench_xception_gru.json"
+timeout -k 10 200 python3 bench.py --model xception_gru --steps 10 --warmup 3 --no-cpu-baseline --no-features --full --detail-out "$out/bench_xception_gru_detail.json" 2>> "$out/bench.err" | tail -n 1 > "$out/bench_xception_gru.json"
 cd /tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/xc_stats" -o xc -- \
     python3 "$root/bench.py" --model xception_gru --steps 5 --warmup 2 --no-cpu-baseline --no-features --no-kernel-timing --detail-out /dev/null > /dev/null 2> "$out/rocprof_xc.log"
 find "$out/xc_stats" -name '*kernel_trace.csv' -delete
 # BASELINE config 5 (resnet50_gru.json; FIRST block per spec/RESNET50_BLOCK.md, 16 clips): bench line + kernel stats
 cd "$root"
-timeout -k 10 200 python3 bench.py --model resnet50_gru --steps 10 --warmup 3 --no-cpu-baseline --no-features --detail-out "$out/bench_resnet50_gru_detail.json" 2>> "$out/bench.err" | tail -n 1 > "$out/bench_resnet50_gru.json"
+timeout -k 10 200 python3 bench.py --model resnet50_gru --steps 10 --warmup 3 --no-cpu-baseline --no-features --full --detail-out "$out/bench_resnet50_gru_detail.json" 2>> "$out/bench.err" | tail -n 1 > "$out/bench_resnet50_gru.json"
 cd /tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/rn_stats" -o rn -- \
     python3 "$root/bench.py" --model resnet50_gru --steps 5 --warmup 2 --no-cpu-baseline --no-features --no-kernel-timing --detail-out /dev/null > /dev/null 2> "$out/rocprof_rn.log"
