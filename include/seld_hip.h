@@ -479,12 +479,21 @@ int seld_k_valu_clock_mhz(int blocks, double* mhz);
  *                       w HWIO.  ksize 1: a product on rows of stride Cin*stride_f; ksize 3: a product on im2col rows (formed on load by the
  *                       split-bf16 kernels when Cin and Cout are powers of two >= 128, else materialised); split-bf16 kernels wherever the
  *                       shape allows unless seld_k_set_option("rn_split_bf16", 0), else the fp32 MFMA GEMM.
+ *   seld_k_rn_conv_stats  the same, and sums (NULL: not computed): device, ceil(Cout/64)*128 + 1 doubles — per 64-channel chunk
+ *                       [sum z | sum z^2] in double from the product's BatchNorm-statistics epilogue (as the training step takes them;
+ *                       channels past Cout 0), then M.
  *   seld_k_rn_conv_bwd  dw (HWIO) and dx from dz
+ *   seld_k_rn_conv_bwd_add  the same, and addg, gate4 (both NULL, or both given with ksize 1, stride_f 1): dx += addg [gate bit],
+ *                       gate4[e >> 2] bit (e & 3), as the training step adds an identity shortcut's gradient (in the product's epilogue
+ *                       where it takes it, else behind it).
  *   seld_k_rn_bn        out = [relu](BatchNormalization(training)(z) [+ res]) over npix x C (C % 32 == 0); mean / invstd optional outputs
  *   seld_k_rn_bn_bwd    dz, dgamma, dbeta from dy gated by (mask > 0) (mask may be NULL) */
 int seld_k_rn_conv(const float* x, const float* w, float* z, int B, int H, int W, int Cin, int Cout, int ksize, int stride_f);
+int seld_k_rn_conv_stats(const float* x, const float* w, float* z, int B, int H, int W, int Cin, int Cout, int ksize, int stride_f, double* sums);
 int seld_k_rn_conv_bwd(const float* x, const float* w, const float* dz, float* dw, float* dx, int B, int H, int W, int Cin, int Cout,
                        int ksize, int stride_f);
+int seld_k_rn_conv_bwd_add(const float* x, const float* w, const float* dz, float* dw, float* dx, int B, int H, int W, int Cin, int Cout,
+                           int ksize, int stride_f, const float* addg, const unsigned char* gate4);
 int seld_k_rn_bn(const float* z, const float* gamma, const float* beta, const float* res, float* out, float* mean, float* invstd,
                  int64_t npix, int C, int relu);
 int seld_k_rn_bn_bwd(const float* z, const float* dy, const float* mask, const float* gamma, float* dz, float* dgamma, float* dbeta,

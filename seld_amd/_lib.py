@@ -173,7 +173,9 @@ SIGNATURES = {
     "seld_m_losses": (_I, [_P, _P, _P, _P, C.POINTER(LossCfg), _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "seld_m_adam": (_I, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _L, _P]),
     "seld_k_rn_conv": (_I, [_P, _P, _P] + [_I] * 7),
+    "seld_k_rn_conv_stats": (_I, [_P, _P, _P] + [_I] * 7 + [_P]),
     "seld_k_rn_conv_bwd": (_I, [_P, _P, _P, _P, _P] + [_I] * 7),
+    "seld_k_rn_conv_bwd_add": (_I, [_P, _P, _P, _P, _P] + [_I] * 7 + [_P, _P]),
     "seld_k_rn_bn": (_I, [_P] * 7 + [_L, _I, _I]),
     "seld_k_rn_bn_bwd": (_I, [_P] * 7 + [_L, _I]),
     "seld_device_clocks": (_I, [_I] + [C.POINTER(C.c_int)] * 4),

@@ -109,6 +109,7 @@ struct seld_ctx {
     // resnet50_block (arch.first_kind == SELD_FIRST_RESNET50): conv[0] is the entry block, then the bottleneck blocks
     std::vector<RnBlock> rn;
     float *rn_part = nullptr, *rn_part_side = nullptr, *rn_gx[2] = {}, *rn_bz[2] = {}, *rn_ba = nullptr, *rn_bb[3] = {}, *rn_bcol = nullptr;
+    size_t rn_part_floats = 0;     // floats each of rn_part / rn_part_side holds (seld_create: the most any statistics launch writes at Bmax, S)
     // resnet50_block backward: the kernel gradients run on the side stream beside the input-gradient chain; the dz buffers rotate
     // (ev_rn_free[slot]: the side stream's product that read the slot is done; slots 0-1 = rn_bz, 2-4 = rn_bb)
     hipEvent_t ev_rn_ready = nullptr, ev_rn_free[5] = {};
@@ -539,8 +540,16 @@ int seld_create(const seld_arch* a, int B, int T, int dtype, int device, seld_ct
                     if (N == 32) { ALLOC(cv->w2, (size_t)9 * 4096); ALLOC(cv->dw2, (size_t)9 * 4096); }
                 }
             }
-        ALLOC(c->rn_part, (size_t)rn_partial_capacity() * 16 * 128);
-        ALLOC(c->rn_part_side, (size_t)rn_partial_capacity() * 16 * 128);
+        // BatchNorm partials: the most floats any launch writes into rn_part / rn_part_side at Bmax — a product's epilogue statistics
+        // (rn_epi_partial_floats), the separate statistics pass and its backward (rn_stats_partial_floats), stage 1's direct 3x3 conv (one 64-channel
+        // chunk, at most conv_sb_partial_capacity() workgroups)
+        size_t npart = (size_t)conv_sb_partial_capacity() * 128;
+        for (auto& R : c->rn)
+            for (RnConv* cv : {&R.c[0], &R.c[1], &R.c[2], &R.sc})
+                if (cv->Cout) npart = std::max({npart, rn_epi_partial_floats((int64_t)B * S * R.Wout, cv->Cout), rn_stats_partial_floats(cv->Cout)});
+        c->rn_part_floats = npart;
+        ALLOC(c->rn_part, npart);
+        ALLOC(c->rn_part_side, npart);
         ALLOC(c->rn_gx[0], mx_in); ALLOC(c->rn_gx[1], mx_in);
         for (auto& b_ : c->rn_bz) ALLOC(b_, mx_out);
         for (auto& b_ : c->rn_bb) ALLOC(b_, mx_w);
@@ -1138,6 +1147,7 @@ static int forward_impl(seld_ctx* c, const float* x, float* sed, float* doa, int
             else rn_weight_prep(c, st, save);
         }
         const float* X = in;      // [B,S,Win,Cin]
+        int rc_ = 0;
         for (auto& R : c->rn) {
             if (c->sync_failed) break;     // a failed SyncBN collective: enqueue nothing further (the error is reported below)
             const int64_t M = (int64_t)B * S * R.Wout;
@@ -1147,15 +1157,17 @@ static int forward_impl(seld_ctx* c, const float* x, float* sed, float* doa, int
             if (sc_side) {
                 hipEventRecord(c->ev_rn_ready, st); hipStreamWaitEvent(c->side, c->ev_rn_ready, 0);
                 int nb_ = 0;
-                launch_rn_product_fwd(c->side, X, R.Cin * R.stride_f, c->params + R.sc.w_off, sb ? R.sc.wsp : nullptr, R.sc.z, (int)M, R.Cin, 4 * w,
-                                      epi_stats ? c->rn_part_side : nullptr, &nb_);
+                if (launch_rn_product_fwd(c->side, X, R.Cin * R.stride_f, c->params + R.sc.w_off, sb ? R.sc.wsp : nullptr, R.sc.z, (int)M, R.Cin, 4 * w,
+                                          epi_stats ? c->rn_part_side : nullptr, &nb_, c->rn_part_floats))
+                    return fail(c, SELD_ERR_INVALID, "resnet50_block: projection shortcut product refused");
                 rn_bn(c, c->side, R.sc, M, training, nb_, c->rn_part_side);
                 hipEventRecord(c->ev_rn_free[0], c->side);
             }
             // 1x1 (frequency stride = doubled row stride of the operand), BN, ReLU
             int nb0 = 0;
-            { PROF3(c, "rn_products_fwd"); launch_rn_product_fwd(st, X, R.Cin * R.stride_f, c->params + R.c[0].w_off, sb ? R.c[0].wsp : nullptr, R.c[0].z, (int)M, R.Cin, w,
-                                                                 epi_stats ? c->rn_part : nullptr, &nb0); }
+            { PROF3(c, "rn_products_fwd"); rc_ = launch_rn_product_fwd(st, X, R.Cin * R.stride_f, c->params + R.c[0].w_off, sb ? R.c[0].wsp : nullptr, R.c[0].z, (int)M, R.Cin, w,
+                                                                       epi_stats ? c->rn_part : nullptr, &nb0, c->rn_part_floats); }
+            if (rc_) return fail(c, SELD_ERR_INVALID, "resnet50_block: reduce convolution's product refused");
             { PROF3(c, "rn_bn_fwd"); rn_bn(c, st, R.c[0], M, training, nb0); }
             { PROF3(c, "rn_bn_fwd"); launch_rn_bn_apply(st, R.c[0].z, R.c[0].coef, nullptr, R.y0, M, w, 1); }
             // 3x3, BN, ReLU: 64 -> 64 (stage 1) on the implicit-GEMM kernel of the conv blocks (BatchNorm's sums from its epilogue),
@@ -1166,36 +1178,42 @@ static int forward_impl(seld_ctx* c, const float* x, float* sed, float* doa, int
                     { PROF3(c, "rn_products_fwd"); launch_conv64_fwd_sb(st, R.y0, R.c[1].wsp9, nullptr, R.c[1].z, nullptr, nullptr, B, S, rn_c1_width(R)); }
                     { PROF3(c, "rn_bn_fwd"); rn_bn(c, st, R.c[1], M, training); }
                 } else {
+                    // the conv epilogue's partial sums land in rn_part: at most conv_sb_partial_capacity() [128]-float partials, which must fit before the launch
+                    if (training && (size_t)conv_sb_partial_capacity() * 128 > c->rn_part_floats)
+                        return fail(c, SELD_ERR_INVALID, "resnet50_block: more BatchNorm partials than rn_part holds");
                     { PROF3(c, "rn_products_fwd"); launch_conv64_fwd_sb(st, R.y0, R.c[1].wsp9, nullptr, R.c[1].z, training ? c->rn_part : nullptr, &npart, B, S, R.Wout); }
-                    // the conv epilogue's partial sums land in rn_part ([rn_partial_capacity()][16][128] floats): the producer's count must fit
-                    if (npart > rn_partial_capacity() * 16) return fail(c, SELD_ERR_INVALID, "resnet50_block: more BatchNorm partials than rn_part holds");
                     { PROF3(c, "rn_bn_fwd"); rn_bn(c, st, R.c[1], M, training, npart); }
                 }
             } else if (sb && rn_c1_implicit(c, R)) {
                 int nb1 = 0;
-                { PROF3(c, "rn_products_fwd"); launch_rn_conv3_fwd(st, R.y0, R.c[1].wsp, R.c[1].z, B, S, R.Wout, w, w, epi_stats ? c->rn_part : nullptr, &nb1); }
+                { PROF3(c, "rn_products_fwd"); rc_ = launch_rn_conv3_fwd(st, R.y0, R.c[1].wsp, R.c[1].z, B, S, R.Wout, w, w, epi_stats ? c->rn_part : nullptr, &nb1,
+                                                                         c->rn_part_floats); }
+                if (rc_) return fail(c, SELD_ERR_INVALID, "resnet50_block: 3x3 convolution's product refused");
                 { PROF3(c, "rn_bn_fwd"); rn_bn(c, st, R.c[1], M, training, nb1); }
             } else {
                 // (only with rn_split_bf16 / rn_implicit3x3 off, or a width no direct kernel takes: the col tensor is allocated here, once)
                 if (!R.c[1].col && dalloc(c, &R.c[1].col, (size_t)M * 9 * w)) return fail(c, SELD_ERR_NOMEM, "im2col tensor");
                 launch_im2col3x3(st, R.y0, R.c[1].col, B, S, R.Wout, w);
                 int nb1 = 0;
-                { PROF3(c, "rn_products_fwd"); launch_rn_product_fwd(st, R.c[1].col, 9 * w, c->params + R.c[1].w_off, sb ? R.c[1].wsp : nullptr, R.c[1].z, (int)M, 9 * w, w,
-                                                                     epi_stats ? c->rn_part : nullptr, &nb1); }
+                { PROF3(c, "rn_products_fwd"); rc_ = launch_rn_product_fwd(st, R.c[1].col, 9 * w, c->params + R.c[1].w_off, sb ? R.c[1].wsp : nullptr, R.c[1].z, (int)M, 9 * w, w,
+                                                                           epi_stats ? c->rn_part : nullptr, &nb1, c->rn_part_floats); }
+                if (rc_) return fail(c, SELD_ERR_INVALID, "resnet50_block: 3x3 convolution's product refused");
                 { PROF3(c, "rn_bn_fwd"); rn_bn(c, st, R.c[1], M, training, nb1); }
             }
             { PROF3(c, "rn_bn_fwd"); launch_rn_bn_apply(st, R.c[1].z, R.c[1].coef, nullptr, R.y1, M, w, 1); }
             // 1x1 expand, BN; shortcut; out = ReLU(y + r)
             int nb2 = 0;
-            { PROF3(c, "rn_products_fwd"); launch_rn_product_fwd(st, R.y1, w, c->params + R.c[2].w_off, sb ? R.c[2].wsp : nullptr, R.c[2].z, (int)M, w, 4 * w,
-                                                                 epi_stats ? c->rn_part : nullptr, &nb2); }
+            { PROF3(c, "rn_products_fwd"); rc_ = launch_rn_product_fwd(st, R.y1, w, c->params + R.c[2].w_off, sb ? R.c[2].wsp : nullptr, R.c[2].z, (int)M, w, 4 * w,
+                                                                       epi_stats ? c->rn_part : nullptr, &nb2, c->rn_part_floats); }
+            if (rc_) return fail(c, SELD_ERR_INVALID, "resnet50_block: expand convolution's product refused");
             { PROF3(c, "rn_bn_fwd"); rn_bn(c, st, R.c[2], M, training, nb2); }
             if (R.proj) {
                 if (sc_side) hipStreamWaitEvent(st, c->ev_rn_free[0], 0);
                 else {
                     int nbs = 0;
-                    { PROF3(c, "rn_products_fwd"); launch_rn_product_fwd(st, X, R.Cin * R.stride_f, c->params + R.sc.w_off, sb ? R.sc.wsp : nullptr, R.sc.z, (int)M, R.Cin, 4 * w,
-                                                                         epi_stats ? c->rn_part : nullptr, &nbs); }
+                    { PROF3(c, "rn_products_fwd"); rc_ = launch_rn_product_fwd(st, X, R.Cin * R.stride_f, c->params + R.sc.w_off, sb ? R.sc.wsp : nullptr, R.sc.z, (int)M, R.Cin, 4 * w,
+                                                                               epi_stats ? c->rn_part : nullptr, &nbs, c->rn_part_floats); }
+                    if (rc_) return fail(c, SELD_ERR_INVALID, "resnet50_block: projection shortcut product refused");
                     { PROF3(c, "rn_bn_fwd"); rn_bn(c, st, R.sc, M, training, nbs); }
                 }
                 { PROF3(c, "rn_bn_fwd"); launch_rn_bn_apply2(st, R.c[2].z, R.c[2].coef, R.sc.z, R.sc.coef, R.out, M, 4 * w, save ? R.gate : nullptr); }

@@ -171,6 +171,8 @@ int launch_bn_bwd_finalize(hipStream_t st, const float* partial, int npartial, d
                            float* dbeta, float* c1c2, int C);
 // resnet.hip: channel-count-generic layers of resnet50_block (spec/RESNET50_BLOCK.md)
 int rn_partial_capacity();
+size_t rn_epi_partial_floats(int64_t M, int N);      // partial floats a product epilogue's statistics of an M x N product take, at most
+size_t rn_stats_partial_floats(int C);               // ... the separate statistics pass (launch_rn_bn_stats / _bwd_reduce) over C channels, at most
 int launch_im2col3x3(hipStream_t st, const float* y, float* col, int B, int H, int W, int C);
 int launch_col2im3x3(hipStream_t st, const float* dcol, float* dy, int B, int H, int W, int C);
 int launch_rn_bn_stats(hipStream_t st, const float* z, float* partial, int* nbx, int64_t npix, int C);
@@ -197,7 +199,7 @@ int rn_sb_fwd_ok(int K, int N);
 int rn_sb_dgrad_ok(int K, int N);
 int rn_sb_wgrad_ok(int K, int N);
 int launch_rn_product_fwd(hipStream_t st, const float* A, int lda, const float* w, const unsigned short* wsp, float* z, int M, int K, int N,
-                          float* stat_part = nullptr, int* nbx = nullptr);
+                          float* stat_part = nullptr, int* nbx = nullptr, size_t part_cap = 0);
 int launch_rn_product_dgrad(hipStream_t st, const float* dz, const float* w, const unsigned short* wsp_t, float* dA, int ldd, int M, int K, int N,
                             int accumulate, const float* addg = nullptr, const unsigned char* gate4 = nullptr);
 int launch_rn_product_wgrad(hipStream_t st, const float* A, int lda, const float* dz, float* slab, int64_t slab_cap, float* dw, int M, int K, int N,
@@ -209,7 +211,7 @@ int launch_rn_w32_embed(hipStream_t st, const float* w, float* w2);
 int launch_rn_w32_extract(hipStream_t st, const float* dw2, float* dw);
 int rn_conv3_sb_ok(int C, int N);
 int launch_rn_conv3_fwd(hipStream_t st, const float* img, const unsigned short* wsp, float* z, int B, int H, int W, int C, int N,
-                        float* stat_part = nullptr, int* nbx = nullptr);
+                        float* stat_part = nullptr, int* nbx = nullptr, size_t part_cap = 0);
 int launch_rn_conv3_dgrad(hipStream_t st, const float* dz, const unsigned short* wsp_flip, float* dimg, int B, int H, int W, int C, int N);
 int launch_rn_conv3_wgrad(hipStream_t st, const float* img, const float* dz, float* slab, int64_t slab_cap, float* dw, int B, int H, int W, int C, int N);
 // xception.hip: middle flow of xception_block (spec/XCEPTION_BLOCK.md)

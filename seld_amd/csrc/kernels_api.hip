@@ -416,32 +416,45 @@ static unsigned short* rn_k_split(Scratch& s, const float* w, int K, int N, int 
     return launch_gemm_split_b(0, 1, src, dst, ldb, tb, Ks, Ns) ? nullptr : d;
 }
 
-int seld_k_rn_conv(const float* x, const float* w, float* z, int B, int H, int W, int Cin, int Cout, int ksize, int stride_f) {
+// sums (optional, device, ceil(Cout / 64) * 128 + 1 doubles): the BatchNorm statistics from the product's epilogue as the model takes them (GemmEpi
+// stat_part, a partial buffer of rn_epi_partial_floats), folded by rn_bn_finalize's phase 1: per 64-channel chunk [sum z | sum z^2], then M
+int seld_k_rn_conv_stats(const float* x, const float* w, float* z, int B, int H, int W, int Cin, int Cout, int ksize, int stride_f, double* sums) {
     if (!x || !w || !z) return SELD_ERR_INVALID;
     if ((ksize != 1 && ksize != 3) || (ksize == 3 && stride_f != 1) || stride_f < 1 || W % stride_f || Cin % 4) return SELD_ERR_UNSUPPORTED;
+    if (sums && Cout % 32) return SELD_ERR_UNSUPPORTED;
     const int Wo = W / stride_f;
     const int M = B * H * Wo, K = ksize * ksize * Cin;
     Scratch s;
     const unsigned short* wsp = rn_k_split(s, w, K, Cout, 0);
+    const size_t cap = sums ? rn_epi_partial_floats(M, Cout) : 0;
+    float* part = sums ? s.get(cap) : nullptr;
+    if (sums && !part) return SELD_ERR_NOMEM;
+    int nbx = 0;
     if (ksize == 1) {
-        if (launch_rn_product_fwd(0, x, Cin * stride_f, w, wsp, z, M, K, Cout)) return SELD_ERR_INVALID;
-        return done();
+        if (launch_rn_product_fwd(0, x, Cin * stride_f, w, wsp, z, M, K, Cout, part, &nbx, cap)) return SELD_ERR_INVALID;
+    } else if (wsp && rn_conv3_sb_ok(Cin, Cout)) {      // im2col rows formed on load
+        if (launch_rn_conv3_fwd(0, x, wsp, z, B, H, W, Cin, Cout, part, &nbx, cap)) return SELD_ERR_INVALID;
+    } else {
+        float* col = s.get((size_t)M * 9 * Cin);
+        if (!col) return SELD_ERR_NOMEM;
+        launch_im2col3x3(0, x, col, B, H, W, Cin);
+        if (launch_rn_product_fwd(0, col, K, w, wsp, z, M, K, Cout, part, &nbx, cap)) return SELD_ERR_INVALID;
     }
-    if (wsp && rn_conv3_sb_ok(Cin, Cout)) {      // im2col rows formed on load
-        if (launch_rn_conv3_fwd(0, x, wsp, z, B, H, W, Cin, Cout)) return SELD_ERR_INVALID;
-        return done();
-    }
-    float* col = s.get((size_t)M * 9 * Cin);
-    if (!col) return SELD_ERR_NOMEM;
-    launch_im2col3x3(0, x, col, B, H, W, Cin);
-    if (launch_rn_product_fwd(0, col, K, w, wsp, z, M, K, Cout)) return SELD_ERR_INVALID;
+    // phase 1 folds the partials and stops: gamma, beta, the moving statistics and the coefficients are not touched
+    if (sums) launch_rn_bn_finalize(0, part, nbx, (double)M, nullptr, nullptr, nullptr, nullptr, nullptr, Cout, 1, sums, 1);
     return done();
 }
+int seld_k_rn_conv(const float* x, const float* w, float* z, int B, int H, int W, int Cin, int Cout, int ksize, int stride_f) {
+    return seld_k_rn_conv_stats(x, w, z, B, H, W, Cin, Cout, ksize, stride_f, nullptr);
+}
 
-int seld_k_rn_conv_bwd(const float* x, const float* w, const float* dz, float* dw, float* dx, int B, int H, int W, int Cin, int Cout,
-                       int ksize, int stride_f) {
-    if (!x || !w || !dz || !dw || !dx) return SELD_ERR_INVALID;
+// addg + gate4 (optional, ksize 1, stride_f 1): dx += addg [gate bit] as the model adds the identity shortcut's gradient — in the input-gradient
+// product's epilogue where launch_rn_product_dgrad takes it, else by launch_rn_add_gated behind it
+int seld_k_rn_conv_bwd_add(const float* x, const float* w, const float* dz, float* dw, float* dx, int B, int H, int W, int Cin, int Cout,
+                           int ksize, int stride_f, const float* addg, const unsigned char* gate4) {
+    if (!x || !w || !dz || !dw || !dx || (!addg != !gate4)) return SELD_ERR_INVALID;
     if ((ksize != 1 && ksize != 3) || (ksize == 3 && stride_f != 1) || stride_f < 1 || W % stride_f || Cin % 4) return SELD_ERR_UNSUPPORTED;
+    if (addg && (ksize != 1 || stride_f != 1)) return SELD_ERR_UNSUPPORTED;
     const int Wo = W / stride_f, M = B * H * Wo, K1 = ksize * ksize * Cin;
     Scratch s;
     const int64_t cap = tn_slab_capacity();     // the model's slab buffer
@@ -467,9 +480,15 @@ int seld_k_rn_conv_bwd(const float* x, const float* w, const float* dz, float* d
         const int ldx = Cin * stride_f;
         if (launch_rn_product_wgrad(0, x, ldx, dz, slab, cap, dw, M, K1, Cout, g_rn_split_bf16)) return SELD_ERR_INVALID;
         if (stride_f > 1 && hipMemsetAsync(dx, 0, (size_t)B * H * W * Cin * sizeof(float), 0) != hipSuccess) return SELD_ERR_HIP;
-        if (launch_rn_product_dgrad(0, dz, w, wsp_t, dx, ldx, M, K1, Cout, 0)) return SELD_ERR_INVALID;
+        const int added = launch_rn_product_dgrad(0, dz, w, wsp_t, dx, ldx, M, K1, Cout, 0, addg, gate4);
+        if (added < 0) return SELD_ERR_INVALID;
+        if (addg && added == 1) launch_rn_add_gated(0, dx, addg, gate4, (int64_t)M * Cin);
     }
     return done();
+}
+int seld_k_rn_conv_bwd(const float* x, const float* w, const float* dz, float* dw, float* dx, int B, int H, int W, int Cin, int Cout,
+                       int ksize, int stride_f) {
+    return seld_k_rn_conv_bwd_add(x, w, dz, dw, dx, B, H, W, Cin, Cout, ksize, stride_f, nullptr, nullptr);
 }
 
 int seld_k_rn_bn(const float* z, const float* gamma, const float* beta, const float* res, float* out, float* mean, float* invstd,

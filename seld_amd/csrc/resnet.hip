@@ -17,6 +17,11 @@
 
 #define RN_MAX_PARTIAL 256
 int rn_partial_capacity() { return RN_MAX_PARTIAL; }
+// floats of [sum | sum of squares] partials a product's epilogue writes for an M x N product: ceil(N / 64) chunks x row blocks x 128, the row
+// blocks counted on the fp32 GEMM's 64-row tiles (the split-bf16 kernels' 128-row tiles write half of it) — a bound whichever kernel takes the shape
+size_t rn_epi_partial_floats(int64_t M, int N) { return (size_t)((N + 63) / 64) * (size_t)((M + 63) / 64) * 128; }
+// ... and the separate statistics pass (rn_reduce: at most RN_MAX_PARTIAL workgroups per 64-channel chunk)
+size_t rn_stats_partial_floats(int C) { return (size_t)RN_MAX_PARTIAL * ((C + 63) / 64) * 128; }
 
 __device__ __forceinline__ float4 rn_fma4(float4 a, float4 b, float4 c) {
     return make_float4(fmaf(a.x, b.x, c.x), fmaf(a.y, b.y, c.y), fmaf(a.z, b.z, c.z), fmaf(a.w, b.w, c.w));
@@ -394,15 +399,16 @@ int rn_sb_dgrad_ok(int K, int N) { return (N % 32) == 0 && (K % 128) == 0; }    
 int rn_sb_wgrad_ok(int K, int N) { return (K % 128) == 0 && (N % 128) == 0; }            // dw = A^T dz       [K,M] x [M,N]
 
 // stat_part (may be null) + nbx: the convolution's BatchNorm statistics leave with the product's epilogue (common.h GemmEpi) — *nbx receives the
-// number of [sum | sum of squares] partials per 64-channel chunk that rn_bn_finalize has to fold
+// number of [sum | sum of squares] partials per 64-channel chunk that rn_bn_finalize has to fold.  part_cap: the floats stat_part holds; a launch
+// whose partials would not fit is refused (-4) before anything is enqueued
 int launch_rn_product_fwd(hipStream_t st, const float* A, int lda, const float* w, const unsigned short* wsp, float* z, int M, int K, int N,
-                          float* stat_part, int* nbx) {
+                          float* stat_part, int* nbx, size_t part_cap) {
     GemmEpiScope epi_(stat_part);
-    if (wsp && rn_sb_fwd_ok(K, N) && gemm_sb_usable(A, lda, N, K)) {
-        if (nbx) *nbx = stat_part ? gemm_epi_row_blocks(M, 1) : 0;
-        return launch_gemm_sb(st, A, nullptr, lda, wsp, nullptr, nullptr, nullptr, z, nullptr, N, M, N, K, 0, 0);
-    }
-    if (nbx) *nbx = stat_part ? gemm_epi_row_blocks(M, 0) : 0;
+    const int sb = wsp && rn_sb_fwd_ok(K, N) && gemm_sb_usable(A, lda, N, K);
+    const int rb = stat_part ? gemm_epi_row_blocks(M, sb) : 0;
+    if (stat_part && (size_t)((N + 63) / 64) * rb * 128 > part_cap) return -4;
+    if (nbx) *nbx = rb;
+    if (sb) return launch_gemm_sb(st, A, nullptr, lda, wsp, nullptr, nullptr, nullptr, z, nullptr, N, M, N, K, 0, 0);
     return launch_gemm(st, A, lda, w, N, nullptr, z, N, M, N, K, 0, 0, 0);
 }
 // wsp_t: the planes of w^T (launch_gemm_split_b with transb = 1, K' = N, N' = K)
@@ -439,10 +445,13 @@ int launch_rn_product_wgrad(hipStream_t st, const float* A, int lda, const float
 // (gemm_sb.hip / gemm_tn_sb.hip: conv_C): no col / dcol tensors, no col2im.  C and N powers of two, multiples of 128 (stages 2-3).
 int rn_conv3_sb_ok(int C, int N) { return C >= 128 && N >= 128 && (C & (C - 1)) == 0 && (N & (N - 1)) == 0; }
 // wsp: launch_gemm_split_b(w [9 C][N], transb 0)
+// stat_part / nbx / part_cap: as launch_rn_product_fwd
 int launch_rn_conv3_fwd(hipStream_t st, const float* img, const unsigned short* wsp, float* z, int B, int H, int W, int C, int N, float* stat_part,
-                        int* nbx) {
+                        int* nbx, size_t part_cap) {
     GemmEpiScope epi_(stat_part);
-    if (nbx) *nbx = stat_part ? gemm_epi_row_blocks(B * H * W, 1) : 0;
+    const int rb = stat_part ? gemm_epi_row_blocks(B * H * W, 1) : 0;
+    if (stat_part && (size_t)((N + 63) / 64) * rb * 128 > part_cap) return -4;
+    if (nbx) *nbx = rb;
     return launch_gemm_sb(st, img, nullptr, C, wsp, nullptr, nullptr, nullptr, z, nullptr, N, B * H * W, N, 9 * C, 0, 0, 0, C, H, W);
 }
 // input gradient = the convolution of dz [.][N] with the flipped, channel-swapped kernel; wsp_flip: launch_gemm_split_b(w, ldb N, transb 2, K 9 N, N C)

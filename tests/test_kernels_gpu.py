@@ -589,14 +589,37 @@ def test_conv1_train_without_pre_bn_tensor(seld_lib, B, H, CIN):
 
 
 # ---- resnet50_block pieces (spec/RESNET50_BLOCK.md) at the shapes its stages run them at: B*S*W pixels with W = 16, 8, 4, 2
+# The row RN_CANCELLATION runs on block-like inputs (x >= 0, channels with |mean| / std = 10, 30, 100): the single-pass variance of the statistics
+RN_CANCELLATION = (4, 60, 8, 512, 128, 1, 1)
+
+
 @pytest.mark.parametrize("B,H,W,Cin,Cout,ksize,stride_f", [(2, 30, 16, 64, 32, 1, 1), (2, 30, 16, 32, 32, 3, 1), (2, 30, 16, 128, 64, 1, 2),
                                                            (4, 60, 2, 256, 256, 3, 1), (4, 60, 2, 256, 1024, 1, 1), (4, 60, 4, 512, 1024, 1, 2),
-                                                           (3, 7, 4, 128, 128, 3, 1), (2, 30, 16, 32, 128, 1, 1), (2, 61, 4, 128, 512, 1, 1), (2, 21, 4, 128, 256, 3, 1), (5, 9, 2, 256, 128, 3, 1)])
+                                                           (3, 7, 4, 128, 128, 3, 1), (2, 30, 16, 32, 128, 1, 1), (2, 61, 4, 128, 512, 1, 1), (2, 21, 4, 128, 256, 3, 1), (5, 9, 2, 256, 128, 3, 1),
+                                                           # every form of the statistics / gated-add epilogues, M ragged against its tile:
+                                                           # gemm.hip N = 32 / 64 (fp32 GEMM at both settings)
+                                                           (3, 37, 16, 128, 32, 1, 1), (5, 21, 8, 256, 64, 1, 1), (3, 13, 4, 128, 64, 1, 1),
+                                                           # gemm_sb16: N = 128, K = 32, 64, 128, 512
+                                                           (3, 37, 16, 32, 128, 1, 1), (3, 37, 16, 64, 128, 1, 1), (5, 21, 8, 128, 128, 1, 1), (3, 13, 4, 512, 128, 1, 1),
+                                                           # gemm_sb (4-wave, N >= 256): K = 64, K = 128 (NG = 4) with a frequency stride of 2, 256 -> 1024
+                                                           (3, 13, 4, 64, 256, 1, 1), (5, 21, 16, 128, 256, 1, 2), (3, 13, 2, 256, 1024, 1, 1),
+                                                           # implicit 3x3 at 128 and 256 channels
+                                                           (3, 13, 4, 128, 128, 3, 1), (3, 13, 2, 256, 256, 3, 1),
+                                                           # M below one tile; more than 256 row blocks per chunk (rn_sum_partials' unrolled loops)
+                                                           (1, 1, 16, 32, 128, 1, 1), (1, 1, 16, 128, 32, 1, 1), (2, 1100, 16, 32, 128, 1, 1), (2, 1100, 16, 128, 32, 1, 1),
+                                                           RN_CANCELLATION])
 @pytest.mark.parametrize("split", [1, 0])
 def test_rn_conv_fwd_bwd(seld_lib, B, H, W, Cin, Cout, ksize, stride_f, split):
     """A resnet50_block convolution as its three products (forward, input gradient, kernel gradient) against float64 autograd: on the
     split-bf16 kernels where the shape allows (Cout, resp. K, a multiple of 128: the last five shapes at least in part) and on the fp32
-    MFMA GEMM (`rn_split_bf16 = 0`, and every other shape)."""
+    MFMA GEMM (`rn_split_bf16 = 0`, and every other shape).
+
+    With the two epilogue extras the training step uses (rn_epi_stats, rn_epi_add):
+      * BatchNorm statistics: the per-tile [sum z | sum z^2] partials of the product's epilogue, folded as rn_bn_finalize folds them, against
+        fp64 sums of the fp64 z (sum z to 1e-5 of sum |z| per channel, sum z^2 to 1e-5 relative; columns past Cout exactly 0), and z is the
+        same bits with and without the statistics;
+      * gated add (1x1, stride 1): dx = dz w^T + addg [gate] against fp64 at 1e-4, and bit for bit the product without addg followed by one
+        fp32 add of the gated addg — what the separate pass computes — for a random (~50 %), an all-off and an all-on gate."""
     assert seld_lib.seld_k_set_option(b"rn_split_bf16", split) == 0
     try:
         _rn_conv_fwd_bwd(seld_lib, B, H, W, Cin, Cout, ksize, stride_f)
@@ -604,10 +627,34 @@ def test_rn_conv_fwd_bwd(seld_lib, B, H, W, Cin, Cout, ksize, stride_f, split):
         seld_lib.seld_k_set_option(b"rn_split_bf16", 1)
 
 
+def _rn_block_like_inputs(rng, B, H, W, Cin, Cout):
+    """x >= 0 as a ReLU output with per-channel offsets; w columns 0-3 / 4-7 / 8-11 mixed from a positive direction and noise so that z's
+    channel has |mean| / std = 10 / 30 / 100 in fp64 (the rest: plain random columns).  Returns x, w and every channel's |mean| / std."""
+    x = np.maximum(rng.uniform(2.0, 10.0, Cin) + rng.standard_normal((B, H, W, Cin)), 0.0).astype(np.float32)
+    w = (rng.standard_normal((Cin, Cout)) / np.sqrt(Cin)).astype(np.float32)
+    xf = x.reshape(-1, Cin).astype(np.float64)
+    zu = xf.mean(axis=1)                               # z of the positive direction ones / Cin
+    for j, R in enumerate([10.0] * 4 + [30.0] * 4 + [100.0] * 4):
+        zr = xf @ w[:, j].astype(np.float64)
+        c0 = -zr.mean() / zu.mean()                      # the column shifted to a zero-mean output first
+        ratio = lambda c: abs(((c0 + c) * zu + zr).mean()) / ((c0 + c) * zu + zr).std()
+        lo, hi = 0.0, 1e6
+        for _ in range(200):                             # from there |mean| / std rises with c towards zu's own ratio
+            mid = 0.5 * (lo + hi)
+            lo, hi = (mid, hi) if ratio(mid) < R else (lo, mid)
+        w[:, j] = ((c0 + hi) / Cin + w[:, j].astype(np.float64)).astype(np.float32)
+    z = xf @ w.astype(np.float64)
+    return x, w.reshape(1, 1, Cin, Cout), np.abs(z.mean(axis=0)) / z.std(axis=0)
+
+
 def _rn_conv_fwd_bwd(seld_lib, B, H, W, Cin, Cout, ksize, stride_f):
     rng = np.random.default_rng(31)
-    x = rng.standard_normal((B, H, W, Cin)).astype(np.float32)
-    w = (rng.standard_normal((ksize, ksize, Cin, Cout)) / np.sqrt(ksize * ksize * Cin)).astype(np.float32)
+    cancel = (B, H, W, Cin, Cout, ksize, stride_f) == RN_CANCELLATION
+    if cancel:
+        x, w, ratios = _rn_block_like_inputs(rng, B, H, W, Cin, Cout)
+    else:
+        x = rng.standard_normal((B, H, W, Cin)).astype(np.float32)
+        w = (rng.standard_normal((ksize, ksize, Cin, Cout)) / np.sqrt(ksize * ksize * Cin)).astype(np.float32)
     Wo = W // stride_f
     dz = rng.standard_normal((B, H, Wo, Cout)).astype(np.float32)
     xt = torch.tensor(x, dtype=torch.float64).permute(0, 3, 1, 2).requires_grad_(True)
@@ -617,12 +664,62 @@ def _rn_conv_fwd_bwd(seld_lib, B, H, W, Cin, Cout, ksize, stride_f):
     z = torch.full((B, H, Wo, Cout), float("nan"), device="cuda")
     xd, wd, dzd = dev(x), dev(w), dev(dz)
     assert seld_lib.seld_k_rn_conv(ptr(xd), ptr(wd), ptr(z), B, H, W, Cin, Cout, ksize, stride_f) == 0
-    check("rn_conv z", z.cpu().numpy(), zt.detach().permute(0, 2, 3, 1).numpy())
+    zref = zt.detach().permute(0, 2, 3, 1).numpy()
+    check("rn_conv z", z.cpu().numpy(), zref)
+
+    # ---- BatchNorm statistics from the product's epilogue
+    M, nch = B * H * Wo, (Cout + 63) // 64
+    sums = torch.full((nch * 128 + 1,), float("nan"), dtype=torch.float64, device="cuda")
+    z2 = torch.full_like(z, float("nan"))
+    assert seld_lib.seld_k_rn_conv_stats(ptr(xd), ptr(wd), ptr(z2), B, H, W, Cin, Cout, ksize, stride_f, ptr(sums)) == 0
+    assert torch.equal(z2.view(torch.int32), z.view(torch.int32)), "the statistics epilogue changed the product"
+    sm = sums.cpu().numpy()
+    assert sm[-1] == M
+    sm = sm[:-1].reshape(nch, 2, 64)
+    s1, s2 = sm[:, 0].reshape(-1), sm[:, 1].reshape(-1)
+    assert (s1[Cout:] == 0).all() and (s2[Cout:] == 0).all(), "columns past Cout must leave zero partials"
+    zr = zref.reshape(-1, Cout)
+    r1, r2, ra = zr.sum(axis=0), (zr * zr).sum(axis=0), np.abs(zr).sum(axis=0)
+    e1 = np.abs(s1[:Cout] - r1) / ra
+    e2 = np.abs(s2[:Cout] - r2) / r2
+    print(f"[stats] {B,H,W,Cin,Cout,ksize,stride_f}: sum z {e1.max():.2e} of sum|z|, sum z^2 {e2.max():.2e} rel")
+    assert e1.max() <= 1e-5 and e2.max() <= 1e-5, (e1.max(), e2.max())
+    if cancel:
+        # single pass as rn_bn_finalize_kernel: mean = S / M, var = Q / M - mean^2 (double), against two-pass fp64 over the fp64 z
+        mean, var = s1[:Cout] / M, s2[:Cout] / M - (s1[:Cout] / M) ** 2
+        mref = zr.mean(axis=0)
+        vref = ((zr - mref) ** 2).mean(axis=0)
+        em, ev = np.abs(mean - mref) / np.sqrt(vref), np.abs(var - vref) / vref
+        for R in (10.0, 30.0, 100.0):
+            k = np.abs(ratios - R) < 1e-3 * R
+            print(f"[stats] single-pass variance at |mean|/std = {R:g}: var rel err {ev[k].max():.2e}, mean err {em[k].max():.2e} std")
+        k = ratios <= 10.0 * (1 + 1e-3)      # the asserted bar: |mean| / std up to 10; 30 and 100 are measured only
+        assert k.sum() >= 4 and em[k].max() <= 1e-4 and ev[k].max() <= 1e-4, (em[k].max(), ev[k].max())
+
+    # ---- the two gradient products
     dw = torch.full((ksize, ksize, Cin, Cout), float("nan"), device="cuda")
     dx = torch.full((B, H, W, Cin), float("nan"), device="cuda")
     assert seld_lib.seld_k_rn_conv_bwd(ptr(xd), ptr(wd), ptr(dzd), ptr(dw), ptr(dx), B, H, W, Cin, Cout, ksize, stride_f) == 0
     check("rn_conv dw", dw.cpu().numpy(), wt.grad.permute(2, 3, 1, 0).numpy())
-    check("rn_conv dx", dx.cpu().numpy(), xt.grad.permute(0, 2, 3, 1).numpy())
+    dxref = xt.grad.permute(0, 2, 3, 1).numpy()
+    check("rn_conv dx", dx.cpu().numpy(), dxref)
+    if ksize != 1 or stride_f != 1:
+        return
+
+    # ---- the identity shortcut's gated gradient added to dx (gate4[e >> 2] bit e & 3)
+    addg = rng.standard_normal((B, H, W, Cin)).astype(np.float32)
+    dx0 = dx.cpu().numpy()
+    for pat in ("random", "off", "on"):
+        gate = {"random": rng.random((B, H, W, Cin)) < 0.5, "off": np.zeros((B, H, W, Cin), bool), "on": np.ones((B, H, W, Cin), bool)}[pat]
+        g4 = gate.reshape(-1, 4).astype(np.uint8)
+        gate4 = torch.as_tensor(g4[:, 0] | (g4[:, 1] << 1) | (g4[:, 2] << 2) | (g4[:, 3] << 3)).cuda()
+        dxa = torch.full((B, H, W, Cin), float("nan"), device="cuda")
+        assert seld_lib.seld_k_rn_conv_bwd_add(ptr(xd), ptr(wd), ptr(dzd), ptr(dw), ptr(dxa), B, H, W, Cin, Cout, ksize, stride_f,
+                                               ptr(dev(addg)), ptr(gate4)) == 0
+        got = dxa.cpu().numpy()
+        check(f"rn_conv dx + addg [{pat} gate]", got, dxref + np.where(gate, addg.astype(np.float64), 0.0))
+        sep = dx0 + np.where(gate, addg, np.float32(0))
+        assert np.array_equal(got.view(np.int32), sep.view(np.int32)), f"{pat} gate: fused add differs from the separate fp32 add"
 
 
 @pytest.mark.parametrize("fused", [1, 0])

@@ -1391,7 +1391,7 @@ def _resnet_routed_grad_check(model, spec, w, st, x, ys, yd, free, kw, label):
 
 @pytest.mark.parametrize("B,T,blocks,doa_loss,split", [(4, 300, [1, 1, 1, 1], "MSE", 1), (4, 300, [1, 1, 1, 1], "MSE", 0), (4, 300, [1, 1, 1, 1], "MSE", 2),
                                                          (3, 300, [2, 1, 1, 1], "MMSE", 1),
-                                                         (2, 300, [3, 4, 6, 3], "MSE", 1)])
+                                                         (2, 300, [3, 4, 6, 3], "MSE", 1), (3, 300, [2, 1, 1, 1], "MSE", 3)])
 def test_resnet50_gru_train_step(resnet50_config, B, T, blocks, doa_loss, split):
     """BASELINE config 5's model (model_config/resnet50_gru.json): FIRST = resnet50_block as published in spec/RESNET50_BLOCK.md (the
     reference snapshot does not define the block: parity is against OUR spec, restated by the oracle) — one test step and one train
@@ -1405,7 +1405,11 @@ def test_resnet50_gru_train_step(resnet50_config, B, T, blocks, doa_loss, split)
           a pre-activation fp32 cannot resolve (|fp64 pre-activation| < 1e-5 of values that are O(1) behind BatchNormalization; 1e-3 for the 16-bottleneck
           [3,4,6,3], whose fp32 forward is itself 1e-4 away from fp64 at the outputs);
       (2) GIVEN the library's decisions (seld_debug_relu_output, seld_debug_pool_routing) the fp64 oracle's gradients agree with
-          the library's to 1e-4 for every variable — for [3,4,6,3] to derived_bar(what the fp32 oracle given the same decisions is off by)."""
+          the library's to 1e-4 for every variable — for [3,4,6,3] to derived_bar(what the fp32 oracle given the same decisions is off by).
+
+    split = 3: the split-bf16 products with both epilogue extras off (rn_epi_stats = rn_epi_add = 0: the separate statistics pass and the
+    separate gated add of the identity shortcut, stage 0's second block taking it) against the same oracle; and the gated add in the reduce
+    convolution's epilogue (rn_epi_add = 1) must give the same gradient bits, as it computes the same fp32 sum."""
     import copy
     import ctypes as C
     from oracle import seldnet_oracle as O
@@ -1423,6 +1427,9 @@ def test_resnet50_gru_train_step(resnet50_config, B, T, blocks, doa_loss, split)
     if split == 2:
         model.set_option("rn_implicit3x3", 0)
         model.set_option("rn_wgrad_side", 0)
+    if split == 3:
+        model.set_option("rn_epi_stats", 0)
+        model.set_option("rn_epi_add", 0)
     tr, nt = O.variable_specs(spec)
     assert [(n, s) for n, _, s in model.variables] == tr and [(n, s) for n, _, s in model.state_variables] == nt
     if blocks == [3, 4, 6, 3]:
@@ -1447,6 +1454,84 @@ def test_resnet50_gru_train_step(resnet50_config, B, T, blocks, doa_loss, split)
     _, st1 = model.get_weights()
     check("resnet50 BN moving stats", st1, ref["new_state"], tol=t_st)
     _resnet_routed_grad_check(model, spec, w, st, x, ys, yd, free, kw, f"resnet50 {blocks}")
+    if split == 3:      # the identity shortcut's gated gradient in the epilogue: the same bits as the separate pass
+        g_sep = model.get_grads().copy()
+        model.set_option("rn_epi_add", 1)
+        model.set_weights(w, st)
+        train.trainstep(model, x, (ys, yd), losses.BinaryCrossentropy(), losses.get_doa_loss(doa_loss), (1.0, 1000.0), train.Adam(1e-3))
+        np.testing.assert_array_equal(model.get_grads(), g_sep)
+
+
+def test_resnet50_epilogue_statistics_at_large_batch(resnet50_config):
+    """BatchNorm statistics from the products' epilogues (rn_epi_stats, the default) against the separate statistics pass at B = 32,
+    T = 3000 (B*S = 19 200 rows per frequency bin: 614 400 floats of stage 0's epilogue partials, more than the fixed 524 288-float partial
+    buffers once held) — one train step each from the same weights, state and batch: outputs, losses and the new moving statistics within
+    1e-5, and, given the same ReLU gates (the separate pass's gates injected where the two runs decide differently), every gradient within
+    1e-4 (a BatchNorm beta's of its gamma's scale, see below).  No fp64 oracle at this size."""
+    import copy
+    import ctypes as C
+    from oracle import seldnet_oracle as O
+    from seld_amd import _lib, losses, models, train
+    cfg = copy.deepcopy(resnet50_config)
+    cfg["FIRST_ARGS"]["block_num"] = [2, 1, 1, 1]
+    spec = O.Spec.from_config(cfg)
+    w, st = O.random_weights(spec, 7)
+    B, T = 32, 3000
+    x, ys, yd = O.synthetic_batch(B, T, seed=29)
+    model = models.seldnet((B, T, 64, 7), cfg)
+    n_blocks = len(O.resnet_plan(spec))
+    buf = torch.empty(B * (T // 5) * 16 * 128, device="cuda")
+    cnt = C.c_int64()
+
+    def step(epi_stats):
+        model.set_option("rn_epi_stats", epi_stats)
+        model.set_weights(w, st)
+        y_p, sl, dl = train.trainstep(model, x, (ys, yd), losses.BinaryCrossentropy(), losses.MSE, (1.0, 1000.0), train.Adam(1e-3))
+        return [y_p[0].cpu().numpy(), y_p[1].cpu().numpy(), sl.cpu().numpy(), dl.cpu().numpy()], model.get_weights()[1], model.get_grads().copy()
+
+    def gates():
+        out = {}
+        for bi in range(n_blocks):
+            for k in range(3):
+                _lib.check(model.lib.seld_debug_relu_output(model.ctx, bi, k, C.c_void_p(buf.data_ptr()), buf.numel(), C.byref(cnt)), model.ctx)
+                out[bi, k] = buf[:cnt.value] > 0
+        return out
+
+    outs_sep, st_sep, g_sep = step(0)
+    gates_sep = gates()
+    outs_epi, st_epi, _ = step(1)
+    n_diff = 0
+    for (bi, k), ge in gates().items():
+        idx = torch.nonzero(ge != gates_sep[bi, k]).flatten()
+        n_diff += idx.numel()
+        v = np.ascontiguousarray(gates_sep[bi, k][idx].cpu().numpy().astype(np.uint8))
+        i64 = np.ascontiguousarray(idx.cpu().numpy().astype(np.int64))
+        _lib.check(model.lib.seld_debug_set_relu_gates(model.ctx, bi, k, v.size, C.c_void_p(i64.ctypes.data), C.c_void_p(v.ctypes.data)), model.ctx)
+    print(f"[epi stats B={B} T={T}] {n_diff} ReLU gates differ between the two statistics paths")
+    for name, a, b in zip(("sed", "doa", "sed loss", "doa loss"), outs_epi, outs_sep):
+        check(f"epi stats vs separate pass: {name}", a, b, tol=1e-5)
+    for n, off, sh in model.state_variables:
+        k = int(np.prod(sh))
+        check(f"epi stats vs separate pass: {n}", st_epi[off:off + k], st_sep[off:off + k], tol=1e-5)
+    _, _, g_epi = step(1)
+    # per variable, 1e-4 of its largest value; a BatchNorm's beta gradient against the larger of its own and its gamma's: both sum the same
+    # per-element gradients (gamma's weighted by xhat, |xhat| ~ 1), and at 614 400 pixels the stem's beta gradient cancels to 1 % of that scale
+    var = {n: (off, int(np.prod(sh))) for n, off, sh in model.variables}
+    errs = {}
+    for n, (off, k) in var.items():
+        a, b = g_epi[off:off + k].astype(np.float64), g_sep[off:off + k].astype(np.float64)
+        if n.startswith("conv") and n.endswith("bias"):      # exactly 0 in exact arithmetic: rounding noise on both sides (as _per_var)
+            assert np.abs(a).max() <= 1e-3 * max(1.0, np.abs(g_sep).max()), n
+            continue
+        den = np.abs(b).max()
+        if n.endswith(".beta"):
+            go, gk = var[n[:-len("beta")] + "gamma"]
+            den = max(den, np.abs(g_sep[go:go + gk]).max())
+        errs[n] = float(np.abs(a - b).max() / den)
+        print(f"[parity] epi stats vs separate pass given the same gates: grad {n:28s} {errs[n]:.3e}")
+    assert np.isfinite(g_epi).all()
+    worst = max(errs, key=errs.get)
+    assert errs[worst] <= 1e-4, (worst, errs[worst])
 
 
 def test_full_size_first_block_gram_form_vs_stored_z_form(seldnet_config):
