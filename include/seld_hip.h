@@ -428,8 +428,12 @@ int seld_debug_set_relu_gates(seld_ctx* ctx, int block, int which, int64_t n, co
  * / mother_stage (modules.py:15-43, 184-298: Conv2D(k, 'same', strides) + BatchNormalization + skip / projection / concatenation +
  * squeeze-and-excitation), and, around them, bidirectional_GRU_block and simple_dense_block at ANY feature width.  NHWC fp32 device tensors,
  * asynchronous on `stream`, no allocation (scratch is the caller's), any channel count / kernel / stride.  The dense products run on the
- * fp32 MFMA GEMM of gemm.hip; everything else is memory-bound elementwise / reduction work. */
-int seld_m_conv_out(int in, int stride);      /* TensorFlow 'SAME': ceil(in / stride) */
+ * fp32 MFMA GEMM of gemm.hip; everything else is memory-bound elementwise / reduction work.
+ * Refusals: every operator returns SELD_ERR_INVALID, before anything is enqueued, for a NULL required pointer (all but gemm's bias, gemm_tn's
+ * colsum, the BatchNormalization scratch, scale_hw_bwd_dx's dmean, gru_fwd's saved_* / out and losses' dsed_pre / ddoa_pre), a size < 1 (B, H, W, C, S, HW, npix, rows, n, nc, M, N, K, K1, kernel and stride extents; count of bn_moving), an unknown kind /
+ * mode, copy_channels with off < 0 or off + Cs > Cd, gemm_tn with seq < 0 or M % seq != 0; the GRU operators return SELD_ERR_UNSUPPORTED for
+ * units != 128.  The *_scratch size functions return -1 for a size < 1.  A call that passes these checks is launched. */
+int seld_m_conv_out(int in, int stride);      /* TensorFlow 'SAME': ceil(in / stride); SELD_ERR_INVALID for in < 1 or stride < 1 */
 /* col[(b,ho,wo)][(ki,kj,c)] of Conv2D(k, 'same', strides) on x [B,H,W,C]; the convolution is col * kernel[kh kw C, filters] + bias */
 int seld_m_im2col(const float* x, float* col, int B, int H, int W, int C, int kh, int kw, int sh, int sw, void* stream);
 int seld_m_col2im(const float* dcol, float* dx, int B, int H, int W, int C, int kh, int kw, int sh, int sw, int accumulate, void* stream);

@@ -328,7 +328,7 @@ inline int ok() { return hipGetLastError() == hipSuccess ? SELD_OK : SELD_ERR_HI
 
 extern "C" {
 
-int seld_m_conv_out(int in, int stride) { return same_out(in, stride); }
+int seld_m_conv_out(int in, int stride) { return in > 0 && stride > 0 ? same_out(in, stride) : SELD_ERR_INVALID; }
 
 int seld_m_im2col(const float* x, float* col, int B, int H, int W, int C, int kh, int kw, int sh, int sw, void* stream) {
     if (!x || !col || B < 1 || H < 1 || W < 1 || C < 1 || kh < 1 || kw < 1 || sh < 1 || sw < 1) return SELD_ERR_INVALID;
@@ -350,18 +350,18 @@ int seld_m_col2im(const float* dcol, float* dx, int B, int H, int W, int C, int 
 
 /* C[M,N] (+)= A[M,K] op(B) + bias on the fp32 MFMA GEMM (gemm.hip); transb = 1: B is [N,K] */
 int seld_m_gemm(const float* A, const float* Bm, const float* bias, float* Cm, int M, int N, int K, int transb, int accumulate, void* stream) {
-    if (!A || !Bm || !Cm) return SELD_ERR_INVALID;
+    if (!A || !Bm || !Cm || M < 1 || N < 1 || K < 1) return SELD_ERR_INVALID;
     if (launch_gemm((hipStream_t)stream, A, K, Bm, transb ? K : N, bias, Cm, N, M, N, K, transb, 0, accumulate)) return SELD_ERR_INVALID;
     return ok();
 }
 
-int64_t seld_m_gemm_tn_scratch(int K1, int N) { return (int64_t)gemm_tn_max_splits() * ((int64_t)K1 * N + N); }
+int64_t seld_m_gemm_tn_scratch(int K1, int N) { return K1 > 0 && N > 0 ? (int64_t)gemm_tn_max_splits() * ((int64_t)K1 * N + N) : -1; }
 
 /* C[K1,N] = A[M,K1]^T B[M,N], colsum[N] = sum_m B[m,:] (may be NULL); slab: caller scratch of seld_m_gemm_tn_scratch(K1, N) floats.
  * seq > 0, shift = -1 | +1: row m of A is replaced by row m + shift of the same length-`seq` sequence, zero outside it (the recurrent
  * kernel's gradient h_prev^T dgh of a GRU direction); seq = 0: no shift */
 int seld_m_gemm_tn(const float* A, const float* Bm, float* Cm, float* colsum, float* slab, int M, int K1, int N, int seq, int shift, void* stream) {
-    if (!A || !Bm || !Cm || !slab || (seq > 0 && M % seq)) return SELD_ERR_INVALID;
+    if (!A || !Bm || !Cm || !slab || M < 1 || K1 < 1 || N < 1 || seq < 0 || (seq > 0 && M % seq)) return SELD_ERR_INVALID;
     int ns = 0;
     if (launch_gemm_tn((hipStream_t)stream, A, K1, Bm, N, slab, &ns, M, K1, N, seq, seq > 0 ? shift : 0, colsum ? 1 : 0, 0, 0)) return SELD_ERR_INVALID;
     if (colsum) launch_reduce_slabs2((hipStream_t)stream, slab, ns, (int64_t)K1 * N + N, Cm, (int64_t)K1 * N, colsum, N);
@@ -385,18 +385,18 @@ int seld_m_bn_stats(const float* z, int64_t npix, int C, float* mean, float* var
 }
 int seld_m_bn_apply(const float* z, const float* mean, const float* var, const float* gamma, const float* beta, float eps, float* out,
                     int64_t npix, int C, int accumulate, void* stream) {
-    if (!z || !mean || !var || !gamma || !beta || !out) return SELD_ERR_INVALID;
+    if (!z || !mean || !var || !gamma || !beta || !out || npix < 1 || C < 1) return SELD_ERR_INVALID;
     hipLaunchKernelGGL(bn_apply_kernel, dim3(nblk(npix * C)), dim3(256), 0, (hipStream_t)stream, z, mean, var, gamma, beta, eps, out, npix * C, C, accumulate);
     return ok();
 }
 int seld_m_bn_moving(const float* mean, const float* var, float* mov_mean, float* mov_var, int C, float momentum, int64_t count, void* stream) {
-    if (!mean || !var || !mov_mean || !mov_var) return SELD_ERR_INVALID;
+    if (!mean || !var || !mov_mean || !mov_var || C < 1 || count < 1) return SELD_ERR_INVALID;
     hipLaunchKernelGGL(bn_moving_kernel, dim3((C + 63) / 64), dim3(64), 0, (hipStream_t)stream, mean, var, mov_mean, mov_var, C, momentum, (double)count);
     return ok();
 }
 int seld_m_bn_bwd(const float* z, const float* dy, const float* mean, const float* var, const float* gamma, float eps, float* dz, float* dgamma,
                   float* dbeta, int64_t npix, int C, float* scratch, void* stream) {
-    if (!z || !dy || !mean || !var || !gamma || !dz || !dgamma || !dbeta) return SELD_ERR_INVALID;
+    if (!z || !dy || !mean || !var || !gamma || !dz || !dgamma || !dbeta || npix < 1 || C < 1) return SELD_ERR_INVALID;
     if (!scratch || C > 256 * BNP_MAX_SLOTS || (reinterpret_cast<uintptr_t>(scratch) & 7))
         hipLaunchKernelGGL(bn_bwd_sums_kernel, dim3(C), dim3(256), 0, (hipStream_t)stream, z, dy, mean, var, eps, npix, C, dgamma, dbeta);
     else {
@@ -411,45 +411,45 @@ int seld_m_bn_bwd(const float* z, const float* dy, const float* mean, const floa
 }
 
 int seld_m_act(const float* x, float* y, int64_t n, int kind, void* stream) {
-    if (!x || !y || kind < 0 || kind > 4) return SELD_ERR_INVALID;
+    if (!x || !y || n < 1 || kind < 0 || kind > 4) return SELD_ERR_INVALID;
     hipLaunchKernelGGL(act_kernel, dim3(nblk(n)), dim3(256), 0, (hipStream_t)stream, x, y, n, kind);
     return ok();
 }
 int seld_m_act_bwd(const float* x, const float* dy, float* dx, int64_t n, int kind, int accumulate, void* stream) {
-    if (!x || !dy || !dx || kind < 0 || kind > 4) return SELD_ERR_INVALID;
+    if (!x || !dy || !dx || n < 1 || kind < 0 || kind > 4) return SELD_ERR_INVALID;
     hipLaunchKernelGGL(act_bwd_kernel, dim3(nblk(n)), dim3(256), 0, (hipStream_t)stream, x, dy, dx, n, kind, accumulate);
     return ok();
 }
 int seld_m_axpy(float* dst, const float* src, int64_t n, float alpha, void* stream) {
-    if (!dst || !src) return SELD_ERR_INVALID;
+    if (!dst || !src || n < 1) return SELD_ERR_INVALID;
     hipLaunchKernelGGL(axpy_kernel, dim3(nblk(n)), dim3(256), 0, (hipStream_t)stream, dst, src, n, alpha);
     return ok();
 }
 int seld_m_copy_channels(float* src, float* dst, int64_t rows, int Cs, int Cd, int off, int mode, void* stream) {
-    if (!src || !dst || Cs < 1 || off < 0 || off + Cs > Cd) return SELD_ERR_INVALID;
+    if (!src || !dst || rows < 1 || Cs < 1 || off < 0 || off + Cs > Cd || mode < 0 || mode > 1) return SELD_ERR_INVALID;
     hipLaunchKernelGGL(copy_channels_kernel, dim3(nblk(rows * Cs)), dim3(256), 0, (hipStream_t)stream, src, dst, rows, Cs, Cd, off, mode);
     return ok();
 }
 int seld_m_mean_hw(const float* x, float* out, int B, int HW, int C, void* stream) {
-    if (!x || !out) return SELD_ERR_INVALID;
+    if (!x || !out || B < 1 || HW < 1 || C < 1) return SELD_ERR_INVALID;
     hipLaunchKernelGGL(mean_hw_kernel, dim3((unsigned)B * C), dim3(256), 0, (hipStream_t)stream, x, out, HW, C);
     return ok();
 }
 int seld_m_scale_hw(const float* x, const float* s, float* y, int B, int HW, int C, void* stream) {
-    if (!x || !s || !y) return SELD_ERR_INVALID;
+    if (!x || !s || !y || B < 1 || HW < 1 || C < 1) return SELD_ERR_INVALID;
     const int64_t n = (int64_t)B * HW * C;
     hipLaunchKernelGGL(scale_hw_kernel, dim3(nblk(n)), dim3(256), 0, (hipStream_t)stream, x, s, y, n, HW, C);
     return ok();
 }
 /* y = x s: ds[b][c] = sum_px dy x */
 int seld_m_scale_hw_bwd_ds(const float* x, const float* dy, float* ds, int B, int HW, int C, void* stream) {
-    if (!x || !dy || !ds) return SELD_ERR_INVALID;
+    if (!x || !dy || !ds || B < 1 || HW < 1 || C < 1) return SELD_ERR_INVALID;
     hipLaunchKernelGGL(scale_hw_bwd_ds_kernel, dim3((unsigned)B * C), dim3(256), 0, (hipStream_t)stream, x, dy, ds, HW, C);
     return ok();
 }
 /* dx (+)= dy s + dmean / HW (dmean may be NULL) */
 int seld_m_scale_hw_bwd_dx(const float* dy, const float* s, const float* dmean, float* dx, int B, int HW, int C, int accumulate, void* stream) {
-    if (!dy || !s || !dx) return SELD_ERR_INVALID;
+    if (!dy || !s || !dx || B < 1 || HW < 1 || C < 1) return SELD_ERR_INVALID;
     const int64_t n = (int64_t)B * HW * C;
     hipLaunchKernelGGL(scale_hw_bwd_dx_kernel, dim3(nblk(n)), dim3(256), 0, (hipStream_t)stream, dy, s, dmean, dx, n, HW, C, accumulate);
     return ok();
@@ -476,7 +476,7 @@ int seld_m_gru_bwd(const float* dout, const float* h_f, const float* h_b, const 
 int64_t seld_m_losses_scratch(int rows) { return rows > 0 ? (int64_t)loss_scratch_floats(rows) + 4 : -1; }
 int seld_m_losses(const float* sed, const float* doa, const float* y_sed, const float* y_doa, const seld_loss_cfg* cfg, float* sloss, float* dloss,
                   float* dsed_pre, float* ddoa_pre, float* scratch, int B, int S, int nc, void* stream) {
-    if (!sed || !doa || !y_sed || !y_doa || !cfg || !sloss || !dloss || !scratch || B < 1 || S < 1) return SELD_ERR_INVALID;
+    if (!sed || !doa || !y_sed || !y_doa || !cfg || !sloss || !dloss || !scratch || B < 1 || S < 1 || nc < 1) return SELD_ERR_INVALID;
     const int rows = B * S;
     float* den = scratch + loss_scratch_floats(rows);
     if (cfg->doa_loss == SELD_DOA_MMSE) {
