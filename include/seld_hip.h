@@ -474,6 +474,39 @@ int64_t seld_m_losses_scratch(int rows);
 int seld_m_losses(const float* sed, const float* doa, const float* y_sed, const float* y_doa, const seld_loss_cfg* cfg, float* sloss, float* dloss,
                   float* dsed_pre, float* ddoa_pre, float* scratch, int B, int S, int nc, void* stream);
 int seld_m_adam(float* theta, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps, int64_t step, void* stream);
+/* ---- attention operators (attention.hip): the shared core of the reference's attention blocks — modules.transformer_encoder_block / _stage
+ * (modules.py:106-126, 379-407), and of conformer_encoder_block / attention_block (modules.py:410-635, layers.py:268-287).  fp32 device
+ * tensors, asynchronous on `stream`, no allocation.  Not seld_m_*: seld_amd/modules.py composes the transformer block from these and seld_m_*.
+ *   seld_attn_fwd   tf.keras.layers.MultiHeadAttention's core (modules.py:392-393; the reference's own MultiHeadAttention, layers.py:268-287):
+ *                   O[b,n,h,:] = sum_m softmax_m(scale Q[b,n,h,:] . K[b,m,h,:]) V[b,m,h,:].  Q, K, V: [B*S, H*d] row-major views with row strides
+ *                   ldq / ldk / ldv floats (>= H*d: column slices of one fused [B*S, 3*H*d] projection need no copy), head h = columns h*d ..
+ *                   h*d+d-1; O [B*S, H*d] contiguous; lse [B, H, S] = the rows' log-sum-exp of the scaled logits, saved for the backward (NULL
+ *                   at inference: O is bit-identical).  No [B,H,S,S] tensor is formed: K / V tiles stream through LDS under an online
+ *                   softmax, the products run on the exact-fp32 MFMA.  Any S >= 1 (edge tiles are masked inside).
+ *   seld_attn_bwd   dQ, dK, dV (row strides lddq / lddk / lddv) from Q, K, V, O, dO [B*S, H*d] and lse: the probabilities are recomputed from
+ *                   lse, rowsum(dO * O) is computed inside.  No atomics: one kernel owns dQ per query tile, one owns dK / dV per key tile; two
+ *                   runs are bit-identical.  scratch: seld_attn_bwd_scratch(B, S, H, d) floats (B*H*S: linear in the rows).
+ *   d (the reference's key_dim) must be a multiple of 8 in 8 .. 64: anything else returns SELD_ERR_UNSUPPORTED (the scratch size -1) before
+ *   any other check, as units != 128 does in seld_m_gru_*.  Then SELD_ERR_INVALID, before anything is enqueued, for a NULL pointer (all but
+ *   lse of seld_attn_fwd), B, S or H < 1, or a row stride < H*d. */
+int seld_attn_fwd(const float* Q, const float* K, const float* V, int ldq, int ldk, int ldv, float* O, float* lse, int B, int S, int H, int d,
+                  float scale, void* stream);
+int64_t seld_attn_bwd_scratch(int B, int S, int H, int d);
+int seld_attn_bwd(const float* Q, const float* K, const float* V, int ldq, int ldk, int ldv, const float* O, const float* dO, const float* lse,
+                  float* dQ, float* dK, float* dV, int lddq, int lddk, int lddv, float* scratch, int B, int S, int H, int d, float scale,
+                  void* stream);
+/*   seld_ln_fwd     tf.keras.layers.LayerNormalization over the last axis of [rows, C] (modules.py:395, 403: biased variance, eps inside the
+ *                   square root): y = xhat gamma + beta, xhat = (z - mean z) / sqrt(var z + eps), z = x + r — the residual r may be NULL, so
+ *                   LayerNormalization()(x + attn) is one pass.  xhat [rows, C] and rstd [rows] are saved for the backward (both may be NULL
+ *                   at inference).  Any C >= 1.
+ *   seld_ln_bwd     dz (the gradient of the summed input z: the caller routes it to both addends), dgamma, dbeta from dy and the saved xhat /
+ *                   rstd.  dgamma / dbeta: a two-stage column reduction through scratch (seld_ln_scratch(rows, C) floats), no atomics.
+ *   SELD_ERR_INVALID for a NULL required pointer (all but r, xhat and rstd of seld_ln_fwd), rows < 1 or C < 1; seld_ln_scratch returns -1. */
+int seld_ln_fwd(const float* x, const float* r, const float* gamma, const float* beta, float eps, float* y, float* xhat, float* rstd, int64_t rows,
+                int C, void* stream);
+int64_t seld_ln_scratch(int64_t rows, int C);
+int seld_ln_bwd(const float* dy, const float* xhat, const float* rstd, const float* gamma, float* dz, float* dgamma, float* dbeta, float* scratch,
+                int64_t rows, int C, void* stream);
 /* Measurement aid (bench.py, SURVEY.md §8(d) "state the step-latency floor"): the shader clock the card holds while `blocks`
  * workgroups of 512 threads run a VALU-only loop (the load shape of the GRU recurrence: 2B workgroups, no MFMA), from
  * s_memtime / s_memrealtime (100 MHz) inside the kernel.  No reference counterpart. */

@@ -172,6 +172,12 @@ SIGNATURES = {
     "seld_m_losses_scratch": (_L, [_I]),
     "seld_m_losses": (_I, [_P, _P, _P, _P, C.POINTER(LossCfg), _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "seld_m_adam": (_I, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _L, _P]),
+    "seld_attn_fwd": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _I, _I, _I, _I, _F, _P]),
+    "seld_attn_bwd_scratch": (_L, [_I, _I, _I, _I]),
+    "seld_attn_bwd": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _I, _I, _I, _I, _F, _P]),
+    "seld_ln_fwd": (_I, [_P, _P, _P, _P, _F, _P, _P, _P, _L, _I, _P]),
+    "seld_ln_scratch": (_L, [_L, _I]),
+    "seld_ln_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _P]),
     "seld_k_rn_conv": (_I, [_P, _P, _P] + [_I] * 7),
     "seld_k_rn_conv_stats": (_I, [_P, _P, _P] + [_I] * 7 + [_P]),
     "seld_k_rn_conv_bwd": (_I, [_P, _P, _P, _P, _P] + [_I] * 7),

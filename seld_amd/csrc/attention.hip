@@ -1,0 +1,383 @@
+// attention.hip — the two operators the reference's attention blocks share (modules.transformer_encoder_block, modules.py:379-407; also the
+// core of conformer_encoder_block and attention_block): multi-head scaled-dot-product self-attention over the frame axis
+// (tf.keras.layers.MultiHeadAttention(n_head, key_dim)(x, x), modules.py:392-393) and LayerNormalization over the last axis (modules.py:395,
+// 403), forward and backward.  C ABI "seld_attn_*" / "seld_ln_*": asynchronous on the caller's stream, no allocation, caller scratch.
+//
+// Attention.  Q, K, V are [B*S, H*d] row-major views with their own row strides (column slices of one fused projection need no copy);
+// head h is columns h*d .. h*d+d-1.  No [B,H,S,S] tensor exists anywhere: a workgroup = 2 waves = 64 query rows (32 per wave) of one
+// (batch, head) streams 64-key tiles of K and V through LDS with an online softmax (running maximum m and sum l per query row), and the
+// backward recomputes the probabilities from the saved log-sum-exp m + ln l.  All products run on v_mfma_f32_32x32x2_f32 (exact fp32).
+//
+// Tile scheme (forward, and the dQ kernel of the backward): the logits are computed TRANSPOSED, S^T[key][query] = K Q^T, so that a lane
+// of the accumulator layout (common.h) holds ONE query (column l & 31) and 16 keys (rows (r & 3) + 8 (r >> 2) + 4 (l >> 5)); lane l ^ 32
+// holds the other 16.  The row maximum and sum of a query are then 16 in-lane operations and one cross-half shuffle, m / l / lse / delta are
+// per-lane scalars, and the accumulator registers p[r] ARE the B operand of the next product O^T[dd][query] += V^T[dd][key] P^T[key][query]
+// (step r contracts keys row(r, 0) and row(r, 1): a sum over keys has no order to respect), so P never crosses LDS.  The dK / dV kernel is
+// the mirror image: S[query][key] with the key on the lane and K, V of the wave's 32 keys in registers, Q and dO tiles through LDS, and
+// p[r] / ds[r] the B operands of dV^T += dO^T P and dK^T += Q^T dS.  Each output element is owned by exactly one lane of one workgroup:
+// no atomics, sums in a fixed order, two runs are bit-identical.
+//
+// LDS rows are d + 1 floats (odd): the [key = lane][dd] operand reads of a 32-lane half then hit 32 different banks, and the
+// [key = row][dd = lane] reads are consecutive addresses.  2 x 64 x 65 x 4 B = 33 KB per workgroup at d = 64 (4 workgroups per CU).
+// Registers: Q (and dO) fragments d / 2 each, logits 16 (+16), outputs 16 ceil(d / 32) (twice that in the dK / dV kernel).
+#include "common.h"
+#include <cmath>
+#include "../../include/seld_hip.h"
+#include <math.h>
+
+namespace {
+
+#define AT_TILE 64      // query rows per workgroup = keys per LDS tile (two 32-row MFMA blocks)
+
+__device__ __forceinline__ float xhalf(float v) { return __shfl_xor(v, 32, 64); }
+
+// rows k0 .. k0 + 63 of one head of a [B*S, ld] view -> LDS [64][D + 1], rows past S as zeros; `mul` scales (the query's 1 / sqrt(key_dim))
+template <int D>
+__device__ __forceinline__ void load_tile(const float* __restrict__ src, int ld, size_t row0, int k0, int S, int col0, float mul, float* dst) {
+    for (int e = threadIdx.x; e < AT_TILE * D; e += 128) {
+        const int kk = e / D, dd = e - kk * D;
+        const int key = k0 + kk;
+        dst[kk * (D + 1) + dd] = key < S ? src[(row0 + key) * (size_t)ld + col0 + dd] * mul : 0.f;
+    }
+}
+
+// the lane's fragment of row `row` (valid: ok) of a view: f[s] = row[2 s + hi] * mul
+template <int D>
+__device__ __forceinline__ void load_frag(const float* __restrict__ src, int ld, size_t row, int col0, bool ok, int hi, float mul, float (&f)[D / 2]) {
+    const float* p = src + row * (size_t)ld + col0 + hi;
+#pragma unroll
+    for (int s = 0; s < D / 2; ++s) f[s] = ok ? p[2 * s] * mul : 0.f;
+}
+
+// out^T[dd][lane's row] accumulators -> out[row][col0 + dd] * mul
+template <int D>
+__device__ __forceinline__ void store_t(const f32x16 (&acc)[(D + 31) / 32], float* __restrict__ out, int ld, size_t row, int col0, bool ok, int hi,
+                                        float mul) {
+    if (!ok) return;
+    float* p = out + row * (size_t)ld + col0;
+#pragma unroll
+    for (int nb = 0; nb < (D + 31) / 32; ++nb)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int dd = nb * 32 + mfma_row(r, hi);
+            if (dd < D) p[dd] = acc[nb][r] * mul;
+        }
+}
+
+template <int D>
+__global__ __launch_bounds__(128) void attn_fwd_kernel(const float* __restrict__ Q, const float* __restrict__ K, const float* __restrict__ V, int ldq,
+                                                       int ldk, int ldv, float* __restrict__ O, float* __restrict__ lse, int S, int H, float scale,
+                                                       int nqt) {
+    constexpr int LD = D + 1, NB = (D + 31) / 32;
+    __shared__ float Ks[AT_TILE * LD], Vs[AT_TILE * LD];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 31, hi = lane >> 5;
+    const int qt = blockIdx.x % nqt, bh = blockIdx.x / nqt, h = bh % H, b = bh / H;
+    const int q = qt * AT_TILE + wave * 32 + li;
+    const bool qok = q < S;
+    const size_t row0 = (size_t)b * S;
+    float qf[D / 2];
+    load_frag<D>(Q, ldq, row0 + (qok ? q : 0), h * D, qok, hi, scale, qf);
+    f32x16 o[NB];
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb) o[nb] = zero16();
+    float m = -INFINITY, l = 0.f;
+    for (int k0 = 0; k0 < S; k0 += AT_TILE) {
+        __syncthreads();
+        load_tile<D>(K, ldk, row0, k0, S, h * D, 1.f, Ks);
+        load_tile<D>(V, ldv, row0, k0, S, h * D, 1.f, Vs);
+        __syncthreads();
+        for (int kb = 0; kb < 2 && k0 + kb * 32 < S; ++kb) {
+            f32x16 s = zero16();
+            const float* kr = Ks + (kb * 32 + li) * LD + hi;
+#pragma unroll
+            for (int st = 0; st < D / 2; ++st) s = MFMA_F32_32x32x2(kr[2 * st], qf[st], s);
+            float mx = m;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                if (k0 + kb * 32 + mfma_row(r, hi) >= S) s[r] = -INFINITY;      // the edge tile's keys past S
+                mx = fmaxf(mx, s[r]);
+            }
+            mx = fmaxf(mx, xhalf(mx));      // finite: the block's first key is < S
+            const float alpha = __expf(m - mx);
+            float ps = 0.f;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) { s[r] = __expf(s[r] - mx); ps += s[r]; }
+            ps += xhalf(ps);
+            l = l * alpha + ps;
+            m = mx;
+#pragma unroll
+            for (int nb = 0; nb < NB; ++nb) {
+                const int dd = nb * 32 + li;
+                const bool dok = dd < D;
+                const float* vr = Vs + kb * 32 * LD + (dok ? dd : 0);
+#pragma unroll
+                for (int r = 0; r < 16; ++r) o[nb][r] *= alpha;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) o[nb] = MFMA_F32_32x32x2(dok ? vr[mfma_row(r, hi) * LD] : 0.f, s[r], o[nb]);
+            }
+        }
+    }
+    store_t<D>(o, O, H * D, row0 + (qok ? q : 0), h * D, qok, hi, 1.f / l);
+    if (lse && qok && hi == 0) lse[(size_t)bh * S + q] = m + logf(l);
+}
+
+// dQ, and delta[b][h][q] = rowsum(dO * O) for the dK / dV kernel that follows.  Same tiling as the forward.
+template <int D>
+__global__ __launch_bounds__(128) void attn_bwd_dq_kernel(const float* __restrict__ Q, const float* __restrict__ K, const float* __restrict__ V, int ldq,
+                                                          int ldk, int ldv, const float* __restrict__ O, const float* __restrict__ dO,
+                                                          const float* __restrict__ lse, float* __restrict__ dQ, int lddq, float* __restrict__ delta,
+                                                          int S, int H, float scale, int nqt) {
+    constexpr int LD = D + 1, NB = (D + 31) / 32;
+    __shared__ float Ks[AT_TILE * LD], Vs[AT_TILE * LD];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 31, hi = lane >> 5;
+    const int qt = blockIdx.x % nqt, bh = blockIdx.x / nqt, h = bh % H, b = bh / H;
+    const int q = qt * AT_TILE + wave * 32 + li;
+    const bool qok = q < S;
+    const size_t row0 = (size_t)b * S, row = row0 + (qok ? q : 0);
+    float qf[D / 2], dof[D / 2];
+    load_frag<D>(Q, ldq, row, h * D, qok, hi, scale, qf);
+    load_frag<D>(dO, H * D, row, h * D, qok, hi, 1.f, dof);
+    float dl = 0.f;
+    {
+        const float* op = O + row * (size_t)(H * D) + h * D + hi;
+#pragma unroll
+        for (int s = 0; s < D / 2; ++s) dl += qok ? dof[s] * op[2 * s] : 0.f;
+    }
+    dl += xhalf(dl);
+    if (qok && hi == 0) delta[(size_t)bh * S + q] = dl;
+    const float lq = qok ? lse[(size_t)bh * S + q] : INFINITY;      // a row past S: p = exp(-inf) = 0
+    f32x16 dq[NB];
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb) dq[nb] = zero16();
+    for (int k0 = 0; k0 < S; k0 += AT_TILE) {
+        __syncthreads();
+        load_tile<D>(K, ldk, row0, k0, S, h * D, 1.f, Ks);
+        load_tile<D>(V, ldv, row0, k0, S, h * D, 1.f, Vs);
+        __syncthreads();
+        for (int kb = 0; kb < 2 && k0 + kb * 32 < S; ++kb) {
+            f32x16 s = zero16(), dp = zero16();
+            const float* kr = Ks + (kb * 32 + li) * LD + hi;
+            const float* vr = Vs + (kb * 32 + li) * LD + hi;
+#pragma unroll
+            for (int st = 0; st < D / 2; ++st) s = MFMA_F32_32x32x2(kr[2 * st], qf[st], s);
+#pragma unroll
+            for (int st = 0; st < D / 2; ++st) dp = MFMA_F32_32x32x2(vr[2 * st], dof[st], dp);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const float p = k0 + kb * 32 + mfma_row(r, hi) < S ? __expf(s[r] - lq) : 0.f;
+                s[r] = p * (dp[r] - dl);
+            }
+#pragma unroll
+            for (int nb = 0; nb < NB; ++nb) {
+                const int dd = nb * 32 + li;
+                const bool dok = dd < D;
+                const float* kc = Ks + kb * 32 * LD + (dok ? dd : 0);
+#pragma unroll
+                for (int r = 0; r < 16; ++r) dq[nb] = MFMA_F32_32x32x2(dok ? kc[mfma_row(r, hi) * LD] : 0.f, s[r], dq[nb]);
+            }
+        }
+    }
+    store_t<D>(dq, dQ, lddq, row, h * D, qok, hi, scale);
+}
+
+// dK and dV: a workgroup owns 64 keys of one (batch, head) (32 per wave, K and V fragments in registers) and sweeps the query tiles
+template <int D>
+__global__ __launch_bounds__(128) void attn_bwd_dkv_kernel(const float* __restrict__ Q, const float* __restrict__ K, const float* __restrict__ V, int ldq,
+                                                           int ldk, int ldv, const float* __restrict__ dO, const float* __restrict__ lse,
+                                                           const float* __restrict__ delta, float* __restrict__ dK, float* __restrict__ dV, int lddk,
+                                                           int lddv, int S, int H, float scale, int nkt) {
+    constexpr int LD = D + 1, NB = (D + 31) / 32;
+    __shared__ float Qs[AT_TILE * LD], Gs[AT_TILE * LD], ls[AT_TILE], ds_[AT_TILE];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 31, hi = lane >> 5;
+    const int kt = blockIdx.x % nkt, bh = blockIdx.x / nkt, h = bh % H, b = bh / H;
+    const int key = kt * AT_TILE + wave * 32 + li;
+    const bool kok = key < S;
+    const size_t row0 = (size_t)b * S, row = row0 + (kok ? key : 0);
+    float kf[D / 2], vf[D / 2];
+    load_frag<D>(K, ldk, row, h * D, kok, hi, 1.f, kf);
+    load_frag<D>(V, ldv, row, h * D, kok, hi, 1.f, vf);
+    f32x16 dk[NB], dv[NB];
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb) { dk[nb] = zero16(); dv[nb] = zero16(); }
+    for (int q0 = 0; q0 < S; q0 += AT_TILE) {
+        __syncthreads();
+        load_tile<D>(Q, ldq, row0, q0, S, h * D, scale, Qs);
+        load_tile<D>(dO, H * D, row0, q0, S, h * D, 1.f, Gs);
+        if (threadIdx.x < AT_TILE) {
+            const int q = q0 + threadIdx.x;
+            ls[threadIdx.x] = q < S ? lse[(size_t)bh * S + q] : INFINITY;      // a row past S: p = exp(-inf) = 0
+            ds_[threadIdx.x] = q < S ? delta[(size_t)bh * S + q] : 0.f;
+        }
+        __syncthreads();
+        for (int qb = 0; qb < 2 && q0 + qb * 32 < S; ++qb) {
+            f32x16 s = zero16(), dp = zero16();
+            const float* qr = Qs + (qb * 32 + li) * LD + hi;
+            const float* gr = Gs + (qb * 32 + li) * LD + hi;
+#pragma unroll
+            for (int st = 0; st < D / 2; ++st) s = MFMA_F32_32x32x2(qr[2 * st], kf[st], s);
+#pragma unroll
+            for (int st = 0; st < D / 2; ++st) dp = MFMA_F32_32x32x2(gr[2 * st], vf[st], dp);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int qq = qb * 32 + mfma_row(r, hi);
+                const float p = kok ? __expf(s[r] - ls[qq]) : 0.f;
+                s[r] = p;
+                dp[r] = p * (dp[r] - ds_[qq]);
+            }
+#pragma unroll
+            for (int nb = 0; nb < NB; ++nb) {
+                const int dd = nb * 32 + li;
+                const bool dok = dd < D;
+                const float* gc = Gs + qb * 32 * LD + (dok ? dd : 0);
+                const float* qc = Qs + qb * 32 * LD + (dok ? dd : 0);
+#pragma unroll
+                for (int r = 0; r < 16; ++r) dv[nb] = MFMA_F32_32x32x2(dok ? gc[mfma_row(r, hi) * LD] : 0.f, s[r], dv[nb]);
+#pragma unroll
+                for (int r = 0; r < 16; ++r) dk[nb] = MFMA_F32_32x32x2(dok ? qc[mfma_row(r, hi) * LD] : 0.f, dp[r], dk[nb]);
+            }
+        }
+    }
+    store_t<D>(dk, dK, lddk, row, h * D, kok, hi, 1.f);
+    store_t<D>(dv, dV, lddv, row, h * D, kok, hi, 1.f);
+}
+
+// ---- LayerNormalization over the last axis of [rows, C] (Keras: biased variance, eps inside the square root).  One wave per row, any C.
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// y = xhat gamma + beta, xhat = (z - mean(z)) rsqrt(var(z) + eps), z = x + r (r may be NULL); xhat / rstd saved when the pointers are given
+__global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x, const float* __restrict__ r, const float* __restrict__ gamma,
+                                                     const float* __restrict__ beta, float eps, float* __restrict__ y, float* __restrict__ xhat,
+                                                     float* __restrict__ rstd, int64_t rows, int C) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const float* xp = x + row * C;
+    const float* rp = r ? r + row * C : nullptr;
+    float s = 0.f;
+    for (int c = lane; c < C; c += 64) s += xp[c] + (rp ? rp[c] : 0.f);
+    const float mean = wave_sum(s) / (float)C;
+    float v = 0.f;
+    for (int c = lane; c < C; c += 64) { const float t = xp[c] + (rp ? rp[c] : 0.f) - mean; v += t * t; }
+    const float is = 1.f / sqrtf(wave_sum(v) / (float)C + eps);
+    for (int c = lane; c < C; c += 64) {
+        const float xh = (xp[c] + (rp ? rp[c] : 0.f) - mean) * is;
+        if (xhat) xhat[row * C + c] = xh;
+        y[row * C + c] = xh * gamma[c] + beta[c];
+    }
+    if (rstd && lane == 0) rstd[row] = is;
+}
+
+// dz = rstd (g - mean(g) - xhat mean(g xhat)), g = dy gamma
+__global__ __launch_bounds__(256) void ln_bwd_dz_kernel(const float* __restrict__ dy, const float* __restrict__ xhat, const float* __restrict__ rstd,
+                                                        const float* __restrict__ gamma, float* __restrict__ dz, int64_t rows, int C) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const float* dp = dy + row * C;
+    const float* hp = xhat + row * C;
+    float a = 0.f, b = 0.f;
+    for (int c = lane; c < C; c += 64) { const float g = dp[c] * gamma[c]; a += g; b += g * hp[c]; }
+    const float ma = wave_sum(a) / (float)C, mb = wave_sum(b) / (float)C, is = rstd[row];
+    for (int c = lane; c < C; c += 64) dz[row * C + c] = is * (dp[c] * gamma[c] - ma - hp[c] * mb);
+}
+
+// dgamma = sum_rows dy xhat, dbeta = sum_rows dy in two stages: workgroup (bx, by) sums a contiguous run of rows of the columns by * 256 + t
+// (coalesced rows, double accumulators) into part[bx][2][C]; then one thread per column adds the partials in workgroup order
+#define LN_MAX_BLOCKS 256
+__global__ __launch_bounds__(256) void ln_bwd_partial_kernel(const float* __restrict__ dy, const float* __restrict__ xhat, float* __restrict__ part,
+                                                             int64_t rows, int C) {
+    const int c = blockIdx.y * 256 + threadIdx.x;
+    if (c >= C) return;
+    const int64_t per = (rows + gridDim.x - 1) / gridDim.x, p0 = (int64_t)blockIdx.x * per, p1 = p0 + per < rows ? p0 + per : rows;
+    double a = 0.0, b = 0.0;
+    for (int64_t p = p0; p < p1; ++p) { const double d = dy[p * C + c]; a += d; b += d * (double)xhat[p * C + c]; }
+    part[(size_t)blockIdx.x * 2 * C + c] = (float)a;
+    part[(size_t)blockIdx.x * 2 * C + C + c] = (float)b;
+}
+__global__ __launch_bounds__(256) void ln_bwd_fold_kernel(const float* __restrict__ part, int nb, int C, float* __restrict__ dgamma,
+                                                          float* __restrict__ dbeta) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= C) return;
+    double a = 0.0, b = 0.0;
+    for (int k = 0; k < nb; ++k) { a += part[(size_t)k * 2 * C + c]; b += part[(size_t)k * 2 * C + C + c]; }
+    dbeta[c] = (float)a;
+    dgamma[c] = (float)b;
+}
+inline int ln_blocks(int64_t rows) { const int64_t b = (rows + 15) / 16; return (int)(b < LN_MAX_BLOCKS ? b : LN_MAX_BLOCKS); }
+
+inline int ok() { return hipGetLastError() == hipSuccess ? SELD_OK : SELD_ERR_HIP; }
+inline bool d_ok(int d) { return d >= 8 && d <= 64 && d % 8 == 0; }
+
+// launch `kern`<d> for d = 8, 16, ..., 64
+#define AT_DISPATCH(kern, d, grid, st, ...)                                                                          \
+    switch (d) {                                                                                                     \
+        case 8: hipLaunchKernelGGL((kern<8>), dim3(grid), dim3(128), 0, st, __VA_ARGS__); break;                     \
+        case 16: hipLaunchKernelGGL((kern<16>), dim3(grid), dim3(128), 0, st, __VA_ARGS__); break;                   \
+        case 24: hipLaunchKernelGGL((kern<24>), dim3(grid), dim3(128), 0, st, __VA_ARGS__); break;                   \
+        case 32: hipLaunchKernelGGL((kern<32>), dim3(grid), dim3(128), 0, st, __VA_ARGS__); break;                   \
+        case 40: hipLaunchKernelGGL((kern<40>), dim3(grid), dim3(128), 0, st, __VA_ARGS__); break;                   \
+        case 48: hipLaunchKernelGGL((kern<48>), dim3(grid), dim3(128), 0, st, __VA_ARGS__); break;                   \
+        case 56: hipLaunchKernelGGL((kern<56>), dim3(grid), dim3(128), 0, st, __VA_ARGS__); break;                   \
+        default: hipLaunchKernelGGL((kern<64>), dim3(grid), dim3(128), 0, st, __VA_ARGS__); break;                   \
+    }
+
+}  // namespace
+
+extern "C" {
+
+int seld_attn_fwd(const float* Q, const float* K, const float* V, int ldq, int ldk, int ldv, float* O, float* lse, int B, int S, int H, int d,
+                  float scale, void* stream) {
+    if (!d_ok(d)) return SELD_ERR_UNSUPPORTED;
+    if (!Q || !K || !V || !O || B < 1 || S < 1 || H < 1 || ldq < H * d || ldk < H * d || ldv < H * d) return SELD_ERR_INVALID;
+    const int nt = (S + AT_TILE - 1) / AT_TILE;
+    const int64_t grid = (int64_t)B * H * nt;
+    if (grid > 0x7fffffff) return SELD_ERR_UNSUPPORTED;
+    AT_DISPATCH(attn_fwd_kernel, d, (unsigned)grid, (hipStream_t)stream, Q, K, V, ldq, ldk, ldv, O, lse, S, H, scale, nt);
+    return ok();
+}
+
+/* floats of caller scratch seld_attn_bwd takes: delta[b][h][q] = rowsum(dO * O) */
+int64_t seld_attn_bwd_scratch(int B, int S, int H, int d) { return d_ok(d) && B > 0 && S > 0 && H > 0 ? (int64_t)B * H * S : -1; }
+
+int seld_attn_bwd(const float* Q, const float* K, const float* V, int ldq, int ldk, int ldv, const float* O, const float* dO, const float* lse,
+                  float* dQ, float* dK, float* dV, int lddq, int lddk, int lddv, float* scratch, int B, int S, int H, int d, float scale,
+                  void* stream) {
+    if (!d_ok(d)) return SELD_ERR_UNSUPPORTED;
+    if (!Q || !K || !V || !O || !dO || !lse || !dQ || !dK || !dV || !scratch || B < 1 || S < 1 || H < 1 || ldq < H * d || ldk < H * d ||
+        ldv < H * d || lddq < H * d || lddk < H * d || lddv < H * d)
+        return SELD_ERR_INVALID;
+    const int nt = (S + AT_TILE - 1) / AT_TILE;
+    const int64_t grid = (int64_t)B * H * nt;
+    if (grid > 0x7fffffff) return SELD_ERR_UNSUPPORTED;
+    AT_DISPATCH(attn_bwd_dq_kernel, d, (unsigned)grid, (hipStream_t)stream, Q, K, V, ldq, ldk, ldv, O, dO, lse, dQ, lddq, scratch, S, H, scale, nt);
+    AT_DISPATCH(attn_bwd_dkv_kernel, d, (unsigned)grid, (hipStream_t)stream, Q, K, V, ldq, ldk, ldv, dO, lse, scratch, dK, dV, lddk, lddv, S, H, scale,
+                nt);
+    return ok();
+}
+
+int seld_ln_fwd(const float* x, const float* r, const float* gamma, const float* beta, float eps, float* y, float* xhat, float* rstd, int64_t rows,
+                int C, void* stream) {
+    if (!x || !gamma || !beta || !y || rows < 1 || C < 1 || (rows + 3) / 4 > 0x7fffffff) return SELD_ERR_INVALID;
+    hipLaunchKernelGGL(ln_fwd_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, r, gamma, beta, eps, y, xhat, rstd, rows, C);
+    return ok();
+}
+
+/* floats of caller scratch seld_ln_bwd takes: the first-stage partial sums of dgamma / dbeta, [workgroups <= 256][2][C] */
+int64_t seld_ln_scratch(int64_t rows, int C) { return rows > 0 && C > 0 ? (int64_t)ln_blocks(rows) * 2 * C : -1; }
+
+int seld_ln_bwd(const float* dy, const float* xhat, const float* rstd, const float* gamma, float* dz, float* dgamma, float* dbeta, float* scratch,
+                int64_t rows, int C, void* stream) {
+    if (!dy || !xhat || !rstd || !gamma || !dz || !dgamma || !dbeta || !scratch || rows < 1 || C < 1 || (rows + 3) / 4 > 0x7fffffff)
+        return SELD_ERR_INVALID;
+    const int nb = ln_blocks(rows);
+    hipLaunchKernelGGL(ln_bwd_partial_kernel, dim3(nb, (C + 255) / 256), dim3(256), 0, (hipStream_t)stream, dy, xhat, scratch, rows, C);
+    hipLaunchKernelGGL(ln_bwd_fold_kernel, dim3((C + 255) / 256), dim3(256), 0, (hipStream_t)stream, scratch, nb, C, dgamma, dbeta);
+    hipLaunchKernelGGL(ln_bwd_dz_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, dy, xhat, rstd, gamma, dz, rows, C);
+    return ok();
+}
+
+}  // extern "C"

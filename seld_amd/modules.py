@@ -9,8 +9,11 @@ else).  There is no CPU or PyTorch fallback.
                                                   skipped, squeeze-and-excitation tail; the ValueErrors of modules.py:202-222
   mother_stage  (modules.py:15-43)                `depth` mother_blocks, strides in the first only
   bidirectional_GRU_block (modules.py:302-319), simple_dense_block (modules.py:350-376; Conv1D kernel_size 1): at ANY feature width
+  transformer_encoder_block / _stage (modules.py:106-126, 379-407)   MultiHeadAttention(n_head, key_dim)(x, x) + LayerNormalization + two
+                                                  Conv1D('same') + LayerNormalization, from seld_attn_* / seld_ln_* (attention.hip) and seld_m_*
 
-`ComposedSeldNet` = models.seldnet(input_shape, model_config) for FIRST in {mother_block, mother_stage}: same surface as
+`ComposedSeldNet` = models.seldnet(input_shape, model_config) for FIRST in {mother_block, mother_stage}, SECOND in {bidirectional_GRU_block,
+transformer_encoder_block, transformer_encoder_stage}: same surface as
 seld_amd.models.SeldNet (variables in Keras creation order, get / set_weights, __call__, train.trainstep / teststep).  The three
 BASELINE configurations do NOT run through here — their blocks are fused kernels inside a seld_ctx (models.SeldNet)."""
 from __future__ import annotations
@@ -27,6 +30,7 @@ from . import _lib
 
 ACT = {None: 0, "linear": 0, "sigmoid": 1, "tanh": 2, "relu": 3, "swish": 4}
 BN_EPS, BN_MOMENTUM = 1e-3, 0.99
+LN_EPS = 1e-3      # tf.keras.layers.LayerNormalization's default epsilon
 
 
 def safe_tuple(v, n=2):
@@ -249,6 +253,200 @@ class _ConvBN:
         self.conv.backward(self.dz, dx, B, accumulate)
 
 
+class LayerNorm:
+    """tf.keras.layers.LayerNormalization() over the last axis of [rows, C], with the residual sum in front of it folded in:
+    forward(x, r) = LN(x + r) (r None: LN(x)); backward gives the gradient of the SUMMED input, which the caller routes to both addends."""
+
+    def __init__(self, rt: _Rt, name: str, rows: int, C: int):
+        self.rt, self.name, self.C = rt, name, int(C)
+        rt.var(f"{name}.gamma", (self.C,))
+        rt.var(f"{name}.beta", (self.C,))
+        self.y, self.xhat, self.rstd, self.dz = rt.empty(rows, self.C), rt.empty(rows, self.C), rt.empty(rows), rt.empty(rows, self.C)
+        self.scratch = rt.empty(int(rt.lib.seld_ln_scratch(rows, self.C)))
+
+    def forward(self, x, r, rows, training):
+        rt, n = self.rt, self.name
+        rt.ck(rt.lib.seld_ln_fwd(rt.p(x), rt.p(r), rt.p(rt.w(f"{n}.gamma")), rt.p(rt.w(f"{n}.beta")), LN_EPS, rt.p(self.y),
+                                 rt.p(self.xhat) if training else None, rt.p(self.rstd) if training else None, rows, self.C, rt.st()))
+        return self.y[:rows]
+
+    def backward(self, dy, rows):
+        rt, n = self.rt, self.name
+        rt.ck(rt.lib.seld_ln_bwd(rt.p(dy), rt.p(self.xhat), rt.p(self.rstd), rt.p(rt.w(f"{n}.gamma")), rt.p(self.dz), rt.p(rt.g(f"{n}.gamma")),
+                                 rt.p(rt.g(f"{n}.beta")), rt.p(self.scratch), rows, self.C, rt.st()))
+        return self.dz[:rows]
+
+
+class MultiHeadAttention:
+    """tf.keras.layers.MultiHeadAttention(n_head, key_dim)(x, x) on [B, S, D] (value_dim = key_dim, biases, no dropout): three projections
+    (one seld_m_gemm each: Keras' kernels [D, H, dk] are [D, H dk] row-major), the query scaled by 1 / sqrt(key_dim), seld_attn_fwd, and
+    the output projection [H dk, D]."""
+
+    def __init__(self, rt: _Rt, name: str, B: int, S: int, D: int, n_head: int, key_dim: int):
+        self.rt, self.name, self.S, self.D, self.H, self.dk = rt, name, int(S), int(D), int(n_head), int(key_dim)
+        H, dk = self.H, self.dk
+        for part in ("query", "key", "value"):
+            rt.var(f"{name}.{part}.kernel", (self.D, H, dk))
+            rt.var(f"{name}.{part}.bias", (H, dk))
+        rt.var(f"{name}.attention_output.kernel", (H, dk, self.D))
+        rt.var(f"{name}.attention_output.bias", (self.D,))
+        if int(rt.lib.seld_attn_bwd_scratch(B, self.S, H, dk)) < 0:
+            raise ValueError(f"key_dim {key_dim!r}: the attention kernels take a multiple of 8 from 8 to 64")
+        R, HD = B * self.S, H * dk
+        self.q, self.k, self.v, self.o, self.do = (rt.empty(R, HD) for _ in range(5))
+        self.dq, self.dk_, self.dv = (rt.empty(R, HD) for _ in range(3))
+        self.lse = rt.empty(B * H * self.S)
+        self.scratch = rt.empty(int(rt.lib.seld_attn_bwd_scratch(B, self.S, H, dk)))
+        self.out = rt.empty(R, self.D)
+        self.scale = 1.0 / math.sqrt(float(dk))
+
+    def forward(self, x, B, training):
+        rt, n = self.rt, self.name
+        R, HD = B * self.S, self.H * self.dk
+        self.x = x
+        for part, buf in (("query", self.q), ("key", self.k), ("value", self.v)):
+            rt.gemm(x, rt.w(f"{n}.{part}.kernel"), rt.w(f"{n}.{part}.bias"), buf, R, HD, self.D)
+        rt.ck(rt.lib.seld_attn_fwd(rt.p(self.q), rt.p(self.k), rt.p(self.v), HD, HD, HD, rt.p(self.o), rt.p(self.lse) if training else None, B, self.S,
+                                   self.H, self.dk, self.scale, rt.st()))
+        rt.gemm(self.o, rt.w(f"{n}.attention_output.kernel"), rt.w(f"{n}.attention_output.bias"), self.out, R, self.D, HD)
+        return self.out[:R]
+
+    def backward(self, dout, dx, B):
+        """dout [R, D] -> every variable's gradient; dx = the input's gradient (overwritten)"""
+        rt, n = self.rt, self.name
+        R, HD = B * self.S, self.H * self.dk
+        rt.gemm_tn(self.o, dout, rt.g(f"{n}.attention_output.kernel"), rt.g(f"{n}.attention_output.bias"), R, HD, self.D)
+        rt.gemm(dout, rt.w(f"{n}.attention_output.kernel"), None, self.do, R, HD, self.D, transb=1)
+        rt.ck(rt.lib.seld_attn_bwd(rt.p(self.q), rt.p(self.k), rt.p(self.v), HD, HD, HD, rt.p(self.o), rt.p(self.do), rt.p(self.lse), rt.p(self.dq),
+                                   rt.p(self.dk_), rt.p(self.dv), HD, HD, HD, rt.p(self.scratch), B, self.S, self.H, self.dk, self.scale, rt.st()))
+        for i, (part, g) in enumerate((("query", self.dq), ("key", self.dk_), ("value", self.dv))):
+            rt.gemm_tn(self.x, g, rt.g(f"{n}.{part}.kernel"), rt.g(f"{n}.{part}.bias"), R, self.D, HD)
+            rt.gemm(g, rt.w(f"{n}.{part}.kernel"), None, dx, R, self.D, HD, transb=1, accumulate=int(i > 0))
+
+
+class Conv1D:
+    """tf.keras.layers.Conv1D(filters, k, padding='same') over the frames of [B, S, Cin]: seld_m_im2col with a (k, 1) window (skipped for
+    k = 1) + the MFMA GEMM; kernel [k, Cin, filters]."""
+
+    def __init__(self, rt: _Rt, name: str, B: int, S: int, Cin: int, filters: int, k: int):
+        self.rt, self.name, self.S, self.Cin, self.N, self.k = rt, name, int(S), int(Cin), int(filters), int(k)
+        self.K = self.k * self.Cin
+        rt.var(f"{name}.kernel", (self.k, self.Cin, self.N))
+        rt.var(f"{name}.bias", (self.N,))
+        self.col = self.dcol = None
+        if self.k > 1:
+            self.col, self.dcol = rt.empty(B * self.S, self.K), rt.empty(B * self.S, self.K)
+        self.z = rt.empty(B * self.S, self.N)
+
+    def forward(self, x, B):
+        rt = self.rt
+        R = B * self.S
+        self.a = x
+        if self.k > 1:
+            rt.ck(rt.lib.seld_m_im2col(rt.p(x), rt.p(self.col), B, self.S, 1, self.Cin, self.k, 1, 1, 1, rt.st()))
+            self.a = self.col
+        rt.gemm(self.a, rt.w(f"{self.name}.kernel"), rt.w(f"{self.name}.bias"), self.z, R, self.N, self.K)
+        return self.z[:R]
+
+    def backward(self, dz, dx, B):
+        rt = self.rt
+        R = B * self.S
+        rt.gemm_tn(self.a, dz, rt.g(f"{self.name}.kernel"), rt.g(f"{self.name}.bias"), R, self.K, self.N)
+        if self.k == 1:
+            rt.gemm(dz, rt.w(f"{self.name}.kernel"), None, dx, R, self.K, self.N, transb=1)
+        else:
+            rt.gemm(dz, rt.w(f"{self.name}.kernel"), None, self.dcol, R, self.K, self.N, transb=1)
+            rt.ck(rt.lib.seld_m_col2im(rt.p(self.dcol), rt.p(dx), B, self.S, 1, self.Cin, self.k, 1, 1, 1, 0, rt.st()))
+
+
+TRANSFORMER_KEYS = ("n_head", "key_dim", "ff_multiplier", "kernel_size")
+
+
+def check_transformer_config(cfg: dict, stage: bool = False) -> None:
+    """the mandatory keys of reference modules.py:380-383 (and `depth`, modules.py:120); what has no kernel here is refused, not ignored"""
+    for key in TRANSFORMER_KEYS + (("depth",) if stage else ()):
+        if key not in cfg:
+            raise ValueError(f"transformer_encoder_{'stage' if stage else 'block'}: missing {key!r}")
+    if cfg.get("activation", "relu") not in ACT:
+        raise ValueError(f"activation {cfg.get('activation')!r}: the module operators know {sorted(k for k in ACT if k)}")
+    if "dropout_rate" not in cfg or float(cfg["dropout_rate"]) != 0.0:
+        raise ValueError("transformer_encoder_block: there is no dropout kernel on this path and the reference's default dropout_rate is 0.1: "
+                         "dropout_rate must be present and 0")
+    if int(cfg["n_head"]) < 1 or int(cfg["kernel_size"]) < 1 or float(cfg["ff_multiplier"]) <= 0 or (stage and int(cfg["depth"]) < 1):
+        raise ValueError("transformer_encoder_block: n_head, kernel_size, depth >= 1 and ff_multiplier > 0")
+    dk = int(cfg["key_dim"])
+    if dk < 8 or dk > 64 or dk % 8:
+        raise ValueError(f"key_dim {dk}: the attention kernels take a multiple of 8 from 8 to 64")
+
+
+class TransformerEncoderBlock:
+    """reference modules.transformer_encoder_block (modules.py:379-407) on [B, S, D]:
+    x = LN(x + MHA(x, x)); ffn = Conv1D(D, k)(Conv1D(int(ff_multiplier D), k, activation)(x)); x = LN(x + ffn)."""
+
+    def __init__(self, rt: _Rt, cfg: dict, S: int, D: int, prefix: str, B: int):
+        check_transformer_config(cfg)
+        self.rt, self.S, self.D, self.B = rt, int(S), int(D), B
+        self.F = int(cfg["ff_multiplier"] * self.D)
+        if self.F < 1:
+            raise ValueError("transformer_encoder_block: int(ff_multiplier * d_model) < 1")
+        k = int(cfg["kernel_size"])
+        self.act = ACT[cfg.get("activation", "relu")]
+        R = B * self.S
+        self.mha = MultiHeadAttention(rt, f"{prefix}.mha", B, self.S, self.D, int(cfg["n_head"]), int(cfg["key_dim"]))
+        self.ln0 = LayerNorm(rt, f"{prefix}.ln0", R, self.D)
+        self.ffn0 = Conv1D(rt, f"{prefix}.ffn0", B, self.S, self.D, self.F, k)
+        self.ffn1 = Conv1D(rt, f"{prefix}.ffn1", B, self.S, self.F, self.D, k)
+        self.ln1 = LayerNorm(rt, f"{prefix}.ln1", R, self.D)
+        self.h, self.dh, self.dpre = rt.empty(R, self.F), rt.empty(R, self.F), rt.empty(R, self.F)
+        self.dx1, self.dx = rt.empty(R, self.D), rt.empty(R, self.D)
+        self.out_shape = (self.S, self.D)
+
+    def forward(self, x, B, training):
+        """x [B*S, D] (or any contiguous view of it) -> [B*S, D]"""
+        rt = self.rt
+        R = B * self.S
+        x = x.reshape(R, self.D)
+        x1 = self.ln0.forward(self.mha.forward(x, B, training), x, R, training)
+        self.pre = self.ffn0.forward(x1, B)
+        rt.act(self.pre, self.h[:R], self.act)
+        return self.ln1.forward(self.ffn1.forward(self.h[:R], B), x1, R, training)
+
+    def backward(self, dy, B):
+        """dy [B*S, D]: the output's gradient -> the input's gradient [B*S, D] (a buffer of this block)"""
+        rt = self.rt
+        R = B * self.S
+        dz1 = self.ln1.backward(dy.reshape(R, self.D), R)          # gradient of x1 + ffn
+        self.ffn1.backward(dz1, self.dh[:R], B)
+        rt.act_bwd(self.pre, self.dh[:R], self.dpre[:R], self.act)
+        dx1 = self.dx1[:R]
+        self.ffn0.backward(self.dpre[:R], dx1, B)
+        rt.axpy(dx1, dz1)
+        dz0 = self.ln0.backward(dx1, R)                             # gradient of x + attn
+        dx = self.dx[:R]
+        self.mha.backward(dz0, dx, B)
+        rt.axpy(dx, dz0)
+        return dx
+
+
+class TransformerEncoderStage:
+    """reference modules.transformer_encoder_stage (modules.py:106-126): `depth` blocks"""
+
+    def __init__(self, rt: _Rt, cfg: dict, S: int, D: int, prefix: str, B: int, depth=None):
+        depth = int(cfg["depth"]) if depth is None else int(depth)
+        self.blocks = [TransformerEncoderBlock(rt, cfg, S, D, f"{prefix}{i}", B) for i in range(depth)]
+        self.S, self.D, self.out_shape = int(S), int(D), (int(S), int(D))
+
+    def forward(self, x, B, training):
+        for blk in self.blocks:
+            x = blk.forward(x, B, training)
+        return x
+
+    def backward(self, dy, B):
+        for blk in reversed(self.blocks):
+            dy = blk.backward(dy, B)
+        return dy
+
+
 class MotherBlock:
     """reference modules.mother_block (modules.py:184-298)."""
 
@@ -449,17 +647,21 @@ class MotherBlock:
         return slots[0]
 
 
+COMPOSED_SECOND = ("bidirectional_GRU_block", "transformer_encoder_block", "transformer_encoder_stage")
+
+
 class ComposedSeldNet:
     """models.seldnet(input_shape, model_config) (reference models.py:18-32) composed from module operators: FIRST = mother_block |
-    mother_stage, SECOND = bidirectional_GRU_block (units 128: the recurrence kernels), SED / DOA = simple_dense_block (kernel_size 1)."""
+    mother_stage, SECOND = bidirectional_GRU_block (units 128: the recurrence kernels) | transformer_encoder_block | transformer_encoder_stage
+    (d_model = F * C of the FIRST stage's output), SED / DOA = simple_dense_block (kernel_size 1)."""
 
     def __init__(self, input_shape, model_config: dict, device=None):
         from .models import canonical_config
         if not torch.cuda.is_available():
             raise RuntimeError("seld_amd needs a HIP device: there is no CPU fallback")
         cfg = canonical_config(model_config)
-        if cfg.get("SECOND") != "bidirectional_GRU_block" or cfg.get("SED") != "simple_dense_block" or cfg.get("DOA") != "simple_dense_block":
-            raise ValueError("composed models: SECOND = bidirectional_GRU_block, SED / DOA = simple_dense_block")
+        if cfg.get("SECOND") not in COMPOSED_SECOND or cfg.get("SED") != "simple_dense_block" or cfg.get("DOA") != "simple_dense_block":
+            raise ValueError(f"composed models: SECOND in {COMPOSED_SECOND}, SED / DOA = simple_dense_block")
         self._dev = torch.device("cuda", torch.cuda.current_device() if device is None else int(device))
         B, T, Fq, Ch = (int(v) for v in input_shape)
         self.input_shape = (B, T, Fq, Ch)
@@ -485,11 +687,15 @@ class ComposedSeldNet:
         self.S = shape[0]
         feat = shape[1] * shape[2]
         sa = cfg["SECOND_ARGS"]
-        if float(sa.get("dropout_rate", 0.0)) != 0.0:
-            raise ValueError("GRU dropout is not implemented")
-        self.gru = []
+        self.gru, self.tf = [], None
         fin = feat
-        for i, u in enumerate(sa["units"]):
+        if cfg["SECOND"] != "bidirectional_GRU_block":
+            stage = cfg["SECOND"] == "transformer_encoder_stage"
+            check_transformer_config(sa, stage)
+            self.tf = TransformerEncoderStage(rt, sa, self.S, feat, "tf", B, depth=None if stage else 1)      # d_model = F * C (force_1d_inputs)
+        elif float(sa.get("dropout_rate", 0.0)) != 0.0:
+            raise ValueError("GRU dropout is not implemented")
+        for i, u in enumerate(sa["units"] if self.tf is None else ()):
             if int(u) != 128:
                 raise ValueError("the recurrence kernels are built for 128 units")
             for dn in ("fwd", "bwd"):
@@ -520,7 +726,7 @@ class ComposedSeldNet:
         rt.finalize()
         self.variables, self.state_variables = rt.variables, rt.state_variables
         self.n_params, self.n_state = rt.n_params, rt.n_state
-        self.dfeat = rt.empty(B * self.S, 128)
+        self.dfeat = rt.empty(B * self.S, fin)
         self.loss_scratch = rt.empty(int(rt.lib.seld_m_losses_scratch(B * self.S)))
         self.dfirst = rt.empty(B, *shape)
         self.adam_step = 0
@@ -650,6 +856,8 @@ class ComposedSeldNet:
                                         rt.p(G["sv"][0]) if training else None, rt.p(G["sv"][1]) if training else None, rt.p(G["out"]), B, self.S, 128,
                                         rt.st()))
             feat = G["out"]
+        if self.tf is not None:
+            feat = self.tf.forward(feat, B, training)
         sed = rt.empty(B, self.S, self.n_classes)
         doa = rt.empty(B, self.S, 3 * self.n_classes)
         for Hd, out in zip(self.heads, (sed, doa)):
@@ -692,6 +900,8 @@ class ComposedSeldNet:
                     rt.gemm(lay["dpre"], rt.w(lay["n"] + ".kernel"), None, self.dfeat, R, lay["in"], lay["out"], transb=1, accumulate=0 if first else 1)
             first = False
         dout = self.dfeat
+        if self.tf is not None:
+            dout = self.tf.backward(dout[:R], B)
         for i in range(len(self.gru) - 1, -1, -1):
             G = self.gru[i]
             rt.ck(rt.lib.seld_m_gru_bwd(rt.p(dout), rt.p(G["h"][0]), rt.p(G["h"][1]), rt.p(G["sv"][0]), rt.p(G["sv"][1]),
@@ -765,3 +975,28 @@ def mother_block(model_config: dict):
         rt = rt or _Rt(torch.device("cuda", torch.cuda.current_device()))
         return MotherBlock(rt, model_config, tuple(int(v) for v in input_shape[-3:]), prefix, B)
     return build
+
+
+def _transformer_factory(model_config: dict, stage: bool):
+    check_transformer_config(model_config, stage)
+
+    def build(input_shape, rt=None, prefix="tf"):
+        """input_shape [B, S, D] or [B, S, F, C] (layers.force_1d_inputs: D = F * C)"""
+        sh = [int(v) for v in input_shape]
+        if len(sh) not in (3, 4):
+            raise ValueError("transformer_encoder_block: input [B, S, D] or [B, S, F, C]")
+        B, S, D = sh[0], sh[1], int(np.prod(sh[2:]))
+        rt = rt or _Rt(torch.device("cuda", torch.cuda.current_device()))
+        return TransformerEncoderStage(rt, model_config, S, D, prefix, B, depth=None if stage else 1)
+    return build
+
+
+def transformer_encoder_block(model_config: dict):
+    """reference modules.transformer_encoder_block(model_config) (modules.py:379-407) -> a factory `(input_shape) -> a one-block
+    TransformerEncoderStage` (forward(x, B, training) / backward(dy, B) on [B*S, D]); configuration errors are raised here, without a device."""
+    return _transformer_factory(model_config, False)
+
+
+def transformer_encoder_stage(model_config: dict):
+    """reference modules.transformer_encoder_stage(model_config) (modules.py:106-126): `depth` blocks"""
+    return _transformer_factory(model_config, True)
