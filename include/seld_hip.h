@@ -488,7 +488,8 @@ int seld_m_adam(float* theta, const float* g, float* m, float* v, int64_t n, flo
  *                   runs are bit-identical.  scratch: seld_attn_bwd_scratch(B, S, H, d) floats (B*H*S: linear in the rows).
  *   d (the reference's key_dim) must be a multiple of 8 in 8 .. 64: anything else returns SELD_ERR_UNSUPPORTED (the scratch size -1) before
  *   any other check, as units != 128 does in seld_m_gru_*.  Then SELD_ERR_INVALID, before anything is enqueued, for a NULL pointer (all but
- *   lse of seld_attn_fwd), B, S or H < 1, or a row stride < H*d. */
+ *   lse of seld_attn_fwd), B, S or H < 1, or a row stride < H*d (the product in 64 bits: an H*d beyond INT_MAX is covered by no stride).  Then
+ *   SELD_ERR_UNSUPPORTED (the scratch size -1) for a grid B * H * ceil(S / 64) beyond INT_MAX. */
 int seld_attn_fwd(const float* Q, const float* K, const float* V, int ldq, int ldk, int ldv, float* O, float* lse, int B, int S, int H, int d,
                   float scale, void* stream);
 int64_t seld_attn_bwd_scratch(int B, int S, int H, int d);

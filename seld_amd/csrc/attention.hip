@@ -311,6 +311,13 @@ inline int ln_blocks(int64_t rows) { const int64_t b = (rows + 15) / 16; return 
 
 inline int ok() { return hipGetLastError() == hipSuccess ? SELD_OK : SELD_ERR_HIP; }
 inline bool d_ok(int d) { return d >= 8 && d <= 64 && d % 8 == 0; }
+// a row stride covers the H * d columns of all heads; the product in 64 bits: H * d past INT_MAX fits no int stride (and the kernels' H * D stays an int)
+inline bool ld_ok(int ld, int H, int d) { return (int64_t)ld >= (int64_t)H * d; }
+// workgroups B * H * ceil(S / 64), or -1 where they do not fit a launch; every product in 64 bits and bounded before the next factor
+inline int64_t at_grid(int B, int S, int H) {
+    const int64_t bh = (int64_t)B * H, nt = ((int64_t)S + AT_TILE - 1) / AT_TILE;
+    return bh > 0x7fffffff || bh * nt > 0x7fffffff ? -1 : bh * nt;
+}
 
 // launch `kern`<d> for d = 8, 16, ..., 64
 #define AT_DISPATCH(kern, d, grid, st, ...)                                                                          \
@@ -332,27 +339,31 @@ extern "C" {
 int seld_attn_fwd(const float* Q, const float* K, const float* V, int ldq, int ldk, int ldv, float* O, float* lse, int B, int S, int H, int d,
                   float scale, void* stream) {
     if (!d_ok(d)) return SELD_ERR_UNSUPPORTED;
-    if (!Q || !K || !V || !O || B < 1 || S < 1 || H < 1 || ldq < H * d || ldk < H * d || ldv < H * d) return SELD_ERR_INVALID;
-    const int nt = (S + AT_TILE - 1) / AT_TILE;
-    const int64_t grid = (int64_t)B * H * nt;
-    if (grid > 0x7fffffff) return SELD_ERR_UNSUPPORTED;
+    if (!Q || !K || !V || !O || B < 1 || S < 1 || H < 1 || !ld_ok(ldq, H, d) || !ld_ok(ldk, H, d) || !ld_ok(ldv, H, d))
+        return SELD_ERR_INVALID;
+    const int64_t grid = at_grid(B, S, H);
+    if (grid < 0) return SELD_ERR_UNSUPPORTED;
+    const int nt = (int)(grid / B / H);
     AT_DISPATCH(attn_fwd_kernel, d, (unsigned)grid, (hipStream_t)stream, Q, K, V, ldq, ldk, ldv, O, lse, S, H, scale, nt);
     return ok();
 }
 
 /* floats of caller scratch seld_attn_bwd takes: delta[b][h][q] = rowsum(dO * O) */
-int64_t seld_attn_bwd_scratch(int B, int S, int H, int d) { return d_ok(d) && B > 0 && S > 0 && H > 0 ? (int64_t)B * H * S : -1; }
+int64_t seld_attn_bwd_scratch(int B, int S, int H, int d) {
+    if (!d_ok(d) || B < 1 || S < 1 || H < 1 || (int64_t)H * d > 0x7fffffff || at_grid(B, S, H) < 0) return -1;      // what seld_attn_bwd refuses
+    return (int64_t)B * H * S;      // B * H fits an int here: no overflow
+}
 
 int seld_attn_bwd(const float* Q, const float* K, const float* V, int ldq, int ldk, int ldv, const float* O, const float* dO, const float* lse,
                   float* dQ, float* dK, float* dV, int lddq, int lddk, int lddv, float* scratch, int B, int S, int H, int d, float scale,
                   void* stream) {
     if (!d_ok(d)) return SELD_ERR_UNSUPPORTED;
-    if (!Q || !K || !V || !O || !dO || !lse || !dQ || !dK || !dV || !scratch || B < 1 || S < 1 || H < 1 || ldq < H * d || ldk < H * d ||
-        ldv < H * d || lddq < H * d || lddk < H * d || lddv < H * d)
+    if (!Q || !K || !V || !O || !dO || !lse || !dQ || !dK || !dV || !scratch || B < 1 || S < 1 || H < 1 || !ld_ok(ldq, H, d) || !ld_ok(ldk, H, d) ||
+        !ld_ok(ldv, H, d) || !ld_ok(lddq, H, d) || !ld_ok(lddk, H, d) || !ld_ok(lddv, H, d))
         return SELD_ERR_INVALID;
-    const int nt = (S + AT_TILE - 1) / AT_TILE;
-    const int64_t grid = (int64_t)B * H * nt;
-    if (grid > 0x7fffffff) return SELD_ERR_UNSUPPORTED;
+    const int64_t grid = at_grid(B, S, H);
+    if (grid < 0) return SELD_ERR_UNSUPPORTED;
+    const int nt = (int)(grid / B / H);
     AT_DISPATCH(attn_bwd_dq_kernel, d, (unsigned)grid, (hipStream_t)stream, Q, K, V, ldq, ldk, ldv, O, dO, lse, dQ, lddq, scratch, S, H, scale, nt);
     AT_DISPATCH(attn_bwd_dkv_kernel, d, (unsigned)grid, (hipStream_t)stream, Q, K, V, ldq, ldk, ldv, dO, lse, scratch, dK, dV, lddk, lddv, S, H, scale,
                 nt);

@@ -9,6 +9,7 @@ import pytest
 import torch
 
 import transformer_oracle as T
+from helpers import rel_err
 from seld_amd import _lib
 
 INVALID, UNSUPPORTED, HIP = -1, -2, -3
@@ -100,6 +101,106 @@ def test_block_parameter_count_is_the_closed_form(D, H, dk, ffm, k):
     assert gd["tf0.mha.key.bias"].abs().max() <= 1e-12 * gw.abs().max() and gd["tf0.mha.query.bias"].abs().max() > 1e-6 * gw.abs().max()
 
 
+# ---------------------------------------------------------------- the stress inputs of tests/test_attention_gpu.py: what plain fp32 gives on them
+FP32_CAP = 5e-5      # half the parity bar: a device miss of 1e-4 on these inputs is then the kernel's error, not the format's
+
+
+def _attention_all(q, k, v, do, scale, dtype):
+    tq, tk, tv = (torch.tensor(a, dtype=dtype, requires_grad=True) for a in (q, k, v))
+    o, lse = T.attention(tq, tk, tv, scale)
+    g = torch.autograd.grad((o * torch.tensor(do, dtype=dtype)).sum(), (tq, tk, tv))
+    return [t.detach().double().numpy() for t in (o, lse) + g]
+
+
+@pytest.mark.parametrize("kind,span,B,S,H,d", T.STRESS_CASES, ids=lambda v: str(v))
+def test_stress_inputs_are_within_reach_of_fp32(kind, span, B, S, H, d):
+    """every generator and shape the device runs: torch's fp32 on the CPU, forward and autograd backward, is within 5e-5 of the fp64 oracle
+    under the project's metric; the inputs do what their names say; no gradient vanishes"""
+    q, k, v, do, scale = T.stress_qkv(kind, span, B, S, H, d)
+    for a in (q, k, v, do):
+        assert a.dtype == np.float64 and np.array_equal(a, a.astype(np.float32).astype(np.float64))
+    q2, k2, _, _, _ = T.stress_qkv(kind, span, B, S, H, d)
+    assert np.array_equal(q, q2) and np.array_equal(k, k2)      # deterministic
+    ref = _attention_all(q, k, v, do, scale, torch.float64)
+    got = _attention_all(q, k, v, do, scale, torch.float32)
+    for name, g, r in zip(("O", "lse", "dQ", "dK", "dV"), got, ref):
+        e = rel_err(g, r)
+        print(f"[fp32 cpu] {kind} span={span} d={d} {name}: {e:.3e} (|ref|max={np.abs(r).max():.3e})")
+        assert e <= FP32_CAP, (name, e)
+    assert min(np.abs(r).max() for r in ref[2:]) > 1e-2
+    logits = np.einsum("bnhd,bmhd->bhnm", q, k) * scale
+    pmax = np.exp(logits - ref[1][..., None]).max(-1)
+    if kind == "gain":
+        assert np.abs(logits).max() > 30 and pmax.mean() > 0.5
+    else:
+        first, last = logits[..., 0].mean(), logits[..., -1].mean()
+        assert abs(abs(last - first) - span) < 1.0 and (last > first) == (kind == "ramp_up")
+        if span >= 100 and kind != "shifted":
+            assert logits.max() > 89      # past the range of fp32 exp: a softmax without the maximum subtraction overflows
+        if kind == "shifted":
+            assert logits.max() < -90      # ... and here it sums zeros
+
+
+def _wave_sum(a):
+    """[rows, 64] float32 -> [rows]: the xor-shuffle tree of a 64-lane wave, in fp32"""
+    n = 64
+    while n > 1:
+        n //= 2
+        a = a[:, :n] + a[:, n:2 * n]
+    return a[:, 0]
+
+
+def _lane_sums(a):
+    """[rows, C] float32 -> [rows, 64]: lane l adds columns l, l + 64, ... in order, in fp32"""
+    rows, Cc = a.shape
+    pad = np.zeros((rows, -(-Cc // 64) * 64), np.float32)
+    pad[:, :Cc] = a
+    acc = np.zeros((rows, 64), np.float32)
+    for j in range(pad.shape[1] // 64):
+        acc = acc + pad[:, 64 * j:64 * j + 64]
+    return acc
+
+
+def _layer_norm_fp32(x, r, gamma, beta, one_pass):
+    """LayerNorm of x + r in fp32 arithmetic throughout, one wave per row (lane-strided sums, then a tree): mean, then either the centred
+    second moment (two passes) or E[z^2] - mean^2 (one pass)"""
+    f = np.float32
+    z = x.astype(f) + r.astype(f)
+    Cc = f(z.shape[1])
+    mean = _wave_sum(_lane_sums(z)) / Cc
+    if one_pass:
+        var = _wave_sum(_lane_sums(z * z)) / Cc - mean * mean
+    else:
+        t = z - mean[:, None]
+        var = _wave_sum(_lane_sums(t * t)) / Cc
+    rstd = f(1) / np.sqrt(var + f(T.LN_EPS))
+    xhat = (z - mean[:, None]) * rstd[:, None]
+    assert xhat.dtype == f
+    return xhat * gamma.astype(f) + beta.astype(f), xhat, rstd
+
+
+@pytest.mark.parametrize("mean,std,rows,Cc", T.LN_OFFSET_CASES)
+def test_offset_rows_tell_a_two_pass_variance_from_a_one_pass_one(mean, std, rows, Cc):
+    """on transformer_oracle.offset_rows a two-pass fp32 LayerNorm is within 5e-5 of the fp64 oracle and a one-pass fp32 variance misses the
+    1e-4 bar: the device test on the same arrays has teeth"""
+    x, r, dy, gamma, beta = T.offset_rows(mean, std, rows, Cc)
+    for a in (x, r, dy, gamma, beta):
+        assert np.array_equal(a, a.astype(np.float32).astype(np.float64))
+    z = torch.tensor(x + r)
+    assert float(z[1].std()) == 0.0 and float(z[2].std()) == 0.0 and float(torch.tensor(x)[1].std()) > 0.1
+    assert np.array_equal((x.astype(np.float32) + r.astype(np.float32))[1:3], np.full((2, Cc), mean, np.float32))
+    assert np.abs(np.log10(np.abs(gamma))).max() > 1.2 and beta.mean() > 49
+    y_ref = T.layer_norm(z, torch.tensor(gamma), torch.tensor(beta)).numpy()
+    zc = (z - z.mean(-1, keepdim=True)).numpy()
+    rstd_ref = 1.0 / np.sqrt((zc ** 2).mean(-1) + T.LN_EPS)
+    xhat_ref = zc * rstd_ref[:, None]
+    two = [rel_err(g, f) for g, f in zip(_layer_norm_fp32(x, r, gamma, beta, False), (y_ref, xhat_ref, rstd_ref))]
+    one = [rel_err(g, f) for g, f in zip(_layer_norm_fp32(x, r, gamma, beta, True), (y_ref, xhat_ref, rstd_ref))]
+    print(f"[fp32 cpu] LayerNorm mean={mean} C={Cc}: two-pass y / xhat / rstd {two}, one-pass {one}")
+    assert max(two) <= FP32_CAP
+    assert min(one[:2]) > 1e-4      # y and xhat; rstd is measured against the constant rows' 1 / sqrt(eps) = 31.6, which hides the other rows' error
+
+
 # ---------------------------------------------------------------- refusals
 @pytest.mark.parametrize("op", sorted(OPS))
 def test_base_call_is_valid(env, op):
@@ -126,6 +227,31 @@ def test_head_width_is_checked_first(env, op):
             == (0 if env[2] else HIP)
     if env[2]:
         torch.cuda.synchronize()
+
+
+def _strides(op, ld):
+    return {n: ld for n, kind, _ in OPS[op] if kind == "l"}
+
+
+@pytest.mark.parametrize("op", ["seld_attn_fwd", "seld_attn_bwd"])
+def test_refuses_heads_times_width_beyond_int(env, op):
+    """H * d is formed in 64 bits: where it passes INT_MAX no int stride covers a row, whatever the 32-bit product wraps to (2^28 * 8 wraps
+    to INT_MIN, 2^29 * 8 to 0, 2^28 * 24 to a positive value).  The pointers are never dereferenced: the refusal comes first."""
+    for H, d in ((1 << 28, 8), (1 << 29, 8), (1 << 28, 24), (0x7fffffff, 64), (1 << 26, 32)):
+        for ld in (16, 0x7fffffff):
+            assert _call(env, op, H=H, d=d, **_strides(op, ld)) == INVALID, (H, d, ld)
+    assert env[0].seld_attn_bwd_scratch(1, 3, 1 << 28, 8) == -1
+
+
+@pytest.mark.parametrize("op", ["seld_attn_fwd", "seld_attn_bwd"])
+def test_refuses_a_grid_beyond_int(env, op):
+    """B * H * ceil(S / 64) workgroups beyond INT_MAX: UNSUPPORTED, also where a narrower product would wrap back into range (2^16 * 2^16 * 1 =
+    2^32 -> 0; S = INT_MAX, whose S + 63 does not fit an int)"""
+    for B, S, H in ((1 << 20, 8192, 32), (1 << 16, 3, 1 << 16), (64, 0x7fffffff, 1), (0x7fffffff, 0x7fffffff, 1 << 20), (1 << 24, 64 * 128 + 1, 1)):
+        assert _call(env, op, B=B, S=S, H=H, d=8, **_strides(op, 8 * H)) == UNSUPPORTED, (B, S, H)
+        assert env[0].seld_attn_bwd_scratch(B, S, H, 8) == -1
+    # the largest grid that fits is not refused here: the scratch size says so without a launch
+    assert env[0].seld_attn_bwd_scratch(1 << 20, 64 * 2047, 1, 8) == (1 << 20) * 64 * 2047
 
 
 def test_optional_pointers_may_be_null(env):

@@ -169,3 +169,65 @@ def train_step(model_config: dict, input_shape, flat_w, flat_state, x, y_sed, y_
     ns = torch.cat([new_st[n].detach().reshape(-1) for n, _ in nt]) if nt else torch.zeros(0, dtype=dtype)
     return {"sed": sed.detach().numpy(), "doa": doa.detach().numpy(), "sloss": sloss.detach().numpy(), "dloss": dloss.detach().numpy(),
             "grad": g.numpy(), "new_w": new_w.numpy(), "new_state": ns.numpy()}
+
+
+# ---- deterministic stress inputs for the attention and LayerNorm operators (tests/test_attention_cpu.py holds the condition a plain fp32
+# evaluation meets on each of them, tests/test_attention_gpu.py runs the device on the same arrays)
+def f32(a) -> np.ndarray:
+    """the fp32-rounded values as float64: what the device receives, so that input rounding is not charged to the kernel"""
+    return np.asarray(a, np.float64).astype(np.float32).astype(np.float64)
+
+
+# (kind, span, B, S, H, d): S of three tiles or more, one narrow and one wide head
+STRESS_CASES = [("gain", 0, 2, 130, 3, 16), ("gain", 0, 2, 130, 2, 64)] + [
+    (kind, span, 2, 200, 2, d) for d in (16, 64) for kind, span in (("ramp_up", 60), ("ramp_down", 60), ("ramp_up", 100), ("ramp_down", 100),
+                                                                    ("shifted", 60))]
+
+
+def stress_qkv(kind: str, span: float, B: int, S: int, H: int, d: int):
+    """-> (q, k, v, do [B, S, H, d] float64 holding fp32 values, scale = 1 / sqrt(d)).
+      gain       q and k unit-normal times 3: logits of tens, most rows one dominant key
+      ramp_up    component 0 of every query is 2 and component 0 of key j adds span * j / (S - 1) to its logit: the running maximum rises
+                 from key block to key block
+      ramp_down  ... adds span * (1 - j / (S - 1)): the late tiles underflow against the first
+      shifted    ramp_down with every key's component 0 lowered until every logit of every row is below -90: a softmax without the
+                 maximum subtraction sums zeros"""
+    rng = np.random.default_rng([S, H, d, int(span), len(kind)])
+    q, k, v, do = (rng.standard_normal((B, S, H, d)) for _ in range(4))
+    scale = 1.0 / math.sqrt(d)
+    if kind == "gain":
+        q, k = 3.0 * q, 3.0 * k
+    elif kind in ("ramp_up", "ramp_down", "shifted"):
+        j = np.arange(S, dtype=np.float64) / max(S - 1, 1)
+        ramp = span * (j if kind == "ramp_up" else 1.0 - j)
+        q[..., 0] = 2.0
+        k[..., 0] = (ramp / (2.0 * scale))[None, :, None]
+        if kind == "shifted":
+            top = float((np.einsum("bnhd,bmhd->bhnm", f32(q), f32(k)) * scale).max())
+            k[..., 0] -= (math.ceil(top) + 95.0) / (2.0 * scale)
+    else:
+        raise ValueError(kind)
+    return f32(q), f32(k), f32(v), f32(do), scale
+
+
+# (mean, std, rows, C)
+LN_OFFSET_CASES = [(10.0, 0.1, 40, 128), (10.0, 0.1, 40, 257), (100.0, 1.0, 40, 128), (100.0, 1.0, 12, 4378)]
+
+
+def offset_rows(mean: float, std: float, rows: int, C: int):
+    """-> (x, r, dy [rows, C], gamma, beta [C]) float64 holding fp32 values.  x + r has the given mean and standard deviation per row —
+    where a one-pass E[z^2] - mean^2 in fp32 loses the variance — gamma spans three decades and beta sits at 50.  Row 1 of x + r is exactly
+    constant although neither x nor r is (r = mean - x there, in fp32 values whose sum is exact), and row 2 of x is constant with r = 0."""
+    rng = np.random.default_rng([rows, C, int(mean)])
+    z = mean + std * rng.standard_normal((rows, C))
+    r = 0.25 * mean + 0.5 * std * rng.standard_normal((rows, C))
+    x = f32(z - f32(r))
+    r = f32(r)
+    if rows > 2:
+        x[1] = np.round(rng.uniform(1, 3, C) * 64) / 64          # multiples of 1 / 64: x + r = mean exactly, in fp32 as well
+        r[1] = mean - x[1]
+        x[2], r[2] = mean, 0.0
+    dy = rng.standard_normal((rows, C))
+    gamma = 10.0 ** rng.uniform(-1.5, 1.5, C) * np.where(rng.random(C) < 0.5, -1.0, 1.0)
+    beta = 50.0 + rng.standard_normal(C)
+    return x, r, f32(dy), f32(gamma), f32(beta)
