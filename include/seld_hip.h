@@ -476,7 +476,7 @@ int seld_m_losses(const float* sed, const float* doa, const float* y_sed, const 
 int seld_m_adam(float* theta, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps, int64_t step, void* stream);
 /* ---- attention operators (attention.hip): the shared core of the reference's attention blocks — modules.transformer_encoder_block / _stage
  * (modules.py:106-126, 379-407), and of conformer_encoder_block / attention_block (modules.py:410-635, layers.py:268-287).  fp32 device
- * tensors, asynchronous on `stream`, no allocation.  Not seld_m_*: seld_amd/modules.py composes the transformer block from these and seld_m_*.
+ * tensors, asynchronous on `stream`, no allocation.  Not seld_m_*: seld_amd/modules.py composes the transformer and conformer blocks from these and seld_m_*.
  *   seld_attn_fwd   tf.keras.layers.MultiHeadAttention's core (modules.py:392-393; the reference's own MultiHeadAttention, layers.py:268-287):
  *                   O[b,n,h,:] = sum_m softmax_m(scale Q[b,n,h,:] . K[b,m,h,:]) V[b,m,h,:].  Q, K, V: [B*S, H*d] row-major views with row strides
  *                   ldq / ldk / ldv floats (>= H*d: column slices of one fused [B*S, 3*H*d] projection need no copy), head h = columns h*d ..
@@ -508,6 +508,30 @@ int seld_ln_fwd(const float* x, const float* r, const float* gamma, const float*
 int64_t seld_ln_scratch(int64_t rows, int C);
 int seld_ln_bwd(const float* dy, const float* xhat, const float* rstd, const float* gamma, float* dz, float* dgamma, float* dbeta, float* scratch,
                 int64_t rows, int C, void* stream);
+/* ---- conformer operators (conformer.hip): what modules.conformer_encoder_block (modules.py:410-508) needs beyond seld_attn_* / seld_ln_* /
+ * seld_m_*.  fp32 device tensors, asynchronous on `stream`, no allocation.
+ *   seld_dwconv1d_fwd   the convolution module's GLU and depthwise Conv1D(groups = C, kernel_size k, strides 1, 'same') in one kernel
+ *                       (modules.py:476-486): u [B*S, 2C] (glu = 1) or [B*S, C] (glu = 0: attention_block's form, modules.py:603-611) with row
+ *                       stride ldu; g[b,s,c] = u[b,s,c] sigmoid(u[b,s,C+c]) (glu = 1) or u[b,s,c]; y[b,s,c] = bias[c] + sum_t w[t,c]
+ *                       g[b, s - pl + t, c], pl = (k - 1) / 2, zero outside [0, S) (TensorFlow 'same': an even k pads one frame more behind);
+ *                       w [k, C] = Keras' depthwise kernel [k, 1, C]; y [B*S, C] contiguous.  g is formed in the loader and never stored; a
+ *                       128-frame tile and its halo are staged once per workgroup in LDS, the channel is the lane.
+ *   seld_dwconv1d_bwd   du (row stride lddu; glu = 1: dg sigmoid(b) in the first half, dg a sigmoid(b) (1 - sigmoid(b)) in the second),
+ *                       dw [k, C], dbias [C] from u, w and dy [B*S, C].  dw / dbias: two stages through scratch
+ *                       (seld_dwconv1d_bwd_scratch(B, S, C, k) floats, bounded in the rows), no atomics: two runs are bit-identical.
+ *   1 <= k <= 64; any B, S (k > S included), C >= 1.  SELD_ERR_INVALID, before anything is enqueued, for a NULL pointer, a size < 1, k > 64,
+ *   glu not 0 / 1, or a row stride below (glu + 1) * C (the product in 64 bits); SELD_ERR_UNSUPPORTED for a grid ceil(C / 64) * ceil(S / 128) * B
+ *   beyond INT_MAX.  The scratch query returns -1 for either.
+ *   seld_pos_add        x[b, s, :] += enc[s, :] on x [B, S, D]: the positional table of layers.basic_pos_encoding (layers.py:53-67), a host-built
+ *                       constant, added in one launch (modules.py:450).
+ *   seld_head_permute   mode 0: dst [D, H, dk] = src [H, D, dk] (the head-major kernels of layers.MultiHeadAttention_, layers.py:148-168, as the
+ *                       [D, H dk] matrix seld_m_gemm takes); mode 1: the inverse (their gradients back). */
+int seld_dwconv1d_fwd(const float* u, int ldu, const float* w, const float* bias, float* y, int B, int S, int C, int k, int glu, void* stream);
+int64_t seld_dwconv1d_bwd_scratch(int B, int S, int C, int k);
+int seld_dwconv1d_bwd(const float* u, int ldu, const float* w, const float* dy, float* du, int lddu, float* dw, float* dbias, float* scratch, int B,
+                      int S, int C, int k, int glu, void* stream);
+int seld_pos_add(float* x, const float* enc, int B, int S, int D, void* stream);
+int seld_head_permute(const float* src, float* dst, int H, int D, int dk, int mode, void* stream);
 /* Measurement aid (bench.py, SURVEY.md §8(d) "state the step-latency floor"): the shader clock the card holds while `blocks`
  * workgroups of 512 threads run a VALU-only loop (the load shape of the GRU recurrence: 2B workgroups, no MFMA), from
  * s_memtime / s_memrealtime (100 MHz) inside the kernel.  No reference counterpart. */

@@ -178,6 +178,11 @@ SIGNATURES = {
     "seld_ln_fwd": (_I, [_P, _P, _P, _P, _F, _P, _P, _P, _L, _I, _P]),
     "seld_ln_scratch": (_L, [_L, _I]),
     "seld_ln_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _P]),
+    "seld_dwconv1d_fwd": (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "seld_dwconv1d_bwd_scratch": (_L, [_I, _I, _I, _I]),
+    "seld_dwconv1d_bwd": (_I, [_P, _I, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "seld_pos_add": (_I, [_P, _P, _I, _I, _I, _P]),
+    "seld_head_permute": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "seld_k_rn_conv": (_I, [_P, _P, _P] + [_I] * 7),
     "seld_k_rn_conv_stats": (_I, [_P, _P, _P] + [_I] * 7 + [_P]),
     "seld_k_rn_conv_bwd": (_I, [_P, _P, _P, _P, _P] + [_I] * 7),

@@ -11,9 +11,12 @@ else).  There is no CPU or PyTorch fallback.
   bidirectional_GRU_block (modules.py:302-319), simple_dense_block (modules.py:350-376; Conv1D kernel_size 1): at ANY feature width
   transformer_encoder_block / _stage (modules.py:106-126, 379-407)   MultiHeadAttention(n_head, key_dim)(x, x) + LayerNormalization + two
                                                   Conv1D('same') + LayerNormalization, from seld_attn_* / seld_ln_* (attention.hip) and seld_m_*
+  conformer_encoder_block / _stage (modules.py:129-152, 410-508)     half-step FFN, positional table, layers.MultiHeadAttention_, the convolution
+                                                  module (pointwise Conv1D, GLU + depthwise Conv1D: seld_dwconv1d_* of conformer.hip,
+                                                  BatchNormalization, swish, pointwise Conv1D), half-step FFN, LayerNormalization
 
 `ComposedSeldNet` = models.seldnet(input_shape, model_config) for FIRST in {mother_block, mother_stage}, SECOND in {bidirectional_GRU_block,
-transformer_encoder_block, transformer_encoder_stage}: same surface as
+transformer_encoder_block, transformer_encoder_stage, conformer_encoder_block, conformer_encoder_stage}: same surface as
 seld_amd.models.SeldNet (variables in Keras creation order, get / set_weights, __call__, train.trainstep / teststep).  The three
 BASELINE configurations do NOT run through here — their blocks are fused kernels inside a seld_ctx (models.SeldNet)."""
 from __future__ import annotations
@@ -447,6 +450,273 @@ class TransformerEncoderStage:
         return dy
 
 
+class Dense:
+    """tf.keras.layers.Dense(units) on the last axis of [rows, Cin]: one MFMA GEMM; kernel [Cin, units]."""
+
+    def __init__(self, rt: _Rt, name: str, rows: int, Cin: int, units: int):
+        self.rt, self.name, self.Cin, self.N = rt, name, int(Cin), int(units)
+        rt.var(f"{name}.kernel", (self.Cin, self.N))
+        rt.var(f"{name}.bias", (self.N,))
+        self.z = rt.empty(rows, self.N)
+
+    def forward(self, x, rows):
+        rt = self.rt
+        self.a = x
+        rt.gemm(x, rt.w(f"{self.name}.kernel"), rt.w(f"{self.name}.bias"), self.z, rows, self.N, self.Cin)
+        return self.z[:rows]
+
+    def backward(self, dz, dx, rows):
+        rt = self.rt
+        rt.gemm_tn(self.a, dz, rt.g(f"{self.name}.kernel"), rt.g(f"{self.name}.bias"), rows, self.Cin, self.N)
+        rt.gemm(dz, rt.w(f"{self.name}.kernel"), None, dx, rows, self.Cin, self.N, transb=1)
+
+
+class MultiHeadAttentionRef:
+    """The reference's own layers.MultiHeadAttention_(n_head, key_dim, use_bias)([x, x, x]) (layers.py:102-287; not Keras' layer) on [B, S, D]:
+    head-major kernels query_kernel / key_kernel / value_kernel [H, D, dk] and projection_kernel [H, dk, D], then (use_bias) projection_bias [D]
+    and q_bias / k_bias / v_bias [H, dk] — created in that order.  The variables keep the reference's layout; seld_head_permute packs a kernel to
+    the [D, H dk] matrix of a GEMM in front of each forward and unpacks its gradient behind each backward.  The query's division by sqrt(dk)
+    (layers.py:275-276, after the bias) is seld_attn_fwd's `scale`."""
+
+    def __init__(self, rt: _Rt, name: str, B: int, S: int, D: int, n_head: int, key_dim: int, use_bias: bool = True):
+        self.rt, self.name, self.S, self.D, self.H, self.dk, self.use_bias = rt, name, int(S), int(D), int(n_head), int(key_dim), bool(use_bias)
+        H, dk = self.H, self.dk
+        for part in ("query", "key", "value"):
+            rt.var(f"{name}.{part}_kernel", (H, self.D, dk))
+        rt.var(f"{name}.projection_kernel", (H, dk, self.D))
+        if self.use_bias:
+            rt.var(f"{name}.projection_bias", (self.D,))
+            for part in "qkv":
+                rt.var(f"{name}.{part}_bias", (H, dk))
+        if int(rt.lib.seld_attn_bwd_scratch(B, self.S, H, dk)) < 0:
+            raise ValueError(f"key_dim {key_dim!r}: the attention kernels take a multiple of 8 from 8 to 64")
+        R, HD = B * self.S, H * dk
+        self.q, self.k, self.v, self.o, self.do = (rt.empty(R, HD) for _ in range(5))
+        self.dq, self.dk_, self.dv = (rt.empty(R, HD) for _ in range(3))
+        self.packed = [rt.empty(self.D, HD) for _ in range(3)]
+        self.dpacked = rt.empty(self.D, HD)
+        self.lse = rt.empty(B * H * self.S)
+        self.scratch = rt.empty(int(rt.lib.seld_attn_bwd_scratch(B, self.S, H, dk)))
+        self.out = rt.empty(R, self.D)
+        self.scale = 1.0 / math.sqrt(float(dk))
+
+    def _bias(self, part, grad=False):
+        if not self.use_bias:
+            return None
+        return (self.rt.g if grad else self.rt.w)(f"{self.name}.{part}")
+
+    def forward(self, x, B, training):
+        rt, n = self.rt, self.name
+        R, HD = B * self.S, self.H * self.dk
+        self.x = x
+        for part, wp, buf in zip(("query", "key", "value"), self.packed, (self.q, self.k, self.v)):
+            rt.ck(rt.lib.seld_head_permute(rt.p(rt.w(f"{n}.{part}_kernel")), rt.p(wp), self.H, self.D, self.dk, 0, rt.st()))
+            rt.gemm(x, wp, self._bias(part[0] + "_bias"), buf, R, HD, self.D)
+        rt.ck(rt.lib.seld_attn_fwd(rt.p(self.q), rt.p(self.k), rt.p(self.v), HD, HD, HD, rt.p(self.o), rt.p(self.lse) if training else None, B, self.S,
+                                   self.H, self.dk, self.scale, rt.st()))
+        rt.gemm(self.o, rt.w(f"{n}.projection_kernel"), self._bias("projection_bias"), self.out, R, self.D, HD)
+        return self.out[:R]
+
+    def backward(self, dout, dx, B):
+        """dout [R, D] -> every variable's gradient; dx = the input's gradient (overwritten)"""
+        rt, n = self.rt, self.name
+        R, HD = B * self.S, self.H * self.dk
+        rt.gemm_tn(self.o, dout, rt.g(f"{n}.projection_kernel"), self._bias("projection_bias", True), R, HD, self.D)
+        rt.gemm(dout, rt.w(f"{n}.projection_kernel"), None, self.do, R, HD, self.D, transb=1)
+        rt.ck(rt.lib.seld_attn_bwd(rt.p(self.q), rt.p(self.k), rt.p(self.v), HD, HD, HD, rt.p(self.o), rt.p(self.do), rt.p(self.lse), rt.p(self.dq),
+                                   rt.p(self.dk_), rt.p(self.dv), HD, HD, HD, rt.p(self.scratch), B, self.S, self.H, self.dk, self.scale, rt.st()))
+        for i, (part, wp, g) in enumerate(zip(("query", "key", "value"), self.packed, (self.dq, self.dk_, self.dv))):
+            rt.gemm_tn(self.x, g, self.dpacked, self._bias(part[0] + "_bias", True), R, self.D, HD)
+            rt.ck(rt.lib.seld_head_permute(rt.p(self.dpacked), rt.p(rt.g(f"{n}.{part}_kernel")), self.H, self.D, self.dk, 1, rt.st()))
+            rt.gemm(g, wp, None, dx, R, self.D, HD, transb=1, accumulate=int(i > 0))
+
+
+class DepthwiseConv1D:
+    """[GLU +] tf.keras.layers.Conv1D(filters=C, kernel_size=k, strides=1, padding='same', groups=C) over the frames of [B, S, C]
+    (modules.py:476-486): seld_dwconv1d_fwd / _bwd.  glu: the input is [B*S, 2C] and a * sigmoid(b) is formed inside the kernel.
+    Keras' kernel [k, 1, C] and bias [C]."""
+
+    def __init__(self, rt: _Rt, name: str, B: int, S: int, C_: int, k: int, glu: bool = True):
+        self.rt, self.name, self.S, self.C, self.k, self.glu = rt, name, int(S), int(C_), int(k), int(bool(glu))
+        rt.var(f"{name}.kernel", (self.k, 1, self.C))
+        rt.var(f"{name}.bias", (self.C,))
+        need = int(rt.lib.seld_dwconv1d_bwd_scratch(B, self.S, self.C, self.k))
+        if need < 0:
+            raise ValueError(f"depthwise Conv1D: kernel_size {k!r} (1 .. 64), B {B}, S {S}, C {C_} are refused by the kernels")
+        self.scratch = rt.empty(need)
+        self.y = rt.empty(B * self.S, self.C)
+
+    def forward(self, u, B):
+        rt, n = self.rt, self.name
+        self.u = u
+        rt.ck(rt.lib.seld_dwconv1d_fwd(rt.p(u), (1 + self.glu) * self.C, rt.p(rt.w(f"{n}.kernel")), rt.p(rt.w(f"{n}.bias")), rt.p(self.y), B, self.S,
+                                       self.C, self.k, self.glu, rt.st()))
+        return self.y[:B * self.S]
+
+    def backward(self, dy, du, B):
+        rt, n = self.rt, self.name
+        ld = (1 + self.glu) * self.C
+        rt.ck(rt.lib.seld_dwconv1d_bwd(rt.p(self.u), ld, rt.p(rt.w(f"{n}.kernel")), rt.p(dy), rt.p(du), ld, rt.p(rt.g(f"{n}.kernel")),
+                                       rt.p(rt.g(f"{n}.bias")), rt.p(self.scratch), B, self.S, self.C, self.k, self.glu, rt.st()))
+
+
+def basic_pos_encoding(S: int, D: int) -> np.ndarray:
+    """layers.basic_pos_encoding (layers.py:53-67) as a [S, D] float32 table: column 2 i = cos(w_i t), column 2 i + 1 = sin(w_i t), w_i =
+    float32(10000 ** (-i / (D // 2))).  The product w t, cos and sin are taken in float64 and rounded once (TensorFlow forms w t in float32:
+    DESIGN.md section 3f)."""
+    k = int(D) // 2
+    w = np.power(10000.0, -np.arange(k, dtype=np.float64) / k).astype(np.float32).astype(np.float64)
+    arg = np.arange(int(S), dtype=np.float64)[:, None] * w[None, :]
+    return np.stack([np.cos(arg), np.sin(arg)], -1).reshape(int(S), 2 * k).astype(np.float32)
+
+
+def check_conformer_config(cfg: dict, stage: bool = False, D=None) -> None:
+    """what reference modules.py:410-430 reads (every key has a default there; `depth` is the stage's, modules.py:146); what has no kernel
+    here is refused, not ignored"""
+    who = f"conformer_encoder_{'stage' if stage else 'block'}"
+    if stage and "depth" not in cfg:
+        raise ValueError(f"{who}: missing 'depth'")
+    if cfg.get("activation", "swish") not in ACT:
+        raise ValueError(f"activation {cfg.get('activation')!r}: the module operators know {sorted(k for k in ACT if k)}")
+    if "dropout_rate" not in cfg or float(cfg["dropout_rate"]) != 0.0:
+        raise ValueError(f"{who}: there is no dropout kernel on this path and the reference's default dropout_rate is 0.1: "
+                         "dropout_rate must be present and 0")
+    if cfg.get("pos_mode", "absolute") != "absolute":
+        raise ValueError(f"{who}: pos_mode {cfg.get('pos_mode')!r}: RelPositionMultiHeadAttention has no kernel here, only 'absolute'")
+    pe = cfg.get("pos_encoding", "basic")
+    if pe == "rff":
+        raise ValueError(f"{who}: pos_encoding 'rff' draws its frequencies from tf.random.normal and stores them nowhere: it cannot be reproduced")
+    if pe not in ("basic", None):
+        raise ValueError(f"{who}: pos_encoding {pe!r}: 'basic' or None")
+    if pe == "basic" and D is not None and int(D) % 2:
+        raise ValueError(f"{who}: pos_encoding 'basic' on an odd width {D}: the reference's table has 2 * (D // 2) columns and does not broadcast")
+    reg = cfg.get("kernel_regularizer", None)
+    if reg is not None and (not isinstance(reg, dict) or set(reg) - {"l1", "l2"}):
+        raise ValueError(f"{who}: kernel_regularizer {reg!r}: a dict of l1 / l2 (it only feeds model.losses, which train.trainstep never adds)")
+    if int(cfg.get("n_head", 4)) < 1 or not 1 <= int(cfg.get("kernel_size", 32)) <= 64 or int(cfg.get("multiplier", 4)) < 1 or \
+            (stage and int(cfg["depth"]) < 1):
+        raise ValueError(f"{who}: n_head, multiplier, depth >= 1 and 1 <= kernel_size <= 64")
+    dk = int(cfg.get("key_dim", 36))
+    if dk < 8 or dk > 64 or dk % 8:
+        raise ValueError(f"key_dim {dk}: the attention kernels take a multiple of 8 from 8 to 64")
+
+
+class ConformerEncoderBlock:
+    """reference modules.conformer_encoder_block (modules.py:432-506) on [B, S, D], every Dropout at rate 0:
+      x  = x + ffn_factor Dense(D)(act(Dense(multiplier D)(LN(x))));  x = x + encoding (pos_encoding 'basic')
+      x  = x + MultiHeadAttention_(LN(x))
+      x' = x + Conv1D(D, 1)(swish(BN(depthwise Conv1D(k)(GLU(Conv1D(2 D, 1)(LN(x)))))))
+      out = LN(x + ffn_factor Dense(D)(act(Dense(multiplier D)(LN(x')))))       — the last residual adds to x, not x' (modules.py:495, 504)."""
+
+    def __init__(self, rt: _Rt, cfg: dict, S: int, D: int, prefix: str, B: int):
+        check_conformer_config(cfg, D=D)
+        self.rt, self.S, self.D, self.B = rt, int(S), int(D), B
+        S, D = self.S, self.D
+        self.F = int(cfg.get("multiplier", 4)) * D
+        self.act = ACT[cfg.get("activation", "swish")]
+        self.ff = float(cfg.get("ffn_factor", 0.5))
+        R = B * S
+        p = prefix
+        self.ln0 = LayerNorm(rt, f"{p}.ln0", R, D)
+        self.ffn0a, self.ffn0b = Dense(rt, f"{p}.ffn0a", R, D, self.F), Dense(rt, f"{p}.ffn0b", R, self.F, D)
+        self.ln1 = LayerNorm(rt, f"{p}.ln1", R, D)
+        self.mha = MultiHeadAttentionRef(rt, f"{p}.mha", B, S, D, int(cfg.get("n_head", 4)), int(cfg.get("key_dim", 36)), cfg.get("use_bias", True))
+        self.ln2 = LayerNorm(rt, f"{p}.ln2", R, D)
+        self.pw0 = Conv1D(rt, f"{p}.pw0", B, S, D, 2 * D, 1)
+        self.dw = DepthwiseConv1D(rt, f"{p}.dw", B, S, D, int(cfg.get("kernel_size", 32)), glu=True)
+        self.bn = BatchNorm(rt, f"{p}.bn", (S, 1, D), B)
+        self.pw1 = Conv1D(rt, f"{p}.pw1", B, S, D, D, 1)
+        self.ln3 = LayerNorm(rt, f"{p}.ln3", R, D)
+        self.ffn1a, self.ffn1b = Dense(rt, f"{p}.ffn1a", R, D, self.F), Dense(rt, f"{p}.ffn1b", R, self.F, D)
+        self.ln4 = LayerNorm(rt, f"{p}.ln4", R, D)
+        self.enc = None
+        if cfg.get("pos_encoding", "basic") == "basic":
+            self.enc = torch.as_tensor(basic_pos_encoding(S, D)).to(rt.dev)
+        e = rt.empty
+        self.h0, self.h1, self.dh, self.dpre = e(R, self.F), e(R, self.F), e(R, self.F), e(R, self.F)
+        self.x1, self.x2, self.x3, self.z = e(R, D), e(R, D), e(R, D), e(R, D)
+        self.bno, self.sw, self.dsw, self.dbn, self.ddw = e(R, D), e(R, D), e(R, D), e(R, D), e(R, D)
+        self.du = e(R, 2 * D)
+        self.dx2, self.dx1, self.dx0, self.df, self.dn = e(R, D), e(R, D), e(R, D), e(R, D), e(R, D)
+        self.out_shape = (S, D)
+
+    def _ffn(self, ln, a, b, h, x, rows, training):
+        """Dense(D)(act(Dense(F)(LN(x)))) -> [rows, D]"""
+        pre = a.forward(ln.forward(x, None, rows, training), rows)
+        self.rt.act(pre, h[:rows], self.act)
+        return b.forward(h[:rows], rows)
+
+    def _ffn_bwd(self, ln, a, b, df, rows):
+        """df: the gradient of the FFN's output -> the gradient of the input of its LayerNormalization"""
+        rt = self.rt
+        b.backward(df, self.dh[:rows], rows)
+        rt.act_bwd(a.z[:rows], self.dh[:rows], self.dpre[:rows], self.act)
+        a.backward(self.dpre[:rows], self.dn[:rows], rows)
+        return ln.backward(self.dn[:rows], rows)
+
+    def forward(self, x, B, training):
+        """x [B*S, D] (or any contiguous view of it) -> [B*S, D]"""
+        rt = self.rt
+        R, D = B * self.S, self.D
+        x = x.reshape(R, D)
+        x1, x2, x3, z = self.x1[:R], self.x2[:R], self.x3[:R], self.z[:R]
+        x1.copy_(x)
+        rt.axpy(x1, self._ffn(self.ln0, self.ffn0a, self.ffn0b, self.h0, x, R, training), self.ff)
+        if self.enc is not None:
+            rt.ck(rt.lib.seld_pos_add(rt.p(x1), rt.p(self.enc), B, self.S, D, rt.st()))
+        x2.copy_(x1)
+        rt.axpy(x2, self.mha.forward(self.ln1.forward(x1, None, R, training), B, training))
+        conv = self.dw.forward(self.pw0.forward(self.ln2.forward(x2, None, R, training), B), B)
+        self.bn.forward(conv, self.bno[:R], B, training, 0)
+        rt.act(self.bno[:R], self.sw[:R], ACT["swish"])
+        x3.copy_(x2)
+        rt.axpy(x3, self.pw1.forward(self.sw[:R], B))
+        z.copy_(x2)
+        rt.axpy(z, self._ffn(self.ln3, self.ffn1a, self.ffn1b, self.h1, x3, R, training), self.ff)
+        return self.ln4.forward(z, None, R, training)
+
+    def _scaled(self, src, rows):
+        """ffn_factor * src in a buffer of this block"""
+        df = self.df[:rows]
+        df.zero_()
+        self.rt.axpy(df, src, self.ff)
+        return df
+
+    def backward(self, dy, B):
+        """dy [B*S, D]: the output's gradient -> the input's gradient [B*S, D] (a buffer of this block)"""
+        rt = self.rt
+        R, D = B * self.S, self.D
+        dx2, dx1, dx0 = self.dx2[:R], self.dx1[:R], self.dx0[:R]
+        dz = self.ln4.backward(dy.reshape(R, D), R)                      # gradient of x2 + ffn_factor ffn1
+        dx2.copy_(dz)
+        dx3 = self._ffn_bwd(self.ln3, self.ffn1a, self.ffn1b, self._scaled(dz, R), R)      # gradient of x3 = x2 + conv
+        rt.axpy(dx2, dx3)
+        self.pw1.backward(dx3, self.dsw[:R], B)
+        rt.act_bwd(self.bno[:R], self.dsw[:R], self.dbn[:R], ACT["swish"])
+        self.bn.backward(self.dbn[:R], self.ddw[:R], B)
+        self.dw.backward(self.ddw[:R], self.du[:R], B)
+        self.pw0.backward(self.du[:R], self.dn[:R], B)
+        rt.axpy(dx2, self.ln2.backward(self.dn[:R], R))
+        dx1.copy_(dx2)
+        self.mha.backward(dx2, self.dn[:R], B)
+        rt.axpy(dx1, self.ln1.backward(self.dn[:R], R))
+        dx0.copy_(dx1)                                                   # the positional table is a constant
+        rt.axpy(dx0, self._ffn_bwd(self.ln0, self.ffn0a, self.ffn0b, self._scaled(dx1, R), R))
+        return dx0
+
+
+class ConformerEncoderStage:
+    """reference modules.conformer_encoder_stage (modules.py:129-152): `depth` blocks"""
+
+    def __init__(self, rt: _Rt, cfg: dict, S: int, D: int, prefix: str, B: int, depth=None):
+        depth = int(cfg["depth"]) if depth is None else int(depth)
+        self.blocks = [ConformerEncoderBlock(rt, cfg, S, D, f"{prefix}{i}", B) for i in range(depth)]
+        self.S, self.D, self.out_shape = int(S), int(D), (int(S), int(D))
+
+    forward = TransformerEncoderStage.forward
+    backward = TransformerEncoderStage.backward
+
+
 class MotherBlock:
     """reference modules.mother_block (modules.py:184-298)."""
 
@@ -648,20 +918,22 @@ class MotherBlock:
 
 
 COMPOSED_SECOND = ("bidirectional_GRU_block", "transformer_encoder_block", "transformer_encoder_stage")
+CONFORMER_SECOND = ("conformer_encoder_block", "conformer_encoder_stage")      # SECOND as well: COMPOSED_SECOND + CONFORMER_SECOND
 
 
 class ComposedSeldNet:
     """models.seldnet(input_shape, model_config) (reference models.py:18-32) composed from module operators: FIRST = mother_block |
-    mother_stage, SECOND = bidirectional_GRU_block (units 128: the recurrence kernels) | transformer_encoder_block | transformer_encoder_stage
-    (d_model = F * C of the FIRST stage's output), SED / DOA = simple_dense_block (kernel_size 1)."""
+    mother_stage, SECOND = bidirectional_GRU_block (units 128: the recurrence kernels) | transformer_encoder_block | transformer_encoder_stage |
+    conformer_encoder_block | conformer_encoder_stage (d_model = F * C of the FIRST stage's output), SED / DOA = simple_dense_block
+    (kernel_size 1).  The conformer stage's BatchNormalization statistics join `state_variables` behind the FIRST block's."""
 
     def __init__(self, input_shape, model_config: dict, device=None):
         from .models import canonical_config
         if not torch.cuda.is_available():
             raise RuntimeError("seld_amd needs a HIP device: there is no CPU fallback")
         cfg = canonical_config(model_config)
-        if cfg.get("SECOND") not in COMPOSED_SECOND or cfg.get("SED") != "simple_dense_block" or cfg.get("DOA") != "simple_dense_block":
-            raise ValueError(f"composed models: SECOND in {COMPOSED_SECOND}, SED / DOA = simple_dense_block")
+        if cfg.get("SECOND") not in COMPOSED_SECOND + CONFORMER_SECOND or cfg.get("SED") != "simple_dense_block" or cfg.get("DOA") != "simple_dense_block":
+            raise ValueError(f"composed models: SECOND in {COMPOSED_SECOND + CONFORMER_SECOND}, SED / DOA = simple_dense_block")
         self._dev = torch.device("cuda", torch.cuda.current_device() if device is None else int(device))
         B, T, Fq, Ch = (int(v) for v in input_shape)
         self.input_shape = (B, T, Fq, Ch)
@@ -687,9 +959,13 @@ class ComposedSeldNet:
         self.S = shape[0]
         feat = shape[1] * shape[2]
         sa = cfg["SECOND_ARGS"]
-        self.gru, self.tf = [], None
+        self.gru, self.tf = [], None      # tf: the attention stage (transformer or conformer), forward(x, B, training) / backward(dy, B)
         fin = feat
-        if cfg["SECOND"] != "bidirectional_GRU_block":
+        if cfg["SECOND"] in CONFORMER_SECOND:
+            stage = cfg["SECOND"] == "conformer_encoder_stage"
+            check_conformer_config(sa, stage, feat)
+            self.tf = ConformerEncoderStage(rt, sa, self.S, feat, "cf", B, depth=None if stage else 1)
+        elif cfg["SECOND"] != "bidirectional_GRU_block":
             stage = cfg["SECOND"] == "transformer_encoder_stage"
             check_transformer_config(sa, stage)
             self.tf = TransformerEncoderStage(rt, sa, self.S, feat, "tf", B, depth=None if stage else 1)      # d_model = F * C (force_1d_inputs)
@@ -1000,3 +1276,29 @@ def transformer_encoder_block(model_config: dict):
 def transformer_encoder_stage(model_config: dict):
     """reference modules.transformer_encoder_stage(model_config) (modules.py:106-126): `depth` blocks"""
     return _transformer_factory(model_config, True)
+
+
+def _conformer_factory(model_config: dict, stage: bool):
+    check_conformer_config(model_config, stage)
+
+    def build(input_shape, rt=None, prefix="cf"):
+        """input_shape [B, S, D] or [B, S, F, C] (layers.force_1d_inputs: D = F * C)"""
+        sh = [int(v) for v in input_shape]
+        if len(sh) not in (3, 4):
+            raise ValueError("conformer_encoder_block: input [B, S, D] or [B, S, F, C]")
+        B, S, D = sh[0], sh[1], int(np.prod(sh[2:]))
+        check_conformer_config(model_config, stage, D)          # the odd-width rule of pos_encoding 'basic' needs D: still without a device
+        rt = rt or _Rt(torch.device("cuda", torch.cuda.current_device()))
+        return ConformerEncoderStage(rt, model_config, S, D, prefix, B, depth=None if stage else 1)
+    return build
+
+
+def conformer_encoder_block(model_config: dict):
+    """reference modules.conformer_encoder_block(model_config) (modules.py:410-508) -> a factory `(input_shape) -> a one-block
+    ConformerEncoderStage` (forward(x, B, training) / backward(dy, B) on [B*S, D]); configuration errors are raised here, without a device."""
+    return _conformer_factory(model_config, False)
+
+
+def conformer_encoder_stage(model_config: dict):
+    """reference modules.conformer_encoder_stage(model_config) (modules.py:129-152): `depth` blocks"""
+    return _conformer_factory(model_config, True)
