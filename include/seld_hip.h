@@ -532,6 +532,38 @@ int seld_dwconv1d_bwd(const float* u, int ldu, const float* w, const float* dy, 
                       int S, int C, int k, int glu, void* stream);
 int seld_pos_add(float* x, const float* enc, int B, int S, int D, void* stream);
 int seld_head_permute(const float* src, float* dst, int H, int D, int dk, int mode, void* stream);
+/* ---- relative-position attention (relattn.hip): the core of layers.RelPositionMultiHeadAttention (layers.py:332-392), the attention of
+ * modules.attention_block with abs_pos_encoding = False (modules.py:585-588), and attention_block's GLU (modules.py:598-601).  fp32 device
+ * tensors, asynchronous on `stream`, no allocation.
+ *   seld_relattn_fwd    O[b,n,h,:] = sum_m softmax_m(scale (qu[b,n,h,:] . K[b,m,h,:] + shifted[b,h,n,m])) V[b,m,h,:], qu = Q + u, qv = Q + vb
+ *                       (layers.py:374-375), shifted = relative_shift(G) of G[b,h,n,m] = qv[b,n,h,:] . P[m,h,:] (layers.py:360-365, 378-379):
+ *                       pad one zero column in front, reshape [S, S+1] -> [S+1, S], drop the first row — shifted[i,j] = G[i, S-1-i+j] for
+ *                       j <= i, 0 for j = i+1, G[i+1, j-i-2] for j >= i+2 (the NEXT query row: the reference's behaviour).  `scale` multiplies
+ *                       the summed logits (layers.py:383-384).  Q, K, V: [B*S, H*d] views with row strides ldq / ldk / ldv, as seld_attn_fwd
+ *                       takes them; P [S, H*d] (row stride ldp): the projected positional table, without a batch axis (layers.py:372); u, vb
+ *                       [H*d]: pos_bias_u / pos_bias_v; O [B*S, H*d] contiguous; lse [B, H, S] (NULL at inference: O is bit-identical).
+ *                       Neither a [B,H,S,S] nor a [B,H,S,S+1] tensor is formed: the positional term of a logit tile is the product of the
+ *                       tile's queries with 127 consecutive rows of the table, read back along the skewed diagonal through LDS.
+ *   seld_relattn_bwd    dQu, dQv (the gradients of qu and qv: the caller adds them for dQ and column-sums them for the two biases), dK, dV
+ *                       (row strides lddqu / lddqv / lddk / lddv) and dP [S, H*d] (row stride lddp), already summed over the batch, from Q, K,
+ *                       V, P, u, vb, O, dO [B*S, H*d] and lse.  The backward of relative_shift is the same index map (every G[i,m] is read
+ *                       once).  No atomics: every output element is owned by one lane or added in a fixed order through scratch
+ *                       (seld_relattn_bwd_scratch(B, S, H, d) = B*H*S*(1 + 2d) floats: linear in the rows); two runs are bit-identical.
+ *   d a multiple of 8 in 8 .. 64, else SELD_ERR_UNSUPPORTED (the scratch size -1) before any other check.  Then SELD_ERR_INVALID, before anything
+ *   is enqueued, for a NULL pointer (all but lse of seld_relattn_fwd), B, S or H < 1, or a row stride < H*d (the product in 64 bits).  Then
+ *   SELD_ERR_UNSUPPORTED (the scratch size -1) for a grid B * H * ceil(S / 64) beyond INT_MAX or S beyond 2^30 - 256.
+ *   seld_glu_fwd        y [rows, C] = u[:, :C] * sigmoid(u[:, C:]) of u [rows, 2C] with row stride ldu (modules.py:599-601).
+ *   seld_glu_bwd        du (row stride lddu): dy sigmoid(b) in the first half, dy a sigmoid'(b) in the second, sigmoid' formed from
+ *                       exp(-|b|) as in seld_dwconv1d_bwd (no cancellation, no overflow).  SELD_ERR_INVALID for a NULL pointer, rows or C < 1
+ *                       or a row stride < 2C; SELD_ERR_UNSUPPORTED for rows * C beyond a launch. */
+int seld_relattn_fwd(const float* Q, const float* K, const float* V, int ldq, int ldk, int ldv, const float* P, int ldp, const float* u,
+                     const float* vb, float* O, float* lse, int B, int S, int H, int d, float scale, void* stream);
+int64_t seld_relattn_bwd_scratch(int B, int S, int H, int d);
+int seld_relattn_bwd(const float* Q, const float* K, const float* V, int ldq, int ldk, int ldv, const float* P, int ldp, const float* u,
+                     const float* vb, const float* O, const float* dO, const float* lse, float* dQu, float* dQv, float* dK, float* dV, float* dP,
+                     int lddqu, int lddqv, int lddk, int lddv, int lddp, float* scratch, int B, int S, int H, int d, float scale, void* stream);
+int seld_glu_fwd(const float* u, int ldu, float* y, int64_t rows, int C, void* stream);
+int seld_glu_bwd(const float* u, int ldu, const float* dy, float* du, int lddu, int64_t rows, int C, void* stream);
 /* Measurement aid (bench.py, SURVEY.md §8(d) "state the step-latency floor"): the shader clock the card holds while `blocks`
  * workgroups of 512 threads run a VALU-only loop (the load shape of the GRU recurrence: 2B workgroups, no MFMA), from
  * s_memtime / s_memrealtime (100 MHz) inside the kernel.  No reference counterpart. */

@@ -183,6 +183,11 @@ SIGNATURES = {
     "seld_dwconv1d_bwd": (_I, [_P, _I, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "seld_pos_add": (_I, [_P, _P, _I, _I, _I, _P]),
     "seld_head_permute": (_I, [_P, _P, _I, _I, _I, _I, _P]),
+    "seld_relattn_fwd": (_I, [_P, _P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P]),
+    "seld_relattn_bwd_scratch": (_L, [_I, _I, _I, _I]),
+    "seld_relattn_bwd": (_I, [_P, _P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P] + [_P] * 5 + [_I] * 5 + [_P, _I, _I, _I, _I, _F, _P]),
+    "seld_glu_fwd": (_I, [_P, _I, _P, _L, _I, _P]),
+    "seld_glu_bwd": (_I, [_P, _I, _P, _P, _I, _L, _I, _P]),
     "seld_k_rn_conv": (_I, [_P, _P, _P] + [_I] * 7),
     "seld_k_rn_conv_stats": (_I, [_P, _P, _P] + [_I] * 7 + [_P]),
     "seld_k_rn_conv_bwd": (_I, [_P, _P, _P, _P, _P] + [_I] * 7),

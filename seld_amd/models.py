@@ -281,8 +281,9 @@ def seldnet(input_shape, model_config, device=None, dtype: str = "float32"):
     """reference models.seldnet (models.py:18-32).  `dtype="bfloat16"`: bf16 single-product mode (SELD_DTYPE_BF16).  FIRST = mother_block /
     mother_stage (modules.py:15-43, 184-298) builds a modules.ComposedSeldNet (layer-by-layer module operators) instead of a fused ctx; only
     there may SECOND be transformer_encoder_block / transformer_encoder_stage (modules.py:106-126, 379-407; modules.COMPOSED_SECOND) or
-    conformer_encoder_block / conformer_encoder_stage (modules.py:129-152, 410-508; modules.CONFORMER_SECOND) — the fused contexts know
-    bidirectional_GRU_block alone, and conformer_encoder_stage as FIRST stays refused."""
+    conformer_encoder_block / conformer_encoder_stage (modules.py:129-152, 410-508; modules.CONFORMER_SECOND) or attention_block /
+    attention_stage (modules.py:155-180, 511-635; modules.ATTENTION_SECOND) — the fused contexts know bidirectional_GRU_block alone, and
+    conformer_encoder_stage / attention_stage as FIRST stay refused."""
     if model_config.get("FIRST") in COMPOSED_FIRST:
         if dtype != "float32":
             raise ValueError("composed models compute in float32")

@@ -15,8 +15,12 @@ else).  There is no CPU or PyTorch fallback.
                                                   module (pointwise Conv1D, GLU + depthwise Conv1D: seld_dwconv1d_* of conformer.hip,
                                                   BatchNormalization, swish, pointwise Conv1D), half-step FFN, LayerNormalization
 
+  attention_block / _stage (modules.py:155-180, 511-635)             FF modules of Conv1D('same'), MultiHeadAttention_ or (abs_pos_encoding False)
+                                                  layers.RelPositionMultiHeadAttention (seld_relattn_* of relattn.hip), GLU (seld_glu_*), the
+                                                  depthwise Conv1D module, LayerNormalization in front or behind
+
 `ComposedSeldNet` = models.seldnet(input_shape, model_config) for FIRST in {mother_block, mother_stage}, SECOND in {bidirectional_GRU_block,
-transformer_encoder_block, transformer_encoder_stage, conformer_encoder_block, conformer_encoder_stage}: same surface as
+transformer_encoder_block, transformer_encoder_stage, conformer_encoder_block, conformer_encoder_stage, attention_block, attention_stage}: same surface as
 seld_amd.models.SeldNet (variables in Keras creation order, get / set_weights, __call__, train.trainstep / teststep).  The three
 BASELINE configurations do NOT run through here — their blocks are fused kernels inside a seld_ctx (models.SeldNet)."""
 from __future__ import annotations
@@ -717,6 +721,329 @@ class ConformerEncoderStage:
     backward = TransformerEncoderStage.backward
 
 
+class GLU:
+    """tf.split(u, 2, -1); u_1 * sigmoid(u_2) on [rows, 2C] (reference modules.py:599-601: attention_block's GLU without a depthwise
+    convolution behind it): seld_glu_fwd / _bwd."""
+
+    def __init__(self, rt: _Rt, rows: int, C_: int):
+        self.rt, self.C = rt, int(C_)
+        self.y = rt.empty(rows, self.C)
+
+    def forward(self, u, rows):
+        rt = self.rt
+        self.u = u
+        rt.ck(rt.lib.seld_glu_fwd(rt.p(u), 2 * self.C, rt.p(self.y), rows, self.C, rt.st()))
+        return self.y[:rows]
+
+    def backward(self, dy, du, rows):
+        rt = self.rt
+        rt.ck(rt.lib.seld_glu_bwd(rt.p(self.u), 2 * self.C, rt.p(dy), rt.p(du), 2 * self.C, rows, self.C, rt.st()))
+
+
+class RelPositionMultiHeadAttention:
+    """The reference's layers.RelPositionMultiHeadAttention(n_head, key_dim, use_bias)([x, x, x, pos]) (layers.py:332-392) on [B, S, D] with the
+    batch-free table pos [S, D] of layers.basic_pos_encoding: variables pos_kernel [H, D, dk], pos_bias_u, pos_bias_v [H, dk], then
+    MultiHeadAttention_'s (layers.py:333-357, 148-205).  q, k, v and P = pos . pos_kernel are seld_head_permute + one GEMM each (P from the
+    host-built table in every forward: the kernel moves); the core is seld_relattn_fwd / _bwd, whose dQu / dQv are added for the query's
+    gradient and column-summed for the two biases; dpos_kernel = pos^T dP."""
+
+    def __init__(self, rt: _Rt, name: str, B: int, S: int, D: int, n_head: int, key_dim: int, use_bias: bool = False):
+        self.rt, self.name, self.S, self.D, self.H, self.dk, self.use_bias = rt, name, int(S), int(D), int(n_head), int(key_dim), bool(use_bias)
+        H, dk = self.H, self.dk
+        rt.var(f"{name}.pos_kernel", (H, self.D, dk))
+        rt.var(f"{name}.pos_bias_u", (H, dk))
+        rt.var(f"{name}.pos_bias_v", (H, dk))
+        for part in ("query", "key", "value"):
+            rt.var(f"{name}.{part}_kernel", (H, self.D, dk))
+        rt.var(f"{name}.projection_kernel", (H, dk, self.D))
+        if self.use_bias:
+            rt.var(f"{name}.projection_bias", (self.D,))
+            for part in "qkv":
+                rt.var(f"{name}.{part}_bias", (H, dk))
+        need = int(rt.lib.seld_relattn_bwd_scratch(B, self.S, H, dk))
+        if need < 0:
+            raise ValueError(f"key_dim {key_dim!r}: the attention kernels take a multiple of 8 from 8 to 64")
+        R, HD = B * self.S, H * dk
+        self.q, self.k, self.v, self.o, self.do = (rt.empty(R, HD) for _ in range(5))
+        self.dqu, self.dqv, self.dk_, self.dv = (rt.empty(R, HD) for _ in range(4))
+        self.packed = [rt.empty(self.D, HD) for _ in range(4)]      # query, key, value, pos
+        self.dpacked, self.dpacked2 = rt.empty(self.D, HD), rt.empty(self.D, HD)
+        self.P, self.dP = rt.empty(self.S, HD), rt.empty(self.S, HD)
+        self.pos = torch.as_tensor(basic_pos_encoding(self.S, self.D)).to(rt.dev)
+        self.lse = rt.empty(B * H * self.S)
+        self.scratch = rt.empty(need)
+        self.out = rt.empty(R, self.D)
+        self.scale = 1.0 / math.sqrt(float(dk))
+
+    def _bias(self, part, grad=False):
+        if not self.use_bias:
+            return None
+        return (self.rt.g if grad else self.rt.w)(f"{self.name}.{part}")
+
+    def forward(self, x, B, training):
+        rt, n = self.rt, self.name
+        R, HD = B * self.S, self.H * self.dk
+        self.x = x
+        for part, wp, buf in zip(("query", "key", "value"), self.packed, (self.q, self.k, self.v)):
+            rt.ck(rt.lib.seld_head_permute(rt.p(rt.w(f"{n}.{part}_kernel")), rt.p(wp), self.H, self.D, self.dk, 0, rt.st()))
+            rt.gemm(x, wp, self._bias(part[0] + "_bias"), buf, R, HD, self.D)
+        rt.ck(rt.lib.seld_head_permute(rt.p(rt.w(f"{n}.pos_kernel")), rt.p(self.packed[3]), self.H, self.D, self.dk, 0, rt.st()))
+        rt.gemm(self.pos, self.packed[3], None, self.P, self.S, HD, self.D)
+        rt.ck(rt.lib.seld_relattn_fwd(rt.p(self.q), rt.p(self.k), rt.p(self.v), HD, HD, HD, rt.p(self.P), HD, rt.p(rt.w(f"{n}.pos_bias_u")),
+                                      rt.p(rt.w(f"{n}.pos_bias_v")), rt.p(self.o), rt.p(self.lse) if training else None, B, self.S, self.H,
+                                      self.dk, self.scale, rt.st()))
+        rt.gemm(self.o, rt.w(f"{n}.projection_kernel"), self._bias("projection_bias"), self.out, R, self.D, HD)
+        return self.out[:R]
+
+    def backward(self, dout, dx, B):
+        """dout [R, D] -> every variable's gradient; dx = the input's gradient (overwritten)"""
+        rt, n = self.rt, self.name
+        R, HD = B * self.S, self.H * self.dk
+        rt.gemm_tn(self.o, dout, rt.g(f"{n}.projection_kernel"), self._bias("projection_bias", True), R, HD, self.D)
+        rt.gemm(dout, rt.w(f"{n}.projection_kernel"), None, self.do, R, HD, self.D, transb=1)
+        rt.ck(rt.lib.seld_relattn_bwd(rt.p(self.q), rt.p(self.k), rt.p(self.v), HD, HD, HD, rt.p(self.P), HD, rt.p(rt.w(f"{n}.pos_bias_u")),
+                                      rt.p(rt.w(f"{n}.pos_bias_v")), rt.p(self.o), rt.p(self.do), rt.p(self.lse), rt.p(self.dqu), rt.p(self.dqv),
+                                      rt.p(self.dk_), rt.p(self.dv), rt.p(self.dP), HD, HD, HD, HD, HD, rt.p(self.scratch), B, self.S, self.H,
+                                      self.dk, self.scale, rt.st()))
+        # the query kernel sees dQu + dQv; the column sums of the two parts are the gradients of pos_bias_u / pos_bias_v
+        rt.gemm_tn(self.x, self.dqu, self.dpacked, rt.g(f"{n}.pos_bias_u"), R, self.D, HD)
+        rt.gemm_tn(self.x, self.dqv, self.dpacked2, rt.g(f"{n}.pos_bias_v"), R, self.D, HD)
+        rt.axpy(self.dpacked, self.dpacked2)
+        rt.ck(rt.lib.seld_head_permute(rt.p(self.dpacked), rt.p(rt.g(f"{n}.query_kernel")), self.H, self.D, self.dk, 1, rt.st()))
+        if self.use_bias:
+            gq = rt.g(f"{n}.q_bias")
+            gq.copy_(rt.g(f"{n}.pos_bias_u"))
+            rt.axpy(gq, rt.g(f"{n}.pos_bias_v"))
+        dq = self.dqu[:R]
+        rt.axpy(dq, self.dqv[:R])
+        rt.gemm(dq, self.packed[0], None, dx, R, self.D, HD, transb=1)
+        for part, wp, g in zip(("key", "value"), self.packed[1:3], (self.dk_, self.dv)):
+            rt.gemm_tn(self.x, g, self.dpacked, self._bias(part[0] + "_bias", True), R, self.D, HD)
+            rt.ck(rt.lib.seld_head_permute(rt.p(self.dpacked), rt.p(rt.g(f"{n}.{part}_kernel")), self.H, self.D, self.dk, 1, rt.st()))
+            rt.gemm(g, wp, None, dx, R, self.D, HD, transb=1, accumulate=1)
+        rt.gemm_tn(self.pos, self.dP, self.dpacked, None, self.S, self.D, HD)
+        rt.ck(rt.lib.seld_head_permute(rt.p(self.dpacked), rt.p(rt.g(f"{n}.pos_kernel")), self.H, self.D, self.dk, 1, rt.st()))
+
+
+ATTENTION_KEYS = ("key_dim", "n_head", "kernel_size", "ff_kernel_size", "ff_multiplier", "ff_factor0", "ff_factor1")
+
+
+def check_attention_config(cfg: dict, stage: bool = False, D=None) -> None:
+    """the mandatory keys and the ValueErrors of reference modules.py:513-551 (`depth` is the stage's, modules.py:174); what has no kernel here
+    is refused, not ignored"""
+    who = f"attention_{'stage' if stage else 'block'}"
+    for key in ATTENTION_KEYS + (("depth",) if stage else ()):
+        if key not in cfg:
+            raise ValueError(f"{who}: missing {key!r}")
+    if cfg.get("activation", "swish") not in ACT:
+        raise ValueError(f"activation {cfg.get('activation')!r}: the module operators know {sorted(k for k in ACT if k)}")
+    if "dropout_rate" not in cfg or float(cfg["dropout_rate"]) != 0.0:
+        raise ValueError(f"{who}: there is no dropout kernel on this path and the reference's default dropout_rate is 0.1: "
+                         "dropout_rate must be present and 0")
+    f0, f1, fk, fm = float(cfg["ff_factor0"]), float(cfg["ff_factor1"]), int(cfg["ff_kernel_size"]), float(cfg["ff_multiplier"])
+    if f0 < 0 or f1 < 0:
+        raise ValueError("ff_factor0, ff_factor1 >= 0 must hold")
+    if f0 == 0 and f1 == 0:
+        if fk > 0:
+            raise ValueError("if FF modules are not used, ff_kernel must be set to 0")
+        if fm > 0:
+            raise ValueError("if FF modules are not used, ff_multiplier must be set to 0")
+    pe, ab = cfg.get("pos_encoding", "basic"), bool(cfg.get("abs_pos_encoding", False))
+    if pe == "rff":
+        raise ValueError(f"{who}: pos_encoding 'rff' draws its frequencies from tf.random.normal and stores them nowhere: it cannot be reproduced")
+    if pe not in ("basic", None):
+        raise ValueError(f"{who}: pos_encoding {pe!r}: 'basic' or None")
+    if not ab and pe is None:
+        raise ValueError("relative pos encoding demands any types of encoding except the null one")
+    if pe == "basic" and D is not None and int(D) % 2:
+        raise ValueError(f"{who}: pos_encoding 'basic' on an odd width {D}: the reference's table has 2 * (D // 2) columns and does not broadcast")
+    if fk < 0 or fm < 0 or ((f0 > 0 or f1 > 0) and (fk < 1 or (D is not None and int(fm * int(D)) < 1))):
+        raise ValueError(f"{who}: a FF module takes ff_kernel_size >= 1 and int(ff_multiplier * d_model) >= 1")
+    if int(cfg["n_head"]) < 1 or not 0 <= int(cfg["kernel_size"]) <= 64 or (stage and int(cfg["depth"]) < 1):
+        raise ValueError(f"{who}: n_head, depth >= 1 and 0 <= kernel_size <= 64")
+    dk = int(cfg["key_dim"])
+    if dk < 8 or dk > 64 or dk % 8:
+        raise ValueError(f"key_dim {dk}: the attention kernels take a multiple of 8 from 8 to 64")
+
+
+class _FFModule:
+    """attention_block's FF module (modules.py:559-572, 619-632): x + factor Conv1D(D, k)(act(Conv1D(int(ff_multiplier D), k)(x))), then
+    LayerNormalization unless layer_norm_in_front — whose own LayerNormalization is dead: the first Conv1D reads x (modules.py:564, 624)."""
+
+    def __init__(self, rt: _Rt, name: str, lname, B: int, S: int, D: int, F: int, k: int, act: int, factor: float):
+        self.rt, self.S, self.D, self.F, self.act, self.factor = rt, S, D, F, act, float(factor)
+        R = B * S
+        self.a, self.b = Conv1D(rt, f"{name}a", B, S, D, F, k), Conv1D(rt, f"{name}b", B, S, F, D, k)
+        self.ln = LayerNorm(rt, lname, R, D) if lname else None
+        self.h, self.dh, self.dpre = rt.empty(R, F), rt.empty(R, F), rt.empty(R, F)
+        self.y, self.df, self.dx = rt.empty(R, D), rt.empty(R, D), rt.empty(R, D)
+
+    def forward(self, x, B, training):
+        rt, R = self.rt, B * self.S
+        self.pre = self.a.forward(x, B)
+        rt.act(self.pre, self.h[:R], self.act)
+        y = self.y[:R]
+        y.copy_(x)
+        rt.axpy(y, self.b.forward(self.h[:R], B), self.factor)
+        return self.ln.forward(y, None, R, training) if self.ln else y
+
+    def backward(self, dy, B):
+        rt, R = self.rt, B * self.S
+        dz = self.ln.backward(dy, R) if self.ln else dy
+        df = self.df[:R]
+        df.zero_()
+        rt.axpy(df, dz, self.factor)
+        self.b.backward(df, self.dh[:R], B)
+        rt.act_bwd(self.pre, self.dh[:R], self.dpre[:R], self.act)
+        dx = self.dx[:R]
+        self.a.backward(self.dpre[:R], dx, B)
+        rt.axpy(dx, dz)
+        return dx
+
+
+class AttentionBlock:
+    """reference modules.attention_block (modules.py:511-635) on [B, S, D], every Dropout at rate 0 (lnf = layer_norm_in_front):
+      x = FF0(x)                                                   (ff_factor0 > 0)
+      a = x; x += table (abs_pos_encoding: AFTER a is taken, so the attention never sees it)
+      x = x + MHA(LN?(a))        MultiHeadAttention_ (abs_pos_encoding) or RelPositionMultiHeadAttention with the table;  x = LN(x) unless lnf
+      c = GLU(Conv1D(2D, 1)(LN?(x)))                              (use_glu; LN? = with lnf)
+      x = x + Conv1D(D, 1)(swish(BN(depthwise Conv1D(k)(c))))     (kernel_size > 0; with lnf and no GLU one LN in front of the depthwise
+                                                                   convolution); x = LN(x) unless lnf.  kernel_size = 0: x = c, nothing else
+      x = FF1(x)                                                   (ff_factor1 > 0)"""
+
+    def __init__(self, rt: _Rt, cfg: dict, S: int, D: int, prefix: str, B: int):
+        check_attention_config(cfg, D=D)
+        self.rt, self.S, self.D, self.B = rt, int(S), int(D), B
+        S, D, p = self.S, self.D, prefix
+        R = B * S
+        act = ACT[cfg.get("activation", "swish")]
+        F, fk = int(cfg["ff_multiplier"] * D), int(cfg["ff_kernel_size"])
+        self.lnf, self.glu, self.k = bool(cfg.get("layer_norm_in_front", False)), bool(cfg.get("use_glu", False)), int(cfg["kernel_size"])
+        self.abs = bool(cfg.get("abs_pos_encoding", False))
+        lnf = self.lnf
+        H, dk, ub = int(cfg["n_head"]), int(cfg["key_dim"]), bool(cfg.get("use_bias", False))
+        f0, f1 = float(cfg["ff_factor0"]), float(cfg["ff_factor1"])
+        self.ff0 = _FFModule(rt, f"{p}.ff0", None if lnf else f"{p}.ln0", B, S, D, F, fk, act, f0) if f0 > 0 else None
+        self.ln1 = LayerNorm(rt, f"{p}.ln1", R, D) if lnf else None
+        if self.abs:
+            self.mha = MultiHeadAttentionRef(rt, f"{p}.mha", B, S, D, H, dk, ub)
+        else:
+            self.mha = RelPositionMultiHeadAttention(rt, f"{p}.mha", B, S, D, H, dk, ub)
+        if not lnf:
+            self.ln1 = LayerNorm(rt, f"{p}.ln1", R, D)
+        self.ln2 = self.pw0 = self.dw = self.gate = None
+        if self.glu:
+            if lnf:
+                self.ln2 = LayerNorm(rt, f"{p}.ln2", R, D)
+            self.pw0 = Conv1D(rt, f"{p}.pw0", B, S, D, 2 * D, 1)
+            if self.k == 0:
+                self.gate = GLU(rt, R, D)
+        if self.k > 0:
+            if lnf and not self.glu:
+                self.ln2 = LayerNorm(rt, f"{p}.ln2", R, D)
+            self.dw = DepthwiseConv1D(rt, f"{p}.dw", B, S, D, self.k, glu=self.glu)
+            self.bn = BatchNorm(rt, f"{p}.bn", (S, 1, D), B)
+            self.pw1 = Conv1D(rt, f"{p}.pw1", B, S, D, D, 1)
+            if not lnf:
+                self.ln2 = LayerNorm(rt, f"{p}.ln2", R, D)
+        self.ff1 = _FFModule(rt, f"{p}.ff1", None if lnf else f"{p}.ln3", B, S, D, F, fk, act, f1) if f1 > 0 else None
+        self.enc = None
+        if self.abs and cfg.get("pos_encoding", "basic") == "basic":
+            self.enc = torch.as_tensor(basic_pos_encoding(S, D)).to(rt.dev)
+        e = rt.empty
+        self.xr, self.xb, self.xc = e(R, D), e(R, D), e(R, D)
+        self.bno, self.sw, self.dsw, self.dbn, self.ddw = e(R, D), e(R, D), e(R, D), e(R, D), e(R, D)
+        self.du, self.dn, self.dxb, self.dxa = e(R, 2 * D), e(R, D), e(R, D), e(R, D)
+        self.out_shape = (S, D)
+
+    def forward(self, x, B, training):
+        """x [B*S, D] (or any contiguous view of it) -> [B*S, D]"""
+        rt = self.rt
+        R, D = B * self.S, self.D
+        x = x.reshape(R, D)
+        if self.ff0:
+            x = self.ff0.forward(x, B, training)
+        attn = self.ln1.forward(x, None, R, training) if self.lnf else x
+        res = x
+        if self.enc is not None:
+            res = self.xr[:R]
+            res.copy_(x)
+            rt.ck(rt.lib.seld_pos_add(rt.p(res), rt.p(self.enc), B, self.S, D, rt.st()))
+        attn = self.mha.forward(attn, B, training)
+        if self.lnf:
+            xb = self.xb[:R]
+            xb.copy_(res)
+            rt.axpy(xb, attn)
+        else:
+            xb = self.ln1.forward(attn, res, R, training)
+        c = xb
+        if self.glu:
+            c = self.pw0.forward(self.ln2.forward(c, None, R, training) if self.lnf else c, B)
+            if self.k == 0:
+                c = self.gate.forward(c, R)
+        if self.k > 0:
+            if self.lnf and not self.glu:
+                c = self.ln2.forward(c, None, R, training)
+            self.bn.forward(self.dw.forward(c, B), self.bno[:R], B, training, 0)
+            rt.act(self.bno[:R], self.sw[:R], ACT["swish"])
+            pw = self.pw1.forward(self.sw[:R], B)
+            if self.lnf:
+                xc = self.xc[:R]
+                xc.copy_(xb)
+                rt.axpy(xc, pw)
+            else:
+                xc = self.ln2.forward(pw, xb, R, training)
+        else:
+            xc = c
+        return self.ff1.forward(xc, B, training) if self.ff1 else xc
+
+    def backward(self, dy, B):
+        """dy [B*S, D]: the output's gradient -> the input's gradient [B*S, D] (a buffer of this block)"""
+        rt = self.rt
+        R, D = B * self.S, self.D
+        d = dy.reshape(R, D)
+        if self.ff1:
+            d = self.ff1.backward(d, B)
+        dxb, dn = self.dxb[:R], self.dn[:R]
+        du = self.du[:R] if self.glu else self.du.view(-1)[:R * D].view(R, D)
+        if self.k > 0:
+            dz = d if self.lnf else self.ln2.backward(d, R)               # gradient of xb + pw
+            dxb.copy_(dz)
+            self.pw1.backward(dz, self.dsw[:R], B)
+            rt.act_bwd(self.bno[:R], self.dsw[:R], self.dbn[:R], ACT["swish"])
+            self.bn.backward(self.dbn[:R], self.ddw[:R], B)
+            self.dw.backward(self.ddw[:R], du, B)
+            if self.glu:
+                self.pw0.backward(du, dn, B)
+                rt.axpy(dxb, self.ln2.backward(dn, R) if self.lnf else dn)
+            else:
+                rt.axpy(dxb, self.ln2.backward(du, R) if self.lnf else du)
+        elif self.glu:
+            self.gate.backward(d, du, R)
+            self.pw0.backward(du, dn, B)
+            dxb.copy_(self.ln2.backward(dn, R) if self.lnf else dn)
+        else:
+            dxb.copy_(d)
+        dz = dxb if self.lnf else self.ln1.backward(dxb, R)               # gradient of attn + x (the table is a constant)
+        dxa = self.dxa[:R]
+        dxa.copy_(dz)
+        self.mha.backward(dz, dn, B)
+        rt.axpy(dxa, self.ln1.backward(dn, R) if self.lnf else dn)
+        return self.ff0.backward(dxa, B) if self.ff0 else dxa
+
+
+class AttentionStage:
+    """reference modules.attention_stage (modules.py:155-180): `depth` blocks"""
+
+    def __init__(self, rt: _Rt, cfg: dict, S: int, D: int, prefix: str, B: int, depth=None):
+        depth = int(cfg["depth"]) if depth is None else int(depth)
+        self.blocks = [AttentionBlock(rt, cfg, S, D, f"{prefix}{i}", B) for i in range(depth)]
+        self.S, self.D, self.out_shape = int(S), int(D), (int(S), int(D))
+
+    forward = TransformerEncoderStage.forward
+    backward = TransformerEncoderStage.backward
+
+
 class MotherBlock:
     """reference modules.mother_block (modules.py:184-298)."""
 
@@ -919,21 +1246,24 @@ class MotherBlock:
 
 COMPOSED_SECOND = ("bidirectional_GRU_block", "transformer_encoder_block", "transformer_encoder_stage")
 CONFORMER_SECOND = ("conformer_encoder_block", "conformer_encoder_stage")      # SECOND as well: COMPOSED_SECOND + CONFORMER_SECOND
+ATTENTION_SECOND = ("attention_block", "attention_stage")                          # SECOND as well, routed as CONFORMER_SECOND is
 
 
 class ComposedSeldNet:
     """models.seldnet(input_shape, model_config) (reference models.py:18-32) composed from module operators: FIRST = mother_block |
     mother_stage, SECOND = bidirectional_GRU_block (units 128: the recurrence kernels) | transformer_encoder_block | transformer_encoder_stage |
-    conformer_encoder_block | conformer_encoder_stage (d_model = F * C of the FIRST stage's output), SED / DOA = simple_dense_block
-    (kernel_size 1).  The conformer stage's BatchNormalization statistics join `state_variables` behind the FIRST block's."""
+    conformer_encoder_block | conformer_encoder_stage | attention_block | attention_stage (d_model = F * C of the FIRST stage's output),
+    SED / DOA = simple_dense_block (kernel_size 1).  The conformer and attention stages' BatchNormalization statistics join `state_variables`
+    behind the FIRST block's."""
 
     def __init__(self, input_shape, model_config: dict, device=None):
         from .models import canonical_config
         if not torch.cuda.is_available():
             raise RuntimeError("seld_amd needs a HIP device: there is no CPU fallback")
         cfg = canonical_config(model_config)
-        if cfg.get("SECOND") not in COMPOSED_SECOND + CONFORMER_SECOND or cfg.get("SED") != "simple_dense_block" or cfg.get("DOA") != "simple_dense_block":
-            raise ValueError(f"composed models: SECOND in {COMPOSED_SECOND + CONFORMER_SECOND}, SED / DOA = simple_dense_block")
+        seconds = COMPOSED_SECOND + CONFORMER_SECOND + ATTENTION_SECOND
+        if cfg.get("SECOND") not in seconds or cfg.get("SED") != "simple_dense_block" or cfg.get("DOA") != "simple_dense_block":
+            raise ValueError(f"composed models: SECOND in {seconds}, SED / DOA = simple_dense_block")
         self._dev = torch.device("cuda", torch.cuda.current_device() if device is None else int(device))
         B, T, Fq, Ch = (int(v) for v in input_shape)
         self.input_shape = (B, T, Fq, Ch)
@@ -965,6 +1295,10 @@ class ComposedSeldNet:
             stage = cfg["SECOND"] == "conformer_encoder_stage"
             check_conformer_config(sa, stage, feat)
             self.tf = ConformerEncoderStage(rt, sa, self.S, feat, "cf", B, depth=None if stage else 1)
+        elif cfg["SECOND"] in ATTENTION_SECOND:
+            stage = cfg["SECOND"] == "attention_stage"
+            check_attention_config(sa, stage, feat)
+            self.tf = AttentionStage(rt, sa, self.S, feat, "at", B, depth=None if stage else 1)
         elif cfg["SECOND"] != "bidirectional_GRU_block":
             stage = cfg["SECOND"] == "transformer_encoder_stage"
             check_transformer_config(sa, stage)
@@ -1017,7 +1351,7 @@ class ComposedSeldNet:
             k = int(np.prod(sh))
             if n.endswith("recurrent_kernel"):
                 w[off:off + k] = np.concatenate([np.linalg.qr(rng.standard_normal((128, 128)))[0] for _ in range(3)], axis=1).reshape(-1)
-            elif n.endswith("kernel"):
+            elif n.endswith(("kernel", "pos_bias_u", "pos_bias_v")):      # the two biases take the kernel initializer (layers.py:343-356)
                 fan_in = int(np.prod(sh[:-1])); fan_out = int(sh[-1]) * (int(np.prod(sh[:-2])) if len(sh) > 2 else 1)
                 lim = math.sqrt(6.0 / (fan_in + fan_out))
                 w[off:off + k] = rng.uniform(-lim, lim, k)
@@ -1302,3 +1636,29 @@ def conformer_encoder_block(model_config: dict):
 def conformer_encoder_stage(model_config: dict):
     """reference modules.conformer_encoder_stage(model_config) (modules.py:129-152): `depth` blocks"""
     return _conformer_factory(model_config, True)
+
+
+def _attention_factory(model_config: dict, stage: bool):
+    check_attention_config(model_config, stage)
+
+    def build(input_shape, rt=None, prefix="at"):
+        """input_shape [B, S, D] or [B, S, F, C] (layers.force_1d_inputs: D = F * C)"""
+        sh = [int(v) for v in input_shape]
+        if len(sh) not in (3, 4):
+            raise ValueError("attention_block: input [B, S, D] or [B, S, F, C]")
+        B, S, D = sh[0], sh[1], int(np.prod(sh[2:]))
+        check_attention_config(model_config, stage, D)          # the rules that need the width: still without a device
+        rt = rt or _Rt(torch.device("cuda", torch.cuda.current_device()))
+        return AttentionStage(rt, model_config, S, D, prefix, B, depth=None if stage else 1)
+    return build
+
+
+def attention_block(model_config: dict):
+    """reference modules.attention_block(model_config) (modules.py:511-635) -> a factory `(input_shape) -> a one-block AttentionStage`
+    (forward(x, B, training) / backward(dy, B) on [B*S, D]); configuration errors are raised here, without a device."""
+    return _attention_factory(model_config, False)
+
+
+def attention_stage(model_config: dict):
+    """reference modules.attention_stage(model_config) (modules.py:155-180): `depth` blocks"""
+    return _attention_factory(model_config, True)
