@@ -470,6 +470,41 @@ int seld_m_gru_fwd(const float* gx_f, const float* gx_b, const float* U_f, const
                    float* h_b, float* saved_f, float* saved_b, float* out, int B, int S, int units, void* stream);
 int seld_m_gru_bwd(const float* dout, const float* h_f, const float* h_b, const float* saved_f, const float* saved_b, const float* U_f,
                    const float* U_b, float* dgx_f, float* dgx_b, float* dgh_f, float* dgh_b, int B, int S, int units, void* stream);
+/* The reference's configurable recurrent block, modules.RNN_block / RNN_stage (modules.py:64-83, 322-347): rnn_type GRU | LSTM, one direction or
+ * Bidirectional with merge_mode mul | concat | ave | sum.  Module operators under the seld_m_* contract above, named seld_rnn_* as the attention
+ * operators are named seld_attn_*: the seld_m_* set is the one tests/test_module_ops_gpu.py calls one by one; these have tests/test_rnn_gpu.py.
+ * Contract of the four recurrence entries: SELD_ERR_UNSUPPORTED for units != 128 before any
+ * other check (and, after the checks below, for S beyond 2^20); SELD_ERR_INVALID, before anything is enqueued, for a NULL required pointer, B or
+ * S < 1, and a half-given second direction.  A NULL gx_b (forward) / dh_b (backward) means ONE direction (bidirectional=False: grid B); every
+ * other *_b argument must then be NULL too.
+ * LSTM(128, return_sequences=True) recurrence (modules.py:337-340; Keras defaults: gate order i | f | c | o, one bias, tanh / sigmoid; lstm.hip):
+ * gx_* [B,S,512] = x*kernel + bias; U_* [128,512] = recurrent_kernel; h_*, c_* [B,S,128] (the backward layer writes at the time index it
+ * consumed); saved_* [B,S,128,4] (per unit: the activations i, f, g, o).  c_* and saved_* are written for the backward pass only: both NULL
+ * (inference) or both given, per call; h is bit-identical either way. */
+int seld_rnn_lstm_fwd(const float* gx_f, const float* gx_b, const float* U_f, const float* U_b, float* h_f, float* h_b, float* c_f, float* c_b,
+                      float* saved_f, float* saved_b, int B, int S, int units, void* stream);
+/* BPTT of the same: dh_* [B,S,128], the gradient w.r.t. each direction's output sequence -> dgx_* [B,S,512], the pre-activation gradients (no
+ * reset gate: input side and recurrent side are the same tensor).  dkernel = x^T dgx, dbias = colsum dgx, dU = h_prev^T dgx (seld_m_gemm_tn with
+ * seq = S, shift = -1 | +1), dx = dgx kernel^T. */
+int seld_rnn_lstm_bwd(const float* dh_f, const float* dh_b, const float* c_f, const float* c_b, const float* saved_f, const float* saved_b,
+                      const float* U_f, const float* U_b, float* dgx_f, float* dgx_b, int B, int S, int units, void* stream);
+/* GRU(128) per direction (modules.py:334-340): seld_m_gru_fwd without the 'mul' merge, seld_m_gru_bwd with the two directions' output gradients
+ * dh_f, dh_b used as given in place of dout * h_other.  The same kernels (gru.hip), other template instantiations. */
+int seld_rnn_gru_fwd(const float* gx_f, const float* gx_b, const float* U_f, const float* U_b, const float* brec_f, const float* brec_b, float* h_f,
+                     float* h_b, float* saved_f, float* saved_b, int B, int S, int units, void* stream);
+int seld_rnn_gru_bwd(const float* dh_f, const float* dh_b, const float* h_f, const float* h_b, const float* saved_f, const float* saved_b,
+                     const float* U_f, const float* U_b, float* dgx_f, float* dgx_b, float* dgh_f, float* dgh_b, int B, int S, int units,
+                     void* stream);
+/* Bidirectional(merge_mode) (modules.py:341-342) on h_f, h_b [rows, units]: out / dout [rows, units], or [rows, 2 units] for SELD_MERGE_CONCAT (the
+ * forward direction first).  Any units >= 1 (float4 where units % 4 == 0 and the pointers are 16-byte aligned); only SELD_MERGE_MUL reads h_* in the
+ * backward (they may be NULL otherwise); SELD_ERR_INVALID for an unknown mode. */
+#define SELD_MERGE_MUL 0
+#define SELD_MERGE_CONCAT 1
+#define SELD_MERGE_AVE 2
+#define SELD_MERGE_SUM 3
+int seld_rnn_merge_fwd(const float* h_f, const float* h_b, float* out, int64_t rows, int units, int mode, void* stream);
+int seld_rnn_merge_bwd(const float* dout, const float* h_f, const float* h_b, float* dh_f, float* dh_b, int64_t rows, int units, int mode,
+                       void* stream);
 int64_t seld_m_losses_scratch(int rows);
 int seld_m_losses(const float* sed, const float* doa, const float* y_sed, const float* y_doa, const seld_loss_cfg* cfg, float* sloss, float* dloss,
                   float* dsed_pre, float* ddoa_pre, float* scratch, int B, int S, int nc, void* stream);

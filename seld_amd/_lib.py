@@ -16,6 +16,7 @@ CSRC = os.path.join(_HERE, "csrc")
 
 SELD_OK = 0
 SELD_DOA_MSE, SELD_DOA_MMSE, SELD_DOA_MAE, SELD_DOA_MSLE = 0, 1, 2, 3
+SELD_MERGE = {"mul": 0, "concat": 1, "ave": 2, "sum": 3}      # Bidirectional's merge_mode -> SELD_MERGE_*
 SELD_DTYPE_F32 = 0
 SELD_DTYPE_F64 = 1
 SELD_DTYPE_BF16 = 2
@@ -169,6 +170,12 @@ SIGNATURES = {
     "seld_m_scale_hw_bwd_dx": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "seld_m_gru_fwd": (_I, [_P] * 11 + [_I] * 3 + [_P]),
     "seld_m_gru_bwd": (_I, [_P] * 11 + [_I] * 3 + [_P]),
+    "seld_rnn_lstm_fwd": (_I, [_P] * 10 + [_I] * 3 + [_P]),
+    "seld_rnn_lstm_bwd": (_I, [_P] * 10 + [_I] * 3 + [_P]),
+    "seld_rnn_gru_fwd": (_I, [_P] * 10 + [_I] * 3 + [_P]),
+    "seld_rnn_gru_bwd": (_I, [_P] * 12 + [_I] * 3 + [_P]),
+    "seld_rnn_merge_fwd": (_I, [_P, _P, _P, _L, _I, _I, _P]),
+    "seld_rnn_merge_bwd": (_I, [_P, _P, _P, _P, _P, _L, _I, _I, _P]),
     "seld_m_losses_scratch": (_L, [_I]),
     "seld_m_losses": (_I, [_P, _P, _P, _P, C.POINTER(LossCfg), _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "seld_m_adam": (_I, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _L, _P]),

@@ -105,7 +105,8 @@ __device__ __forceinline__ float quad_sum(float v) {
 // rm = 0 | 1 / (1 - rate), constant over the sequence, before it is used — GRUCell.call, implementation 2: `h_tm1 = h_tm1 * rec_dp_mask[0]`
 // ahead of the recurrent product AND of the blend z * h_tm1 + (1 - z) * hh.  The layer's output stays the unmasked h (stored to H);
 // the masked state is what the exchange buffer / h_own carry and, for the backward pass, what HM receives.
-template <int VAR, bool SAVE, bool PRIO = false, bool DROP = false>
+// UNI (seld_rnn_gru_fwd with one direction: reference modules.RNN_block, bidirectional=False): workgroup = clip, forward direction alone
+template <int VAR, bool SAVE, bool PRIO = false, bool DROP = false, bool UNI = false>
 __global__ __launch_bounds__(512) void gru_fwd_kernel(const float* __restrict__ gx_f, const float* __restrict__ gx_b,
                                                       const float* __restrict__ U_f, const float* __restrict__ U_b,
                                                       const float* __restrict__ brec_f, const float* __restrict__ brec_b,
@@ -113,7 +114,7 @@ __global__ __launch_bounds__(512) void gru_fwd_kernel(const float* __restrict__ 
                                                       float* __restrict__ sv_f, float* __restrict__ sv_b, int S,
                                                       const float* __restrict__ rm_f = nullptr, const float* __restrict__ rm_b = nullptr,
                                                       float* __restrict__ hm_f = nullptr, float* __restrict__ hm_b = nullptr) {
-    const int b = blockIdx.x >> 1, dir = blockIdx.x & 1;
+    const int b = UNI ? blockIdx.x : blockIdx.x >> 1, dir = UNI ? 0 : blockIdx.x & 1;
     const float* gx = (dir ? gx_b : gx_f) + (size_t)b * S * GRU_G;
     const float* U = dir ? U_b : U_f;
     const float* brec = dir ? brec_b : brec_f;
@@ -373,6 +374,13 @@ int launch_gru_fwd(hipStream_t st, const float* gx_f, const float* gx_b, const f
     return 0;
 }
 
+// seld_rnn_gru_fwd with one direction: the default step body (VAR 1, falling issue priority), grid B
+int launch_gru_fwd_uni(hipStream_t st, const float* gx, const float* U, const float* brec, float* h, float* sv, int B, int S) {
+    if (sv) hipLaunchKernelGGL((gru_fwd_kernel<1, true, true, false, true>), dim3(B), dim3(512), 0, st, gx, nullptr, U, nullptr, brec, nullptr, h, nullptr, sv, nullptr, S);
+    else hipLaunchKernelGGL((gru_fwd_kernel<1, false, true, false, true>), dim3(B), dim3(512), 0, st, gx, nullptr, U, nullptr, brec, nullptr, h, nullptr, sv, nullptr, S);
+    return 0;
+}
+
 // ------------------------------------------------------------------------------------------------
 // BPTT.  Per step (reverse of the forward processing order):
 //   dh = dout[t]*h_other[t] + carry
@@ -400,7 +408,10 @@ __device__ __forceinline__ float row16_allsum(float v) {
 // region and the step is one basic block; (c) the exchange write is pinned ahead of the output stores.
 // DROP (see gru_fwd_kernel): h_prev is the MASKED state sequence (hm_*, written by the forward), and the gradient carried to the previous step
 // is the gradient w.r.t. that masked state times the mask: carry = rm * (dh z + dgh U^T); h_other (the merge partner) stays the unmasked output
-template <int VAR, bool PRIO = false, bool DROP = false>
+// MODE (seld_rnn_gru_bwd: reference modules.RNN_block, any merge_mode): 0 = the gradient of the 'mul' merge is formed here, dh = dout * h_other;
+// 1 = dout / dh_b ARE the two directions' output gradients, used as given (the h_other slot of the staged row repeats them, unread); 2 = the same
+// with one direction (workgroup = clip)
+template <int VAR, bool PRIO = false, bool DROP = false, int MODE = 0>
 __global__ __launch_bounds__(512) void gru_bwd_kernel(const float* __restrict__ dout, const float* __restrict__ h_f,
                                                       const float* __restrict__ h_b, const float* __restrict__ sv_f,
                                                       const float* __restrict__ sv_b, const float* __restrict__ U_f,
@@ -408,11 +419,12 @@ __global__ __launch_bounds__(512) void gru_bwd_kernel(const float* __restrict__ 
                                                       float* __restrict__ dgx_b, float* __restrict__ dgh_f,
                                                       float* __restrict__ dgh_b, int S,
                                                       const float* __restrict__ rm_f = nullptr, const float* __restrict__ rm_b = nullptr,
-                                                      const float* __restrict__ hm_f = nullptr, const float* __restrict__ hm_b = nullptr) {
-    const int b = blockIdx.x >> 1, dir = blockIdx.x & 1;
-    const float* dO = dout + (size_t)b * S * GRU_U;
+                                                      const float* __restrict__ hm_f = nullptr, const float* __restrict__ hm_b = nullptr,
+                                                      const float* __restrict__ dh_b = nullptr) {
+    const int b = MODE == 2 ? blockIdx.x : blockIdx.x >> 1, dir = MODE == 2 ? 0 : blockIdx.x & 1;
+    const float* dO = (MODE != 0 && dir ? dh_b : dout) + (size_t)b * S * GRU_U;
     const float* Hown = (DROP ? (dir ? hm_b : hm_f) : (dir ? h_b : h_f)) + (size_t)b * S * GRU_U;
-    const float* Hoth = (dir ? h_f : h_b) + (size_t)b * S * GRU_U;
+    const float* Hoth = MODE != 0 ? dO : (dir ? h_f : h_b) + (size_t)b * S * GRU_U;
     const float* sv = (dir ? sv_b : sv_f) + (size_t)b * S * 4 * GRU_U;
     const float* U = dir ? U_b : U_f;
     float* dgx = (dir ? dgx_b : dgx_f) + (size_t)b * S * GRU_G;
@@ -503,7 +515,8 @@ __global__ __launch_bounds__(512) void gru_bwd_kernel(const float* __restrict__ 
     const float m_z = (qr == 0 || qr == 3) ? 1.f : 0.f, m_r = qr == 1 ? 1.f : 0.f, m_h = qr == 2 ? 1.f : 0.f;
     auto pre = [&](const float* sbuf, int row) {
         const float* rp = sbuf + row * GRUB_ROW + jm;
-        k_do = rp[0] * rp[128];
+        if constexpr (MODE != 0) k_do = rp[0];
+        else k_do = rp[0] * rp[128];
         const float4 sg4 = *reinterpret_cast<const float4*>(sbuf + row * GRUB_ROW + 256 + 4 * jm);   // saved gates [unit][z r hh gh]
         const float c_z = sg4.x, c_r = sg4.y, c_hh = sg4.z, c_gh = sg4.w, hp = rp[768];
         const float kh = (1.f - c_z) * (1.f - c_hh * c_hh);
@@ -668,13 +681,24 @@ int launch_gru_bwd(hipStream_t st, const float* dout, const float* h_f, const fl
         if (!rm_b || !hm_f || !hm_b) return -1;
         auto kd = gru_bwd_kernel<1, false, true>;
         hipFuncSetAttribute(reinterpret_cast<const void*>(kd), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        hipLaunchKernelGGL(kd, dim3(2 * B), dim3(512), smem, st, dout, h_f, h_b, sv_f, sv_b, U_f, U_b, dgx_f, dgx_b, dgh_f, dgh_b, S, rm_f, rm_b, hm_f, hm_b);
+        hipLaunchKernelGGL(kd, dim3(2 * B), dim3(512), smem, st, dout, h_f, h_b, sv_f, sv_b, U_f, U_b, dgx_f, dgx_b, dgh_f, dgh_b, S, rm_f, rm_b, hm_f, hm_b, nullptr);
         return 0;
     }
     auto kern = (g_gru_var & 2) ? ((g_gru_var & 8) ? gru_bwd_kernel<1, true> : gru_bwd_kernel<1, false>) : gru_bwd_kernel<0, false>;
     hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
     hipLaunchKernelGGL(kern, dim3(2 * B), dim3(512), smem, st, dout, h_f, h_b, sv_f, sv_b, U_f, U_b, dgx_f, dgx_b,
-                       dgh_f, dgh_b, S, nullptr, nullptr, nullptr, nullptr);
+                       dgh_f, dgh_b, S, nullptr, nullptr, nullptr, nullptr, nullptr);
+    return 0;
+}
+
+// seld_rnn_gru_bwd: the two directions' output gradients as given (dh_b == nullptr: one direction, grid B); the default step body
+int launch_gru_bwd_dh(hipStream_t st, const float* dh_f, const float* dh_b, const float* h_f, const float* h_b, const float* sv_f, const float* sv_b,
+                      const float* U_f, const float* U_b, float* dgx_f, float* dgx_b, float* dgh_f, float* dgh_b, int B, int S) {
+    const size_t smem = (size_t)(2 * GRUB_CH * GRUB_ROW + 2 * GRUB_GL) * sizeof(float);
+    auto kern = dh_b ? gru_bwd_kernel<1, true, false, 1> : gru_bwd_kernel<1, true, false, 2>;
+    hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    hipLaunchKernelGGL(kern, dim3((dh_b ? 2 : 1) * B), dim3(512), smem, st, dh_f, h_f, h_b, sv_f, sv_b, U_f, U_b, dgx_f, dgx_b, dgh_f, dgh_b, S,
+                       nullptr, nullptr, nullptr, nullptr, dh_b);
     return 0;
 }
 

@@ -321,6 +321,45 @@ __global__ __launch_bounds__(256) void scale_hw_bwd_dx_kernel(const float* __res
     dx[e] = accumulate ? dx[e] + g : g;
 }
 
+// Bidirectional's merge of the two directions' outputs [rows, units] (Keras merge_mode; reference modules.py:341-342) and its gradient, one pass.
+// T = float4 when units % 4 == 0 and every pointer is 16-byte aligned (n and units then count float4), else float.
+// mode: SELD_MERGE_MUL | _CONCAT (out [rows, 2 units], the forward direction first) | _AVE | _SUM
+__device__ __forceinline__ float mul_(float a, float b) { return a * b; }
+__device__ __forceinline__ float4 mul_(float4 a, float4 b) { return make_float4(a.x * b.x, a.y * b.y, a.z * b.z, a.w * b.w); }
+__device__ __forceinline__ float add_(float a, float b) { return a + b; }
+__device__ __forceinline__ float4 add_(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
+__device__ __forceinline__ float half_(float a) { return 0.5f * a; }
+__device__ __forceinline__ float4 half_(float4 a) { return make_float4(0.5f * a.x, 0.5f * a.y, 0.5f * a.z, 0.5f * a.w); }
+template <typename T>
+__global__ __launch_bounds__(256) void rnn_merge_fwd_kernel(const T* __restrict__ hf, const T* __restrict__ hb, T* __restrict__ out, int64_t n,
+                                                            int units, int mode) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= n) return;
+    const T a = hf[e], b = hb[e];
+    if (mode == SELD_MERGE_CONCAT) {
+        const int64_t r = e / units;
+        out[e + r * units] = a;
+        out[e + (r + 1) * units] = b;
+    } else
+        out[e] = mode == SELD_MERGE_MUL ? mul_(a, b) : (mode == SELD_MERGE_AVE ? half_(add_(a, b)) : add_(a, b));
+}
+template <typename T>
+__global__ __launch_bounds__(256) void rnn_merge_bwd_kernel(const T* __restrict__ dout, const T* __restrict__ hf, const T* __restrict__ hb,
+                                                            T* __restrict__ dhf, T* __restrict__ dhb, int64_t n, int units, int mode) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= n) return;
+    if (mode == SELD_MERGE_CONCAT) {
+        const int64_t r = e / units;
+        dhf[e] = dout[e + r * units];
+        dhb[e] = dout[e + (r + 1) * units];
+        return;
+    }
+    const T d = dout[e];
+    if (mode == SELD_MERGE_MUL) { dhf[e] = mul_(d, hb[e]); dhb[e] = mul_(d, hf[e]); }      // the only mode that reads h_*
+    else { const T g = mode == SELD_MERGE_AVE ? half_(d) : d; dhf[e] = g; dhb[e] = g; }
+}
+inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
 inline unsigned nblk(int64_t n) { return (unsigned)((n + 255) / 256); }
 inline int ok() { return hipGetLastError() == hipSuccess ? SELD_OK : SELD_ERR_HIP; }
 
@@ -470,6 +509,73 @@ int seld_m_gru_bwd(const float* dout, const float* h_f, const float* h_b, const 
     if (units != 128) return SELD_ERR_UNSUPPORTED;
     if (!dout || !h_f || !h_b || !saved_f || !saved_b || !U_f || !U_b || !dgx_f || !dgx_b || !dgh_f || !dgh_b || B < 1 || S < 1) return SELD_ERR_INVALID;
     launch_gru_bwd((hipStream_t)stream, dout, h_f, h_b, saved_f, saved_b, U_f, U_b, dgx_f, dgx_b, dgh_f, dgh_b, B, S);
+    return ok();
+}
+/* ---- reference modules.RNN_block / RNN_stage (modules.py:64-83, 322-347): the LSTM recurrence (lstm.hip), the GRU recurrence per direction
+ * with the output gradients as given (gru.hip's kernels), Bidirectional's merge ----------------------------------------------------------- */
+#define RNN_MAX_S (1 << 20)      /* the kernels form in-sequence byte offsets in 32 bits: S * 2048 B < 2^31 */
+int seld_rnn_lstm_fwd(const float* gx_f, const float* gx_b, const float* U_f, const float* U_b, float* h_f, float* h_b, float* c_f, float* c_b,
+                      float* saved_f, float* saved_b, int B, int S, int units, void* stream) {
+    if (units != 128) return SELD_ERR_UNSUPPORTED;
+    if (!gx_f || !U_f || !h_f || B < 1 || S < 1 || (!c_f) != (!saved_f)) return SELD_ERR_INVALID;
+    if (gx_b ? (!U_b || !h_b || (!c_b) != (!c_f) || (!saved_b) != (!saved_f)) : (U_b || h_b || c_b || saved_b)) return SELD_ERR_INVALID;
+    if (S > RNN_MAX_S || B > 0x3fffffff) return SELD_ERR_UNSUPPORTED;
+    if (launch_lstm_fwd((hipStream_t)stream, gx_f, gx_b, U_f, U_b, h_f, h_b, c_f, c_b, saved_f, saved_b, B, S)) return SELD_ERR_HIP;
+    return ok();
+}
+int seld_rnn_lstm_bwd(const float* dh_f, const float* dh_b, const float* c_f, const float* c_b, const float* saved_f, const float* saved_b,
+                      const float* U_f, const float* U_b, float* dgx_f, float* dgx_b, int B, int S, int units, void* stream) {
+    if (units != 128) return SELD_ERR_UNSUPPORTED;
+    if (!dh_f || !c_f || !saved_f || !U_f || !dgx_f || B < 1 || S < 1) return SELD_ERR_INVALID;
+    if (dh_b ? (!c_b || !saved_b || !U_b || !dgx_b) : (c_b || saved_b || U_b || dgx_b)) return SELD_ERR_INVALID;      // a half-given backward side
+    if (S > RNN_MAX_S || B > 0x3fffffff) return SELD_ERR_UNSUPPORTED;
+    if (launch_lstm_bwd((hipStream_t)stream, dh_f, dh_b, c_f, c_b, saved_f, saved_b, U_f, U_b, dgx_f, dgx_b, B, S)) return SELD_ERR_HIP;
+    return ok();
+}
+int seld_rnn_gru_fwd(const float* gx_f, const float* gx_b, const float* U_f, const float* U_b, const float* brec_f, const float* brec_b, float* h_f,
+                     float* h_b, float* saved_f, float* saved_b, int B, int S, int units, void* stream) {
+    if (units != 128) return SELD_ERR_UNSUPPORTED;
+    if (!gx_f || !U_f || !brec_f || !h_f || B < 1 || S < 1) return SELD_ERR_INVALID;
+    if (gx_b ? (!U_b || !brec_b || !h_b || (!saved_b) != (!saved_f)) : (U_b || brec_b || h_b || saved_b)) return SELD_ERR_INVALID;
+    if (S > RNN_MAX_S || B > 0x3fffffff) return SELD_ERR_UNSUPPORTED;
+    if (gx_b) launch_gru_fwd((hipStream_t)stream, gx_f, gx_b, U_f, U_b, brec_f, brec_b, h_f, h_b, saved_f, saved_b, B, S);
+    else launch_gru_fwd_uni((hipStream_t)stream, gx_f, U_f, brec_f, h_f, saved_f, B, S);
+    return ok();
+}
+int seld_rnn_gru_bwd(const float* dh_f, const float* dh_b, const float* h_f, const float* h_b, const float* saved_f, const float* saved_b,
+                     const float* U_f, const float* U_b, float* dgx_f, float* dgx_b, float* dgh_f, float* dgh_b, int B, int S, int units,
+                     void* stream) {
+    if (units != 128) return SELD_ERR_UNSUPPORTED;
+    if (!dh_f || !h_f || !saved_f || !U_f || !dgx_f || !dgh_f || B < 1 || S < 1) return SELD_ERR_INVALID;
+    if (dh_b ? (!h_b || !saved_b || !U_b || !dgx_b || !dgh_b) : (h_b || saved_b || U_b || dgx_b || dgh_b)) return SELD_ERR_INVALID;
+    if (S > RNN_MAX_S || B > 0x3fffffff) return SELD_ERR_UNSUPPORTED;
+    launch_gru_bwd_dh((hipStream_t)stream, dh_f, dh_b, h_f, h_b, saved_f, saved_b, U_f, U_b, dgx_f, dgx_b, dgh_f, dgh_b, B, S);
+    return ok();
+}
+int seld_rnn_merge_fwd(const float* h_f, const float* h_b, float* out, int64_t rows, int units, int mode, void* stream) {
+    if (!h_f || !h_b || !out || rows < 1 || units < 1 || mode < SELD_MERGE_MUL || mode > SELD_MERGE_SUM) return SELD_ERR_INVALID;
+    int64_t n = rows * units;
+    if (n > (int64_t)0x7fffffff * 256) return SELD_ERR_UNSUPPORTED;
+    if (units % 4 == 0 && al16(h_f) && al16(h_b) && al16(out))
+        hipLaunchKernelGGL((rnn_merge_fwd_kernel<float4>), dim3(nblk(n / 4)), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const float4*>(h_f),
+                           reinterpret_cast<const float4*>(h_b), reinterpret_cast<float4*>(out), n / 4, units / 4, mode);
+    else
+        hipLaunchKernelGGL((rnn_merge_fwd_kernel<float>), dim3(nblk(n)), dim3(256), 0, (hipStream_t)stream, h_f, h_b, out, n, units, mode);
+    return ok();
+}
+int seld_rnn_merge_bwd(const float* dout, const float* h_f, const float* h_b, float* dh_f, float* dh_b, int64_t rows, int units, int mode,
+                       void* stream) {
+    if (!dout || !dh_f || !dh_b || rows < 1 || units < 1 || mode < SELD_MERGE_MUL || mode > SELD_MERGE_SUM) return SELD_ERR_INVALID;
+    if (mode == SELD_MERGE_MUL && (!h_f || !h_b)) return SELD_ERR_INVALID;
+    int64_t n = rows * units;
+    if (n > (int64_t)0x7fffffff * 256) return SELD_ERR_UNSUPPORTED;
+    const bool hal = mode != SELD_MERGE_MUL || (al16(h_f) && al16(h_b));
+    if (units % 4 == 0 && al16(dout) && al16(dh_f) && al16(dh_b) && hal)
+        hipLaunchKernelGGL((rnn_merge_bwd_kernel<float4>), dim3(nblk(n / 4)), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const float4*>(dout),
+                           reinterpret_cast<const float4*>(h_f), reinterpret_cast<const float4*>(h_b), reinterpret_cast<float4*>(dh_f),
+                           reinterpret_cast<float4*>(dh_b), n / 4, units / 4, mode);
+    else
+        hipLaunchKernelGGL((rnn_merge_bwd_kernel<float>), dim3(nblk(n)), dim3(256), 0, (hipStream_t)stream, dout, h_f, h_b, dh_f, dh_b, n, units, mode);
     return ok();
 }
 /* floats of caller scratch seld_m_losses needs for `rows` = B * S label frames */

@@ -282,8 +282,9 @@ def seldnet(input_shape, model_config, device=None, dtype: str = "float32"):
     mother_stage (modules.py:15-43, 184-298) builds a modules.ComposedSeldNet (layer-by-layer module operators) instead of a fused ctx; only
     there may SECOND be transformer_encoder_block / transformer_encoder_stage (modules.py:106-126, 379-407; modules.COMPOSED_SECOND) or
     conformer_encoder_block / conformer_encoder_stage (modules.py:129-152, 410-508; modules.CONFORMER_SECOND) or attention_block /
-    attention_stage (modules.py:155-180, 511-635; modules.ATTENTION_SECOND) — the fused contexts know bidirectional_GRU_block alone, and
-    conformer_encoder_stage / attention_stage as FIRST stay refused."""
+    attention_stage (modules.py:155-180, 511-635; modules.ATTENTION_SECOND) or RNN_block / RNN_stage (modules.py:64-83, 322-347;
+    modules.RNN_SECOND: GRU or LSTM of 128 units, one direction or Bidirectional with merge_mode mul | concat | ave | sum) — the fused contexts
+    know bidirectional_GRU_block alone, and conformer_encoder_stage / attention_stage / RNN_stage as FIRST stay refused."""
     if model_config.get("FIRST") in COMPOSED_FIRST:
         if dtype != "float32":
             raise ValueError("composed models compute in float32")

@@ -19,8 +19,12 @@ else).  There is no CPU or PyTorch fallback.
                                                   layers.RelPositionMultiHeadAttention (seld_relattn_* of relattn.hip), GLU (seld_glu_*), the
                                                   depthwise Conv1D module, LayerNormalization in front or behind
 
+  RNN_block / RNN_stage (modules.py:64-83, 322-347)                  GRU or LSTM (units 128: the recurrence kernels of gru.hip / lstm.hip), one direction or
+                                                  Bidirectional with merge_mode mul | concat | ave | sum (seld_rnn_*)
+
 `ComposedSeldNet` = models.seldnet(input_shape, model_config) for FIRST in {mother_block, mother_stage}, SECOND in {bidirectional_GRU_block,
-transformer_encoder_block, transformer_encoder_stage, conformer_encoder_block, conformer_encoder_stage, attention_block, attention_stage}: same surface as
+transformer_encoder_block, transformer_encoder_stage, conformer_encoder_block, conformer_encoder_stage, attention_block, attention_stage, RNN_block,
+RNN_stage}: same surface as
 seld_amd.models.SeldNet (variables in Keras creation order, get / set_weights, __call__, train.trainstep / teststep).  The three
 BASELINE configurations do NOT run through here — their blocks are fused kernels inside a seld_ctx (models.SeldNet)."""
 from __future__ import annotations
@@ -1044,6 +1048,122 @@ class AttentionStage:
     backward = TransformerEncoderStage.backward
 
 
+RNN_MERGE = ("mul", "concat", "ave", "sum")      # what tf.keras.layers.Bidirectional merges into ONE tensor
+
+
+def check_rnn_config(cfg: dict, stage: bool = False) -> None:
+    """reference modules.RNN_block / RNN_stage (modules.py:64-83, 322-347): the mandatory keys; what has no kernel here is refused, not ignored"""
+    who = f"RNN_{'stage' if stage else 'block'}"
+    for key in ("units",) + (("depth",) if stage else ()):
+        if key not in cfg:
+            raise ValueError(f"{who}: missing {key!r}")
+    if isinstance(cfg["units"], (list, tuple)) or int(cfg["units"]) != 128:
+        raise ValueError(f"{who}: units {cfg['units']!r}: the recurrence kernels are built for 128 units")
+    if stage and int(cfg["depth"]) < 1:
+        raise ValueError(f"{who}: depth >= 1")
+    if float(cfg.get("dropout_rate", 0.0) or 0.0) != 0.0:
+        raise ValueError(f"{who}: dropout / recurrent_dropout are not implemented on the composed path: dropout_rate must be 0")
+    if bool(cfg.get("bidirectional", True)) and cfg.get("merge_mode", "mul") not in RNN_MERGE:
+        # None makes Bidirectional return a LIST (the reference's graph breaks on it); 'avg' (the reference's comment) is rejected by Keras itself
+        raise ValueError(f"{who}: merge_mode {cfg.get('merge_mode')!r}: one of {RNN_MERGE}")
+
+
+class RNNBlock:
+    """reference modules.RNN_block (modules.py:322-347) on [B*S, D]: rnn_type 'GRU' -> GRU(128, reset_after=True), ANYTHING else -> LSTM(128)
+    (modules.py:334-337), return_sequences=True; bidirectional -> Bidirectional(merge_mode), whose variables are the forward layer's, then the
+    backward layer's (`{prefix}.fwd.*`, `{prefix}.bwd.*`; one direction: `{prefix}.*`).  With bidirectional=False merge_mode is ignored.
+    GRU: kernel (D, 384), recurrent_kernel (128, 384), bias (2, 384);  LSTM: kernel (D, 512), recurrent_kernel (128, 512), bias (512,)."""
+
+    def __init__(self, rt: _Rt, cfg: dict, S: int, D: int, prefix: str, B: int):
+        check_rnn_config(cfg)
+        self.rt, self.S, self.D, self.B, self.prefix = rt, int(S), int(D), B, prefix
+        self.lstm = cfg.get("rnn_type", "GRU") != "GRU"
+        self.bi = bool(cfg.get("bidirectional", True))
+        self.mode = _lib.SELD_MERGE[cfg.get("merge_mode", "mul")] if self.bi else None
+        G = self.G = 512 if self.lstm else 384
+        self.names = [f"{prefix}.fwd", f"{prefix}.bwd"] if self.bi else [prefix]
+        for n in self.names:
+            rt.var(f"{n}.kernel", (self.D, G)); rt.var(f"{n}.recurrent_kernel", (128, G)); rt.var(f"{n}.bias", (512,) if self.lstm else (2, 384))
+        self.out_dim = 256 if self.bi and cfg.get("merge_mode", "mul") == "concat" else 128
+        R, nd = B * self.S, len(self.names)
+        e = rt.empty
+        self.gx, self.h, self.sv = [e(R, G) for _ in range(nd)], [e(R, 128) for _ in range(nd)], [e(R, 512) for _ in range(nd)]
+        self.c = [e(R, 128) for _ in range(nd)] if self.lstm else None
+        self.dgx = [e(R, G) for _ in range(nd)]
+        self.dgh = [e(R, G) for _ in range(nd)] if not self.lstm else self.dgx      # no reset gate: one pre-activation gradient
+        self.dh = [e(R, 128) for _ in range(nd)] if self.bi else None
+        self.out = e(R, self.out_dim) if self.bi else None
+        self.din = e(R, self.D)
+        self.out_shape = (self.S, self.out_dim)
+
+    def _two(self, ts, none=False):
+        """the (forward, backward) pointer pair of a per-direction buffer list; one direction: (pointer, NULL)"""
+        p = self.rt.p
+        return (None, None) if none else (p(ts[0]), p(ts[1]) if self.bi else None)
+
+    def forward(self, x, B, training):
+        """x [B*S, D] (or any contiguous view of it) -> [B*S, out_dim]"""
+        rt, lib = self.rt, self.rt.lib
+        R = B * self.S
+        x = self.x = x.reshape(R, self.D)
+        for d, n in enumerate(self.names):
+            rt.gemm(x, rt.w(f"{n}.kernel"), rt.w(f"{n}.bias")[:self.G], self.gx[d], R, self.G, self.D)
+        U = self._two([rt.w(f"{n}.recurrent_kernel") for n in self.names])
+        if self.lstm:
+            rt.ck(lib.seld_rnn_lstm_fwd(*self._two(self.gx), *U, *self._two(self.h), *self._two(self.c, not training), *self._two(self.sv, not training),
+                                        B, self.S, 128, rt.st()))
+        else:
+            brec = self._two([rt.w(f"{n}.bias")[384:] for n in self.names])
+            rt.ck(lib.seld_rnn_gru_fwd(*self._two(self.gx), *U, *brec, *self._two(self.h), *self._two(self.sv, not training), B, self.S, 128, rt.st()))
+        if not self.bi:
+            return self.h[0][:R]
+        rt.ck(lib.seld_rnn_merge_fwd(rt.p(self.h[0]), rt.p(self.h[1]), rt.p(self.out), R, 128, self.mode, rt.st()))
+        return self.out[:R]
+
+    def backward(self, dy, B):
+        """dy [B*S, out_dim]: the output's gradient (after a training forward) -> the input's gradient [B*S, D] (a buffer of this block)"""
+        rt, lib = self.rt, self.rt.lib
+        R = B * self.S
+        dy = dy.reshape(R, self.out_dim)
+        if self.bi:
+            rt.ck(lib.seld_rnn_merge_bwd(rt.p(dy), rt.p(self.h[0]), rt.p(self.h[1]), rt.p(self.dh[0]), rt.p(self.dh[1]), R, 128, self.mode, rt.st()))
+            dh = self._two(self.dh)
+        else:
+            self._dy = dy.contiguous()      # kept: the kernel reads it after this call returns
+            dh = (rt.p(self._dy), None)
+        U = self._two([rt.w(f"{n}.recurrent_kernel") for n in self.names])
+        if self.lstm:
+            rt.ck(lib.seld_rnn_lstm_bwd(*dh, *self._two(self.c), *self._two(self.sv), *U, *self._two(self.dgx), B, self.S, 128, rt.st()))
+        else:
+            rt.ck(lib.seld_rnn_gru_bwd(*dh, *self._two(self.h), *self._two(self.sv), *U, *self._two(self.dgx), *self._two(self.dgh), B, self.S, 128,
+                                       rt.st()))
+        for d, n in enumerate(self.names):
+            gb = rt.g(f"{n}.bias")
+            rt.gemm_tn(self.x, self.dgx[d], rt.g(f"{n}.kernel"), gb[:self.G], R, self.D, self.G)
+            # recurrent kernel: h_prev^T dgh — the forward direction saw h[t-1], the backward direction h[t+1]
+            rt.gemm_tn(self.h[d], self.dgh[d], rt.g(f"{n}.recurrent_kernel"), None if self.lstm else gb[384:], R, 128, self.G, seq=self.S,
+                       shift=-1 if d == 0 else 1)
+            rt.gemm(self.dgx[d], rt.w(f"{n}.kernel"), None, self.din, R, self.D, self.G, transb=1, accumulate=d)
+        return self.din[:R]
+
+
+class RNNStage:
+    """reference modules.RNN_stage (modules.py:64-83): `depth` RNN_blocks of the same configuration; behind a 'concat' block the next one reads 256
+    features"""
+
+    def __init__(self, rt: _Rt, cfg: dict, S: int, D: int, prefix: str, B: int, depth=None):
+        check_rnn_config(cfg, depth is None)
+        depth = int(cfg["depth"]) if depth is None else int(depth)
+        self.blocks = []
+        for i in range(depth):
+            self.blocks.append(RNNBlock(rt, cfg, S, D, f"{prefix}{i}", B))
+            D = self.blocks[-1].out_dim
+        self.S, self.D, self.out_dim, self.out_shape = int(S), int(self.blocks[0].D), int(D), (int(S), int(D))
+
+    forward = TransformerEncoderStage.forward
+    backward = TransformerEncoderStage.backward
+
+
 class MotherBlock:
     """reference modules.mother_block (modules.py:184-298)."""
 
@@ -1247,12 +1367,14 @@ class MotherBlock:
 COMPOSED_SECOND = ("bidirectional_GRU_block", "transformer_encoder_block", "transformer_encoder_stage")
 CONFORMER_SECOND = ("conformer_encoder_block", "conformer_encoder_stage")      # SECOND as well: COMPOSED_SECOND + CONFORMER_SECOND
 ATTENTION_SECOND = ("attention_block", "attention_stage")                          # SECOND as well, routed as CONFORMER_SECOND is
+RNN_SECOND = ("RNN_block", "RNN_stage")                                            # SECOND as well; the heads read the stage's out_dim
 
 
 class ComposedSeldNet:
     """models.seldnet(input_shape, model_config) (reference models.py:18-32) composed from module operators: FIRST = mother_block |
     mother_stage, SECOND = bidirectional_GRU_block (units 128: the recurrence kernels) | transformer_encoder_block | transformer_encoder_stage |
-    conformer_encoder_block | conformer_encoder_stage | attention_block | attention_stage (d_model = F * C of the FIRST stage's output),
+    conformer_encoder_block | conformer_encoder_stage | attention_block | attention_stage (d_model = F * C of the FIRST stage's output) |
+    RNN_block | RNN_stage (GRU or LSTM, units 128; the heads read 128 features, or 256 behind merge_mode 'concat'),
     SED / DOA = simple_dense_block (kernel_size 1).  The conformer and attention stages' BatchNormalization statistics join `state_variables`
     behind the FIRST block's."""
 
@@ -1261,7 +1383,7 @@ class ComposedSeldNet:
         if not torch.cuda.is_available():
             raise RuntimeError("seld_amd needs a HIP device: there is no CPU fallback")
         cfg = canonical_config(model_config)
-        seconds = COMPOSED_SECOND + CONFORMER_SECOND + ATTENTION_SECOND
+        seconds = COMPOSED_SECOND + CONFORMER_SECOND + ATTENTION_SECOND + RNN_SECOND
         if cfg.get("SECOND") not in seconds or cfg.get("SED") != "simple_dense_block" or cfg.get("DOA") != "simple_dense_block":
             raise ValueError(f"composed models: SECOND in {seconds}, SED / DOA = simple_dense_block")
         self._dev = torch.device("cuda", torch.cuda.current_device() if device is None else int(device))
@@ -1299,6 +1421,11 @@ class ComposedSeldNet:
             stage = cfg["SECOND"] == "attention_stage"
             check_attention_config(sa, stage, feat)
             self.tf = AttentionStage(rt, sa, self.S, feat, "at", B, depth=None if stage else 1)
+        elif cfg["SECOND"] in RNN_SECOND:
+            stage = cfg["SECOND"] == "RNN_stage"
+            check_rnn_config(sa, stage)
+            self.tf = RNNStage(rt, sa, self.S, feat, "rnn", B, depth=None if stage else 1)
+            fin = self.tf.out_dim
         elif cfg["SECOND"] != "bidirectional_GRU_block":
             stage = cfg["SECOND"] == "transformer_encoder_stage"
             check_transformer_config(sa, stage)
@@ -1349,8 +1476,13 @@ class ComposedSeldNet:
         w = np.zeros(self.n_params, np.float32)
         for n, off, sh in self.variables:
             k = int(np.prod(sh))
-            if n.endswith("recurrent_kernel"):
+            if n.endswith("recurrent_kernel") and sh[1] == 512:      # LSTM: Keras' Orthogonal over the whole [128, 512]
+                q, r = np.linalg.qr(rng.standard_normal((512, 128)))
+                w[off:off + k] = (q * np.sign(np.diag(r))).T.reshape(-1)
+            elif n.endswith("recurrent_kernel"):
                 w[off:off + k] = np.concatenate([np.linalg.qr(rng.standard_normal((128, 128)))[0] for _ in range(3)], axis=1).reshape(-1)
+            elif n.startswith("rnn") and n.endswith("bias") and sh == (512,):
+                w[off + 128:off + 256] = 1.0                          # LSTM unit_forget_bias: the forget slice of i | f | c | o
             elif n.endswith(("kernel", "pos_bias_u", "pos_bias_v")):      # the two biases take the kernel initializer (layers.py:343-356)
                 fan_in = int(np.prod(sh[:-1])); fan_out = int(sh[-1]) * (int(np.prod(sh[:-2])) if len(sh) > 2 else 1)
                 lim = math.sqrt(6.0 / (fan_in + fan_out))
@@ -1662,3 +1794,28 @@ def attention_block(model_config: dict):
 def attention_stage(model_config: dict):
     """reference modules.attention_stage(model_config) (modules.py:155-180): `depth` blocks"""
     return _attention_factory(model_config, True)
+
+
+def _rnn_factory(model_config: dict, stage: bool):
+    check_rnn_config(model_config, stage)
+
+    def build(input_shape, rt=None, prefix="rnn"):
+        """input_shape [B, S, D] or [B, S, F, C] (layers.force_1d_inputs: D = F * C)"""
+        sh = [int(v) for v in input_shape]
+        if len(sh) not in (3, 4):
+            raise ValueError("RNN_block: input [B, S, D] or [B, S, F, C]")
+        B, S, D = sh[0], sh[1], int(np.prod(sh[2:]))
+        rt = rt or _Rt(torch.device("cuda", torch.cuda.current_device()))
+        return RNNStage(rt, model_config, S, D, prefix, B, depth=None if stage else 1)
+    return build
+
+
+def RNN_block(model_config: dict):
+    """reference modules.RNN_block(model_config) (modules.py:322-347) -> a factory `(input_shape) -> a one-block RNNStage` (forward(x, B, training)
+    / backward(dy, B) on [B*S, D] -> [B*S, out_dim]); configuration errors are raised here, without a device."""
+    return _rnn_factory(model_config, False)
+
+
+def RNN_stage(model_config: dict):
+    """reference modules.RNN_stage(model_config) (modules.py:64-83): `depth` blocks"""
+    return _rnn_factory(model_config, True)
