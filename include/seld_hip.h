@@ -223,6 +223,41 @@ int seld_test_step(seld_ctx* ctx, const float* x, const float* y_sed, const floa
 /* sum(mask) of losses.MMSE for this batch (1 float, device) — for the DP denominator all-reduce */
 int seld_mmse_den(seld_ctx* ctx, const float* y_doa, float* den);
 
+/* ---- the step of the reference's second training script (trainv2.py:23-56; DESIGN.md "The trainv2 recipe"): class-weighted BCE or
+ * focal loss with optional label smoothing, losses.MMSE_with_cls_weights, an L2 kernel regulariser, AGC on every step, AdaBelief, and
+ * stochastic weight averaging.  Purely additive: train.py's entry points above are unchanged. */
+#define SELD_SED_BCE 0   /* mean(K.binary_crossentropy(t, p) * cls_weights) (trainv2.py:41, :293) */
+#define SELD_SED_FOCAL 1 /* mean(losses.focal_loss(t, p) * cls_weights) = focal * mean(cls_weights) (losses.py:29-34: the loss is a scalar) */
+#define SELD_V2_MAX_CLASSES 32
+typedef struct seld_v2_cfg {
+    int32_t sed_loss;                         /* SELD_SED_BCE | SELD_SED_FOCAL */
+    float w_sed, w_doa;                       /* loss_weights */
+    float label_smoothing;                    /* [0, 1): t = y (1 - ls) + 0.5 ls when > 0 (trainv2.py:38-39) */
+    float focal_alpha, focal_gamma;           /* losses.focal_loss defaults: 0.25, 2 */
+    float cls_weights[SELD_V2_MAX_CLASSES];   /* the first n_classes are read (trainv2.py:25-30: mean(train_samples) / train_samples) */
+} seld_v2_cfg;
+/* seld_train_fwd_bwd with the v2 loss stage: objective = sloss w_sed + dloss w_doa, both scalars (sloss, dloss: 1 float each, may be
+ * NULL).  The weighted MMSE denominator is computed on the device from the labels.  SELD_ERR_INVALID, before anything is enqueued, for a
+ * NULL required pointer, n_classes > SELD_V2_MAX_CLASSES, an unknown sed_loss or label_smoothing outside [0, 1); SELD_ERR_UNSUPPORTED on a
+ * context with a data-parallel communicator (the reference defines no weighted denominator / loss scaling across ranks). */
+int seld_train_fwd_bwd_v2(seld_ctx* ctx, const float* x, const float* y_sed, const float* y_doa, const seld_v2_cfg* cfg, float* sed,
+                          float* doa, float* sloss, float* dloss);
+/* utils.apply_kernel_regularizer (utils.py:343-350): flags[i] != 0 marks trainable variable i (seld_variable_info order) as carrying the L2
+ * term l2 sum(w^2) in the objective.  Default: none.  SELD_ERR_INVALID unless n_trainable_variables == seld_variable_count(ctx, 1). */
+int seld_set_regularized(seld_ctx* ctx, const int32_t* flags, int n_trainable_variables);
+/* The optimizer stage of trainv2.trainstep in two launches, whatever the number of variables: g' = (g + 2 l2 w flag) * clip, the clip of
+ * utils.adaptive_clip_grad (utils.py:86-96; clip_factor 0.01 in the reference, <= 0: no clipping) per unit on the regularised gradient; then
+ * utils.AdaBelief (utils.py:157-182, amsgrad=False): m = b1 m + (1 - b1) g', v = b2 v + (1 - b2) (g' - m)^2 with the UPDATED m,
+ * w -= lr sqrt(1 - b2^t) / (1 - b1^t) m / (sqrt(v) + eps).  The moments are the context's Adam slots (seld_get_adam_host / seld_set_adam_host
+ * serve both optimizers); g' is written back to the gradient buffer. */
+int seld_v2_opt_step(seld_ctx* ctx, float lr, float beta1, float beta2, float eps, float l2, float clip_factor);
+/* swa.SWA (swa.py:25-32) over the weights AND the BatchNorm moving statistics (model.get_weights() holds both): update folds the current
+ * values into the running mean swa = (swa cnt + w) / (cnt + 1) in fp32 (the first update copies; buffers are allocated then); count = the
+ * number of updates so far; apply = on_train_end's model.set_weights(swa_weights) — SELD_ERR_INVALID before the first update. */
+int seld_swa_update(seld_ctx* ctx);
+int seld_swa_count(const seld_ctx* ctx);
+int seld_swa_apply(seld_ctx* ctx);
+
 /* ---- feature stage: replaces feature_extractor.extract_features (feature_extractor.py:53-88) and, for the
  * in-loop variant, apply_normalizer + preprocess_features_labels (:117-149, :226-234).
  * complex_spec (:153-173) = torchaudio spectrogram(hann(win_length) periodic, n_fft, hop, power=None, center, reflect);
@@ -397,6 +432,15 @@ int seld_k_losses(const float* sed, const float* doa, const float* y_sed, const 
 /* Keras Adam update (train.py:311,34); step is 1-based */
 int seld_k_adam(float* theta, const float* g, float* m, float* v, int64_t n, float lr, float beta1,
                 float beta2, float eps, int64_t step);
+/* The v2 loss stage alone (trainv2.py:38-44), like seld_k_losses: sed / y_sed [B,S,nc], doa / y_doa [B,S,3nc]; sloss, dloss 1 float each;
+ * dsed_pre / ddoa_pre (may be NULL): the objective's gradients w.r.t. the heads' pre-activations.  Refusals as seld_train_fwd_bwd_v2. */
+int seld_k_losses_v2(const float* sed, const float* doa, const float* y_sed, const float* y_doa, const seld_v2_cfg* cfg, float* sloss,
+                     float* dloss, float* dsed_pre, float* ddoa_pre, int B, int S, int nc);
+/* The v2 optimizer stage alone, like seld_k_adam: n_vars variables in flat buffers of n floats, variable i = [rows[i]][cols[i]] at off[i]
+ * with one clip unit per column (HOST arrays; offsets ascending, no overlap), reg[i] != 0: regularised.  step is 1-based. */
+int seld_k_reg_agc_adabelief(float* theta, float* g, float* m, float* v, int64_t n, int n_vars, const int64_t* off_host,
+                             const int32_t* rows_host, const int32_t* cols_host, const int32_t* reg_host, float lr, float beta1, float beta2,
+                             float eps, float l2, float clip_factor, int64_t step);
 /* Test aid (tests/test_model_gpu.py::test_parity_given_identical_routing): after seld_train_fwd_bwd, the routing decision the
  * backward pass took for every pooled element of conv block `block` — MaxPooling2D's argmax as window position row*pf + col and
  * ReLU's gate (pooled value > 0) — as two device byte arrays [B, H/pt, W/pf, 64].  MaxPoolGrad / ReluGrad of the reference

@@ -54,6 +54,15 @@ class LossCfg(C.Structure):
                 ("sed_grad_scale", C.c_float), ("mmse_den", C.c_float)]
 
 
+SELD_SED_BCE, SELD_SED_FOCAL = 0, 1
+V2_MAX_CLASSES = 32
+
+
+class V2Cfg(C.Structure):
+    _fields_ = [("sed_loss", C.c_int32), ("w_sed", C.c_float), ("w_doa", C.c_float), ("label_smoothing", C.c_float),
+                ("focal_alpha", C.c_float), ("focal_gamma", C.c_float), ("cls_weights", C.c_float * V2_MAX_CLASSES)]
+
+
 _P = C.c_void_p
 _I = C.c_int
 _L = C.c_int64
@@ -101,6 +110,12 @@ SIGNATURES = {
     "seld_train_step": (_I, [_P, _P, _P, _P, C.POINTER(LossCfg), _F, _I, _P, _P, _P, _P]),
     "seld_test_step": (_I, [_P, _P, _P, _P, C.POINTER(LossCfg), _P, _P, _P, _P]),
     "seld_mmse_den": (_I, [_P, _P, _P]),
+    "seld_train_fwd_bwd_v2": (_I, [_P, _P, _P, _P, C.POINTER(V2Cfg), _P, _P, _P, _P]),
+    "seld_set_regularized": (_I, [_P, C.POINTER(C.c_int32), _I]),
+    "seld_v2_opt_step": (_I, [_P, _F, _F, _F, _F, _F, _F]),
+    "seld_swa_update": (_I, [_P]),
+    "seld_swa_count": (_I, [_P]),
+    "seld_swa_apply": (_I, [_P]),
     "seld_feat_create": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(_P)]),
     "seld_feat_destroy": (None, [_P]),
     "seld_feat_last_error": (C.c_char_p, [_P]),
@@ -144,6 +159,9 @@ SIGNATURES = {
     "seld_k_gru_bwd": (_I, [_P] * 11 + [_I] * 3),
     "seld_k_losses": (_I, [_P, _P, _P, _P, C.POINTER(LossCfg), _P, _P, _P, _P, _I, _I, _I]),
     "seld_k_adam": (_I, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _L]),
+    "seld_k_losses_v2": (_I, [_P, _P, _P, _P, C.POINTER(V2Cfg), _P, _P, _P, _P, _I, _I, _I]),
+    "seld_k_reg_agc_adabelief": (_I, [_P, _P, _P, _P, _L, _I, C.POINTER(_L), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                 _F, _F, _F, _F, _F, _F, _L]),
     "seld_debug_pool_routing": (_I, [_P, _I, _P, _P]),
     "seld_debug_relu_output": (_I, [_P, _I, _I, _P, _L, C.POINTER(C.c_int64)]),
     "seld_debug_set_routing": (_I, [_P, _I, _L, _P, _P]),

@@ -460,6 +460,7 @@ int seld_create(const seld_arch* a, int B, int T, int dtype, int device, seld_ct
     ALLOC(c->loss_scratch, (size_t)loss_scratch_floats((int)rows));
     ALLOC(c->den_dev, 4); ALLOC(c->loss_out, rows + 4);
 #undef ALLOC
+    { int rc_ = v2_tables_create(c); if (rc_) { g_create_err = c->err; seld_destroy(c); return rc_; } }
     if (hipDeviceSynchronize() != hipSuccess) { seld_destroy(c); return fail(nullptr, SELD_ERR_HIP, "device sync after allocation failed"); }
     *out = c;
     return SELD_OK;

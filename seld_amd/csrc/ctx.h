@@ -172,6 +172,11 @@ struct seld_ctx {
     float *loss_scratch = nullptr, *den_dev = nullptr, *loss_out = nullptr;
     float *fin_sl = nullptr, *fin_dl = nullptr;   // deferred loss finalize of the running training step
     int fin_doa_loss = 0;
+    // trainv2 (trainv2.hip): device tables of the regulariser + AGC + AdaBelief stage, built once by seld_create from `tr` — column tiles of the
+    // unit-norm kernel, segments of the update kernel, one regularised flag per variable (seld_set_regularized), one clip factor per unit
+    struct V2Tab { void *tiles = nullptr, *segs = nullptr; int32_t* reg = nullptr; float* scale = nullptr; int ntiles = 0, nsegs = 0; } v2;
+    float *swa_w = nullptr, *swa_s = nullptr;     // stochastic weight averaging (seld_swa_update): running means of params / state, allocated on first use
+    int swa_cnt = 0;
     std::vector<void*> allocs;
     std::string err;
     int prof = 0;   // 0 off, 1 major kernel groups, 2 every group
@@ -244,6 +249,9 @@ bool rn_c1_direct(const RnBlock& R);
 // ---- the passes (forward.hip, backward.hip)
 int forward_impl(seld_ctx* c, const float* x, float* sed, float* doa, int training, bool save);
 int backward_impl(seld_ctx* c, const float* x);
+
+// ---- trainv2 (trainv2.hip): the v2 optimizer stage's device tables, at the end of seld_create
+int v2_tables_create(seld_ctx* c);
 
 // ---- data parallelism (dp.hip)
 // in-place SUM over the ranks of the library's communicator; 0 = enqueued

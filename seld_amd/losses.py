@@ -46,8 +46,30 @@ class _MSLE(_MSE):
     code = _lib.SELD_DOA_MSLE
 
 
+class _MMSEWithClsWeights(_Loss):
+    """losses.MMSE_with_cls_weights (losses.py:16-26): MMSE whose mask is multiplied by the class weights, scalar.  The DOA loss of
+    trainv2.generate_trainstep; without weights (trainv2.generate_teststep calls it so) it is losses.MMSE."""
+    name = "MMSE_with_cls_weights"
+    code = _lib.SELD_DOA_MMSE
+
+
+class _FocalLoss(_Loss):
+    """losses.focal_loss (losses.py:29-34): scalar mean of -t a (1 - p)^g log p - (1 - t) a p^g log(1 - p), p clipped to [1e-7, 1 - 1e-7].
+    `focal_loss` is the reference's function with its defaults; `focal_loss(alpha=, gamma=)` gives a selector with other constants."""
+    name = "focal_loss"
+    code = _lib.SELD_SED_FOCAL
+
+    def __init__(self, alpha: float = 0.25, gamma: float = 2.0):
+        self.alpha, self.gamma = float(alpha), float(gamma)
+
+    def __call__(self, alpha: float = 0.25, gamma: float = 2.0):
+        return _FocalLoss(alpha, gamma)
+
+
 MSE = _MSE()
 MMSE = _MMSE()
+MMSE_with_cls_weights = _MMSEWithClsWeights()
+focal_loss = _FocalLoss()
 MAE = _MAE()
 MSLE = _MSLE()
 
