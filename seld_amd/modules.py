@@ -22,6 +22,16 @@ else).  There is no CPU or PyTorch fallback.
   RNN_block / RNN_stage (modules.py:64-83, 322-347)                  GRU or LSTM (units 128: the recurrence kernels of gru.hip / lstm.hip), one direction or
                                                   Bidirectional with merge_mode mul | concat | ave | sum (seld_rnn_*)
 
+The shared pieces, each in one place:
+  Linear               GEMM + bias with its backward: Dense, Conv1D and Conv2D (im2col in front of it where the window is wider than one
+                       sample), the heads' layers (Head) and the squeeze-and-excitation pair (_SqueezeExcite)
+  _FeedForward         layer -> activation -> layer over Dense or Conv1D: the transformer's, both of the conformer's, the attention block's
+  _ConvTail            depthwise Conv1D -> BatchNormalization -> swish -> pointwise Conv1D: the conformer's and the attention block's
+  _Attention           the attention layers' buffers; _HeadMajorAttention: the reference's own two layers' packing and projections
+  _Recurrent           the recurrent blocks' variables, input projections and weight gradients (RNNBlock, BidirectionalGRUBlock)
+  Stage, SECOND_KINDS  every SECOND kind is a Stage of blocks of one class; the table names the class, its config check and its prefix, and
+                       the eight factories and ComposedSeldNet build from it (_second_factory, _build_second)
+
 `ComposedSeldNet` = models.seldnet(input_shape, model_config) for FIRST in {mother_block, mother_stage}, SECOND in {bidirectional_GRU_block,
 transformer_encoder_block, transformer_encoder_stage, conformer_encoder_block, conformer_encoder_stage, attention_block, attention_stage, RNN_block,
 RNN_stage}: same surface as
@@ -32,7 +42,7 @@ from __future__ import annotations
 import copy
 import ctypes as C
 import math
-from typing import Dict, List, Sequence, Tuple
+from typing import Dict, List, Tuple
 
 import numpy as np
 import torch
@@ -46,6 +56,36 @@ LN_EPS = 1e-3      # tf.keras.layers.LayerNormalization's default epsilon
 
 def safe_tuple(v, n=2):
     return tuple(int(a) for a in v) if isinstance(v, (list, tuple)) else (int(v),) * n
+
+
+def _check_activation(cfg: dict, default: str, key: str = "activation") -> None:
+    if cfg.get(key, default) not in ACT:
+        raise ValueError(f"{key} {cfg.get(key)!r}: the module operators know {sorted(k for k in ACT if k)}")
+
+
+def _check_no_dropout(cfg: dict, who: str) -> None:
+    if "dropout_rate" not in cfg or float(cfg["dropout_rate"]) != 0.0:
+        raise ValueError(f"{who}: there is no dropout kernel on this path and the reference's default dropout_rate is 0.1: "
+                         "dropout_rate must be present and 0")
+
+
+def _check_key_dim(key_dim) -> None:
+    dk = int(key_dim)
+    if dk < 8 or dk > 64 or dk % 8:
+        raise ValueError(f"key_dim {dk}: the attention kernels take a multiple of 8 from 8 to 64")
+
+
+def _check_pos_encoding(cfg: dict, who: str, D, relative: bool = False) -> None:
+    """relative: the table feeds RelPositionMultiHeadAttention, which cannot do without one (reference modules.py:549-551)"""
+    pe = cfg.get("pos_encoding", "basic")
+    if pe == "rff":
+        raise ValueError(f"{who}: pos_encoding 'rff' draws its frequencies from tf.random.normal and stores them nowhere: it cannot be reproduced")
+    if pe not in ("basic", None):
+        raise ValueError(f"{who}: pos_encoding {pe!r}: 'basic' or None")
+    if relative and pe is None:
+        raise ValueError("relative pos encoding demands any types of encoding except the null one")
+    if pe == "basic" and D is not None and int(D) % 2:
+        raise ValueError(f"{who}: pos_encoding 'basic' on an odd width {D}: the reference's table has 2 * (D // 2) columns and does not broadcast")
 
 
 def check_mother_config(cfg: dict) -> None:
@@ -70,8 +110,7 @@ def check_mother_config(cfg: dict) -> None:
     if f[1] == 0 and tuple(strides) != (1, 1):
         raise ValueError("if strides are set, the second layer must be active")
     for key in ("activation", "se_activation"):
-        if cfg.get(key, "relu") not in ACT:
-            raise ValueError(f"{key} {cfg.get(key)!r}: the module operators know {sorted(k for k in ACT if k)}")
+        _check_activation(cfg, "relu", key)
 
 
 def dead_layers(cfg: dict):
@@ -169,48 +208,65 @@ class _Rt:
 
 
 
-class Conv2D:
-    """tf.keras.layers.Conv2D(filters, k, strides, padding='same', use_bias=True): im2col (skipped for 1x1 stride 1) + the MFMA GEMM."""
+class Linear:
+    """A layer that is exactly GEMM + bias on [rows, K]: variables `kernel` (of `kshape`, any shape whose product is K * N; default
+    [K, N]) and `bias` [N], the output buffer `z`.  backward: kernel / bias gradients by seld_m_gemm_tn; dx (+)= dz kernel^T (dx None: not
+    needed).  The buffers hold the LARGEST batch's rows; a call works on its own `rows` only."""
+
+    def __init__(self, rt: _Rt, name: str, rows: int, K: int, N: int, kshape=None):
+        self.rt, self.name, self.K, self.N = rt, name, int(K), int(N)
+        rt.var(f"{name}.kernel", kshape or (self.K, self.N))
+        rt.var(f"{name}.bias", (self.N,))
+        self.z = rt.empty(rows, self.N)
+
+    def forward(self, x, rows):
+        rt = self.rt
+        self.a = x
+        rt.gemm(x, rt.w(f"{self.name}.kernel"), rt.w(f"{self.name}.bias"), self.z, rows, self.N, self.K)
+        return self.z[:rows]
+
+    def backward(self, dz, dx, rows, accumulate=0):
+        rt = self.rt
+        rt.gemm_tn(self.a, dz, rt.g(f"{self.name}.kernel"), rt.g(f"{self.name}.bias"), rows, self.K, self.N)
+        if dx is not None:
+            rt.gemm(dz, rt.w(f"{self.name}.kernel"), None, dx, rows, self.K, self.N, transb=1, accumulate=int(accumulate))
+
+
+class Dense(Linear):
+    """tf.keras.layers.Dense(units) on the last axis of [rows, Cin]: Dense(rt, name, rows, Cin, units); kernel [Cin, units]."""
+
+
+class Conv2D(Linear):
+    """tf.keras.layers.Conv2D(filters, k, strides, padding='same', use_bias=True): im2col (skipped for 1x1 stride 1) + the MFMA GEMM over
+    the K = k k Cin columns."""
 
     def __init__(self, rt: _Rt, name: str, in_shape, filters: int, k: int, strides=(1, 1), B: int = 1):
-        self.rt, self.name, self.k, self.s = rt, name, int(k), tuple(strides)
+        self.k, self.s = int(k), tuple(strides)
         self.H, self.W, self.Cin = in_shape
-        self.N = int(filters)
         self.Ho, self.Wo = -(-self.H // self.s[0]), -(-self.W // self.s[1])
-        self.K = self.k * self.k * self.Cin
+        super().__init__(rt, name, B * self.Ho * self.Wo, self.k * self.k * self.Cin, filters, (self.k, self.k, self.Cin, int(filters)))
         self.out_shape = (self.Ho, self.Wo, self.N)
-        rt.var(f"{name}.kernel", (self.k, self.k, self.Cin, self.N))
-        rt.var(f"{name}.bias", (self.N,))
         self.direct = self.k == 1 and self.s == (1, 1)
         self.B = B
         self.col = None if self.direct else rt.empty(B * self.Ho * self.Wo, self.K)
         self.dcol = None if self.direct else rt.empty(B * self.Ho * self.Wo, self.K)
-        self.z = rt.empty(B, self.Ho, self.Wo, self.N)
 
     def forward(self, x, B):
         rt = self.rt
-        M = B * self.Ho * self.Wo
-        if self.direct:
-            self.a = x
-        else:
+        if not self.direct:
             rt.ck(rt.lib.seld_m_im2col(rt.p(x), rt.p(self.col), B, self.H, self.W, self.Cin, self.k, self.k, self.s[0], self.s[1], rt.st()))
-            self.a = self.col
-        rt.gemm(self.a, rt.w(f"{self.name}.kernel"), rt.w(f"{self.name}.bias"), self.z, M, self.N, self.K)
-        return self.z[:B]
+            x = self.col
+        return Linear.forward(self, x, B * self.Ho * self.Wo).view(B, *self.out_shape)
 
     def backward(self, dz, dx, B, accumulate):
         """dz [B,Ho,Wo,N] -> kernel / bias gradients; dx (+)= the input gradient (dx None: not needed)"""
         rt = self.rt
         M = B * self.Ho * self.Wo
-        rt.gemm_tn(self.a, dz, rt.g(f"{self.name}.kernel"), rt.g(f"{self.name}.bias"), M, self.K, self.N)
-        if dx is None:
-            return
-        if self.direct:
-            rt.gemm(dz, rt.w(f"{self.name}.kernel"), None, dx, M, self.K, self.N, transb=1, accumulate=int(accumulate))
-        else:
-            rt.gemm(dz, rt.w(f"{self.name}.kernel"), None, self.dcol, M, self.K, self.N, transb=1)
-            rt.ck(rt.lib.seld_m_col2im(rt.p(self.dcol), rt.p(dx), B, self.H, self.W, self.Cin, self.k, self.k, self.s[0], self.s[1],
-                                       int(accumulate), rt.st()))
+        if self.direct or dx is None:
+            return Linear.backward(self, dz, dx, M, accumulate)
+        Linear.backward(self, dz, self.dcol, M)
+        rt.ck(rt.lib.seld_m_col2im(rt.p(self.dcol), rt.p(dx), B, self.H, self.W, self.Cin, self.k, self.k, self.s[0], self.s[1],
+                                   int(accumulate), rt.st()))
 
 
 class BatchNorm:
@@ -288,28 +344,37 @@ class LayerNorm:
         return self.dz[:rows]
 
 
-class MultiHeadAttention:
+class _Attention:
+    """What the three attention layers allocate alike on [B, S, D] with H heads of dk: q k v o do, the gradients dq dk_ dv, the softmax's lse,
+    the backward kernel's scratch (`scratch_fn(B, S, H, dk)` floats; negative: the kernels refuse this key_dim), the output and the scale."""
+
+    def __init__(self, rt: _Rt, name: str, B: int, S: int, D: int, n_head: int, key_dim: int, scratch_fn):
+        self.rt, self.name, self.S, self.D, self.H, self.dk = rt, name, int(S), int(D), int(n_head), int(key_dim)
+        need = int(scratch_fn(B, self.S, self.H, self.dk))
+        if need < 0:
+            raise ValueError(f"key_dim {key_dim!r}: the attention kernels take a multiple of 8 from 8 to 64")
+        R, HD = B * self.S, self.H * self.dk
+        self.q, self.k, self.v, self.o, self.do = (rt.empty(R, HD) for _ in range(5))
+        self.dq, self.dk_, self.dv = (rt.empty(R, HD) for _ in range(3))
+        self.lse = rt.empty(B * self.H * self.S)
+        self.scratch = rt.empty(need)
+        self.out = rt.empty(R, self.D)
+        self.scale = 1.0 / math.sqrt(float(self.dk))
+
+
+class MultiHeadAttention(_Attention):
     """tf.keras.layers.MultiHeadAttention(n_head, key_dim)(x, x) on [B, S, D] (value_dim = key_dim, biases, no dropout): three projections
     (one seld_m_gemm each: Keras' kernels [D, H, dk] are [D, H dk] row-major), the query scaled by 1 / sqrt(key_dim), seld_attn_fwd, and
     the output projection [H dk, D]."""
 
     def __init__(self, rt: _Rt, name: str, B: int, S: int, D: int, n_head: int, key_dim: int):
-        self.rt, self.name, self.S, self.D, self.H, self.dk = rt, name, int(S), int(D), int(n_head), int(key_dim)
+        super().__init__(rt, name, B, S, D, n_head, key_dim, rt.lib.seld_attn_bwd_scratch)
         H, dk = self.H, self.dk
         for part in ("query", "key", "value"):
             rt.var(f"{name}.{part}.kernel", (self.D, H, dk))
             rt.var(f"{name}.{part}.bias", (H, dk))
         rt.var(f"{name}.attention_output.kernel", (H, dk, self.D))
         rt.var(f"{name}.attention_output.bias", (self.D,))
-        if int(rt.lib.seld_attn_bwd_scratch(B, self.S, H, dk)) < 0:
-            raise ValueError(f"key_dim {key_dim!r}: the attention kernels take a multiple of 8 from 8 to 64")
-        R, HD = B * self.S, H * dk
-        self.q, self.k, self.v, self.o, self.do = (rt.empty(R, HD) for _ in range(5))
-        self.dq, self.dk_, self.dv = (rt.empty(R, HD) for _ in range(3))
-        self.lse = rt.empty(B * H * self.S)
-        self.scratch = rt.empty(int(rt.lib.seld_attn_bwd_scratch(B, self.S, H, dk)))
-        self.out = rt.empty(R, self.D)
-        self.scale = 1.0 / math.sqrt(float(dk))
 
     def forward(self, x, B, training):
         rt, n = self.rt, self.name
@@ -335,39 +400,88 @@ class MultiHeadAttention:
             rt.gemm(g, rt.w(f"{n}.{part}.kernel"), None, dx, R, self.D, HD, transb=1, accumulate=int(i > 0))
 
 
-class Conv1D:
-    """tf.keras.layers.Conv1D(filters, k, padding='same') over the frames of [B, S, Cin]: seld_m_im2col with a (k, 1) window (skipped for
-    k = 1) + the MFMA GEMM; kernel [k, Cin, filters]."""
+class Conv1D(Linear):
+    """tf.keras.layers.Conv1D(filters, k, padding='same') over the frames of [rows, Cin], rows = B * S: seld_m_im2col with a (k, 1) window
+    (skipped for k = 1) + the MFMA GEMM over the K = k Cin columns; kernel [k, Cin, filters]."""
 
     def __init__(self, rt: _Rt, name: str, B: int, S: int, Cin: int, filters: int, k: int):
-        self.rt, self.name, self.S, self.Cin, self.N, self.k = rt, name, int(S), int(Cin), int(filters), int(k)
-        self.K = self.k * self.Cin
-        rt.var(f"{name}.kernel", (self.k, self.Cin, self.N))
-        rt.var(f"{name}.bias", (self.N,))
+        self.S, self.Cin, self.k = int(S), int(Cin), int(k)
+        super().__init__(rt, name, B * self.S, self.k * self.Cin, filters, (self.k, self.Cin, int(filters)))
         self.col = self.dcol = None
         if self.k > 1:
             self.col, self.dcol = rt.empty(B * self.S, self.K), rt.empty(B * self.S, self.K)
-        self.z = rt.empty(B * self.S, self.N)
 
-    def forward(self, x, B):
+    def forward(self, x, rows):
         rt = self.rt
-        R = B * self.S
-        self.a = x
         if self.k > 1:
-            rt.ck(rt.lib.seld_m_im2col(rt.p(x), rt.p(self.col), B, self.S, 1, self.Cin, self.k, 1, 1, 1, rt.st()))
-            self.a = self.col
-        rt.gemm(self.a, rt.w(f"{self.name}.kernel"), rt.w(f"{self.name}.bias"), self.z, R, self.N, self.K)
-        return self.z[:R]
+            rt.ck(rt.lib.seld_m_im2col(rt.p(x), rt.p(self.col), rows // self.S, self.S, 1, self.Cin, self.k, 1, 1, 1, rt.st()))
+            x = self.col
+        return Linear.forward(self, x, rows)
 
-    def backward(self, dz, dx, B):
+    def backward(self, dz, dx, rows):
         rt = self.rt
-        R = B * self.S
-        rt.gemm_tn(self.a, dz, rt.g(f"{self.name}.kernel"), rt.g(f"{self.name}.bias"), R, self.K, self.N)
         if self.k == 1:
-            rt.gemm(dz, rt.w(f"{self.name}.kernel"), None, dx, R, self.K, self.N, transb=1)
-        else:
-            rt.gemm(dz, rt.w(f"{self.name}.kernel"), None, self.dcol, R, self.K, self.N, transb=1)
-            rt.ck(rt.lib.seld_m_col2im(rt.p(self.dcol), rt.p(dx), B, self.S, 1, self.Cin, self.k, 1, 1, 1, 0, rt.st()))
+            return Linear.backward(self, dz, dx, rows)
+        Linear.backward(self, dz, self.dcol, rows)
+        rt.ck(rt.lib.seld_m_col2im(rt.p(self.dcol), rt.p(dx), rows // self.S, self.S, 1, self.Cin, self.k, 1, 1, 1, 0, rt.st()))
+
+
+class _FeedForward:
+    """second(act(first(x))) on [rows, D], first / second two Linear layers (Dense or Conv1D) that the owner built: the hidden buffer h, and
+    a backward that takes the output's gradient (times `factor`, the owner's residual scale, where one is given) to the input's.  `scratch`:
+    the backward buffers (dh, dpre[, df]) of an owner that shares them among its cores; None: this core's own."""
+
+    def __init__(self, rt: _Rt, first: Linear, second: Linear, rows: int, act: int, factor=None, scratch=None):
+        self.rt, self.first, self.second, self.act, self.factor = rt, first, second, act, factor
+        self.h = rt.empty(rows, first.N)
+        self.dh, self.dpre, self.df = scratch or (rt.empty(rows, first.N), rt.empty(rows, first.N), None)
+        if factor is not None and self.df is None:
+            self.df = rt.empty(rows, second.N)
+
+    def hidden(self, x, rows):
+        """act(first(x)): for an owner that has something to launch between the two layers; forward() otherwise"""
+        self.pre = self.first.forward(x, rows)
+        self.rt.act(self.pre, self.h[:rows], self.act)
+        return self.h[:rows]
+
+    def forward(self, x, rows):
+        return self.second.forward(self.hidden(x, rows), rows)
+
+    def backward(self, dy, dx, rows):
+        """dy [rows, D]: the gradient of the (scaled) output -> dx = the input's gradient (overwritten)"""
+        rt = self.rt
+        if self.factor is not None:
+            df = self.df[:rows]
+            df.zero_()
+            rt.axpy(df, dy, self.factor)
+            dy = df
+        self.second.backward(dy, self.dh[:rows], rows)
+        rt.act_bwd(self.pre, self.dh[:rows], self.dpre[:rows], self.act)
+        self.first.backward(self.dpre[:rows], dx, rows)
+
+
+class Stage:
+    """`depth` blocks of one kind in a row (reference modules.py:64-83, 106-180: the *_stage functions; a *_block is a stage of one): every
+    block is `block(rt, cfg, S, D, prefix + index, B)` with forward(x, B, training) / backward(dy, B) on [B*S, D] -> [B*S, out_dim], and
+    reads the width the one in front of it gives (behind an RNN_block with merge_mode 'concat': 256)."""
+
+    def __init__(self, rt: _Rt, block, cfg: dict, S: int, D: int, prefix: str, B: int, depth: int):
+        self.blocks = []
+        self.S, self.D = int(S), int(D)
+        for i in range(int(depth)):
+            self.blocks.append(block(rt, cfg, S, D, f"{prefix}{i}", B))
+            D = self.blocks[-1].out_dim
+        self.out_dim, self.out_shape = int(D), (self.S, int(D))
+
+    def forward(self, x, B, training):
+        for blk in self.blocks:
+            x = blk.forward(x, B, training)
+        return x
+
+    def backward(self, dy, B):
+        for blk in reversed(self.blocks):
+            dy = blk.backward(dy, B)
+        return dy
 
 
 TRANSFORMER_KEYS = ("n_head", "key_dim", "ff_multiplier", "kernel_size")
@@ -378,16 +492,11 @@ def check_transformer_config(cfg: dict, stage: bool = False) -> None:
     for key in TRANSFORMER_KEYS + (("depth",) if stage else ()):
         if key not in cfg:
             raise ValueError(f"transformer_encoder_{'stage' if stage else 'block'}: missing {key!r}")
-    if cfg.get("activation", "relu") not in ACT:
-        raise ValueError(f"activation {cfg.get('activation')!r}: the module operators know {sorted(k for k in ACT if k)}")
-    if "dropout_rate" not in cfg or float(cfg["dropout_rate"]) != 0.0:
-        raise ValueError("transformer_encoder_block: there is no dropout kernel on this path and the reference's default dropout_rate is 0.1: "
-                         "dropout_rate must be present and 0")
+    _check_activation(cfg, "relu")
+    _check_no_dropout(cfg, "transformer_encoder_block")
     if int(cfg["n_head"]) < 1 or int(cfg["kernel_size"]) < 1 or float(cfg["ff_multiplier"]) <= 0 or (stage and int(cfg["depth"]) < 1):
         raise ValueError("transformer_encoder_block: n_head, kernel_size, depth >= 1 and ff_multiplier > 0")
-    dk = int(cfg["key_dim"])
-    if dk < 8 or dk > 64 or dk % 8:
-        raise ValueError(f"key_dim {dk}: the attention kernels take a multiple of 8 from 8 to 64")
+    _check_key_dim(cfg["key_dim"])
 
 
 class TransformerEncoderBlock:
@@ -401,36 +510,29 @@ class TransformerEncoderBlock:
         if self.F < 1:
             raise ValueError("transformer_encoder_block: int(ff_multiplier * d_model) < 1")
         k = int(cfg["kernel_size"])
-        self.act = ACT[cfg.get("activation", "relu")]
         R = B * self.S
         self.mha = MultiHeadAttention(rt, f"{prefix}.mha", B, self.S, self.D, int(cfg["n_head"]), int(cfg["key_dim"]))
         self.ln0 = LayerNorm(rt, f"{prefix}.ln0", R, self.D)
-        self.ffn0 = Conv1D(rt, f"{prefix}.ffn0", B, self.S, self.D, self.F, k)
-        self.ffn1 = Conv1D(rt, f"{prefix}.ffn1", B, self.S, self.F, self.D, k)
+        self.ffn = _FeedForward(rt, Conv1D(rt, f"{prefix}.ffn0", B, self.S, self.D, self.F, k), Conv1D(rt, f"{prefix}.ffn1", B, self.S, self.F, self.D, k),
+                                R, ACT[cfg.get("activation", "relu")])
         self.ln1 = LayerNorm(rt, f"{prefix}.ln1", R, self.D)
-        self.h, self.dh, self.dpre = rt.empty(R, self.F), rt.empty(R, self.F), rt.empty(R, self.F)
         self.dx1, self.dx = rt.empty(R, self.D), rt.empty(R, self.D)
-        self.out_shape = (self.S, self.D)
+        self.out_dim, self.out_shape = self.D, (self.S, self.D)
 
     def forward(self, x, B, training):
         """x [B*S, D] (or any contiguous view of it) -> [B*S, D]"""
-        rt = self.rt
         R = B * self.S
         x = x.reshape(R, self.D)
         x1 = self.ln0.forward(self.mha.forward(x, B, training), x, R, training)
-        self.pre = self.ffn0.forward(x1, B)
-        rt.act(self.pre, self.h[:R], self.act)
-        return self.ln1.forward(self.ffn1.forward(self.h[:R], B), x1, R, training)
+        return self.ln1.forward(self.ffn.forward(x1, R), x1, R, training)
 
     def backward(self, dy, B):
         """dy [B*S, D]: the output's gradient -> the input's gradient [B*S, D] (a buffer of this block)"""
         rt = self.rt
         R = B * self.S
         dz1 = self.ln1.backward(dy.reshape(R, self.D), R)          # gradient of x1 + ffn
-        self.ffn1.backward(dz1, self.dh[:R], B)
-        rt.act_bwd(self.pre, self.dh[:R], self.dpre[:R], self.act)
         dx1 = self.dx1[:R]
-        self.ffn0.backward(self.dpre[:R], dx1, B)
+        self.ffn.backward(dz1, dx1, R)
         rt.axpy(dx1, dz1)
         dz0 = self.ln0.backward(dx1, R)                             # gradient of x + attn
         dx = self.dx[:R]
@@ -439,104 +541,91 @@ class TransformerEncoderBlock:
         return dx
 
 
-class TransformerEncoderStage:
-    """reference modules.transformer_encoder_stage (modules.py:106-126): `depth` blocks"""
+class _HeadMajorAttention(_Attention):
+    """What the reference's own two attention layers share (layers.py:102-287, 332-392; not Keras' layer): head-major kernels query_kernel /
+    key_kernel / value_kernel [H, D, dk] and projection_kernel [H, dk, D], then (use_bias) projection_bias [D] and q_bias / k_bias / v_bias
+    [H, dk] — created in that order.  The variables keep the reference's layout; seld_head_permute packs a kernel to the [D, H dk] matrix of a
+    GEMM in front of each forward and unpacks its gradient behind each backward.  The query's division by sqrt(dk) (layers.py:275-276, after
+    the bias) is the core kernel's `scale`."""
+    PARTS = ("query", "key", "value")
 
-    def __init__(self, rt: _Rt, cfg: dict, S: int, D: int, prefix: str, B: int, depth=None):
-        depth = int(cfg["depth"]) if depth is None else int(depth)
-        self.blocks = [TransformerEncoderBlock(rt, cfg, S, D, f"{prefix}{i}", B) for i in range(depth)]
-        self.S, self.D, self.out_shape = int(S), int(D), (int(S), int(D))
-
-    def forward(self, x, B, training):
-        for blk in self.blocks:
-            x = blk.forward(x, B, training)
-        return x
-
-    def backward(self, dy, B):
-        for blk in reversed(self.blocks):
-            dy = blk.backward(dy, B)
-        return dy
-
-
-class Dense:
-    """tf.keras.layers.Dense(units) on the last axis of [rows, Cin]: one MFMA GEMM; kernel [Cin, units]."""
-
-    def __init__(self, rt: _Rt, name: str, rows: int, Cin: int, units: int):
-        self.rt, self.name, self.Cin, self.N = rt, name, int(Cin), int(units)
-        rt.var(f"{name}.kernel", (self.Cin, self.N))
-        rt.var(f"{name}.bias", (self.N,))
-        self.z = rt.empty(rows, self.N)
-
-    def forward(self, x, rows):
-        rt = self.rt
-        self.a = x
-        rt.gemm(x, rt.w(f"{self.name}.kernel"), rt.w(f"{self.name}.bias"), self.z, rows, self.N, self.Cin)
-        return self.z[:rows]
-
-    def backward(self, dz, dx, rows):
-        rt = self.rt
-        rt.gemm_tn(self.a, dz, rt.g(f"{self.name}.kernel"), rt.g(f"{self.name}.bias"), rows, self.Cin, self.N)
-        rt.gemm(dz, rt.w(f"{self.name}.kernel"), None, dx, rows, self.Cin, self.N, transb=1)
-
-
-class MultiHeadAttentionRef:
-    """The reference's own layers.MultiHeadAttention_(n_head, key_dim, use_bias)([x, x, x]) (layers.py:102-287; not Keras' layer) on [B, S, D]:
-    head-major kernels query_kernel / key_kernel / value_kernel [H, D, dk] and projection_kernel [H, dk, D], then (use_bias) projection_bias [D]
-    and q_bias / k_bias / v_bias [H, dk] — created in that order.  The variables keep the reference's layout; seld_head_permute packs a kernel to
-    the [D, H dk] matrix of a GEMM in front of each forward and unpacks its gradient behind each backward.  The query's division by sqrt(dk)
-    (layers.py:275-276, after the bias) is seld_attn_fwd's `scale`."""
-
-    def __init__(self, rt: _Rt, name: str, B: int, S: int, D: int, n_head: int, key_dim: int, use_bias: bool = True):
-        self.rt, self.name, self.S, self.D, self.H, self.dk, self.use_bias = rt, name, int(S), int(D), int(n_head), int(key_dim), bool(use_bias)
+    def __init__(self, rt: _Rt, name: str, B: int, S: int, D: int, n_head: int, key_dim: int, use_bias: bool, scratch_fn, n_packed: int = 3):
+        super().__init__(rt, name, B, S, D, n_head, key_dim, scratch_fn)
+        self.use_bias = bool(use_bias)
         H, dk = self.H, self.dk
-        for part in ("query", "key", "value"):
+        for part in self.PARTS:
             rt.var(f"{name}.{part}_kernel", (H, self.D, dk))
         rt.var(f"{name}.projection_kernel", (H, dk, self.D))
         if self.use_bias:
             rt.var(f"{name}.projection_bias", (self.D,))
             for part in "qkv":
                 rt.var(f"{name}.{part}_bias", (H, dk))
-        if int(rt.lib.seld_attn_bwd_scratch(B, self.S, H, dk)) < 0:
-            raise ValueError(f"key_dim {key_dim!r}: the attention kernels take a multiple of 8 from 8 to 64")
-        R, HD = B * self.S, H * dk
-        self.q, self.k, self.v, self.o, self.do = (rt.empty(R, HD) for _ in range(5))
-        self.dq, self.dk_, self.dv = (rt.empty(R, HD) for _ in range(3))
-        self.packed = [rt.empty(self.D, HD) for _ in range(3)]
-        self.dpacked = rt.empty(self.D, HD)
-        self.lse = rt.empty(B * H * self.S)
-        self.scratch = rt.empty(int(rt.lib.seld_attn_bwd_scratch(B, self.S, H, dk)))
-        self.out = rt.empty(R, self.D)
-        self.scale = 1.0 / math.sqrt(float(dk))
+        self.packed = [rt.empty(self.D, H * dk) for _ in range(n_packed)]      # query, key, value (, pos)
+        self.dpacked = rt.empty(self.D, H * dk)
 
     def _bias(self, part, grad=False):
         if not self.use_bias:
             return None
         return (self.rt.g if grad else self.rt.w)(f"{self.name}.{part}")
 
-    def forward(self, x, B, training):
-        rt, n = self.rt, self.name
-        R, HD = B * self.S, self.H * self.dk
+    def _pack(self, kernel, wp):
+        rt = self.rt
+        rt.ck(rt.lib.seld_head_permute(rt.p(rt.w(f"{self.name}.{kernel}")), rt.p(wp), self.H, self.D, self.dk, 0, rt.st()))
+
+    def _unpack(self, kernel):
+        """dpacked [D, H dk] -> the gradient of `kernel` [H, D, dk]"""
+        rt = self.rt
+        rt.ck(rt.lib.seld_head_permute(rt.p(self.dpacked), rt.p(rt.g(f"{self.name}.{kernel}")), self.H, self.D, self.dk, 1, rt.st()))
+
+    def _qkv(self, x, R):
         self.x = x
-        for part, wp, buf in zip(("query", "key", "value"), self.packed, (self.q, self.k, self.v)):
-            rt.ck(rt.lib.seld_head_permute(rt.p(rt.w(f"{n}.{part}_kernel")), rt.p(wp), self.H, self.D, self.dk, 0, rt.st()))
-            rt.gemm(x, wp, self._bias(part[0] + "_bias"), buf, R, HD, self.D)
+        for part, wp, buf in zip(self.PARTS, self.packed, (self.q, self.k, self.v)):
+            self._pack(f"{part}_kernel", wp)
+            self.rt.gemm(x, wp, self._bias(part[0] + "_bias"), buf, R, self.H * self.dk, self.D)
+
+    def _project(self, R):
+        rt = self.rt
+        rt.gemm(self.o, rt.w(f"{self.name}.projection_kernel"), self._bias("projection_bias"), self.out, R, self.D, self.H * self.dk)
+        return self.out[:R]
+
+    def _project_bwd(self, dout, R):
+        """dout [R, D] -> the projection's gradients and do"""
+        rt, HD = self.rt, self.H * self.dk
+        rt.gemm_tn(self.o, dout, rt.g(f"{self.name}.projection_kernel"), self._bias("projection_bias", True), R, HD, self.D)
+        rt.gemm(dout, rt.w(f"{self.name}.projection_kernel"), None, self.do, R, HD, self.D, transb=1)
+
+    def _input_bwd(self, i, g, dx, R, accumulate):
+        """g: the gradient of q, k or v (i = 0, 1, 2) -> its kernel's and bias's gradients; dx (+)= g kernel^T"""
+        rt, part, HD = self.rt, self.PARTS[i], self.H * self.dk
+        rt.gemm_tn(self.x, g, self.dpacked, self._bias(part[0] + "_bias", True), R, self.D, HD)
+        self._unpack(f"{part}_kernel")
+        rt.gemm(g, self.packed[i], None, dx, R, self.D, HD, transb=1, accumulate=accumulate)
+
+
+class MultiHeadAttentionRef(_HeadMajorAttention):
+    """The reference's layers.MultiHeadAttention_(n_head, key_dim, use_bias)([x, x, x]) (layers.py:102-287) on [B, S, D]: seld_attn_fwd / _bwd
+    between the shared projections."""
+
+    def __init__(self, rt: _Rt, name: str, B: int, S: int, D: int, n_head: int, key_dim: int, use_bias: bool = True):
+        super().__init__(rt, name, B, S, D, n_head, key_dim, use_bias, rt.lib.seld_attn_bwd_scratch)
+
+    def forward(self, x, B, training):
+        rt = self.rt
+        R, HD = B * self.S, self.H * self.dk
+        self._qkv(x, R)
         rt.ck(rt.lib.seld_attn_fwd(rt.p(self.q), rt.p(self.k), rt.p(self.v), HD, HD, HD, rt.p(self.o), rt.p(self.lse) if training else None, B, self.S,
                                    self.H, self.dk, self.scale, rt.st()))
-        rt.gemm(self.o, rt.w(f"{n}.projection_kernel"), self._bias("projection_bias"), self.out, R, self.D, HD)
-        return self.out[:R]
+        return self._project(R)
 
     def backward(self, dout, dx, B):
         """dout [R, D] -> every variable's gradient; dx = the input's gradient (overwritten)"""
-        rt, n = self.rt, self.name
+        rt = self.rt
         R, HD = B * self.S, self.H * self.dk
-        rt.gemm_tn(self.o, dout, rt.g(f"{n}.projection_kernel"), self._bias("projection_bias", True), R, HD, self.D)
-        rt.gemm(dout, rt.w(f"{n}.projection_kernel"), None, self.do, R, HD, self.D, transb=1)
+        self._project_bwd(dout, R)
         rt.ck(rt.lib.seld_attn_bwd(rt.p(self.q), rt.p(self.k), rt.p(self.v), HD, HD, HD, rt.p(self.o), rt.p(self.do), rt.p(self.lse), rt.p(self.dq),
                                    rt.p(self.dk_), rt.p(self.dv), HD, HD, HD, rt.p(self.scratch), B, self.S, self.H, self.dk, self.scale, rt.st()))
-        for i, (part, wp, g) in enumerate(zip(("query", "key", "value"), self.packed, (self.dq, self.dk_, self.dv))):
-            rt.gemm_tn(self.x, g, self.dpacked, self._bias(part[0] + "_bias", True), R, self.D, HD)
-            rt.ck(rt.lib.seld_head_permute(rt.p(self.dpacked), rt.p(rt.g(f"{n}.{part}_kernel")), self.H, self.D, self.dk, 1, rt.st()))
-            rt.gemm(g, wp, None, dx, R, self.D, HD, transb=1, accumulate=int(i > 0))
+        for i, g in enumerate((self.dq, self.dk_, self.dv)):
+            self._input_bwd(i, g, dx, R, accumulate=int(i > 0))
 
 
 class DepthwiseConv1D:
@@ -568,6 +657,37 @@ class DepthwiseConv1D:
                                        rt.p(rt.g(f"{n}.bias")), rt.p(self.scratch), B, self.S, self.C, self.k, self.glu, rt.st()))
 
 
+class _ConvTail:
+    """The convolution module's tail (reference modules.py:476-493, 603-613): depthwise Conv1D(k) [on the GLU of a 2 D wide input] ->
+    BatchNormalization -> swish -> pointwise Conv1D(D, 1), variables `{prefix}.dw`, `.bn`, `.pw1` in that order.  What sits in front of it
+    (LayerNormalization, the pointwise Conv1D(2 D, 1) of the GLU) and the residual behind it are the owning block's."""
+
+    def __init__(self, rt: _Rt, prefix: str, B: int, S: int, D: int, k: int, glu: bool):
+        self.rt, self.S = rt, int(S)
+        self.dw = DepthwiseConv1D(rt, f"{prefix}.dw", B, S, D, k, glu=glu)
+        self.bn = BatchNorm(rt, f"{prefix}.bn", (S, 1, D), B)
+        self.pw1 = Conv1D(rt, f"{prefix}.pw1", B, S, D, D, 1)
+        self.bno, self.sw, self.dsw, self.dbn, self.ddw = (rt.empty(B * S, D) for _ in range(5))
+
+    def hidden(self, c, B, training):
+        """swish(BN(depthwise(c))): for an owner that has something to launch in front of the pointwise layer; forward() otherwise"""
+        rt, R = self.rt, B * self.S
+        self.bn.forward(self.dw.forward(c, B), self.bno[:R], B, training, 0)
+        rt.act(self.bno[:R], self.sw[:R], ACT["swish"])
+        return self.sw[:R]
+
+    def forward(self, c, B, training):
+        return self.pw1.forward(self.hidden(c, B, training), B * self.S)
+
+    def backward(self, dy, du, B):
+        """dy [B*S, D]: the output's gradient -> du = the gradient of the depthwise convolution's input (overwritten)"""
+        rt, R = self.rt, B * self.S
+        self.pw1.backward(dy, self.dsw[:R], R)
+        rt.act_bwd(self.bno[:R], self.dsw[:R], self.dbn[:R], ACT["swish"])
+        self.bn.backward(self.dbn[:R], self.ddw[:R], B)
+        self.dw.backward(self.ddw[:R], du, B)
+
+
 def basic_pos_encoding(S: int, D: int) -> np.ndarray:
     """layers.basic_pos_encoding (layers.py:53-67) as a [S, D] float32 table: column 2 i = cos(w_i t), column 2 i + 1 = sin(w_i t), w_i =
     float32(10000 ** (-i / (D // 2))).  The product w t, cos and sin are taken in float64 and rounded once (TensorFlow forms w t in float32:
@@ -584,29 +704,18 @@ def check_conformer_config(cfg: dict, stage: bool = False, D=None) -> None:
     who = f"conformer_encoder_{'stage' if stage else 'block'}"
     if stage and "depth" not in cfg:
         raise ValueError(f"{who}: missing 'depth'")
-    if cfg.get("activation", "swish") not in ACT:
-        raise ValueError(f"activation {cfg.get('activation')!r}: the module operators know {sorted(k for k in ACT if k)}")
-    if "dropout_rate" not in cfg or float(cfg["dropout_rate"]) != 0.0:
-        raise ValueError(f"{who}: there is no dropout kernel on this path and the reference's default dropout_rate is 0.1: "
-                         "dropout_rate must be present and 0")
+    _check_activation(cfg, "swish")
+    _check_no_dropout(cfg, who)
     if cfg.get("pos_mode", "absolute") != "absolute":
         raise ValueError(f"{who}: pos_mode {cfg.get('pos_mode')!r}: RelPositionMultiHeadAttention has no kernel here, only 'absolute'")
-    pe = cfg.get("pos_encoding", "basic")
-    if pe == "rff":
-        raise ValueError(f"{who}: pos_encoding 'rff' draws its frequencies from tf.random.normal and stores them nowhere: it cannot be reproduced")
-    if pe not in ("basic", None):
-        raise ValueError(f"{who}: pos_encoding {pe!r}: 'basic' or None")
-    if pe == "basic" and D is not None and int(D) % 2:
-        raise ValueError(f"{who}: pos_encoding 'basic' on an odd width {D}: the reference's table has 2 * (D // 2) columns and does not broadcast")
+    _check_pos_encoding(cfg, who, D)
     reg = cfg.get("kernel_regularizer", None)
     if reg is not None and (not isinstance(reg, dict) or set(reg) - {"l1", "l2"}):
         raise ValueError(f"{who}: kernel_regularizer {reg!r}: a dict of l1 / l2 (it only feeds model.losses, which train.trainstep never adds)")
     if int(cfg.get("n_head", 4)) < 1 or not 1 <= int(cfg.get("kernel_size", 32)) <= 64 or int(cfg.get("multiplier", 4)) < 1 or \
             (stage and int(cfg["depth"]) < 1):
         raise ValueError(f"{who}: n_head, multiplier, depth >= 1 and 1 <= kernel_size <= 64")
-    dk = int(cfg.get("key_dim", 36))
-    if dk < 8 or dk > 64 or dk % 8:
-        raise ValueError(f"key_dim {dk}: the attention kernels take a multiple of 8 from 8 to 64")
+    _check_key_dim(cfg.get("key_dim", 36))
 
 
 class ConformerEncoderBlock:
@@ -621,45 +730,36 @@ class ConformerEncoderBlock:
         self.rt, self.S, self.D, self.B = rt, int(S), int(D), B
         S, D = self.S, self.D
         self.F = int(cfg.get("multiplier", 4)) * D
-        self.act = ACT[cfg.get("activation", "swish")]
         self.ff = float(cfg.get("ffn_factor", 0.5))
         R = B * S
         p = prefix
+        e = rt.empty
+        scratch = (e(R, self.F), e(R, self.F), e(R, D))      # dh, dpre, df: the two FFNs run one after the other
+
+        def ffn(name):
+            return _FeedForward(rt, Dense(rt, f"{name}a", R, D, self.F), Dense(rt, f"{name}b", R, self.F, D), R, ACT[cfg.get("activation", "swish")],
+                                self.ff, scratch)
         self.ln0 = LayerNorm(rt, f"{p}.ln0", R, D)
-        self.ffn0a, self.ffn0b = Dense(rt, f"{p}.ffn0a", R, D, self.F), Dense(rt, f"{p}.ffn0b", R, self.F, D)
+        self.ffn0 = ffn(f"{p}.ffn0")
         self.ln1 = LayerNorm(rt, f"{p}.ln1", R, D)
         self.mha = MultiHeadAttentionRef(rt, f"{p}.mha", B, S, D, int(cfg.get("n_head", 4)), int(cfg.get("key_dim", 36)), cfg.get("use_bias", True))
         self.ln2 = LayerNorm(rt, f"{p}.ln2", R, D)
         self.pw0 = Conv1D(rt, f"{p}.pw0", B, S, D, 2 * D, 1)
-        self.dw = DepthwiseConv1D(rt, f"{p}.dw", B, S, D, int(cfg.get("kernel_size", 32)), glu=True)
-        self.bn = BatchNorm(rt, f"{p}.bn", (S, 1, D), B)
-        self.pw1 = Conv1D(rt, f"{p}.pw1", B, S, D, D, 1)
+        self.tail = _ConvTail(rt, p, B, S, D, int(cfg.get("kernel_size", 32)), glu=True)
         self.ln3 = LayerNorm(rt, f"{p}.ln3", R, D)
-        self.ffn1a, self.ffn1b = Dense(rt, f"{p}.ffn1a", R, D, self.F), Dense(rt, f"{p}.ffn1b", R, self.F, D)
+        self.ffn1 = ffn(f"{p}.ffn1")
         self.ln4 = LayerNorm(rt, f"{p}.ln4", R, D)
         self.enc = None
         if cfg.get("pos_encoding", "basic") == "basic":
             self.enc = torch.as_tensor(basic_pos_encoding(S, D)).to(rt.dev)
-        e = rt.empty
-        self.h0, self.h1, self.dh, self.dpre = e(R, self.F), e(R, self.F), e(R, self.F), e(R, self.F)
         self.x1, self.x2, self.x3, self.z = e(R, D), e(R, D), e(R, D), e(R, D)
-        self.bno, self.sw, self.dsw, self.dbn, self.ddw = e(R, D), e(R, D), e(R, D), e(R, D), e(R, D)
         self.du = e(R, 2 * D)
-        self.dx2, self.dx1, self.dx0, self.df, self.dn = e(R, D), e(R, D), e(R, D), e(R, D), e(R, D)
-        self.out_shape = (S, D)
+        self.dx2, self.dx1, self.dx0, self.dn = e(R, D), e(R, D), e(R, D), e(R, D)
+        self.out_dim, self.out_shape = D, (S, D)
 
-    def _ffn(self, ln, a, b, h, x, rows, training):
-        """Dense(D)(act(Dense(F)(LN(x)))) -> [rows, D]"""
-        pre = a.forward(ln.forward(x, None, rows, training), rows)
-        self.rt.act(pre, h[:rows], self.act)
-        return b.forward(h[:rows], rows)
-
-    def _ffn_bwd(self, ln, a, b, df, rows):
-        """df: the gradient of the FFN's output -> the gradient of the input of its LayerNormalization"""
-        rt = self.rt
-        b.backward(df, self.dh[:rows], rows)
-        rt.act_bwd(a.z[:rows], self.dh[:rows], self.dpre[:rows], self.act)
-        a.backward(self.dpre[:rows], self.dn[:rows], rows)
+    def _ffn_bwd(self, ln, ffn, dy, rows):
+        """dy: the gradient of ffn_factor * the FFN's output -> the gradient of the input of its LayerNormalization"""
+        ffn.backward(dy, self.dn[:rows], rows)
         return ln.backward(self.dn[:rows], rows)
 
     def forward(self, x, B, training):
@@ -669,26 +769,17 @@ class ConformerEncoderBlock:
         x = x.reshape(R, D)
         x1, x2, x3, z = self.x1[:R], self.x2[:R], self.x3[:R], self.z[:R]
         x1.copy_(x)
-        rt.axpy(x1, self._ffn(self.ln0, self.ffn0a, self.ffn0b, self.h0, x, R, training), self.ff)
+        rt.axpy(x1, self.ffn0.forward(self.ln0.forward(x, None, R, training), R), self.ff)
         if self.enc is not None:
             rt.ck(rt.lib.seld_pos_add(rt.p(x1), rt.p(self.enc), B, self.S, D, rt.st()))
         x2.copy_(x1)
         rt.axpy(x2, self.mha.forward(self.ln1.forward(x1, None, R, training), B, training))
-        conv = self.dw.forward(self.pw0.forward(self.ln2.forward(x2, None, R, training), B), B)
-        self.bn.forward(conv, self.bno[:R], B, training, 0)
-        rt.act(self.bno[:R], self.sw[:R], ACT["swish"])
+        sw = self.tail.hidden(self.pw0.forward(self.ln2.forward(x2, None, R, training), R), B, training)
         x3.copy_(x2)
-        rt.axpy(x3, self.pw1.forward(self.sw[:R], B))
+        rt.axpy(x3, self.tail.pw1.forward(sw, R))
         z.copy_(x2)
-        rt.axpy(z, self._ffn(self.ln3, self.ffn1a, self.ffn1b, self.h1, x3, R, training), self.ff)
+        rt.axpy(z, self.ffn1.forward(self.ln3.forward(x3, None, R, training), R), self.ff)
         return self.ln4.forward(z, None, R, training)
-
-    def _scaled(self, src, rows):
-        """ffn_factor * src in a buffer of this block"""
-        df = self.df[:rows]
-        df.zero_()
-        self.rt.axpy(df, src, self.ff)
-        return df
 
     def backward(self, dy, B):
         """dy [B*S, D]: the output's gradient -> the input's gradient [B*S, D] (a buffer of this block)"""
@@ -697,32 +788,17 @@ class ConformerEncoderBlock:
         dx2, dx1, dx0 = self.dx2[:R], self.dx1[:R], self.dx0[:R]
         dz = self.ln4.backward(dy.reshape(R, D), R)                      # gradient of x2 + ffn_factor ffn1
         dx2.copy_(dz)
-        dx3 = self._ffn_bwd(self.ln3, self.ffn1a, self.ffn1b, self._scaled(dz, R), R)      # gradient of x3 = x2 + conv
+        dx3 = self._ffn_bwd(self.ln3, self.ffn1, dz, R)                  # gradient of x3 = x2 + conv
         rt.axpy(dx2, dx3)
-        self.pw1.backward(dx3, self.dsw[:R], B)
-        rt.act_bwd(self.bno[:R], self.dsw[:R], self.dbn[:R], ACT["swish"])
-        self.bn.backward(self.dbn[:R], self.ddw[:R], B)
-        self.dw.backward(self.ddw[:R], self.du[:R], B)
-        self.pw0.backward(self.du[:R], self.dn[:R], B)
+        self.tail.backward(dx3, self.du[:R], B)
+        self.pw0.backward(self.du[:R], self.dn[:R], R)
         rt.axpy(dx2, self.ln2.backward(self.dn[:R], R))
         dx1.copy_(dx2)
         self.mha.backward(dx2, self.dn[:R], B)
         rt.axpy(dx1, self.ln1.backward(self.dn[:R], R))
         dx0.copy_(dx1)                                                   # the positional table is a constant
-        rt.axpy(dx0, self._ffn_bwd(self.ln0, self.ffn0a, self.ffn0b, self._scaled(dx1, R), R))
+        rt.axpy(dx0, self._ffn_bwd(self.ln0, self.ffn0, dx1, R))
         return dx0
-
-
-class ConformerEncoderStage:
-    """reference modules.conformer_encoder_stage (modules.py:129-152): `depth` blocks"""
-
-    def __init__(self, rt: _Rt, cfg: dict, S: int, D: int, prefix: str, B: int, depth=None):
-        depth = int(cfg["depth"]) if depth is None else int(depth)
-        self.blocks = [ConformerEncoderBlock(rt, cfg, S, D, f"{prefix}{i}", B) for i in range(depth)]
-        self.S, self.D, self.out_shape = int(S), int(D), (int(S), int(D))
-
-    forward = TransformerEncoderStage.forward
-    backward = TransformerEncoderStage.backward
 
 
 class GLU:
@@ -744,89 +820,59 @@ class GLU:
         rt.ck(rt.lib.seld_glu_bwd(rt.p(self.u), 2 * self.C, rt.p(dy), rt.p(du), 2 * self.C, rows, self.C, rt.st()))
 
 
-class RelPositionMultiHeadAttention:
+class RelPositionMultiHeadAttention(_HeadMajorAttention):
     """The reference's layers.RelPositionMultiHeadAttention(n_head, key_dim, use_bias)([x, x, x, pos]) (layers.py:332-392) on [B, S, D] with the
     batch-free table pos [S, D] of layers.basic_pos_encoding: variables pos_kernel [H, D, dk], pos_bias_u, pos_bias_v [H, dk], then
-    MultiHeadAttention_'s (layers.py:333-357, 148-205).  q, k, v and P = pos . pos_kernel are seld_head_permute + one GEMM each (P from the
-    host-built table in every forward: the kernel moves); the core is seld_relattn_fwd / _bwd, whose dQu / dQv are added for the query's
+    MultiHeadAttention_'s (layers.py:333-357, 148-205).  P = pos . pos_kernel is seld_head_permute + one GEMM as q, k, v are (from the
+    host-built table in every forward: the kernel moves); the core is seld_relattn_fwd / _bwd, whose dQu (`dq`) / dQv are added for the query's
     gradient and column-summed for the two biases; dpos_kernel = pos^T dP."""
 
     def __init__(self, rt: _Rt, name: str, B: int, S: int, D: int, n_head: int, key_dim: int, use_bias: bool = False):
-        self.rt, self.name, self.S, self.D, self.H, self.dk, self.use_bias = rt, name, int(S), int(D), int(n_head), int(key_dim), bool(use_bias)
-        H, dk = self.H, self.dk
-        rt.var(f"{name}.pos_kernel", (H, self.D, dk))
-        rt.var(f"{name}.pos_bias_u", (H, dk))
-        rt.var(f"{name}.pos_bias_v", (H, dk))
-        for part in ("query", "key", "value"):
-            rt.var(f"{name}.{part}_kernel", (H, self.D, dk))
-        rt.var(f"{name}.projection_kernel", (H, dk, self.D))
-        if self.use_bias:
-            rt.var(f"{name}.projection_bias", (self.D,))
-            for part in "qkv":
-                rt.var(f"{name}.{part}_bias", (H, dk))
-        need = int(rt.lib.seld_relattn_bwd_scratch(B, self.S, H, dk))
-        if need < 0:
-            raise ValueError(f"key_dim {key_dim!r}: the attention kernels take a multiple of 8 from 8 to 64")
-        R, HD = B * self.S, H * dk
-        self.q, self.k, self.v, self.o, self.do = (rt.empty(R, HD) for _ in range(5))
-        self.dqu, self.dqv, self.dk_, self.dv = (rt.empty(R, HD) for _ in range(4))
-        self.packed = [rt.empty(self.D, HD) for _ in range(4)]      # query, key, value, pos
-        self.dpacked, self.dpacked2 = rt.empty(self.D, HD), rt.empty(self.D, HD)
+        rt.var(f"{name}.pos_kernel", (int(n_head), int(D), int(key_dim)))
+        rt.var(f"{name}.pos_bias_u", (int(n_head), int(key_dim)))
+        rt.var(f"{name}.pos_bias_v", (int(n_head), int(key_dim)))
+        super().__init__(rt, name, B, S, D, n_head, key_dim, use_bias, rt.lib.seld_relattn_bwd_scratch, n_packed=4)
+        HD = self.H * self.dk
+        self.dqv, self.dpacked2 = rt.empty(B * self.S, HD), rt.empty(self.D, HD)
         self.P, self.dP = rt.empty(self.S, HD), rt.empty(self.S, HD)
         self.pos = torch.as_tensor(basic_pos_encoding(self.S, self.D)).to(rt.dev)
-        self.lse = rt.empty(B * H * self.S)
-        self.scratch = rt.empty(need)
-        self.out = rt.empty(R, self.D)
-        self.scale = 1.0 / math.sqrt(float(dk))
-
-    def _bias(self, part, grad=False):
-        if not self.use_bias:
-            return None
-        return (self.rt.g if grad else self.rt.w)(f"{self.name}.{part}")
 
     def forward(self, x, B, training):
         rt, n = self.rt, self.name
         R, HD = B * self.S, self.H * self.dk
-        self.x = x
-        for part, wp, buf in zip(("query", "key", "value"), self.packed, (self.q, self.k, self.v)):
-            rt.ck(rt.lib.seld_head_permute(rt.p(rt.w(f"{n}.{part}_kernel")), rt.p(wp), self.H, self.D, self.dk, 0, rt.st()))
-            rt.gemm(x, wp, self._bias(part[0] + "_bias"), buf, R, HD, self.D)
-        rt.ck(rt.lib.seld_head_permute(rt.p(rt.w(f"{n}.pos_kernel")), rt.p(self.packed[3]), self.H, self.D, self.dk, 0, rt.st()))
+        self._qkv(x, R)
+        self._pack("pos_kernel", self.packed[3])
         rt.gemm(self.pos, self.packed[3], None, self.P, self.S, HD, self.D)
         rt.ck(rt.lib.seld_relattn_fwd(rt.p(self.q), rt.p(self.k), rt.p(self.v), HD, HD, HD, rt.p(self.P), HD, rt.p(rt.w(f"{n}.pos_bias_u")),
                                       rt.p(rt.w(f"{n}.pos_bias_v")), rt.p(self.o), rt.p(self.lse) if training else None, B, self.S, self.H,
                                       self.dk, self.scale, rt.st()))
-        rt.gemm(self.o, rt.w(f"{n}.projection_kernel"), self._bias("projection_bias"), self.out, R, self.D, HD)
-        return self.out[:R]
+        return self._project(R)
 
     def backward(self, dout, dx, B):
         """dout [R, D] -> every variable's gradient; dx = the input's gradient (overwritten)"""
         rt, n = self.rt, self.name
         R, HD = B * self.S, self.H * self.dk
-        rt.gemm_tn(self.o, dout, rt.g(f"{n}.projection_kernel"), self._bias("projection_bias", True), R, HD, self.D)
-        rt.gemm(dout, rt.w(f"{n}.projection_kernel"), None, self.do, R, HD, self.D, transb=1)
+        self._project_bwd(dout, R)
         rt.ck(rt.lib.seld_relattn_bwd(rt.p(self.q), rt.p(self.k), rt.p(self.v), HD, HD, HD, rt.p(self.P), HD, rt.p(rt.w(f"{n}.pos_bias_u")),
-                                      rt.p(rt.w(f"{n}.pos_bias_v")), rt.p(self.o), rt.p(self.do), rt.p(self.lse), rt.p(self.dqu), rt.p(self.dqv),
+                                      rt.p(rt.w(f"{n}.pos_bias_v")), rt.p(self.o), rt.p(self.do), rt.p(self.lse), rt.p(self.dq), rt.p(self.dqv),
                                       rt.p(self.dk_), rt.p(self.dv), rt.p(self.dP), HD, HD, HD, HD, HD, rt.p(self.scratch), B, self.S, self.H,
                                       self.dk, self.scale, rt.st()))
         # the query kernel sees dQu + dQv; the column sums of the two parts are the gradients of pos_bias_u / pos_bias_v
-        rt.gemm_tn(self.x, self.dqu, self.dpacked, rt.g(f"{n}.pos_bias_u"), R, self.D, HD)
+        rt.gemm_tn(self.x, self.dq, self.dpacked, rt.g(f"{n}.pos_bias_u"), R, self.D, HD)
         rt.gemm_tn(self.x, self.dqv, self.dpacked2, rt.g(f"{n}.pos_bias_v"), R, self.D, HD)
         rt.axpy(self.dpacked, self.dpacked2)
-        rt.ck(rt.lib.seld_head_permute(rt.p(self.dpacked), rt.p(rt.g(f"{n}.query_kernel")), self.H, self.D, self.dk, 1, rt.st()))
+        self._unpack("query_kernel")
         if self.use_bias:
             gq = rt.g(f"{n}.q_bias")
             gq.copy_(rt.g(f"{n}.pos_bias_u"))
             rt.axpy(gq, rt.g(f"{n}.pos_bias_v"))
-        dq = self.dqu[:R]
+        dq = self.dq[:R]
         rt.axpy(dq, self.dqv[:R])
         rt.gemm(dq, self.packed[0], None, dx, R, self.D, HD, transb=1)
-        for part, wp, g in zip(("key", "value"), self.packed[1:3], (self.dk_, self.dv)):
-            rt.gemm_tn(self.x, g, self.dpacked, self._bias(part[0] + "_bias", True), R, self.D, HD)
-            rt.ck(rt.lib.seld_head_permute(rt.p(self.dpacked), rt.p(rt.g(f"{n}.{part}_kernel")), self.H, self.D, self.dk, 1, rt.st()))
-            rt.gemm(g, wp, None, dx, R, self.D, HD, transb=1, accumulate=1)
+        for i, g in ((1, self.dk_), (2, self.dv)):
+            self._input_bwd(i, g, dx, R, accumulate=1)
         rt.gemm_tn(self.pos, self.dP, self.dpacked, None, self.S, self.D, HD)
-        rt.ck(rt.lib.seld_head_permute(rt.p(self.dpacked), rt.p(rt.g(f"{n}.pos_kernel")), self.H, self.D, self.dk, 1, rt.st()))
+        self._unpack("pos_kernel")
 
 
 ATTENTION_KEYS = ("key_dim", "n_head", "kernel_size", "ff_kernel_size", "ff_multiplier", "ff_factor0", "ff_factor1")
@@ -839,11 +885,8 @@ def check_attention_config(cfg: dict, stage: bool = False, D=None) -> None:
     for key in ATTENTION_KEYS + (("depth",) if stage else ()):
         if key not in cfg:
             raise ValueError(f"{who}: missing {key!r}")
-    if cfg.get("activation", "swish") not in ACT:
-        raise ValueError(f"activation {cfg.get('activation')!r}: the module operators know {sorted(k for k in ACT if k)}")
-    if "dropout_rate" not in cfg or float(cfg["dropout_rate"]) != 0.0:
-        raise ValueError(f"{who}: there is no dropout kernel on this path and the reference's default dropout_rate is 0.1: "
-                         "dropout_rate must be present and 0")
+    _check_activation(cfg, "swish")
+    _check_no_dropout(cfg, who)
     f0, f1, fk, fm = float(cfg["ff_factor0"]), float(cfg["ff_factor1"]), int(cfg["ff_kernel_size"]), float(cfg["ff_multiplier"])
     if f0 < 0 or f1 < 0:
         raise ValueError("ff_factor0, ff_factor1 >= 0 must hold")
@@ -852,22 +895,12 @@ def check_attention_config(cfg: dict, stage: bool = False, D=None) -> None:
             raise ValueError("if FF modules are not used, ff_kernel must be set to 0")
         if fm > 0:
             raise ValueError("if FF modules are not used, ff_multiplier must be set to 0")
-    pe, ab = cfg.get("pos_encoding", "basic"), bool(cfg.get("abs_pos_encoding", False))
-    if pe == "rff":
-        raise ValueError(f"{who}: pos_encoding 'rff' draws its frequencies from tf.random.normal and stores them nowhere: it cannot be reproduced")
-    if pe not in ("basic", None):
-        raise ValueError(f"{who}: pos_encoding {pe!r}: 'basic' or None")
-    if not ab and pe is None:
-        raise ValueError("relative pos encoding demands any types of encoding except the null one")
-    if pe == "basic" and D is not None and int(D) % 2:
-        raise ValueError(f"{who}: pos_encoding 'basic' on an odd width {D}: the reference's table has 2 * (D // 2) columns and does not broadcast")
+    _check_pos_encoding(cfg, who, D, relative=not bool(cfg.get("abs_pos_encoding", False)))
     if fk < 0 or fm < 0 or ((f0 > 0 or f1 > 0) and (fk < 1 or (D is not None and int(fm * int(D)) < 1))):
         raise ValueError(f"{who}: a FF module takes ff_kernel_size >= 1 and int(ff_multiplier * d_model) >= 1")
     if int(cfg["n_head"]) < 1 or not 0 <= int(cfg["kernel_size"]) <= 64 or (stage and int(cfg["depth"]) < 1):
         raise ValueError(f"{who}: n_head, depth >= 1 and 0 <= kernel_size <= 64")
-    dk = int(cfg["key_dim"])
-    if dk < 8 or dk > 64 or dk % 8:
-        raise ValueError(f"key_dim {dk}: the attention kernels take a multiple of 8 from 8 to 64")
+    _check_key_dim(cfg["key_dim"])
 
 
 class _FFModule:
@@ -875,32 +908,25 @@ class _FFModule:
     LayerNormalization unless layer_norm_in_front — whose own LayerNormalization is dead: the first Conv1D reads x (modules.py:564, 624)."""
 
     def __init__(self, rt: _Rt, name: str, lname, B: int, S: int, D: int, F: int, k: int, act: int, factor: float):
-        self.rt, self.S, self.D, self.F, self.act, self.factor = rt, S, D, F, act, float(factor)
+        self.rt, self.S, self.factor = rt, S, float(factor)
         R = B * S
-        self.a, self.b = Conv1D(rt, f"{name}a", B, S, D, F, k), Conv1D(rt, f"{name}b", B, S, F, D, k)
+        self.ffn = _FeedForward(rt, Conv1D(rt, f"{name}a", B, S, D, F, k), Conv1D(rt, f"{name}b", B, S, F, D, k), R, act, self.factor)
         self.ln = LayerNorm(rt, lname, R, D) if lname else None
-        self.h, self.dh, self.dpre = rt.empty(R, F), rt.empty(R, F), rt.empty(R, F)
-        self.y, self.df, self.dx = rt.empty(R, D), rt.empty(R, D), rt.empty(R, D)
+        self.y, self.dx = rt.empty(R, D), rt.empty(R, D)
 
     def forward(self, x, B, training):
         rt, R = self.rt, B * self.S
-        self.pre = self.a.forward(x, B)
-        rt.act(self.pre, self.h[:R], self.act)
+        h = self.ffn.hidden(x, R)
         y = self.y[:R]
         y.copy_(x)
-        rt.axpy(y, self.b.forward(self.h[:R], B), self.factor)
+        rt.axpy(y, self.ffn.second.forward(h, R), self.factor)
         return self.ln.forward(y, None, R, training) if self.ln else y
 
     def backward(self, dy, B):
         rt, R = self.rt, B * self.S
         dz = self.ln.backward(dy, R) if self.ln else dy
-        df = self.df[:R]
-        df.zero_()
-        rt.axpy(df, dz, self.factor)
-        self.b.backward(df, self.dh[:R], B)
-        rt.act_bwd(self.pre, self.dh[:R], self.dpre[:R], self.act)
         dx = self.dx[:R]
-        self.a.backward(self.dpre[:R], dx, B)
+        self.ffn.backward(dz, dx, R)
         rt.axpy(dx, dz)
         return dx
 
@@ -935,7 +961,7 @@ class AttentionBlock:
             self.mha = RelPositionMultiHeadAttention(rt, f"{p}.mha", B, S, D, H, dk, ub)
         if not lnf:
             self.ln1 = LayerNorm(rt, f"{p}.ln1", R, D)
-        self.ln2 = self.pw0 = self.dw = self.gate = None
+        self.ln2 = self.pw0 = self.tail = self.gate = None
         if self.glu:
             if lnf:
                 self.ln2 = LayerNorm(rt, f"{p}.ln2", R, D)
@@ -945,9 +971,7 @@ class AttentionBlock:
         if self.k > 0:
             if lnf and not self.glu:
                 self.ln2 = LayerNorm(rt, f"{p}.ln2", R, D)
-            self.dw = DepthwiseConv1D(rt, f"{p}.dw", B, S, D, self.k, glu=self.glu)
-            self.bn = BatchNorm(rt, f"{p}.bn", (S, 1, D), B)
-            self.pw1 = Conv1D(rt, f"{p}.pw1", B, S, D, D, 1)
+            self.tail = _ConvTail(rt, p, B, S, D, self.k, glu=self.glu)
             if not lnf:
                 self.ln2 = LayerNorm(rt, f"{p}.ln2", R, D)
         self.ff1 = _FFModule(rt, f"{p}.ff1", None if lnf else f"{p}.ln3", B, S, D, F, fk, act, f1) if f1 > 0 else None
@@ -956,9 +980,8 @@ class AttentionBlock:
             self.enc = torch.as_tensor(basic_pos_encoding(S, D)).to(rt.dev)
         e = rt.empty
         self.xr, self.xb, self.xc = e(R, D), e(R, D), e(R, D)
-        self.bno, self.sw, self.dsw, self.dbn, self.ddw = e(R, D), e(R, D), e(R, D), e(R, D), e(R, D)
         self.du, self.dn, self.dxb, self.dxa = e(R, 2 * D), e(R, D), e(R, D), e(R, D)
-        self.out_shape = (S, D)
+        self.out_dim, self.out_shape = D, (S, D)
 
     def forward(self, x, B, training):
         """x [B*S, D] (or any contiguous view of it) -> [B*S, D]"""
@@ -982,15 +1005,13 @@ class AttentionBlock:
             xb = self.ln1.forward(attn, res, R, training)
         c = xb
         if self.glu:
-            c = self.pw0.forward(self.ln2.forward(c, None, R, training) if self.lnf else c, B)
+            c = self.pw0.forward(self.ln2.forward(c, None, R, training) if self.lnf else c, R)
             if self.k == 0:
                 c = self.gate.forward(c, R)
         if self.k > 0:
             if self.lnf and not self.glu:
                 c = self.ln2.forward(c, None, R, training)
-            self.bn.forward(self.dw.forward(c, B), self.bno[:R], B, training, 0)
-            rt.act(self.bno[:R], self.sw[:R], ACT["swish"])
-            pw = self.pw1.forward(self.sw[:R], B)
+            pw = self.tail.forward(c, B, training)
             if self.lnf:
                 xc = self.xc[:R]
                 xc.copy_(xb)
@@ -1013,18 +1034,15 @@ class AttentionBlock:
         if self.k > 0:
             dz = d if self.lnf else self.ln2.backward(d, R)               # gradient of xb + pw
             dxb.copy_(dz)
-            self.pw1.backward(dz, self.dsw[:R], B)
-            rt.act_bwd(self.bno[:R], self.dsw[:R], self.dbn[:R], ACT["swish"])
-            self.bn.backward(self.dbn[:R], self.ddw[:R], B)
-            self.dw.backward(self.ddw[:R], du, B)
+            self.tail.backward(dz, du, B)
             if self.glu:
-                self.pw0.backward(du, dn, B)
+                self.pw0.backward(du, dn, R)
                 rt.axpy(dxb, self.ln2.backward(dn, R) if self.lnf else dn)
             else:
                 rt.axpy(dxb, self.ln2.backward(du, R) if self.lnf else du)
         elif self.glu:
             self.gate.backward(d, du, R)
-            self.pw0.backward(du, dn, B)
+            self.pw0.backward(du, dn, R)
             dxb.copy_(self.ln2.backward(dn, R) if self.lnf else dn)
         else:
             dxb.copy_(d)
@@ -1034,18 +1052,6 @@ class AttentionBlock:
         self.mha.backward(dz, dn, B)
         rt.axpy(dxa, self.ln1.backward(dn, R) if self.lnf else dn)
         return self.ff0.backward(dxa, B) if self.ff0 else dxa
-
-
-class AttentionStage:
-    """reference modules.attention_stage (modules.py:155-180): `depth` blocks"""
-
-    def __init__(self, rt: _Rt, cfg: dict, S: int, D: int, prefix: str, B: int, depth=None):
-        depth = int(cfg["depth"]) if depth is None else int(depth)
-        self.blocks = [AttentionBlock(rt, cfg, S, D, f"{prefix}{i}", B) for i in range(depth)]
-        self.S, self.D, self.out_shape = int(S), int(D), (int(S), int(D))
-
-    forward = TransformerEncoderStage.forward
-    backward = TransformerEncoderStage.backward
 
 
 RNN_MERGE = ("mul", "concat", "ave", "sum")      # what tf.keras.layers.Bidirectional merges into ONE tensor
@@ -1068,7 +1074,44 @@ def check_rnn_config(cfg: dict, stage: bool = False) -> None:
         raise ValueError(f"{who}: merge_mode {cfg.get('merge_mode')!r}: one of {RNN_MERGE}")
 
 
-class RNNBlock:
+class _Recurrent:
+    """What the recurrent blocks share on [B*S, D] with 128 units and gate width G (GRU, reset_after=True: 384, LSTM: 512), per direction
+    `name` of `names`: the variables kernel (D, G), recurrent_kernel (128, G), bias (GRU (2, 384): input row | recurrent row; LSTM (512,)),
+    the input projections gx, the states h and sv, the pre-activation gradients dgx (GRU: and dgh, behind the reset gate), the input's
+    gradient din — and the GEMMs in front of and behind the recurrence kernels."""
+
+    def __init__(self, rt: _Rt, names, S: int, D: int, G: int, B: int):
+        self.rt, self.names, self.S, self.D, self.G, self.B = rt, names, int(S), int(D), G, B
+        for n in names:
+            rt.var(f"{n}.kernel", (self.D, G)); rt.var(f"{n}.recurrent_kernel", (128, G)); rt.var(f"{n}.bias", (512,) if G == 512 else (2, 384))
+        R, nd = B * self.S, len(names)
+        e = rt.empty
+        self.gx, self.h, self.sv = [e(R, G) for _ in range(nd)], [e(R, 128) for _ in range(nd)], [e(R, 512) for _ in range(nd)]
+        self.dgx = [e(R, G) for _ in range(nd)]
+        self.dgh = [e(R, G) for _ in range(nd)] if G == 384 else self.dgx      # LSTM: no reset gate, one pre-activation gradient
+        self.din = e(R, self.D)
+
+    def _project(self, x, R):
+        """gx = x kernel + the input bias, per direction"""
+        rt = self.rt
+        self.x = x
+        for d, n in enumerate(self.names):
+            rt.gemm(x, rt.w(f"{n}.kernel"), rt.w(f"{n}.bias")[:self.G], self.gx[d], R, self.G, self.D)
+
+    def _weight_grads(self, R):
+        """dgx, dgh -> every variable's gradient and the input's [R, D]"""
+        rt = self.rt
+        for d, n in enumerate(self.names):
+            gb = rt.g(f"{n}.bias")
+            rt.gemm_tn(self.x, self.dgx[d], rt.g(f"{n}.kernel"), gb[:self.G], R, self.D, self.G)
+            # recurrent kernel: h_prev^T dgh — the forward direction saw h[t-1], the backward direction h[t+1]
+            rt.gemm_tn(self.h[d], self.dgh[d], rt.g(f"{n}.recurrent_kernel"), gb[384:] if self.G == 384 else None, R, 128, self.G, seq=self.S,
+                       shift=-1 if d == 0 else 1)
+            rt.gemm(self.dgx[d], rt.w(f"{n}.kernel"), None, self.din, R, self.D, self.G, transb=1, accumulate=d)
+        return self.din[:R]
+
+
+class RNNBlock(_Recurrent):
     """reference modules.RNN_block (modules.py:322-347) on [B*S, D]: rnn_type 'GRU' -> GRU(128, reset_after=True), ANYTHING else -> LSTM(128)
     (modules.py:334-337), return_sequences=True; bidirectional -> Bidirectional(merge_mode), whose variables are the forward layer's, then the
     backward layer's (`{prefix}.fwd.*`, `{prefix}.bwd.*`; one direction: `{prefix}.*`).  With bidirectional=False merge_mode is ignored.
@@ -1076,24 +1119,17 @@ class RNNBlock:
 
     def __init__(self, rt: _Rt, cfg: dict, S: int, D: int, prefix: str, B: int):
         check_rnn_config(cfg)
-        self.rt, self.S, self.D, self.B, self.prefix = rt, int(S), int(D), B, prefix
+        self.prefix = prefix
         self.lstm = cfg.get("rnn_type", "GRU") != "GRU"
         self.bi = bool(cfg.get("bidirectional", True))
         self.mode = _lib.SELD_MERGE[cfg.get("merge_mode", "mul")] if self.bi else None
-        G = self.G = 512 if self.lstm else 384
-        self.names = [f"{prefix}.fwd", f"{prefix}.bwd"] if self.bi else [prefix]
-        for n in self.names:
-            rt.var(f"{n}.kernel", (self.D, G)); rt.var(f"{n}.recurrent_kernel", (128, G)); rt.var(f"{n}.bias", (512,) if self.lstm else (2, 384))
+        super().__init__(rt, [f"{prefix}.fwd", f"{prefix}.bwd"] if self.bi else [prefix], S, D, 512 if self.lstm else 384, B)
         self.out_dim = 256 if self.bi and cfg.get("merge_mode", "mul") == "concat" else 128
         R, nd = B * self.S, len(self.names)
         e = rt.empty
-        self.gx, self.h, self.sv = [e(R, G) for _ in range(nd)], [e(R, 128) for _ in range(nd)], [e(R, 512) for _ in range(nd)]
         self.c = [e(R, 128) for _ in range(nd)] if self.lstm else None
-        self.dgx = [e(R, G) for _ in range(nd)]
-        self.dgh = [e(R, G) for _ in range(nd)] if not self.lstm else self.dgx      # no reset gate: one pre-activation gradient
         self.dh = [e(R, 128) for _ in range(nd)] if self.bi else None
         self.out = e(R, self.out_dim) if self.bi else None
-        self.din = e(R, self.D)
         self.out_shape = (self.S, self.out_dim)
 
     def _two(self, ts, none=False):
@@ -1105,9 +1141,7 @@ class RNNBlock:
         """x [B*S, D] (or any contiguous view of it) -> [B*S, out_dim]"""
         rt, lib = self.rt, self.rt.lib
         R = B * self.S
-        x = self.x = x.reshape(R, self.D)
-        for d, n in enumerate(self.names):
-            rt.gemm(x, rt.w(f"{n}.kernel"), rt.w(f"{n}.bias")[:self.G], self.gx[d], R, self.G, self.D)
+        self._project(x.reshape(R, self.D), R)
         U = self._two([rt.w(f"{n}.recurrent_kernel") for n in self.names])
         if self.lstm:
             rt.ck(lib.seld_rnn_lstm_fwd(*self._two(self.gx), *U, *self._two(self.h), *self._two(self.c, not training), *self._two(self.sv, not training),
@@ -1137,31 +1171,80 @@ class RNNBlock:
         else:
             rt.ck(lib.seld_rnn_gru_bwd(*dh, *self._two(self.h), *self._two(self.sv), *U, *self._two(self.dgx), *self._two(self.dgh), B, self.S, 128,
                                        rt.st()))
-        for d, n in enumerate(self.names):
-            gb = rt.g(f"{n}.bias")
-            rt.gemm_tn(self.x, self.dgx[d], rt.g(f"{n}.kernel"), gb[:self.G], R, self.D, self.G)
-            # recurrent kernel: h_prev^T dgh — the forward direction saw h[t-1], the backward direction h[t+1]
-            rt.gemm_tn(self.h[d], self.dgh[d], rt.g(f"{n}.recurrent_kernel"), None if self.lstm else gb[384:], R, 128, self.G, seq=self.S,
-                       shift=-1 if d == 0 else 1)
-            rt.gemm(self.dgx[d], rt.w(f"{n}.kernel"), None, self.din, R, self.D, self.G, transb=1, accumulate=d)
-        return self.din[:R]
+        return self._weight_grads(R)
 
 
-class RNNStage:
-    """reference modules.RNN_stage (modules.py:64-83): `depth` RNN_blocks of the same configuration; behind a 'concat' block the next one reads 256
-    features"""
+def check_gru_config(cfg: dict, stage: bool = False) -> None:
+    """reference modules.bidirectional_GRU_block (modules.py:302-319): one layer per entry of `units`"""
+    if float(cfg.get("dropout_rate", 0.0)) != 0.0:
+        raise ValueError("GRU dropout is not implemented")
+    if any(int(u) != 128 for u in cfg["units"]):
+        raise ValueError("the recurrence kernels are built for 128 units")
 
-    def __init__(self, rt: _Rt, cfg: dict, S: int, D: int, prefix: str, B: int, depth=None):
-        check_rnn_config(cfg, depth is None)
-        depth = int(cfg["depth"]) if depth is None else int(depth)
-        self.blocks = []
-        for i in range(depth):
-            self.blocks.append(RNNBlock(rt, cfg, S, D, f"{prefix}{i}", B))
-            D = self.blocks[-1].out_dim
-        self.S, self.D, self.out_dim, self.out_shape = int(S), int(self.blocks[0].D), int(D), (int(S), int(D))
 
-    forward = TransformerEncoderStage.forward
-    backward = TransformerEncoderStage.backward
+class BidirectionalGRUBlock(_Recurrent):
+    """One layer of reference modules.bidirectional_GRU_block (modules.py:302-319) on [B*S, D]: Bidirectional(GRU(128, return_sequences=True),
+    merge_mode='mul'), the recurrences and the merge in the fused operators seld_m_gru_fwd / _bwd."""
+
+    def __init__(self, rt: _Rt, cfg: dict, S: int, D: int, prefix: str, B: int):
+        check_gru_config(cfg)
+        super().__init__(rt, [f"{prefix}.fwd", f"{prefix}.bwd"], S, D, 384, B)
+        self.out = rt.empty(B * self.S, 128)
+        self.out_dim, self.out_shape = 128, (self.S, 128)
+
+    def forward(self, x, B, training):
+        rt, p = self.rt, self.rt.p
+        R = B * self.S
+        self._project(x.reshape(R, self.D), R)
+        U = [p(rt.w(f"{n}.recurrent_kernel")) for n in self.names]
+        brec = [p(rt.w(f"{n}.bias")[384:]) for n in self.names]
+        rt.ck(rt.lib.seld_m_gru_fwd(p(self.gx[0]), p(self.gx[1]), *U, *brec, p(self.h[0]), p(self.h[1]), p(self.sv[0]) if training else None,
+                                    p(self.sv[1]) if training else None, p(self.out), B, self.S, 128, rt.st()))
+        return self.out[:R]
+
+    def backward(self, dy, B):
+        rt, p = self.rt, self.rt.p
+        R = B * self.S
+        U = [p(rt.w(f"{n}.recurrent_kernel")) for n in self.names]
+        rt.ck(rt.lib.seld_m_gru_bwd(p(dy), p(self.h[0]), p(self.h[1]), p(self.sv[0]), p(self.sv[1]), *U, p(self.dgx[0]), p(self.dgx[1]),
+                                    p(self.dgh[0]), p(self.dgh[1]), B, self.S, 128, rt.st()))
+        return self._weight_grads(R)
+
+
+class _SqueezeExcite:
+    """mother_block's squeeze-and-excitation tail (reference modules.py:281-296) on [B, H, W, C]: x * sigmoid(Conv2D(C, 1)(act(Conv2D(sf, 1)(
+    mean over H, W of x)))) — on one pixel the two 1x1 convolutions are Linear layers with Keras' kernels (1, 1, C, sf) and (1, 1, sf, C)."""
+
+    def __init__(self, rt: _Rt, prefix: str, shape, sf: int, act: int, B: int):
+        self.rt, self.shape, self.act = rt, tuple(shape), act
+        Cc = self.shape[2]
+        self.se0 = Linear(rt, f"{prefix}.se0", B, Cc, sf, (1, 1, Cc, sf))
+        self.se1 = Linear(rt, f"{prefix}.se1", B, sf, Cc, (1, 1, sf, Cc))
+        e = rt.empty
+        self.m, self.s1, self.s2, self.y = e(B, Cc), e(B, sf), e(B, Cc), e(B, *self.shape)
+        self.ds2, self.da2, self.ds1, self.da1, self.dm, self.din = e(B, Cc), e(B, Cc), e(B, sf), e(B, sf), e(B, Cc), e(B, *self.shape)
+
+    def forward(self, x, B):
+        rt = self.rt
+        Hh, Ww, Cc = self.shape
+        self.x = x
+        rt.ck(rt.lib.seld_m_mean_hw(rt.p(x), rt.p(self.m), B, Hh * Ww, Cc, rt.st()))
+        rt.act(self.se0.forward(self.m, B), self.s1[:B], self.act)
+        rt.act(self.se1.forward(self.s1, B), self.s2[:B], ACT["sigmoid"])
+        rt.ck(rt.lib.seld_m_scale_hw(rt.p(x), rt.p(self.s2), rt.p(self.y), B, Hh * Ww, Cc, rt.st()))
+        return self.y[:B]
+
+    def backward(self, dy, B):
+        """dy: the output's gradient -> the input's (a buffer of this layer)"""
+        rt = self.rt
+        Hh, Ww, Cc = self.shape
+        rt.ck(rt.lib.seld_m_scale_hw_bwd_ds(rt.p(self.x), rt.p(dy), rt.p(self.ds2), B, Hh * Ww, Cc, rt.st()))
+        rt.act_bwd(self.se1.z[:B], self.ds2[:B], self.da2[:B], ACT["sigmoid"])
+        self.se1.backward(self.da2, self.ds1, B)
+        rt.act_bwd(self.se0.z[:B], self.ds1[:B], self.da1[:B], self.act)
+        self.se0.backward(self.da1, self.dm, B)
+        rt.ck(rt.lib.seld_m_scale_hw_bwd_dx(rt.p(dy), rt.p(self.s2), rt.p(self.dm), rt.p(self.din), B, Hh * Ww, Cc, 0, rt.st()))
+        return self.din[:B]
 
 
 class MotherBlock:
@@ -1228,14 +1311,7 @@ class MotherBlock:
         sq = float(cfg.get("squeeze_ratio", 0))
         self.se = None
         if sq > 0:
-            Cc = self.out_shape[2]
-            sf = int(sq * Cc)
-            rt.var(f"{prefix}.se0.kernel", (1, 1, Cc, sf)); rt.var(f"{prefix}.se0.bias", (sf,))
-            rt.var(f"{prefix}.se1.kernel", (1, 1, sf, Cc)); rt.var(f"{prefix}.se1.bias", (Cc,))
-            self.se = {"p": prefix, "sf": sf, "act": ACT[cfg.get("se_activation", "relu")], "m": rt.empty(B, Cc), "a1": rt.empty(B, sf),
-                       "s1": rt.empty(B, sf), "a2": rt.empty(B, Cc), "s2": rt.empty(B, Cc), "y": rt.empty(B, *self.out_shape),
-                       "ds2": rt.empty(B, Cc), "da2": rt.empty(B, Cc), "ds1": rt.empty(B, sf), "da1": rt.empty(B, sf), "dm": rt.empty(B, Cc),
-                       "din": rt.empty(B, *self.out_shape)}
+            self.se = _SqueezeExcite(rt, prefix, self.out_shape, int(sq * self.out_shape[2]), ACT[cfg.get("se_activation", "relu")], B)
         # gradients w.r.t. outputs[0..2] (outputs[0] = the block input) are accumulated here during backward
         self.gout = [rt.empty(B, *s) for s in shapes]
 
@@ -1273,37 +1349,14 @@ class MotherBlock:
             else:
                 res = y
         self.outputs = outputs
-        if self.se is not None:
-            se = self.se
-            Hh, Ww, Cc = self.out_shape
-            p_ = se["p"]
-            self.se_in = res
-            rt.ck(rt.lib.seld_m_mean_hw(rt.p(res), rt.p(se["m"]), B, Hh * Ww, Cc, rt.st()))
-            rt.gemm(se["m"], rt.w(f"{p_}.se0.kernel"), rt.w(f"{p_}.se0.bias"), se["a1"], B, se["sf"], Cc)
-            rt.act(se["a1"][:B], se["s1"][:B], se["act"])
-            rt.gemm(se["s1"], rt.w(f"{p_}.se1.kernel"), rt.w(f"{p_}.se1.bias"), se["a2"], B, Cc, se["sf"])
-            rt.act(se["a2"][:B], se["s2"][:B], ACT["sigmoid"])
-            rt.ck(rt.lib.seld_m_scale_hw(rt.p(res), rt.p(se["s2"]), rt.p(se["y"]), B, Hh * Ww, Cc, rt.st()))
-            res = se["y"][:B]
-        return res
+        return res if self.se is None else self.se.forward(res, B)
 
     # ---------------------------------------------------------------- backward
     def backward(self, dy, dx, B, need_dx=True):
         """dy: gradient w.r.t. the block output; dx (= the caller's buffer for the block input's gradient, overwritten) or None"""
         rt = self.rt
         if self.se is not None:
-            se = self.se
-            Hh, Ww, Cc = self.out_shape
-            p_ = se["p"]
-            rt.ck(rt.lib.seld_m_scale_hw_bwd_ds(rt.p(self.se_in), rt.p(dy), rt.p(se["ds2"]), B, Hh * Ww, Cc, rt.st()))
-            rt.act_bwd(se["a2"][:B], se["ds2"][:B], se["da2"][:B], ACT["sigmoid"])
-            rt.gemm_tn(se["s1"], se["da2"], rt.g(f"{p_}.se1.kernel"), rt.g(f"{p_}.se1.bias"), B, se["sf"], Cc)
-            rt.gemm(se["da2"], rt.w(f"{p_}.se1.kernel"), None, se["ds1"], B, se["sf"], Cc, transb=1)
-            rt.act_bwd(se["a1"][:B], se["ds1"][:B], se["da1"][:B], se["act"])
-            rt.gemm_tn(se["m"], se["da1"], rt.g(f"{p_}.se0.kernel"), rt.g(f"{p_}.se0.bias"), B, Cc, se["sf"])
-            rt.gemm(se["da1"], rt.w(f"{p_}.se0.kernel"), None, se["dm"], B, Cc, se["sf"], transb=1)
-            rt.ck(rt.lib.seld_m_scale_hw_bwd_dx(rt.p(dy), rt.p(se["s2"]), rt.p(se["dm"]), rt.p(se["din"]), B, Hh * Ww, Cc, 0, rt.st()))
-            dy = se["din"][:B]
+            dy = self.se.backward(dy, B)
         # gradient slots of outputs[0..2]; outputs[1] may alias outputs[0] (first layer skipped): then they share one slot
         alias0 = self.layers[0]["kind"] == "alias"
         slots = [self.gout[0][:B], self.gout[0][:B] if alias0 else self.gout[1][:B], self.gout[2][:B]]
@@ -1370,6 +1423,62 @@ ATTENTION_SECOND = ("attention_block", "attention_stage")                       
 RNN_SECOND = ("RNN_block", "RNN_stage")                                            # SECOND as well; the heads read the stage's out_dim
 
 
+# SECOND kind -> (block class, its config check, the variables' prefix, a *_stage of cfg['depth'] blocks?, does the check take the width D?)
+SECOND_KINDS = {
+    "bidirectional_GRU_block": (BidirectionalGRUBlock, check_gru_config, "gru", False, False),      # one layer per entry of `units`
+    "transformer_encoder_block": (TransformerEncoderBlock, check_transformer_config, "tf", False, False),
+    "transformer_encoder_stage": (TransformerEncoderBlock, check_transformer_config, "tf", True, False),
+    "conformer_encoder_block": (ConformerEncoderBlock, check_conformer_config, "cf", False, True),
+    "conformer_encoder_stage": (ConformerEncoderBlock, check_conformer_config, "cf", True, True),
+    "attention_block": (AttentionBlock, check_attention_config, "at", False, True),
+    "attention_stage": (AttentionBlock, check_attention_config, "at", True, True),
+    "RNN_block": (RNNBlock, check_rnn_config, "rnn", False, False),
+    "RNN_stage": (RNNBlock, check_rnn_config, "rnn", True, False),
+}
+assert tuple(SECOND_KINDS) == COMPOSED_SECOND + CONFORMER_SECOND + ATTENTION_SECOND + RNN_SECOND
+
+
+def _build_second(kind: str, rt, cfg: dict, S: int, D: int, B: int, prefix=None) -> Stage:
+    """the SECOND stage `kind` on [B*S, D] (rt None: on a runtime of its own on the current device); the configuration errors, those that
+    need the width among them (pos_encoding 'basic' on an odd one, the FF width), are raised first, without a device"""
+    block, check, pre, stage, with_d = SECOND_KINDS[kind]
+    check(cfg, stage, D) if with_d else check(cfg, stage)
+    rt = rt or _Rt(torch.device("cuda", torch.cuda.current_device()))
+    depth = int(cfg["depth"]) if stage else len(cfg["units"]) if block is BidirectionalGRUBlock else 1
+    return Stage(rt, block, cfg, S, D, prefix or pre, B, depth)
+
+
+class Head:
+    """reference modules.simple_dense_block (modules.py:350-376) with kernel_size 1 on [rows, Cin]: a Conv1D(u, 1) (kernel (1, Cin, u)) +
+    `hact` per entry of `units`, then Dense(n_out) (kernel (Cin, n_out)) + `act`.  backward starts from `dpre`, the gradient of the output
+    layer's pre-activation, which the loss kernel writes."""
+
+    def __init__(self, rt: _Rt, name: str, rows: int, Cin: int, units, hact: int, n_out: int, act: int):
+        self.rt, self.hact, self.act = rt, hact, act
+        self.hidden = []      # (layer, its activation y, the gradients of its pre-activation and of y)
+        for j, u in enumerate(int(u) for u in units):
+            self.hidden.append((Linear(rt, f"{name}.dense{j}", rows, Cin, u, (1, Cin, u)), rt.empty(rows, u), rt.empty(rows, u), rt.empty(rows, u)))
+            Cin = u
+        self.out = Linear(rt, f"{name}.out", rows, Cin, n_out)
+        self.dpre = rt.empty(rows, n_out)
+
+    def forward(self, x, y, rows):
+        """x [rows, Cin] -> y [rows, n_out] (the caller's)"""
+        for lin, a, _, _ in self.hidden:
+            self.rt.act(lin.forward(x, rows), a[:rows], self.hact)
+            x = a
+        self.rt.act(self.out.forward(x, rows), y, self.act)
+
+    def backward(self, dx, rows, accumulate):
+        """dpre -> every variable's gradient; dx (+)= the input's gradient"""
+        lin, dz = self.out, self.dpre
+        for hid, _, dpre, da in reversed(self.hidden):
+            lin.backward(dz, da, rows)
+            self.rt.act_bwd(hid.z[:rows], da[:rows], dpre[:rows], self.hact)
+            lin, dz = hid, dpre
+        lin.backward(dz, dx, rows, accumulate)
+
+
 class ComposedSeldNet:
     """models.seldnet(input_shape, model_config) (reference models.py:18-32) composed from module operators: FIRST = mother_block |
     mother_stage, SECOND = bidirectional_GRU_block (units 128: the recurrence kernels) | transformer_encoder_block | transformer_encoder_stage |
@@ -1383,7 +1492,7 @@ class ComposedSeldNet:
         if not torch.cuda.is_available():
             raise RuntimeError("seld_amd needs a HIP device: there is no CPU fallback")
         cfg = canonical_config(model_config)
-        seconds = COMPOSED_SECOND + CONFORMER_SECOND + ATTENTION_SECOND + RNN_SECOND
+        seconds = tuple(SECOND_KINDS)
         if cfg.get("SECOND") not in seconds or cfg.get("SED") != "simple_dense_block" or cfg.get("DOA") != "simple_dense_block":
             raise ValueError(f"composed models: SECOND in {seconds}, SED / DOA = simple_dense_block")
         self._dev = torch.device("cuda", torch.cuda.current_device() if device is None else int(device))
@@ -1409,57 +1518,17 @@ class ComposedSeldNet:
             self.blocks.append(blk)
             shape = blk.out_shape
         self.S = shape[0]
-        feat = shape[1] * shape[2]
-        sa = cfg["SECOND_ARGS"]
-        self.gru, self.tf = [], None      # tf: the attention stage (transformer or conformer), forward(x, B, training) / backward(dy, B)
-        fin = feat
-        if cfg["SECOND"] in CONFORMER_SECOND:
-            stage = cfg["SECOND"] == "conformer_encoder_stage"
-            check_conformer_config(sa, stage, feat)
-            self.tf = ConformerEncoderStage(rt, sa, self.S, feat, "cf", B, depth=None if stage else 1)
-        elif cfg["SECOND"] in ATTENTION_SECOND:
-            stage = cfg["SECOND"] == "attention_stage"
-            check_attention_config(sa, stage, feat)
-            self.tf = AttentionStage(rt, sa, self.S, feat, "at", B, depth=None if stage else 1)
-        elif cfg["SECOND"] in RNN_SECOND:
-            stage = cfg["SECOND"] == "RNN_stage"
-            check_rnn_config(sa, stage)
-            self.tf = RNNStage(rt, sa, self.S, feat, "rnn", B, depth=None if stage else 1)
-            fin = self.tf.out_dim
-        elif cfg["SECOND"] != "bidirectional_GRU_block":
-            stage = cfg["SECOND"] == "transformer_encoder_stage"
-            check_transformer_config(sa, stage)
-            self.tf = TransformerEncoderStage(rt, sa, self.S, feat, "tf", B, depth=None if stage else 1)      # d_model = F * C (force_1d_inputs)
-        elif float(sa.get("dropout_rate", 0.0)) != 0.0:
-            raise ValueError("GRU dropout is not implemented")
-        for i, u in enumerate(sa["units"] if self.tf is None else ()):
-            if int(u) != 128:
-                raise ValueError("the recurrence kernels are built for 128 units")
-            for dn in ("fwd", "bwd"):
-                rt.var(f"gru{i}.{dn}.kernel", (fin, 384)); rt.var(f"gru{i}.{dn}.recurrent_kernel", (128, 384)); rt.var(f"gru{i}.{dn}.bias", (2, 384))
-            R = B * self.S
-            self.gru.append({"in": fin, "gx": [rt.empty(R, 384) for _ in range(2)], "h": [rt.empty(R, 128) for _ in range(2)],
-                             "sv": [rt.empty(R, 512) for _ in range(2)], "out": rt.empty(R, 128), "dgx": [rt.empty(R, 384) for _ in range(2)],
-                             "dgh": [rt.empty(R, 384) for _ in range(2)], "din": rt.empty(R, fin)})
-            fin = 128
+        self.second = _build_second(cfg["SECOND"], rt, cfg["SECOND_ARGS"], self.S, shape[1] * shape[2], B)      # d_model = F * C (force_1d_inputs)
+        fin = self.second.out_dim
         self.heads = []
-        for head, key, n_out in (("sed", "SED_ARGS", self.n_classes), ("doa", "DOA_ARGS", 3 * self.n_classes)):
+        for head, key, n_out, act in (("sed", "SED_ARGS", self.n_classes, "sigmoid"), ("doa", "DOA_ARGS", 3 * self.n_classes, "tanh")):
             ha = cfg[key]
             if int(ha.get("kernel_size", 1)) != 1 or float(ha.get("dropout_rate", 0)) != 0:
                 raise ValueError("composed heads: kernel_size 1, no dropout")
             hact = ha.get("dense_activation", None)
             if hact not in ACT:
                 raise ValueError(f"dense_activation {hact!r}")
-            a = fin
-            lays = []
-            for j, u in enumerate(ha.get("units", [])):
-                rt.var(f"{head}.dense{j}.kernel", (1, a, int(u))); rt.var(f"{head}.dense{j}.bias", (int(u),))
-                lays.append({"n": f"{head}.dense{j}", "in": a, "out": int(u), "pre": rt.empty(B * self.S, int(u)), "y": rt.empty(B * self.S, int(u)),
-                             "dpre": rt.empty(B * self.S, int(u)), "dy": rt.empty(B * self.S, int(u))})
-                a = int(u)
-            rt.var(f"{head}.out.kernel", (a, n_out)); rt.var(f"{head}.out.bias", (n_out,))
-            self.heads.append({"name": head, "hact": ACT[hact], "layers": lays, "in": a, "out": n_out, "pre": rt.empty(B * self.S, n_out),
-                               "dpre": rt.empty(B * self.S, n_out), "act": ACT["sigmoid"] if head == "sed" else ACT["tanh"]})
+            self.heads.append(Head(rt, head, B * self.S, fin, ha.get("units", []), ACT[hact], n_out, ACT[act]))
         rt.finalize()
         self.variables, self.state_variables = rt.variables, rt.state_variables
         self.n_params, self.n_state = rt.n_params, rt.n_state
@@ -1585,33 +1654,11 @@ class ComposedSeldNet:
             h = blk.forward(h, B, training)
         self._mark("first_fwd")
         R = B * self.S
-        feat = h.reshape(R, -1)          # layers.force_1d_inputs (layers.py:41-47): feature = f * C + c
-        self.feat0 = feat
-        for i, G in enumerate(self.gru):
-            G["x"] = feat
-            for d, dn in enumerate(("fwd", "bwd")):
-                b = rt.w(f"gru{i}.{dn}.bias")
-                rt.gemm(feat, rt.w(f"gru{i}.{dn}.kernel"), b[:384], G["gx"][d], R, 384, G["in"])
-            bf, bb = rt.w(f"gru{i}.fwd.bias"), rt.w(f"gru{i}.bwd.bias")
-            rt.ck(rt.lib.seld_m_gru_fwd(rt.p(G["gx"][0]), rt.p(G["gx"][1]), rt.p(rt.w(f"gru{i}.fwd.recurrent_kernel")),
-                                        rt.p(rt.w(f"gru{i}.bwd.recurrent_kernel")), rt.p(bf[384:]), rt.p(bb[384:]), rt.p(G["h"][0]), rt.p(G["h"][1]),
-                                        rt.p(G["sv"][0]) if training else None, rt.p(G["sv"][1]) if training else None, rt.p(G["out"]), B, self.S, 128,
-                                        rt.st()))
-            feat = G["out"]
-        if self.tf is not None:
-            feat = self.tf.forward(feat, B, training)
+        feat = self.second.forward(h.reshape(R, -1), B, training)      # layers.force_1d_inputs (layers.py:41-47): feature = f * C + c
         sed = rt.empty(B, self.S, self.n_classes)
         doa = rt.empty(B, self.S, 3 * self.n_classes)
-        for Hd, out in zip(self.heads, (sed, doa)):
-            a = feat
-            for lay in Hd["layers"]:
-                lay["x"] = a
-                rt.gemm(a, rt.w(lay["n"] + ".kernel"), rt.w(lay["n"] + ".bias"), lay["pre"], R, lay["out"], lay["in"])
-                rt.act(lay["pre"][:R], lay["y"][:R], Hd["hact"])         # the buffers hold the LARGEST batch's rows: this batch's R only
-                a = lay["y"]
-            Hd["x"] = a
-            rt.gemm(a, rt.w(Hd["name"] + ".out.kernel"), rt.w(Hd["name"] + ".out.bias"), Hd["pre"], R, Hd["out"], Hd["in"])
-            rt.act(Hd["pre"][:R], out.view(R, -1), Hd["act"])
+        for head, out in zip(self.heads, (sed, doa)):
+            head.forward(feat, out.view(R, -1), R)
         self._mark("gru_heads_fwd")
         return sed, doa
 
@@ -1621,41 +1668,11 @@ class ComposedSeldNet:
         return [sed, doa]
 
     def _backward(self, B):
-        """from the heads' pre-activation gradients (Hd['dpre'], written by seld_k_losses) to every variable's gradient"""
-        rt = self.rt
+        """from the heads' pre-activation gradients (Head.dpre, written by seld_m_losses) to every variable's gradient"""
         R = B * self.S
-        first = True
-        for Hd in self.heads:
-            n = Hd["name"]
-            rt.gemm_tn(Hd["x"], Hd["dpre"], rt.g(n + ".out.kernel"), rt.g(n + ".out.bias"), R, Hd["in"], Hd["out"])
-            if Hd["layers"]:
-                rt.gemm(Hd["dpre"], rt.w(n + ".out.kernel"), None, Hd["layers"][-1]["dy"], R, Hd["in"], Hd["out"], transb=1)
-            else:
-                rt.gemm(Hd["dpre"], rt.w(n + ".out.kernel"), None, self.dfeat, R, Hd["in"], Hd["out"], transb=1, accumulate=0 if first else 1)
-            for j in range(len(Hd["layers"]) - 1, -1, -1):
-                lay = Hd["layers"][j]
-                rt.act_bwd(lay["pre"][:R], lay["dy"][:R], lay["dpre"][:R], Hd["hact"])
-                rt.gemm_tn(lay["x"], lay["dpre"], rt.g(lay["n"] + ".kernel"), rt.g(lay["n"] + ".bias"), R, lay["in"], lay["out"])
-                if j > 0:
-                    rt.gemm(lay["dpre"], rt.w(lay["n"] + ".kernel"), None, Hd["layers"][j - 1]["dy"], R, lay["in"], lay["out"], transb=1)
-                else:
-                    rt.gemm(lay["dpre"], rt.w(lay["n"] + ".kernel"), None, self.dfeat, R, lay["in"], lay["out"], transb=1, accumulate=0 if first else 1)
-            first = False
-        dout = self.dfeat
-        if self.tf is not None:
-            dout = self.tf.backward(dout[:R], B)
-        for i in range(len(self.gru) - 1, -1, -1):
-            G = self.gru[i]
-            rt.ck(rt.lib.seld_m_gru_bwd(rt.p(dout), rt.p(G["h"][0]), rt.p(G["h"][1]), rt.p(G["sv"][0]), rt.p(G["sv"][1]),
-                                        rt.p(rt.w(f"gru{i}.fwd.recurrent_kernel")), rt.p(rt.w(f"gru{i}.bwd.recurrent_kernel")), rt.p(G["dgx"][0]),
-                                        rt.p(G["dgx"][1]), rt.p(G["dgh"][0]), rt.p(G["dgh"][1]), B, self.S, 128, rt.st()))
-            for d, dn in enumerate(("fwd", "bwd")):
-                gb = rt.g(f"gru{i}.{dn}.bias")
-                rt.gemm_tn(G["x"], G["dgx"][d], rt.g(f"gru{i}.{dn}.kernel"), gb[:384], R, G["in"], 384)
-                # recurrent kernel: h_prev^T dgh — the forward direction saw h[t-1], the backward direction h[t+1]
-                rt.gemm_tn(G["h"][d], G["dgh"][d], rt.g(f"gru{i}.{dn}.recurrent_kernel"), gb[384:], R, 128, 384, seq=self.S, shift=-1 if d == 0 else 1)
-                rt.gemm(G["dgx"][d], rt.w(f"gru{i}.{dn}.kernel"), None, G["din"], R, G["in"], 384, transb=1, accumulate=d)
-            dout = G["din"]
+        for i, head in enumerate(self.heads):
+            head.backward(self.dfeat, R, accumulate=int(i > 0))      # the second head adds to the first one's
+        dout = self.second.backward(self.dfeat[:R], B)
         self._mark("heads_gru_bwd")
         dy = dout[:R].view(B, *self.blocks[-1].out_shape)
         for bi in range(len(self.blocks) - 1, -1, -1):
@@ -1676,7 +1693,7 @@ class ComposedSeldNet:
         sloss = torch.empty((), dtype=torch.float32, device=self._dev)
         dloss = torch.empty((B, self.S) if cfg.doa_loss != 1 else (), dtype=torch.float32, device=self._dev)
         rt.ck(rt.lib.seld_m_losses(rt.p(sed), rt.p(doa), rt.p(ys), rt.p(yd), C.byref(cfg), rt.p(sloss), rt.p(dloss),
-                                   rt.p(self.heads[0]["dpre"]) if want_grads else None, rt.p(self.heads[1]["dpre"]) if want_grads else None,
+                                   rt.p(self.heads[0].dpre) if want_grads else None, rt.p(self.heads[1].dpre) if want_grads else None,
                                    rt.p(self.loss_scratch), B, self.S, self.n_classes, rt.st()))
         return sloss, dloss
 
@@ -1719,103 +1736,58 @@ def mother_block(model_config: dict):
     return build
 
 
-def _transformer_factory(model_config: dict, stage: bool):
-    check_transformer_config(model_config, stage)
+def _second_factory(kind: str, model_config: dict):
+    _, check, pre, stage, _ = SECOND_KINDS[kind]
+    check(model_config, stage)
 
-    def build(input_shape, rt=None, prefix="tf"):
+    def build(input_shape, rt=None, prefix=pre):
         """input_shape [B, S, D] or [B, S, F, C] (layers.force_1d_inputs: D = F * C)"""
         sh = [int(v) for v in input_shape]
         if len(sh) not in (3, 4):
-            raise ValueError("transformer_encoder_block: input [B, S, D] or [B, S, F, C]")
-        B, S, D = sh[0], sh[1], int(np.prod(sh[2:]))
-        rt = rt or _Rt(torch.device("cuda", torch.cuda.current_device()))
-        return TransformerEncoderStage(rt, model_config, S, D, prefix, B, depth=None if stage else 1)
+            raise ValueError(f"{kind.replace('_stage', '_block')}: input [B, S, D] or [B, S, F, C]")
+        return _build_second(kind, rt, model_config, sh[1], int(np.prod(sh[2:])), sh[0], prefix)
     return build
 
 
 def transformer_encoder_block(model_config: dict):
-    """reference modules.transformer_encoder_block(model_config) (modules.py:379-407) -> a factory `(input_shape) -> a one-block
-    TransformerEncoderStage` (forward(x, B, training) / backward(dy, B) on [B*S, D]); configuration errors are raised here, without a device."""
-    return _transformer_factory(model_config, False)
+    """reference modules.transformer_encoder_block(model_config) (modules.py:379-407) -> a factory `(input_shape) -> a one-block Stage`
+    (forward(x, B, training) / backward(dy, B) on [B*S, D]); configuration errors are raised here, without a device."""
+    return _second_factory("transformer_encoder_block", model_config)
 
 
 def transformer_encoder_stage(model_config: dict):
     """reference modules.transformer_encoder_stage(model_config) (modules.py:106-126): `depth` blocks"""
-    return _transformer_factory(model_config, True)
-
-
-def _conformer_factory(model_config: dict, stage: bool):
-    check_conformer_config(model_config, stage)
-
-    def build(input_shape, rt=None, prefix="cf"):
-        """input_shape [B, S, D] or [B, S, F, C] (layers.force_1d_inputs: D = F * C)"""
-        sh = [int(v) for v in input_shape]
-        if len(sh) not in (3, 4):
-            raise ValueError("conformer_encoder_block: input [B, S, D] or [B, S, F, C]")
-        B, S, D = sh[0], sh[1], int(np.prod(sh[2:]))
-        check_conformer_config(model_config, stage, D)          # the odd-width rule of pos_encoding 'basic' needs D: still without a device
-        rt = rt or _Rt(torch.device("cuda", torch.cuda.current_device()))
-        return ConformerEncoderStage(rt, model_config, S, D, prefix, B, depth=None if stage else 1)
-    return build
+    return _second_factory("transformer_encoder_stage", model_config)
 
 
 def conformer_encoder_block(model_config: dict):
-    """reference modules.conformer_encoder_block(model_config) (modules.py:410-508) -> a factory `(input_shape) -> a one-block
-    ConformerEncoderStage` (forward(x, B, training) / backward(dy, B) on [B*S, D]); configuration errors are raised here, without a device."""
-    return _conformer_factory(model_config, False)
+    """reference modules.conformer_encoder_block(model_config) (modules.py:410-508) -> a factory `(input_shape) -> a one-block Stage`
+    (forward(x, B, training) / backward(dy, B) on [B*S, D]); configuration errors are raised here, without a device."""
+    return _second_factory("conformer_encoder_block", model_config)
 
 
 def conformer_encoder_stage(model_config: dict):
     """reference modules.conformer_encoder_stage(model_config) (modules.py:129-152): `depth` blocks"""
-    return _conformer_factory(model_config, True)
-
-
-def _attention_factory(model_config: dict, stage: bool):
-    check_attention_config(model_config, stage)
-
-    def build(input_shape, rt=None, prefix="at"):
-        """input_shape [B, S, D] or [B, S, F, C] (layers.force_1d_inputs: D = F * C)"""
-        sh = [int(v) for v in input_shape]
-        if len(sh) not in (3, 4):
-            raise ValueError("attention_block: input [B, S, D] or [B, S, F, C]")
-        B, S, D = sh[0], sh[1], int(np.prod(sh[2:]))
-        check_attention_config(model_config, stage, D)          # the rules that need the width: still without a device
-        rt = rt or _Rt(torch.device("cuda", torch.cuda.current_device()))
-        return AttentionStage(rt, model_config, S, D, prefix, B, depth=None if stage else 1)
-    return build
+    return _second_factory("conformer_encoder_stage", model_config)
 
 
 def attention_block(model_config: dict):
-    """reference modules.attention_block(model_config) (modules.py:511-635) -> a factory `(input_shape) -> a one-block AttentionStage`
+    """reference modules.attention_block(model_config) (modules.py:511-635) -> a factory `(input_shape) -> a one-block Stage`
     (forward(x, B, training) / backward(dy, B) on [B*S, D]); configuration errors are raised here, without a device."""
-    return _attention_factory(model_config, False)
+    return _second_factory("attention_block", model_config)
 
 
 def attention_stage(model_config: dict):
     """reference modules.attention_stage(model_config) (modules.py:155-180): `depth` blocks"""
-    return _attention_factory(model_config, True)
-
-
-def _rnn_factory(model_config: dict, stage: bool):
-    check_rnn_config(model_config, stage)
-
-    def build(input_shape, rt=None, prefix="rnn"):
-        """input_shape [B, S, D] or [B, S, F, C] (layers.force_1d_inputs: D = F * C)"""
-        sh = [int(v) for v in input_shape]
-        if len(sh) not in (3, 4):
-            raise ValueError("RNN_block: input [B, S, D] or [B, S, F, C]")
-        B, S, D = sh[0], sh[1], int(np.prod(sh[2:]))
-        rt = rt or _Rt(torch.device("cuda", torch.cuda.current_device()))
-        return RNNStage(rt, model_config, S, D, prefix, B, depth=None if stage else 1)
-    return build
+    return _second_factory("attention_stage", model_config)
 
 
 def RNN_block(model_config: dict):
-    """reference modules.RNN_block(model_config) (modules.py:322-347) -> a factory `(input_shape) -> a one-block RNNStage` (forward(x, B, training)
+    """reference modules.RNN_block(model_config) (modules.py:322-347) -> a factory `(input_shape) -> a one-block Stage` (forward(x, B, training)
     / backward(dy, B) on [B*S, D] -> [B*S, out_dim]); configuration errors are raised here, without a device."""
-    return _rnn_factory(model_config, False)
+    return _second_factory("RNN_block", model_config)
 
 
 def RNN_stage(model_config: dict):
     """reference modules.RNN_stage(model_config) (modules.py:64-83): `depth` blocks"""
-    return _rnn_factory(model_config, True)
+    return _second_factory("RNN_stage", model_config)
