@@ -500,6 +500,14 @@ int seld_m_bn_bwd(const float* z, const float* dy, const float* mean, const floa
 int seld_m_act(const float* x, float* y, int64_t n, int kind, void* stream);
 int seld_m_act_bwd(const float* x, const float* dy, float* dx, int64_t n, int kind, int accumulate, void* stream);
 int seld_m_axpy(float* dst, const float* src, int64_t n, float alpha, void* stream);      /* dst += alpha src */
+/* tf.keras.layers.Dropout(rate) in training, on the library's counter-based draws: out[e] = (accumulate ? out[e] : 0) + alpha in[e] M[e], M[e] = 0
+ * where u[e] < rate, else 1 / (1 - rate); u = the Philox4x32-10 uniforms of (seed, layer, step, e) that the fused path's Dropout draws (word e & 3
+ * of counter (e >> 2, layer, step, e >> 34) under the key (seed lo, seed hi), u = (word >> 8) * 2^-24), at any n >= 1.  A pure function of its
+ * arguments: the backward calls it again on the gradient, in place (in == out with accumulate 0 is allowed).  x + f Dropout(y) is one call with
+ * alpha = f, accumulate = 1.  SELD_ERR_INVALID for a NULL pointer, n < 1 or a rate outside [0, 1).  Under the seld_m_* contract (module_ops.hip), named
+ * with seld_attn_drop_*, the other half of the composed path's Dropout; tests/test_dropout_gpu.py calls it. */
+int seld_dropout(const float* in, float* out, int64_t n, float rate, float alpha, int accumulate, uint64_t seed, unsigned layer, unsigned step,
+                   void* stream);
 /* tf.concat(axis=-1) piece: mode 0 dst[r][off + c] = src[r][c]; mode 1 (its gradient) src[r][c] += dst[r][off + c] */
 int seld_m_copy_channels(float* src, float* dst, int64_t rows, int Cs, int Cd, int off, int mode, void* stream);
 /* squeeze-and-excitation (modules.py:287-294): reduce_mean over (H, W); out = se * out; and their gradients */
@@ -575,6 +583,19 @@ int64_t seld_attn_bwd_scratch(int B, int S, int H, int d);
 int seld_attn_bwd(const float* Q, const float* K, const float* V, int ldq, int ldk, int ldv, const float* O, const float* dO, const float* lse,
                   float* dQ, float* dK, float* dV, int lddq, int lddk, int lddv, float* scratch, int B, int S, int H, int d, float scale,
                   void* stream);
+/*   seld_attn_drop_fwd / _bwd   the same with Dropout(rate) on the softmax probabilities, as tf.keras.layers.MultiHeadAttention(dropout = rate) and
+ *                   layers.MultiHeadAttention_ (layers.py:253-257) apply it in training: O[b,n,h,:] = sum_m P[n,m] M[b,h,n,m] V[b,m,h,:] with P the
+ *                   full softmax (lse is bit-equal to seld_attn_fwd's) and M[b,h,n,m] = 0 where u < rate, else 1 / (1 - rate); u = (word >> 8) *
+ *                   2^-24 of word (m & 3) of Philox4x32-10 at counter (m >> 2, layer, step, (b H + h) S + n) under the key (seed lo, seed hi).
+ *                   The backward recomputes M from the same arguments (dV = (P M)^T dO, dS = P (M (dO V^T) - rowsum(dO * O))): no mask, no
+ *                   [B,H,S,S] tensor is stored, no atomics, two runs are bit-identical.  scratch: seld_attn_bwd_scratch.  rate 0 launches
+ *                   exactly what seld_attn_fwd / _bwd launch: the same bits.  Contract of seld_attn_* in the same order, with SELD_ERR_INVALID
+ *                   also for a rate outside [0, 1), and last SELD_ERR_UNSUPPORTED for B * H * S beyond 2^32 (the counter word) at rate > 0. */
+int seld_attn_drop_fwd(const float* Q, const float* K, const float* V, int ldq, int ldk, int ldv, float* O, float* lse, int B, int S, int H, int d,
+                       float scale, float rate, uint64_t seed, unsigned layer, unsigned step, void* stream);
+int seld_attn_drop_bwd(const float* Q, const float* K, const float* V, int ldq, int ldk, int ldv, const float* O, const float* dO, const float* lse,
+                       float* dQ, float* dK, float* dV, int lddq, int lddk, int lddv, float* scratch, int B, int S, int H, int d, float scale,
+                       float rate, uint64_t seed, unsigned layer, unsigned step, void* stream);
 /*   seld_ln_fwd     tf.keras.layers.LayerNormalization over the last axis of [rows, C] (modules.py:395, 403: biased variance, eps inside the
  *                   square root): y = xhat gamma + beta, xhat = (z - mean z) / sqrt(var z + eps), z = x + r — the residual r may be NULL, so
  *                   LayerNormalization()(x + attn) is one pass.  xhat [rows, C] and rstd [rows] are saved for the backward (both may be NULL

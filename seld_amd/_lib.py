@@ -68,6 +68,8 @@ _I = C.c_int
 _L = C.c_int64
 _F = C.c_float
 _FP = C.POINTER(C.c_float)
+_U = C.c_uint
+_U64 = C.c_uint64
 
 # name -> (restype, argtypes); must list every symbol include/seld_hip.h declares
 SIGNATURES = {
@@ -181,6 +183,7 @@ SIGNATURES = {
     "seld_m_act": (_I, [_P, _P, _L, _I, _P]),
     "seld_m_act_bwd": (_I, [_P, _P, _P, _L, _I, _I, _P]),
     "seld_m_axpy": (_I, [_P, _P, _L, _F, _P]),
+    "seld_dropout": (_I, [_P, _P, _L, _F, _F, _I, _U64, _U, _U, _P]),
     "seld_m_copy_channels": (_I, [_P, _P, _L, _I, _I, _I, _I, _P]),
     "seld_m_mean_hw": (_I, [_P, _P, _I, _I, _I, _P]),
     "seld_m_scale_hw": (_I, [_P, _P, _P, _I, _I, _I, _P]),
@@ -200,6 +203,8 @@ SIGNATURES = {
     "seld_attn_fwd": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _I, _I, _I, _I, _F, _P]),
     "seld_attn_bwd_scratch": (_L, [_I, _I, _I, _I]),
     "seld_attn_bwd": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _I, _I, _I, _I, _F, _P]),
+    "seld_attn_drop_fwd": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _I, _I, _I, _I, _F, _F, _U64, _U, _U, _P]),
+    "seld_attn_drop_bwd": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _I, _I, _I, _I, _F, _F, _U64, _U, _U, _P]),
     "seld_ln_fwd": (_I, [_P, _P, _P, _P, _F, _P, _P, _P, _L, _I, _P]),
     "seld_ln_scratch": (_L, [_L, _I]),
     "seld_ln_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _P]),

@@ -20,6 +20,19 @@
 // LDS rows are d + 1 floats (odd): the [key = lane][dd] operand reads of a 32-lane half then hit 32 different banks, and the
 // [key = row][dd = lane] reads are consecutive addresses.  2 x 64 x 65 x 4 B = 33 KB per workgroup at d = 64 (4 workgroups per CU).
 // Registers: Q (and dO) fragments d / 2 each, logits 16 (+16), outputs 16 ceil(d / 32) (twice that in the dK / dV kernel).
+//
+// Dropped probabilities (seld_attn_drop_*: tf.keras.layers.MultiHeadAttention(dropout = r), layers.MultiHeadAttention_, layers.py:253-257).
+// The three kernels take the mask as a template parameter (DROP; the seld_attn_* entry points instantiate it off and stay bit-identical):
+//   O[b,n,h,:] = sum_m P[n,m] M[b,h,n,m] V[b,m,h,:],  P the FULL softmax (m, l and lse see the undropped probabilities),
+//   M[b,h,n,m] = 0 where u < rate, else 1 / (1 - rate);  u = (word >> 8) * 2^-24, word = word (m & 3) of
+//   Philox4x32-10(counter = (m >> 2, layer, step, (b H + h) S + n), key = (seed lo, seed hi))            — attn_mask_words / attn_mask_word
+// and in the backward dV_m = sum_n P M dO_n, dPd = M (dO_n . V_m), dS = P (dPd - delta), delta = rowsum(dO * O) = sum_m P M (dO . V_m): the dQ
+// kernel's delta pass is the undropped one.  M is recomputed in all three kernels from that one function and never stored.  In the forward and
+// dQ kernels a lane holds one query and its keys in aligned groups of four (mfma_row: (r & 3) + 8 (r >> 2) + 4 hi), so one Philox call feeds
+// the four registers 4 g .. 4 g + 3.  In the dK / dV kernel the lane holds one key and 16 queries, and the four lanes of a quad hold the four keys
+// of one group and the SAME 16 queries: each lane draws the words of four of them (register 4 g + (lane & 3), g = 0 .. 3) and the quad exchanges
+// the keep bits by DPP — four Philox calls per 32 x 32 block and lane there too, in place of one per element.
+// (b H + h) S + n must fit 32 bits: B H S <= 2^32, checked by the entry points.
 #include "common.h"
 #include <cmath>
 #include "../../include/seld_hip.h"
@@ -64,10 +77,41 @@ __device__ __forceinline__ void store_t(const f32x16 (&acc)[(D + 31) / 32], floa
         }
 }
 
-template <int D>
+// what the DROP instantiations read (the others ignore it): the fp32 rate, 1 / (1 - rate), the Philox key and the stream
+struct AttnDrop { float rate, keep; unsigned seed_lo, seed_hi, layer, step; };
+
+// the four mask words of query element `w` = (b H + h) S + n and keys 4 m4 .. 4 m4 + 3
+__device__ __forceinline__ uint4 attn_mask_words(const AttnDrop& dr, unsigned m4, unsigned w) {
+    return philox4x32_10(make_uint4(m4, dr.layer, dr.step, w), make_uint2(dr.seed_lo, dr.seed_hi));
+}
+// lane C of every quad's value, in all four lanes of the quad
+template <int C>
+__device__ __forceinline__ unsigned quad_bcast(unsigned v) {
+    return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, C * 0x55 /*quad_perm [C,C,C,C]*/, 0xF, 0xF, true);
+}
+// the keep decisions of the four keys 4 m4 .. 4 m4 + 3 for query element w, as bits 0 .. 3
+__device__ __forceinline__ unsigned attn_keep_bits(const AttnDrop& dr, unsigned m4, unsigned w) {
+    const uint4 r = attn_mask_words(dr, m4, w);
+    return (philox_keep(r.x, dr.rate) ? 1u : 0u) | (philox_keep(r.y, dr.rate) ? 2u : 0u) | (philox_keep(r.z, dr.rate) ? 4u : 0u) |
+           (philox_keep(r.w, dr.rate) ? 8u : 0u);
+}
+
+// M of the lane's 16 keys key0 + mfma_row(r, hi) (key0 a multiple of 32) of query element w: four Philox calls
+__device__ __forceinline__ void attn_mask16(const AttnDrop& dr, int key0, int hi, unsigned w, float (&mk)[16]) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        const uint4 r = attn_mask_words(dr, (unsigned)(key0 >> 2) + 2 * g + hi, w);
+        mk[4 * g] = philox_keep(r.x, dr.rate) ? dr.keep : 0.f;
+        mk[4 * g + 1] = philox_keep(r.y, dr.rate) ? dr.keep : 0.f;
+        mk[4 * g + 2] = philox_keep(r.z, dr.rate) ? dr.keep : 0.f;
+        mk[4 * g + 3] = philox_keep(r.w, dr.rate) ? dr.keep : 0.f;
+    }
+}
+
+template <int D, bool DROP>
 __global__ __launch_bounds__(128) void attn_fwd_kernel(const float* __restrict__ Q, const float* __restrict__ K, const float* __restrict__ V, int ldq,
                                                        int ldk, int ldv, float* __restrict__ O, float* __restrict__ lse, int S, int H, float scale,
-                                                       int nqt) {
+                                                       int nqt, AttnDrop dr) {
     constexpr int LD = D + 1, NB = (D + 31) / 32;
     __shared__ float Ks[AT_TILE * LD], Vs[AT_TILE * LD];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 31, hi = lane >> 5;
@@ -105,6 +149,12 @@ __global__ __launch_bounds__(128) void attn_fwd_kernel(const float* __restrict__
             ps += xhalf(ps);
             l = l * alpha + ps;
             m = mx;
+            if constexpr (DROP) {      // after the sums: l and lse are the full softmax's
+                float mk[16];
+                attn_mask16(dr, k0 + kb * 32, hi, (unsigned)bh * (unsigned)S + (unsigned)q, mk);
+#pragma unroll
+                for (int r = 0; r < 16; ++r) s[r] *= mk[r];
+            }
 #pragma unroll
             for (int nb = 0; nb < NB; ++nb) {
                 const int dd = nb * 32 + li;
@@ -122,11 +172,11 @@ __global__ __launch_bounds__(128) void attn_fwd_kernel(const float* __restrict__
 }
 
 // dQ, and delta[b][h][q] = rowsum(dO * O) for the dK / dV kernel that follows.  Same tiling as the forward.
-template <int D>
+template <int D, bool DROP>
 __global__ __launch_bounds__(128) void attn_bwd_dq_kernel(const float* __restrict__ Q, const float* __restrict__ K, const float* __restrict__ V, int ldq,
                                                           int ldk, int ldv, const float* __restrict__ O, const float* __restrict__ dO,
                                                           const float* __restrict__ lse, float* __restrict__ dQ, int lddq, float* __restrict__ delta,
-                                                          int S, int H, float scale, int nqt) {
+                                                          int S, int H, float scale, int nqt, AttnDrop dr) {
     constexpr int LD = D + 1, NB = (D + 31) / 32;
     __shared__ float Ks[AT_TILE * LD], Vs[AT_TILE * LD];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 31, hi = lane >> 5;
@@ -162,6 +212,12 @@ __global__ __launch_bounds__(128) void attn_bwd_dq_kernel(const float* __restric
             for (int st = 0; st < D / 2; ++st) s = MFMA_F32_32x32x2(kr[2 * st], qf[st], s);
 #pragma unroll
             for (int st = 0; st < D / 2; ++st) dp = MFMA_F32_32x32x2(vr[2 * st], dof[st], dp);
+            if constexpr (DROP) {      // dPd = M (dO . V)
+                float mk[16];
+                attn_mask16(dr, k0 + kb * 32, hi, (unsigned)bh * (unsigned)S + (unsigned)q, mk);
+#pragma unroll
+                for (int r = 0; r < 16; ++r) dp[r] *= mk[r];
+            }
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const float p = k0 + kb * 32 + mfma_row(r, hi) < S ? __expf(s[r] - lq) : 0.f;
@@ -181,11 +237,11 @@ __global__ __launch_bounds__(128) void attn_bwd_dq_kernel(const float* __restric
 }
 
 // dK and dV: a workgroup owns 64 keys of one (batch, head) (32 per wave, K and V fragments in registers) and sweeps the query tiles
-template <int D>
+template <int D, bool DROP>
 __global__ __launch_bounds__(128) void attn_bwd_dkv_kernel(const float* __restrict__ Q, const float* __restrict__ K, const float* __restrict__ V, int ldq,
                                                            int ldk, int ldv, const float* __restrict__ dO, const float* __restrict__ lse,
                                                            const float* __restrict__ delta, float* __restrict__ dK, float* __restrict__ dV, int lddk,
-                                                           int lddv, int S, int H, float scale, int nkt) {
+                                                           int lddv, int S, int H, float scale, int nkt, AttnDrop dr) {
     constexpr int LD = D + 1, NB = (D + 31) / 32;
     __shared__ float Qs[AT_TILE * LD], Gs[AT_TILE * LD], ls[AT_TILE], ds_[AT_TILE];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 31, hi = lane >> 5;
@@ -217,12 +273,32 @@ __global__ __launch_bounds__(128) void attn_bwd_dkv_kernel(const float* __restri
             for (int st = 0; st < D / 2; ++st) s = MFMA_F32_32x32x2(qr[2 * st], kf[st], s);
 #pragma unroll
             for (int st = 0; st < D / 2; ++st) dp = MFMA_F32_32x32x2(gr[2 * st], vf[st], dp);
+            if constexpr (DROP) {      // dV takes P M, dS = P (M (dO . V) - delta)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int qq = qb * 32 + mfma_row(r, hi);
-                const float p = kok ? __expf(s[r] - ls[qq]) : 0.f;
-                s[r] = p;
-                dp[r] = p * (dp[r] - ds_[qq]);
+                for (int r = 0; r < 16; ++r) s[r] = kok ? __expf(s[r] - ls[qb * 32 + mfma_row(r, hi)]) : 0.f;
+                // the quad's lanes j = 0 .. 3 hold keys 4 m4 + j and the same 16 queries: lane j draws the words of query register 4 g + j, and
+                // every lane takes bit j of the lane that drew register 4 g + c (all lanes of the wave are here: DPP)
+                const int j = li & 3;
+                const unsigned w0 = (unsigned)bh * (unsigned)S + (unsigned)(q0 + qb * 32);
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const unsigned bits = attn_keep_bits(dr, (unsigned)key >> 2, w0 + (unsigned)(j + 8 * g + 4 * hi));
+                    const float m0 = (quad_bcast<0>(bits) >> j) & 1u ? dr.keep : 0.f, m1 = (quad_bcast<1>(bits) >> j) & 1u ? dr.keep : 0.f;
+                    const float m2 = (quad_bcast<2>(bits) >> j) & 1u ? dr.keep : 0.f, m3 = (quad_bcast<3>(bits) >> j) & 1u ? dr.keep : 0.f;
+                    const float* dl = ds_ + qb * 32 + 8 * g + 4 * hi;
+                    dp[4 * g] = s[4 * g] * (m0 * dp[4 * g] - dl[0]);             s[4 * g] *= m0;
+                    dp[4 * g + 1] = s[4 * g + 1] * (m1 * dp[4 * g + 1] - dl[1]); s[4 * g + 1] *= m1;
+                    dp[4 * g + 2] = s[4 * g + 2] * (m2 * dp[4 * g + 2] - dl[2]); s[4 * g + 2] *= m2;
+                    dp[4 * g + 3] = s[4 * g + 3] * (m3 * dp[4 * g + 3] - dl[3]); s[4 * g + 3] *= m3;
+                }
+            } else {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int qq = qb * 32 + mfma_row(r, hi);
+                    const float p = kok ? __expf(s[r] - ls[qq]) : 0.f;
+                    s[r] = p;
+                    dp[r] = p * (dp[r] - ds_[qq]);
+                }
             }
 #pragma unroll
             for (int nb = 0; nb < NB; ++nb) {
@@ -319,18 +395,70 @@ inline int64_t at_grid(int B, int S, int H) {
     return bh > 0x7fffffff || bh * nt > 0x7fffffff ? -1 : bh * nt;
 }
 
-// launch `kern`<d> for d = 8, 16, ..., 64
-#define AT_DISPATCH(kern, d, grid, st, ...)                                                                          \
+// launch `kern`<d, drop> for d = 8, 16, ..., 64
+#define AT_DISPATCH(kern, drop, d, grid, st, ...)                                                                        \
     switch (d) {                                                                                                     \
-        case 8: hipLaunchKernelGGL((kern<8>), dim3(grid), dim3(128), 0, st, __VA_ARGS__); break;                     \
-        case 16: hipLaunchKernelGGL((kern<16>), dim3(grid), dim3(128), 0, st, __VA_ARGS__); break;                   \
-        case 24: hipLaunchKernelGGL((kern<24>), dim3(grid), dim3(128), 0, st, __VA_ARGS__); break;                   \
-        case 32: hipLaunchKernelGGL((kern<32>), dim3(grid), dim3(128), 0, st, __VA_ARGS__); break;                   \
-        case 40: hipLaunchKernelGGL((kern<40>), dim3(grid), dim3(128), 0, st, __VA_ARGS__); break;                   \
-        case 48: hipLaunchKernelGGL((kern<48>), dim3(grid), dim3(128), 0, st, __VA_ARGS__); break;                   \
-        case 56: hipLaunchKernelGGL((kern<56>), dim3(grid), dim3(128), 0, st, __VA_ARGS__); break;                   \
-        default: hipLaunchKernelGGL((kern<64>), dim3(grid), dim3(128), 0, st, __VA_ARGS__); break;                   \
+        case 8: hipLaunchKernelGGL((kern<8, drop>), dim3(grid), dim3(128), 0, st, __VA_ARGS__); break;                     \
+        case 16: hipLaunchKernelGGL((kern<16, drop>), dim3(grid), dim3(128), 0, st, __VA_ARGS__); break;                   \
+        case 24: hipLaunchKernelGGL((kern<24, drop>), dim3(grid), dim3(128), 0, st, __VA_ARGS__); break;                   \
+        case 32: hipLaunchKernelGGL((kern<32, drop>), dim3(grid), dim3(128), 0, st, __VA_ARGS__); break;                   \
+        case 40: hipLaunchKernelGGL((kern<40, drop>), dim3(grid), dim3(128), 0, st, __VA_ARGS__); break;                   \
+        case 48: hipLaunchKernelGGL((kern<48, drop>), dim3(grid), dim3(128), 0, st, __VA_ARGS__); break;                   \
+        case 56: hipLaunchKernelGGL((kern<56, drop>), dim3(grid), dim3(128), 0, st, __VA_ARGS__); break;                   \
+        default: hipLaunchKernelGGL((kern<64, drop>), dim3(grid), dim3(128), 0, st, __VA_ARGS__); break;                   \
     }
+
+inline bool rate_ok(float rate) { return rate >= 0.f && rate < 1.f; }      // (a NaN fails both)
+// the mask counter's last word (b H + h) S + n is 32 bits wide
+inline bool ctr_ok(int B, int S, int H) { return (int64_t)B * H * S <= ((int64_t)1 << 32); }      // B * H fits an int behind at_grid: no overflow
+inline AttnDrop at_drop(float rate, uint64_t seed, unsigned layer, unsigned step) {
+    return AttnDrop{rate, 1.f / (1.f - rate), (unsigned)seed, (unsigned)(seed >> 32), layer, step};
+}
+
+// seld_attn_fwd (rate 0: the mask-free instantiations, whatever seed / layer / step) and seld_attn_drop_fwd
+int attn_fwd_impl(const float* Q, const float* K, const float* V, int ldq, int ldk, int ldv, float* O, float* lse, int B, int S, int H, int d,
+                  float scale, float rate, uint64_t seed, unsigned layer, unsigned step, void* stream) {
+    if (!d_ok(d)) return SELD_ERR_UNSUPPORTED;
+    if (!Q || !K || !V || !O || B < 1 || S < 1 || H < 1 || !ld_ok(ldq, H, d) || !ld_ok(ldk, H, d) || !ld_ok(ldv, H, d) || !rate_ok(rate))
+        return SELD_ERR_INVALID;
+    const int64_t grid = at_grid(B, S, H);
+    if (grid < 0) return SELD_ERR_UNSUPPORTED;
+    const int nt = (int)(grid / B / H);
+    const AttnDrop dr = at_drop(rate, seed, layer, step);
+    if (rate > 0.f) {
+        if (!ctr_ok(B, S, H)) return SELD_ERR_UNSUPPORTED;
+        AT_DISPATCH(attn_fwd_kernel, true, d, (unsigned)grid, (hipStream_t)stream, Q, K, V, ldq, ldk, ldv, O, lse, S, H, scale, nt, dr);
+    } else {
+        AT_DISPATCH(attn_fwd_kernel, false, d, (unsigned)grid, (hipStream_t)stream, Q, K, V, ldq, ldk, ldv, O, lse, S, H, scale, nt, dr);
+    }
+    return ok();
+}
+
+int attn_bwd_impl(const float* Q, const float* K, const float* V, int ldq, int ldk, int ldv, const float* O, const float* dO, const float* lse,
+                  float* dQ, float* dK, float* dV, int lddq, int lddk, int lddv, float* scratch, int B, int S, int H, int d, float scale,
+                  float rate, uint64_t seed, unsigned layer, unsigned step, void* stream) {
+    if (!d_ok(d)) return SELD_ERR_UNSUPPORTED;
+    if (!Q || !K || !V || !O || !dO || !lse || !dQ || !dK || !dV || !scratch || B < 1 || S < 1 || H < 1 || !ld_ok(ldq, H, d) || !ld_ok(ldk, H, d) ||
+        !ld_ok(ldv, H, d) || !ld_ok(lddq, H, d) || !ld_ok(lddk, H, d) || !ld_ok(lddv, H, d) || !rate_ok(rate))
+        return SELD_ERR_INVALID;
+    const int64_t grid = at_grid(B, S, H);
+    if (grid < 0) return SELD_ERR_UNSUPPORTED;
+    const int nt = (int)(grid / B / H);
+    const AttnDrop dr = at_drop(rate, seed, layer, step);
+    if (rate > 0.f) {
+        if (!ctr_ok(B, S, H)) return SELD_ERR_UNSUPPORTED;
+        AT_DISPATCH(attn_bwd_dq_kernel, true, d, (unsigned)grid, (hipStream_t)stream, Q, K, V, ldq, ldk, ldv, O, dO, lse, dQ, lddq, scratch, S, H, scale,
+                    nt, dr);
+        AT_DISPATCH(attn_bwd_dkv_kernel, true, d, (unsigned)grid, (hipStream_t)stream, Q, K, V, ldq, ldk, ldv, dO, lse, scratch, dK, dV, lddk, lddv, S, H,
+                    scale, nt, dr);
+    } else {
+        AT_DISPATCH(attn_bwd_dq_kernel, false, d, (unsigned)grid, (hipStream_t)stream, Q, K, V, ldq, ldk, ldv, O, dO, lse, dQ, lddq, scratch, S, H, scale,
+                    nt, dr);
+        AT_DISPATCH(attn_bwd_dkv_kernel, false, d, (unsigned)grid, (hipStream_t)stream, Q, K, V, ldq, ldk, ldv, dO, lse, scratch, dK, dV, lddk, lddv, S, H,
+                    scale, nt, dr);
+    }
+    return ok();
+}
 
 }  // namespace
 
@@ -338,14 +466,7 @@ extern "C" {
 
 int seld_attn_fwd(const float* Q, const float* K, const float* V, int ldq, int ldk, int ldv, float* O, float* lse, int B, int S, int H, int d,
                   float scale, void* stream) {
-    if (!d_ok(d)) return SELD_ERR_UNSUPPORTED;
-    if (!Q || !K || !V || !O || B < 1 || S < 1 || H < 1 || !ld_ok(ldq, H, d) || !ld_ok(ldk, H, d) || !ld_ok(ldv, H, d))
-        return SELD_ERR_INVALID;
-    const int64_t grid = at_grid(B, S, H);
-    if (grid < 0) return SELD_ERR_UNSUPPORTED;
-    const int nt = (int)(grid / B / H);
-    AT_DISPATCH(attn_fwd_kernel, d, (unsigned)grid, (hipStream_t)stream, Q, K, V, ldq, ldk, ldv, O, lse, S, H, scale, nt);
-    return ok();
+    return attn_fwd_impl(Q, K, V, ldq, ldk, ldv, O, lse, B, S, H, d, scale, 0.f, 0, 0, 0, stream);
 }
 
 /* floats of caller scratch seld_attn_bwd takes: delta[b][h][q] = rowsum(dO * O) */
@@ -357,17 +478,20 @@ int64_t seld_attn_bwd_scratch(int B, int S, int H, int d) {
 int seld_attn_bwd(const float* Q, const float* K, const float* V, int ldq, int ldk, int ldv, const float* O, const float* dO, const float* lse,
                   float* dQ, float* dK, float* dV, int lddq, int lddk, int lddv, float* scratch, int B, int S, int H, int d, float scale,
                   void* stream) {
-    if (!d_ok(d)) return SELD_ERR_UNSUPPORTED;
-    if (!Q || !K || !V || !O || !dO || !lse || !dQ || !dK || !dV || !scratch || B < 1 || S < 1 || H < 1 || !ld_ok(ldq, H, d) || !ld_ok(ldk, H, d) ||
-        !ld_ok(ldv, H, d) || !ld_ok(lddq, H, d) || !ld_ok(lddk, H, d) || !ld_ok(lddv, H, d))
-        return SELD_ERR_INVALID;
-    const int64_t grid = at_grid(B, S, H);
-    if (grid < 0) return SELD_ERR_UNSUPPORTED;
-    const int nt = (int)(grid / B / H);
-    AT_DISPATCH(attn_bwd_dq_kernel, d, (unsigned)grid, (hipStream_t)stream, Q, K, V, ldq, ldk, ldv, O, dO, lse, dQ, lddq, scratch, S, H, scale, nt);
-    AT_DISPATCH(attn_bwd_dkv_kernel, d, (unsigned)grid, (hipStream_t)stream, Q, K, V, ldq, ldk, ldv, dO, lse, scratch, dK, dV, lddk, lddv, S, H, scale,
-                nt);
-    return ok();
+    return attn_bwd_impl(Q, K, V, ldq, ldk, ldv, O, dO, lse, dQ, dK, dV, lddq, lddk, lddv, scratch, B, S, H, d, scale, 0.f, 0, 0, 0, stream);
+}
+
+/* the same with the probabilities dropped (header comment): rate 0 launches exactly what seld_attn_fwd / _bwd launch */
+int seld_attn_drop_fwd(const float* Q, const float* K, const float* V, int ldq, int ldk, int ldv, float* O, float* lse, int B, int S, int H, int d,
+                       float scale, float rate, uint64_t seed, unsigned layer, unsigned step, void* stream) {
+    return attn_fwd_impl(Q, K, V, ldq, ldk, ldv, O, lse, B, S, H, d, scale, rate, seed, layer, step, stream);
+}
+
+int seld_attn_drop_bwd(const float* Q, const float* K, const float* V, int ldq, int ldk, int ldv, const float* O, const float* dO, const float* lse,
+                       float* dQ, float* dK, float* dV, int lddq, int lddk, int lddv, float* scratch, int B, int S, int H, int d, float scale,
+                       float rate, uint64_t seed, unsigned layer, unsigned step, void* stream) {
+    return attn_bwd_impl(Q, K, V, ldq, ldk, ldv, O, dO, lse, dQ, dK, dV, lddq, lddk, lddv, scratch, B, S, H, d, scale, rate, seed, layer, step,
+                         stream);
 }
 
 int seld_ln_fwd(const float* x, const float* r, const float* gamma, const float* beta, float eps, float* y, float* xhat, float* rstd, int64_t rows,

@@ -40,6 +40,22 @@ __device__ __forceinline__ float4 quad_transpose4(float x0, float x1, float x2, 
 }
 
 
+// ---- Philox4x32-10 (Salmon et al., SC11; Random123): the counter-based generator behind every dropout mask of the library — a pure function
+// of (counter, key), so a backward pass recomputes a mask instead of storing it.  Users: loss_adam.hip::dropout_kernel, module_ops.hip
+// (seld_dropout: the same draws at any n) and attention.hip (the probability masks of seld_attn_drop_*).
+__device__ __forceinline__ uint4 philox4x32_10(uint4 ctr, uint2 key) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const unsigned hi0 = __umulhi(0xD2511F53u, ctr.x), lo0 = 0xD2511F53u * ctr.x;
+        const unsigned hi1 = __umulhi(0xCD9E8D57u, ctr.z), lo1 = 0xCD9E8D57u * ctr.z;
+        ctr = make_uint4(hi1 ^ ctr.y ^ key.x, lo1, hi0 ^ ctr.w ^ key.y, lo0);
+        key.x += 0x9E3779B9u; key.y += 0xBB67AE85u;
+    }
+    return ctr;
+}
+// Keras' Dropout decision from one Philox word: u = (word >> 8) * 2^-24 (exact in fp32); kept where u >= rate
+__device__ __forceinline__ bool philox_keep(unsigned word, float rate) { return (float)(word >> 8) * (1.f / 16777216.f) >= rate; }
+
 // Workgroup barrier that orders LDS traffic only.  __syncthreads() also drains vmcnt (it is a
 // workgroup-scope fence for global memory), which would serialise the prefetched global loads and the
 // epilogue stores of the pipelined conv kernels behind every barrier.

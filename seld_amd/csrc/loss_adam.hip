@@ -352,16 +352,7 @@ int launch_time_fold(hipStream_t st, const float* dxe, float* dx, int B, int S, 
 // TensorFlow's generator, which no other program reproduces; here the uniforms are Philox4x32-10 words of the counter
 // (element / 4, layer, step, 0) under the key (seed lo, seed hi), u = (word >> 8) * 2^-24 — a pure function of (seed, step, layer, element)
 // that the oracle restates (oracle/seldnet_oracle.py::philox_uniform), so the backward pass recomputes the mask instead of storing it.
-__device__ __forceinline__ uint4 philox4x32_10(uint4 ctr, uint2 key) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned hi0 = __umulhi(0xD2511F53u, ctr.x), lo0 = 0xD2511F53u * ctr.x;
-        const unsigned hi1 = __umulhi(0xCD9E8D57u, ctr.z), lo1 = 0xCD9E8D57u * ctr.z;
-        ctr = make_uint4(hi1 ^ ctr.y ^ key.x, lo1, hi0 ^ ctr.w ^ key.y, lo0);
-        key.x += 0x9E3779B9u; key.y += 0xBB67AE85u;
-    }
-    return ctr;
-}
+// philox4x32_10: common.h (shared with the attention kernels' probability masks and seld_dropout).
 // out = in * mask / (1 - rate)  (forward: in = the layer's activations; backward: in = out = the gradient, in place)
 __global__ __launch_bounds__(256) void dropout_kernel(const float4* __restrict__ in, float4* __restrict__ out, int64_t n4, float rate, float scale,
                                                       unsigned seed_lo, unsigned seed_hi, unsigned layer, unsigned step) {

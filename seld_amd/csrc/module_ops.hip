@@ -266,6 +266,25 @@ __global__ __launch_bounds__(256) void axpy_kernel(float* __restrict__ dst, cons
     if (e < n) dst[e] += alpha * src[e];
 }
 
+// Keras Dropout on the draws of loss_adam.hip::dropout_kernel at ANY n: thread i draws the Philox4x32-10 words of counter (i, layer, step, i >> 32)
+// for elements 4 i .. 4 i + 3 (oracle/seldnet_oracle.py::philox_uniform) and handles the tail element by element.  out = (accumulate ? out : 0)
+// + in * sc where kept, sc = alpha / (1 - rate) held in double: one rounding per output.  in == out is fine: an element is read, then written,
+// by its own thread only.
+__global__ __launch_bounds__(256) void m_dropout_kernel(const float* in, float* out, int64_t n, float rate, double sc, int accumulate,
+                                                        unsigned seed_lo, unsigned seed_hi, unsigned layer, unsigned step) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (4 * i >= n) return;
+    const uint4 r = philox4x32_10(make_uint4((unsigned)i, layer, step, (unsigned)(i >> 32)), make_uint2(seed_lo, seed_hi));
+    const unsigned w[4] = {r.x, r.y, r.z, r.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int64_t e = 4 * i + j;
+        if (e >= n) break;
+        const double v = philox_keep(w[j], rate) ? (double)in[e] * sc : 0.0;
+        out[e] = (float)(accumulate ? (double)out[e] + v : v);
+    }
+}
+
 // mode 0: dst[r][off + c] = src[r][c];  mode 1 (backward of the concatenation): src[r][c] += dst[r][off + c]
 __global__ __launch_bounds__(256) void copy_channels_kernel(float* __restrict__ src, float* __restrict__ dst, int64_t rows, int Cs, int Cd, int off,
                                                             int mode) {
@@ -462,6 +481,13 @@ int seld_m_act_bwd(const float* x, const float* dy, float* dx, int64_t n, int ki
 int seld_m_axpy(float* dst, const float* src, int64_t n, float alpha, void* stream) {
     if (!dst || !src || n < 1) return SELD_ERR_INVALID;
     hipLaunchKernelGGL(axpy_kernel, dim3(nblk(n)), dim3(256), 0, (hipStream_t)stream, dst, src, n, alpha);
+    return ok();
+}
+int seld_dropout(const float* in, float* out, int64_t n, float rate, float alpha, int accumulate, uint64_t seed, unsigned layer, unsigned step,
+                   void* stream) {
+    if (!in || !out || n < 1 || !(rate >= 0.f && rate < 1.f)) return SELD_ERR_INVALID;
+    hipLaunchKernelGGL(m_dropout_kernel, dim3(nblk((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, in, out, n, rate,
+                       (double)alpha / (1.0 - (double)rate), accumulate, (unsigned)seed, (unsigned)(seed >> 32), layer, step);
     return ok();
 }
 int seld_m_copy_channels(float* src, float* dst, int64_t rows, int Cs, int Cd, int off, int mode, void* stream) {

@@ -29,6 +29,8 @@ The shared pieces, each in one place:
   _ConvTail            depthwise Conv1D -> BatchNormalization -> swish -> pointwise Conv1D: the conformer's and the attention block's
   _Attention           the attention layers' buffers; _HeadMajorAttention: the reference's own two layers' packing and projections
   _Recurrent           the recurrent blocks' variables, input projections and weight gradients (RNNBlock, BidirectionalGRUBlock)
+  _Drop                one block's Dropout layers (transformer, conformer and absolute-position attention blocks; training only): the draw
+                       streams and the calls of seld_dropout; the attention probabilities are dropped inside seld_attn_drop_fwd / _bwd
   Stage, SECOND_KINDS  every SECOND kind is a Stage of blocks of one class; the table names the class, its config check and its prefix, and
                        the eight factories and ComposedSeldNet build from it (_second_factory, _build_second)
 
@@ -63,10 +65,28 @@ def _check_activation(cfg: dict, default: str, key: str = "activation") -> None:
         raise ValueError(f"{key} {cfg.get(key)!r}: the module operators know {sorted(k for k in ACT if k)}")
 
 
+DROPOUT_DEFAULT = 0.1      # the reference's default of the three attention kinds (modules.py:386, 416, 529)
+DROP_STREAM0 = 4096        # the composed path's first draw stream: clear of the fused path's 16 hd + j, 64 + i and 96 + 4 i + d
+
+
 def _check_no_dropout(cfg: dict, who: str) -> None:
     if "dropout_rate" not in cfg or float(cfg["dropout_rate"]) != 0.0:
-        raise ValueError(f"{who}: there is no dropout kernel on this path and the reference's default dropout_rate is 0.1: "
-                         "dropout_rate must be present and 0")
+        raise ValueError(f"{who}: the reference's Dropout draws from TensorFlow's generator, which this path cannot reproduce, and the reference's "
+                         "default dropout_rate is 0.1: dropout_rate must be present and 0 — or the caller accepts the library's own counter-based "
+                         "draws: dropout=True (models.seldnet does)")
+
+
+def _dropout_rate(cfg: dict, who: str, dropout: bool = True) -> float:
+    """dropout_rate as the fp32 the kernels compare with (absent: the reference's 0.1); 0 <= rate < 1.  Without `dropout` (the caller has not
+    accepted the library's draws in place of TensorFlow's) the key must be present and 0, as before there were dropout kernels."""
+    if not dropout:
+        _check_no_dropout(cfg, who)
+        return 0.0
+    r = cfg.get("dropout_rate", DROPOUT_DEFAULT)
+    r = float(np.float32(DROPOUT_DEFAULT if r is None else r))
+    if not 0.0 <= r < 1.0:
+        raise ValueError(f"{who}: dropout_rate {cfg.get('dropout_rate')!r}: 0 <= dropout_rate < 1")
+    return r
 
 
 def _check_key_dim(key_dim) -> None:
@@ -135,6 +155,17 @@ class _Rt:
         self.params = self.grads = self.state = None
         self._slab = None
         self._bn_scratch = None
+        # Dropout draws, with the semantics of the fused path's context (csrc/ctx.h): every training forward of a model takes
+        # dropout_cur = dropout_step++ and its backward recomputes the masks of dropout_cur
+        self.dropout_seed = 0x5e1d5e1d5e1d5e1d
+        self.dropout_step = 0
+        self.dropout_cur = 0
+        self.dropout = False      # the blocks built on this runtime may draw (the owner accepted the library's draws: _dropout_rate)
+
+    def next_draws(self):
+        """a model's training forward begins: new masks (Keras), backward or not"""
+        self.dropout_cur = int(self.dropout_step) & 0xffffffff
+        self.dropout_step = (self.dropout_cur + 1) & 0xffffffff
 
     # ---- variables
     def var(self, name, shape, trainable=True):
@@ -205,6 +236,47 @@ class _Rt:
 
     def axpy(self, dst, src, alpha=1.0):
         self.ck(self.lib.seld_m_axpy(self.p(dst), self.p(src), dst.numel(), alpha, self.st()))
+
+
+class _Drop:
+    """One block's Dropout layers (reference modules.py:392-402, 440-502, 566-628): the rate, whether the current forward draws (`on`:
+    training and rate > 0 — otherwise every caller launches exactly what it launches without dropout) and the block's draw streams
+
+        layer = DROP_STREAM0 (4096) + 32 * (index of the block in its Stage) + site,      site = the Dropout's rank in reference order:
+
+        site  transformer_encoder_block     conformer_encoder_block          attention_block
+        0     attention probabilities       first FFN, behind the activation first FF, behind the activation
+        1     behind the attention          first FFN, behind its output     first FF, behind its output
+        2     FFN, behind the activation    attention probabilities          attention probabilities
+        3     FFN, behind its output        behind the attention             behind the attention
+        4                                   behind the convolution module    behind the depthwise tail
+        5                                   second FFN, behind the activation second FF, behind the activation
+        6                                   second FFN, behind its output    second FF, behind its output
+
+    (a site keeps its number where a configuration leaves its module out).  Element e of a [rows, C] tensor draws word e & 3 of counter
+    (e >> 2, layer, step, e >> 34): seld_dropout; the attention probabilities draw inside the kernels: seld_attn_drop_fwd / _bwd.  Nothing is
+    stored: the backward calls the same operators with the runtime's dropout_cur.  The rate is above 0 only where the owner of the runtime accepted
+    these draws in place of TensorFlow's (_Rt.dropout: a ComposedSeldNet, or a factory called with dropout=True)."""
+
+    def __init__(self, rt: "_Rt", rate: float):
+        self.rt, self.rate, self.base, self.on = rt, float(rate), DROP_STREAM0, False
+
+    def begin(self, training) -> None:
+        self.on = bool(training) and self.rate > 0.0
+
+    def apply(self, site: int, src, dst, alpha: float = 1.0, accumulate: int = 0):
+        """dst (+)= alpha * Dropout(src) with the mask of `site` (forward: activations; backward: gradients); src is dst: in place"""
+        rt = self.rt
+        rt.ck(rt.lib.seld_dropout(rt.p(src), rt.p(dst), src.numel(), self.rate, alpha, int(accumulate), rt.dropout_seed, self.base + site,
+                                    rt.dropout_cur, rt.st()))
+        return dst
+
+    def add(self, site: int, dst, src, alpha: float = 1.0) -> None:
+        """dst += alpha * Dropout(src): one pass; without dropout the axpy it replaces"""
+        if self.on:
+            self.apply(site, src, dst, alpha, 1)
+        else:
+            self.rt.axpy(dst, src, alpha)
 
 
 
@@ -348,8 +420,9 @@ class _Attention:
     """What the three attention layers allocate alike on [B, S, D] with H heads of dk: q k v o do, the gradients dq dk_ dv, the softmax's lse,
     the backward kernel's scratch (`scratch_fn(B, S, H, dk)` floats; negative: the kernels refuse this key_dim), the output and the scale."""
 
-    def __init__(self, rt: _Rt, name: str, B: int, S: int, D: int, n_head: int, key_dim: int, scratch_fn):
+    def __init__(self, rt: _Rt, name: str, B: int, S: int, D: int, n_head: int, key_dim: int, scratch_fn, drop: _Drop = None, site: int = 0):
         self.rt, self.name, self.S, self.D, self.H, self.dk = rt, name, int(S), int(D), int(n_head), int(key_dim)
+        self.drop, self.site = drop, site      # the probabilities' Dropout (None: none)
         need = int(scratch_fn(B, self.S, self.H, self.dk))
         if need < 0:
             raise ValueError(f"key_dim {key_dim!r}: the attention kernels take a multiple of 8 from 8 to 64")
@@ -361,14 +434,34 @@ class _Attention:
         self.out = rt.empty(R, self.D)
         self.scale = 1.0 / math.sqrt(float(self.dk))
 
+    def _core_fwd(self, B, training):
+        """o = softmax(scale q k^T) v per head (seld_attn_fwd), the probabilities dropped where the block's Dropout draws (seld_attn_drop_fwd)"""
+        rt, HD = self.rt, self.H * self.dk
+        args = (rt.p(self.q), rt.p(self.k), rt.p(self.v), HD, HD, HD, rt.p(self.o), rt.p(self.lse) if training else None, B, self.S, self.H, self.dk,
+                self.scale)
+        if self.drop is not None and self.drop.on:
+            rt.ck(rt.lib.seld_attn_drop_fwd(*args, self.drop.rate, rt.dropout_seed, self.drop.base + self.site, rt.dropout_cur, rt.st()))
+        else:
+            rt.ck(rt.lib.seld_attn_fwd(*args, rt.st()))
+
+    def _core_bwd(self, B):
+        """dq, dk_, dv from do (seld_attn_bwd / seld_attn_drop_bwd with the forward's masks)"""
+        rt, HD = self.rt, self.H * self.dk
+        args = (rt.p(self.q), rt.p(self.k), rt.p(self.v), HD, HD, HD, rt.p(self.o), rt.p(self.do), rt.p(self.lse), rt.p(self.dq), rt.p(self.dk_),
+                rt.p(self.dv), HD, HD, HD, rt.p(self.scratch), B, self.S, self.H, self.dk, self.scale)
+        if self.drop is not None and self.drop.on:
+            rt.ck(rt.lib.seld_attn_drop_bwd(*args, self.drop.rate, rt.dropout_seed, self.drop.base + self.site, rt.dropout_cur, rt.st()))
+        else:
+            rt.ck(rt.lib.seld_attn_bwd(*args, rt.st()))
+
 
 class MultiHeadAttention(_Attention):
-    """tf.keras.layers.MultiHeadAttention(n_head, key_dim)(x, x) on [B, S, D] (value_dim = key_dim, biases, no dropout): three projections
-    (one seld_m_gemm each: Keras' kernels [D, H, dk] are [D, H dk] row-major), the query scaled by 1 / sqrt(key_dim), seld_attn_fwd, and
-    the output projection [H dk, D]."""
+    """tf.keras.layers.MultiHeadAttention(n_head, key_dim, dropout)(x, x) on [B, S, D] (value_dim = key_dim, biases): three projections
+    (one seld_m_gemm each: Keras' kernels [D, H, dk] are [D, H dk] row-major), the query scaled by 1 / sqrt(key_dim), seld_attn_fwd (in
+    training with `drop`: seld_attn_drop_fwd), and the output projection [H dk, D]."""
 
-    def __init__(self, rt: _Rt, name: str, B: int, S: int, D: int, n_head: int, key_dim: int):
-        super().__init__(rt, name, B, S, D, n_head, key_dim, rt.lib.seld_attn_bwd_scratch)
+    def __init__(self, rt: _Rt, name: str, B: int, S: int, D: int, n_head: int, key_dim: int, drop: _Drop = None, site: int = 0):
+        super().__init__(rt, name, B, S, D, n_head, key_dim, rt.lib.seld_attn_bwd_scratch, drop, site)
         H, dk = self.H, self.dk
         for part in ("query", "key", "value"):
             rt.var(f"{name}.{part}.kernel", (self.D, H, dk))
@@ -382,8 +475,7 @@ class MultiHeadAttention(_Attention):
         self.x = x
         for part, buf in (("query", self.q), ("key", self.k), ("value", self.v)):
             rt.gemm(x, rt.w(f"{n}.{part}.kernel"), rt.w(f"{n}.{part}.bias"), buf, R, HD, self.D)
-        rt.ck(rt.lib.seld_attn_fwd(rt.p(self.q), rt.p(self.k), rt.p(self.v), HD, HD, HD, rt.p(self.o), rt.p(self.lse) if training else None, B, self.S,
-                                   self.H, self.dk, self.scale, rt.st()))
+        self._core_fwd(B, training)
         rt.gemm(self.o, rt.w(f"{n}.attention_output.kernel"), rt.w(f"{n}.attention_output.bias"), self.out, R, self.D, HD)
         return self.out[:R]
 
@@ -393,8 +485,7 @@ class MultiHeadAttention(_Attention):
         R, HD = B * self.S, self.H * self.dk
         rt.gemm_tn(self.o, dout, rt.g(f"{n}.attention_output.kernel"), rt.g(f"{n}.attention_output.bias"), R, HD, self.D)
         rt.gemm(dout, rt.w(f"{n}.attention_output.kernel"), None, self.do, R, HD, self.D, transb=1)
-        rt.ck(rt.lib.seld_attn_bwd(rt.p(self.q), rt.p(self.k), rt.p(self.v), HD, HD, HD, rt.p(self.o), rt.p(self.do), rt.p(self.lse), rt.p(self.dq),
-                                   rt.p(self.dk_), rt.p(self.dv), HD, HD, HD, rt.p(self.scratch), B, self.S, self.H, self.dk, self.scale, rt.st()))
+        self._core_bwd(B)
         for i, (part, g) in enumerate((("query", self.dq), ("key", self.dk_), ("value", self.dv))):
             rt.gemm_tn(self.x, g, rt.g(f"{n}.{part}.kernel"), rt.g(f"{n}.{part}.bias"), R, self.D, HD)
             rt.gemm(g, rt.w(f"{n}.{part}.kernel"), None, dx, R, self.D, HD, transb=1, accumulate=int(i > 0))
@@ -429,33 +520,44 @@ class Conv1D(Linear):
 class _FeedForward:
     """second(act(first(x))) on [rows, D], first / second two Linear layers (Dense or Conv1D) that the owner built: the hidden buffer h, and
     a backward that takes the output's gradient (times `factor`, the owner's residual scale, where one is given) to the input's.  `scratch`:
-    the backward buffers (dh, dpre[, df]) of an owner that shares them among its cores; None: this core's own."""
+    the backward buffers (dh, dpre[, df]) of an owner that shares them among its cores; None: this core's own.  `drop` / `sites`: the owner's
+    Dropout and the sites of the two Dropout layers of the reference's FFNs — behind the activation (applied here, in place on h) and behind
+    the second layer (the OWNER applies it, with its residual sum: drop.add; the backward here masks the incoming gradient)."""
 
-    def __init__(self, rt: _Rt, first: Linear, second: Linear, rows: int, act: int, factor=None, scratch=None):
+    def __init__(self, rt: _Rt, first: Linear, second: Linear, rows: int, act: int, factor=None, scratch=None, drop: _Drop = None, sites=(0, 1)):
         self.rt, self.first, self.second, self.act, self.factor = rt, first, second, act, factor
+        self.drop, self.sites = drop, sites
         self.h = rt.empty(rows, first.N)
         self.dh, self.dpre, self.df = scratch or (rt.empty(rows, first.N), rt.empty(rows, first.N), None)
-        if factor is not None and self.df is None:
+        if (factor is not None or (drop is not None and drop.rate > 0)) and self.df is None:
             self.df = rt.empty(rows, second.N)
 
     def hidden(self, x, rows):
-        """act(first(x)): for an owner that has something to launch between the two layers; forward() otherwise"""
+        """Dropout(act(first(x))): for an owner that has something to launch between the two layers; forward() otherwise"""
         self.pre = self.first.forward(x, rows)
-        self.rt.act(self.pre, self.h[:rows], self.act)
-        return self.h[:rows]
+        h = self.h[:rows]
+        self.rt.act(self.pre, h, self.act)
+        if self.drop is not None and self.drop.on:
+            self.drop.apply(self.sites[0], h, h)
+        return h
 
     def forward(self, x, rows):
         return self.second.forward(self.hidden(x, rows), rows)
 
     def backward(self, dy, dx, rows):
-        """dy [rows, D]: the gradient of the (scaled) output -> dx = the input's gradient (overwritten)"""
+        """dy [rows, D]: the gradient of the (scaled) output, behind its Dropout -> dx = the input's gradient (overwritten)"""
         rt = self.rt
-        if self.factor is not None:
+        on = self.drop is not None and self.drop.on
+        if on:
+            dy = self.drop.apply(self.sites[1], dy, self.df[:rows], 1.0 if self.factor is None else self.factor)
+        elif self.factor is not None:
             df = self.df[:rows]
             df.zero_()
             rt.axpy(df, dy, self.factor)
             dy = df
         self.second.backward(dy, self.dh[:rows], rows)
+        if on:
+            self.drop.apply(self.sites[0], self.dh[:rows], self.dh[:rows])
         rt.act_bwd(self.pre, self.dh[:rows], self.dpre[:rows], self.act)
         self.first.backward(self.dpre[:rows], dx, rows)
 
@@ -467,13 +569,18 @@ class Stage:
 
     def __init__(self, rt: _Rt, block, cfg: dict, S: int, D: int, prefix: str, B: int, depth: int):
         self.blocks = []
-        self.S, self.D = int(S), int(D)
+        self.rt, self.S, self.D = rt, int(S), int(D)
+        self.model = False      # True: this stage IS the model (a factory built it on a runtime of its own), so its training forwards count the draws
         for i in range(int(depth)):
             self.blocks.append(block(rt, cfg, S, D, f"{prefix}{i}", B))
             D = self.blocks[-1].out_dim
+            if getattr(self.blocks[-1], "drop", None) is not None:
+                self.blocks[-1].drop.base = DROP_STREAM0 + 32 * i
         self.out_dim, self.out_shape = int(D), (self.S, int(D))
 
     def forward(self, x, B, training):
+        if self.model and training:
+            self.rt.next_draws()
         for blk in self.blocks:
             x = blk.forward(x, B, training)
         return x
@@ -487,13 +594,13 @@ class Stage:
 TRANSFORMER_KEYS = ("n_head", "key_dim", "ff_multiplier", "kernel_size")
 
 
-def check_transformer_config(cfg: dict, stage: bool = False) -> None:
+def check_transformer_config(cfg: dict, stage: bool = False, dropout: bool = False) -> None:
     """the mandatory keys of reference modules.py:380-383 (and `depth`, modules.py:120); what has no kernel here is refused, not ignored"""
     for key in TRANSFORMER_KEYS + (("depth",) if stage else ()):
         if key not in cfg:
             raise ValueError(f"transformer_encoder_{'stage' if stage else 'block'}: missing {key!r}")
     _check_activation(cfg, "relu")
-    _check_no_dropout(cfg, "transformer_encoder_block")
+    _dropout_rate(cfg, "transformer_encoder_block", dropout)
     if int(cfg["n_head"]) < 1 or int(cfg["kernel_size"]) < 1 or float(cfg["ff_multiplier"]) <= 0 or (stage and int(cfg["depth"]) < 1):
         raise ValueError("transformer_encoder_block: n_head, kernel_size, depth >= 1 and ff_multiplier > 0")
     _check_key_dim(cfg["key_dim"])
@@ -501,30 +608,41 @@ def check_transformer_config(cfg: dict, stage: bool = False) -> None:
 
 class TransformerEncoderBlock:
     """reference modules.transformer_encoder_block (modules.py:379-407) on [B, S, D]:
-    x = LN(x + MHA(x, x)); ffn = Conv1D(D, k)(Conv1D(int(ff_multiplier D), k, activation)(x)); x = LN(x + ffn)."""
+    x = LN(x + Dropout(MHA(x, x))); ffn = Dropout(Conv1D(D, k)(Dropout(Conv1D(int(ff_multiplier D), k, activation)(x)))); x = LN(x + ffn);
+    the MultiHeadAttention drops its probabilities at the same rate.  The Dropouts draw in training only (_Drop: sites 0 - 3)."""
 
     def __init__(self, rt: _Rt, cfg: dict, S: int, D: int, prefix: str, B: int):
-        check_transformer_config(cfg)
+        check_transformer_config(cfg, dropout=rt.dropout)
         self.rt, self.S, self.D, self.B = rt, int(S), int(D), B
         self.F = int(cfg["ff_multiplier"] * self.D)
         if self.F < 1:
             raise ValueError("transformer_encoder_block: int(ff_multiplier * d_model) < 1")
         k = int(cfg["kernel_size"])
         R = B * self.S
-        self.mha = MultiHeadAttention(rt, f"{prefix}.mha", B, self.S, self.D, int(cfg["n_head"]), int(cfg["key_dim"]))
+        self.drop = _Drop(rt, _dropout_rate(cfg, "transformer_encoder_block", rt.dropout))
+        self.mha = MultiHeadAttention(rt, f"{prefix}.mha", B, self.S, self.D, int(cfg["n_head"]), int(cfg["key_dim"]), self.drop, 0)
         self.ln0 = LayerNorm(rt, f"{prefix}.ln0", R, self.D)
         self.ffn = _FeedForward(rt, Conv1D(rt, f"{prefix}.ffn0", B, self.S, self.D, self.F, k), Conv1D(rt, f"{prefix}.ffn1", B, self.S, self.F, self.D, k),
-                                R, ACT[cfg.get("activation", "relu")])
+                                R, ACT[cfg.get("activation", "relu")], drop=self.drop, sites=(2, 3))
         self.ln1 = LayerNorm(rt, f"{prefix}.ln1", R, self.D)
         self.dx1, self.dx = rt.empty(R, self.D), rt.empty(R, self.D)
+        self.dd = rt.empty(R, self.D) if self.drop.rate > 0 else None      # a gradient behind a Dropout
         self.out_dim, self.out_shape = self.D, (self.S, self.D)
 
     def forward(self, x, B, training):
         """x [B*S, D] (or any contiguous view of it) -> [B*S, D]"""
         R = B * self.S
         x = x.reshape(R, self.D)
-        x1 = self.ln0.forward(self.mha.forward(x, B, training), x, R, training)
-        return self.ln1.forward(self.ffn.forward(x1, R), x1, R, training)
+        drop = self.drop
+        drop.begin(training)
+        attn = self.mha.forward(x, B, training)
+        if drop.on:
+            drop.apply(1, attn, attn)
+        x1 = self.ln0.forward(attn, x, R, training)
+        ffn = self.ffn.forward(x1, R)
+        if drop.on:
+            drop.apply(3, ffn, ffn)
+        return self.ln1.forward(ffn, x1, R, training)
 
     def backward(self, dy, B):
         """dy [B*S, D]: the output's gradient -> the input's gradient [B*S, D] (a buffer of this block)"""
@@ -536,7 +654,7 @@ class TransformerEncoderBlock:
         rt.axpy(dx1, dz1)
         dz0 = self.ln0.backward(dx1, R)                             # gradient of x + attn
         dx = self.dx[:R]
-        self.mha.backward(dz0, dx, B)
+        self.mha.backward(self.drop.apply(1, dz0, self.dd[:R]) if self.drop.on else dz0, dx, B)
         rt.axpy(dx, dz0)
         return dx
 
@@ -549,8 +667,9 @@ class _HeadMajorAttention(_Attention):
     the bias) is the core kernel's `scale`."""
     PARTS = ("query", "key", "value")
 
-    def __init__(self, rt: _Rt, name: str, B: int, S: int, D: int, n_head: int, key_dim: int, use_bias: bool, scratch_fn, n_packed: int = 3):
-        super().__init__(rt, name, B, S, D, n_head, key_dim, scratch_fn)
+    def __init__(self, rt: _Rt, name: str, B: int, S: int, D: int, n_head: int, key_dim: int, use_bias: bool, scratch_fn, n_packed: int = 3,
+                 drop: _Drop = None, site: int = 0):
+        super().__init__(rt, name, B, S, D, n_head, key_dim, scratch_fn, drop, site)
         self.use_bias = bool(use_bias)
         H, dk = self.H, self.dk
         for part in self.PARTS:
@@ -603,27 +722,24 @@ class _HeadMajorAttention(_Attention):
 
 
 class MultiHeadAttentionRef(_HeadMajorAttention):
-    """The reference's layers.MultiHeadAttention_(n_head, key_dim, use_bias)([x, x, x]) (layers.py:102-287) on [B, S, D]: seld_attn_fwd / _bwd
-    between the shared projections."""
+    """The reference's layers.MultiHeadAttention_(n_head, key_dim, use_bias, dropout)([x, x, x]) (layers.py:102-287) on [B, S, D]: seld_attn_fwd /
+    _bwd (in training with `drop`, the probabilities' Dropout of layers.py:253-257: seld_attn_drop_fwd / _bwd) between the shared projections."""
 
-    def __init__(self, rt: _Rt, name: str, B: int, S: int, D: int, n_head: int, key_dim: int, use_bias: bool = True):
-        super().__init__(rt, name, B, S, D, n_head, key_dim, use_bias, rt.lib.seld_attn_bwd_scratch)
+    def __init__(self, rt: _Rt, name: str, B: int, S: int, D: int, n_head: int, key_dim: int, use_bias: bool = True, drop: _Drop = None,
+                 site: int = 0):
+        super().__init__(rt, name, B, S, D, n_head, key_dim, use_bias, rt.lib.seld_attn_bwd_scratch, drop=drop, site=site)
 
     def forward(self, x, B, training):
-        rt = self.rt
-        R, HD = B * self.S, self.H * self.dk
+        R = B * self.S
         self._qkv(x, R)
-        rt.ck(rt.lib.seld_attn_fwd(rt.p(self.q), rt.p(self.k), rt.p(self.v), HD, HD, HD, rt.p(self.o), rt.p(self.lse) if training else None, B, self.S,
-                                   self.H, self.dk, self.scale, rt.st()))
+        self._core_fwd(B, training)
         return self._project(R)
 
     def backward(self, dout, dx, B):
         """dout [R, D] -> every variable's gradient; dx = the input's gradient (overwritten)"""
-        rt = self.rt
-        R, HD = B * self.S, self.H * self.dk
+        R = B * self.S
         self._project_bwd(dout, R)
-        rt.ck(rt.lib.seld_attn_bwd(rt.p(self.q), rt.p(self.k), rt.p(self.v), HD, HD, HD, rt.p(self.o), rt.p(self.do), rt.p(self.lse), rt.p(self.dq),
-                                   rt.p(self.dk_), rt.p(self.dv), HD, HD, HD, rt.p(self.scratch), B, self.S, self.H, self.dk, self.scale, rt.st()))
+        self._core_bwd(B)
         for i, g in enumerate((self.dq, self.dk_, self.dv)):
             self._input_bwd(i, g, dx, R, accumulate=int(i > 0))
 
@@ -698,14 +814,14 @@ def basic_pos_encoding(S: int, D: int) -> np.ndarray:
     return np.stack([np.cos(arg), np.sin(arg)], -1).reshape(int(S), 2 * k).astype(np.float32)
 
 
-def check_conformer_config(cfg: dict, stage: bool = False, D=None) -> None:
+def check_conformer_config(cfg: dict, stage: bool = False, D=None, dropout: bool = False) -> None:
     """what reference modules.py:410-430 reads (every key has a default there; `depth` is the stage's, modules.py:146); what has no kernel
     here is refused, not ignored"""
     who = f"conformer_encoder_{'stage' if stage else 'block'}"
     if stage and "depth" not in cfg:
         raise ValueError(f"{who}: missing 'depth'")
     _check_activation(cfg, "swish")
-    _check_no_dropout(cfg, who)
+    _dropout_rate(cfg, who, dropout)
     if cfg.get("pos_mode", "absolute") != "absolute":
         raise ValueError(f"{who}: pos_mode {cfg.get('pos_mode')!r}: RelPositionMultiHeadAttention has no kernel here, only 'absolute'")
     _check_pos_encoding(cfg, who, D)
@@ -719,14 +835,16 @@ def check_conformer_config(cfg: dict, stage: bool = False, D=None) -> None:
 
 
 class ConformerEncoderBlock:
-    """reference modules.conformer_encoder_block (modules.py:432-506) on [B, S, D], every Dropout at rate 0:
+    """reference modules.conformer_encoder_block (modules.py:432-506) on [B, S, D].  In training with dropout_rate > 0 the seven Dropouts draw
+    (_Drop: behind each FFN's activation and output, on the attention probabilities, behind the attention and behind the convolution module);
+    written without them:
       x  = x + ffn_factor Dense(D)(act(Dense(multiplier D)(LN(x))));  x = x + encoding (pos_encoding 'basic')
       x  = x + MultiHeadAttention_(LN(x))
       x' = x + Conv1D(D, 1)(swish(BN(depthwise Conv1D(k)(GLU(Conv1D(2 D, 1)(LN(x)))))))
       out = LN(x + ffn_factor Dense(D)(act(Dense(multiplier D)(LN(x')))))       — the last residual adds to x, not x' (modules.py:495, 504)."""
 
     def __init__(self, rt: _Rt, cfg: dict, S: int, D: int, prefix: str, B: int):
-        check_conformer_config(cfg, D=D)
+        check_conformer_config(cfg, D=D, dropout=rt.dropout)
         self.rt, self.S, self.D, self.B = rt, int(S), int(D), B
         S, D = self.S, self.D
         self.F = int(cfg.get("multiplier", 4)) * D
@@ -735,19 +853,21 @@ class ConformerEncoderBlock:
         p = prefix
         e = rt.empty
         scratch = (e(R, self.F), e(R, self.F), e(R, D))      # dh, dpre, df: the two FFNs run one after the other
+        self.drop = _Drop(rt, _dropout_rate(cfg, "conformer_encoder_block", rt.dropout))
 
-        def ffn(name):
+        def ffn(name, sites):
             return _FeedForward(rt, Dense(rt, f"{name}a", R, D, self.F), Dense(rt, f"{name}b", R, self.F, D), R, ACT[cfg.get("activation", "swish")],
-                                self.ff, scratch)
+                                self.ff, scratch, self.drop, sites)
         self.ln0 = LayerNorm(rt, f"{p}.ln0", R, D)
-        self.ffn0 = ffn(f"{p}.ffn0")
+        self.ffn0 = ffn(f"{p}.ffn0", (0, 1))
         self.ln1 = LayerNorm(rt, f"{p}.ln1", R, D)
-        self.mha = MultiHeadAttentionRef(rt, f"{p}.mha", B, S, D, int(cfg.get("n_head", 4)), int(cfg.get("key_dim", 36)), cfg.get("use_bias", True))
+        self.mha = MultiHeadAttentionRef(rt, f"{p}.mha", B, S, D, int(cfg.get("n_head", 4)), int(cfg.get("key_dim", 36)), cfg.get("use_bias", True),
+                                         self.drop, 2)
         self.ln2 = LayerNorm(rt, f"{p}.ln2", R, D)
         self.pw0 = Conv1D(rt, f"{p}.pw0", B, S, D, 2 * D, 1)
         self.tail = _ConvTail(rt, p, B, S, D, int(cfg.get("kernel_size", 32)), glu=True)
         self.ln3 = LayerNorm(rt, f"{p}.ln3", R, D)
-        self.ffn1 = ffn(f"{p}.ffn1")
+        self.ffn1 = ffn(f"{p}.ffn1", (5, 6))
         self.ln4 = LayerNorm(rt, f"{p}.ln4", R, D)
         self.enc = None
         if cfg.get("pos_encoding", "basic") == "basic":
@@ -755,6 +875,7 @@ class ConformerEncoderBlock:
         self.x1, self.x2, self.x3, self.z = e(R, D), e(R, D), e(R, D), e(R, D)
         self.du = e(R, 2 * D)
         self.dx2, self.dx1, self.dx0, self.dn = e(R, D), e(R, D), e(R, D), e(R, D)
+        self.dd = e(R, D) if self.drop.rate > 0 else None      # a gradient behind a Dropout
         self.out_dim, self.out_shape = D, (S, D)
 
     def _ffn_bwd(self, ln, ffn, dy, rows):
@@ -768,17 +889,19 @@ class ConformerEncoderBlock:
         R, D = B * self.S, self.D
         x = x.reshape(R, D)
         x1, x2, x3, z = self.x1[:R], self.x2[:R], self.x3[:R], self.z[:R]
+        drop = self.drop
+        drop.begin(training)
         x1.copy_(x)
-        rt.axpy(x1, self.ffn0.forward(self.ln0.forward(x, None, R, training), R), self.ff)
+        drop.add(1, x1, self.ffn0.forward(self.ln0.forward(x, None, R, training), R), self.ff)
         if self.enc is not None:
             rt.ck(rt.lib.seld_pos_add(rt.p(x1), rt.p(self.enc), B, self.S, D, rt.st()))
         x2.copy_(x1)
-        rt.axpy(x2, self.mha.forward(self.ln1.forward(x1, None, R, training), B, training))
+        drop.add(3, x2, self.mha.forward(self.ln1.forward(x1, None, R, training), B, training))
         sw = self.tail.hidden(self.pw0.forward(self.ln2.forward(x2, None, R, training), R), B, training)
         x3.copy_(x2)
-        rt.axpy(x3, self.tail.pw1.forward(sw, R))
+        drop.add(4, x3, self.tail.pw1.forward(sw, R))
         z.copy_(x2)
-        rt.axpy(z, self.ffn1.forward(self.ln3.forward(x3, None, R, training), R), self.ff)
+        drop.add(6, z, self.ffn1.forward(self.ln3.forward(x3, None, R, training), R), self.ff)
         return self.ln4.forward(z, None, R, training)
 
     def backward(self, dy, B):
@@ -790,11 +913,11 @@ class ConformerEncoderBlock:
         dx2.copy_(dz)
         dx3 = self._ffn_bwd(self.ln3, self.ffn1, dz, R)                  # gradient of x3 = x2 + conv
         rt.axpy(dx2, dx3)
-        self.tail.backward(dx3, self.du[:R], B)
+        self.tail.backward(self.drop.apply(4, dx3, self.dd[:R]) if self.drop.on else dx3, self.du[:R], B)
         self.pw0.backward(self.du[:R], self.dn[:R], R)
         rt.axpy(dx2, self.ln2.backward(self.dn[:R], R))
         dx1.copy_(dx2)
-        self.mha.backward(dx2, self.dn[:R], B)
+        self.mha.backward(self.drop.apply(3, dx2, self.dd[:R]) if self.drop.on else dx2, self.dn[:R], B)
         rt.axpy(dx1, self.ln1.backward(self.dn[:R], R))
         dx0.copy_(dx1)                                                   # the positional table is a constant
         rt.axpy(dx0, self._ffn_bwd(self.ln0, self.ffn0, dx1, R))
@@ -878,7 +1001,7 @@ class RelPositionMultiHeadAttention(_HeadMajorAttention):
 ATTENTION_KEYS = ("key_dim", "n_head", "kernel_size", "ff_kernel_size", "ff_multiplier", "ff_factor0", "ff_factor1")
 
 
-def check_attention_config(cfg: dict, stage: bool = False, D=None) -> None:
+def check_attention_config(cfg: dict, stage: bool = False, D=None, dropout: bool = False) -> None:
     """the mandatory keys and the ValueErrors of reference modules.py:513-551 (`depth` is the stage's, modules.py:174); what has no kernel here
     is refused, not ignored"""
     who = f"attention_{'stage' if stage else 'block'}"
@@ -886,7 +1009,10 @@ def check_attention_config(cfg: dict, stage: bool = False, D=None) -> None:
         if key not in cfg:
             raise ValueError(f"{who}: missing {key!r}")
     _check_activation(cfg, "swish")
-    _check_no_dropout(cfg, who)
+    if _dropout_rate(cfg, who, dropout) > 0 and not bool(cfg.get("abs_pos_encoding", False)):
+        raise ValueError(f"{who}: dropout_rate > 0 (absent: the reference's {DROPOUT_DEFAULT}) with abs_pos_encoding False: the relative-position "
+                         "kernels (seld_relattn_*) cannot drop their probabilities yet — their backward is four differently laid-out kernels; "
+                         "set abs_pos_encoding True or dropout_rate 0")
     f0, f1, fk, fm = float(cfg["ff_factor0"]), float(cfg["ff_factor1"]), int(cfg["ff_kernel_size"]), float(cfg["ff_multiplier"])
     if f0 < 0 or f1 < 0:
         raise ValueError("ff_factor0, ff_factor1 >= 0 must hold")
@@ -907,10 +1033,10 @@ class _FFModule:
     """attention_block's FF module (modules.py:559-572, 619-632): x + factor Conv1D(D, k)(act(Conv1D(int(ff_multiplier D), k)(x))), then
     LayerNormalization unless layer_norm_in_front — whose own LayerNormalization is dead: the first Conv1D reads x (modules.py:564, 624)."""
 
-    def __init__(self, rt: _Rt, name: str, lname, B: int, S: int, D: int, F: int, k: int, act: int, factor: float):
-        self.rt, self.S, self.factor = rt, S, float(factor)
+    def __init__(self, rt: _Rt, name: str, lname, B: int, S: int, D: int, F: int, k: int, act: int, factor: float, drop: _Drop, sites):
+        self.rt, self.S, self.factor, self.drop = rt, S, float(factor), drop
         R = B * S
-        self.ffn = _FeedForward(rt, Conv1D(rt, f"{name}a", B, S, D, F, k), Conv1D(rt, f"{name}b", B, S, F, D, k), R, act, self.factor)
+        self.ffn = _FeedForward(rt, Conv1D(rt, f"{name}a", B, S, D, F, k), Conv1D(rt, f"{name}b", B, S, F, D, k), R, act, self.factor, None, drop, sites)
         self.ln = LayerNorm(rt, lname, R, D) if lname else None
         self.y, self.dx = rt.empty(R, D), rt.empty(R, D)
 
@@ -919,7 +1045,7 @@ class _FFModule:
         h = self.ffn.hidden(x, R)
         y = self.y[:R]
         y.copy_(x)
-        rt.axpy(y, self.ffn.second.forward(h, R), self.factor)
+        self.drop.add(self.ffn.sites[1], y, self.ffn.second.forward(h, R), self.factor)
         return self.ln.forward(y, None, R, training) if self.ln else y
 
     def backward(self, dy, B):
@@ -932,7 +1058,9 @@ class _FFModule:
 
 
 class AttentionBlock:
-    """reference modules.attention_block (modules.py:511-635) on [B, S, D], every Dropout at rate 0 (lnf = layer_norm_in_front):
+    """reference modules.attention_block (modules.py:511-635) on [B, S, D].  In training with dropout_rate > 0 (abs_pos_encoding only) the
+    Dropouts draw (_Drop: behind each FF module's activation and output, on the attention probabilities, behind the attention and behind the
+    depthwise tail); written without them (lnf = layer_norm_in_front):
       x = FF0(x)                                                   (ff_factor0 > 0)
       a = x; x += table (abs_pos_encoding: AFTER a is taken, so the attention never sees it)
       x = x + MHA(LN?(a))        MultiHeadAttention_ (abs_pos_encoding) or RelPositionMultiHeadAttention with the table;  x = LN(x) unless lnf
@@ -942,7 +1070,7 @@ class AttentionBlock:
       x = FF1(x)                                                   (ff_factor1 > 0)"""
 
     def __init__(self, rt: _Rt, cfg: dict, S: int, D: int, prefix: str, B: int):
-        check_attention_config(cfg, D=D)
+        check_attention_config(cfg, D=D, dropout=rt.dropout)
         self.rt, self.S, self.D, self.B = rt, int(S), int(D), B
         S, D, p = self.S, self.D, prefix
         R = B * S
@@ -953,10 +1081,11 @@ class AttentionBlock:
         lnf = self.lnf
         H, dk, ub = int(cfg["n_head"]), int(cfg["key_dim"]), bool(cfg.get("use_bias", False))
         f0, f1 = float(cfg["ff_factor0"]), float(cfg["ff_factor1"])
-        self.ff0 = _FFModule(rt, f"{p}.ff0", None if lnf else f"{p}.ln0", B, S, D, F, fk, act, f0) if f0 > 0 else None
+        self.drop = _Drop(rt, _dropout_rate(cfg, "attention_block", rt.dropout))
+        self.ff0 = _FFModule(rt, f"{p}.ff0", None if lnf else f"{p}.ln0", B, S, D, F, fk, act, f0, self.drop, (0, 1)) if f0 > 0 else None
         self.ln1 = LayerNorm(rt, f"{p}.ln1", R, D) if lnf else None
         if self.abs:
-            self.mha = MultiHeadAttentionRef(rt, f"{p}.mha", B, S, D, H, dk, ub)
+            self.mha = MultiHeadAttentionRef(rt, f"{p}.mha", B, S, D, H, dk, ub, self.drop, 2)
         else:
             self.mha = RelPositionMultiHeadAttention(rt, f"{p}.mha", B, S, D, H, dk, ub)
         if not lnf:
@@ -974,13 +1103,14 @@ class AttentionBlock:
             self.tail = _ConvTail(rt, p, B, S, D, self.k, glu=self.glu)
             if not lnf:
                 self.ln2 = LayerNorm(rt, f"{p}.ln2", R, D)
-        self.ff1 = _FFModule(rt, f"{p}.ff1", None if lnf else f"{p}.ln3", B, S, D, F, fk, act, f1) if f1 > 0 else None
+        self.ff1 = _FFModule(rt, f"{p}.ff1", None if lnf else f"{p}.ln3", B, S, D, F, fk, act, f1, self.drop, (5, 6)) if f1 > 0 else None
         self.enc = None
         if self.abs and cfg.get("pos_encoding", "basic") == "basic":
             self.enc = torch.as_tensor(basic_pos_encoding(S, D)).to(rt.dev)
         e = rt.empty
         self.xr, self.xb, self.xc = e(R, D), e(R, D), e(R, D)
         self.du, self.dn, self.dxb, self.dxa = e(R, 2 * D), e(R, D), e(R, D), e(R, D)
+        self.dd = e(R, D) if self.drop.rate > 0 else None      # a gradient behind a Dropout
         self.out_dim, self.out_shape = D, (S, D)
 
     def forward(self, x, B, training):
@@ -988,6 +1118,8 @@ class AttentionBlock:
         rt = self.rt
         R, D = B * self.S, self.D
         x = x.reshape(R, D)
+        drop = self.drop
+        drop.begin(training)
         if self.ff0:
             x = self.ff0.forward(x, B, training)
         attn = self.ln1.forward(x, None, R, training) if self.lnf else x
@@ -1000,9 +1132,9 @@ class AttentionBlock:
         if self.lnf:
             xb = self.xb[:R]
             xb.copy_(res)
-            rt.axpy(xb, attn)
+            drop.add(3, xb, attn)
         else:
-            xb = self.ln1.forward(attn, res, R, training)
+            xb = self.ln1.forward(drop.apply(3, attn, attn) if drop.on else attn, res, R, training)
         c = xb
         if self.glu:
             c = self.pw0.forward(self.ln2.forward(c, None, R, training) if self.lnf else c, R)
@@ -1015,9 +1147,9 @@ class AttentionBlock:
             if self.lnf:
                 xc = self.xc[:R]
                 xc.copy_(xb)
-                rt.axpy(xc, pw)
+                drop.add(4, xc, pw)
             else:
-                xc = self.ln2.forward(pw, xb, R, training)
+                xc = self.ln2.forward(drop.apply(4, pw, pw) if drop.on else pw, xb, R, training)
         else:
             xc = c
         return self.ff1.forward(xc, B, training) if self.ff1 else xc
@@ -1034,7 +1166,7 @@ class AttentionBlock:
         if self.k > 0:
             dz = d if self.lnf else self.ln2.backward(d, R)               # gradient of xb + pw
             dxb.copy_(dz)
-            self.tail.backward(dz, du, B)
+            self.tail.backward(self.drop.apply(4, dz, self.dd[:R]) if self.drop.on else dz, du, B)
             if self.glu:
                 self.pw0.backward(du, dn, R)
                 rt.axpy(dxb, self.ln2.backward(dn, R) if self.lnf else dn)
@@ -1049,7 +1181,7 @@ class AttentionBlock:
         dz = dxb if self.lnf else self.ln1.backward(dxb, R)               # gradient of attn + x (the table is a constant)
         dxa = self.dxa[:R]
         dxa.copy_(dz)
-        self.mha.backward(dz, dn, B)
+        self.mha.backward(self.drop.apply(3, dz, self.dd[:R]) if self.drop.on else dz, dn, B)
         rt.axpy(dxa, self.ln1.backward(dn, R) if self.lnf else dn)
         return self.ff0.backward(dxa, B) if self.ff0 else dxa
 
@@ -1068,7 +1200,8 @@ def check_rnn_config(cfg: dict, stage: bool = False) -> None:
     if stage and int(cfg["depth"]) < 1:
         raise ValueError(f"{who}: depth >= 1")
     if float(cfg.get("dropout_rate", 0.0) or 0.0) != 0.0:
-        raise ValueError(f"{who}: dropout / recurrent_dropout are not implemented on the composed path: dropout_rate must be 0")
+        raise ValueError(f"{who}: dropout / recurrent_dropout inside the recurrence kernels (per-clip input and state masks) are not implemented on "
+                         "the composed path, whose Dropout (seld_dropout, seld_attn_drop_*) covers the attention kinds only: dropout_rate must be 0")
     if bool(cfg.get("bidirectional", True)) and cfg.get("merge_mode", "mul") not in RNN_MERGE:
         # None makes Bidirectional return a LIST (the reference's graph breaks on it); 'avg' (the reference's comment) is rejected by Keras itself
         raise ValueError(f"{who}: merge_mode {cfg.get('merge_mode')!r}: one of {RNN_MERGE}")
@@ -1177,7 +1310,8 @@ class RNNBlock(_Recurrent):
 def check_gru_config(cfg: dict, stage: bool = False) -> None:
     """reference modules.bidirectional_GRU_block (modules.py:302-319): one layer per entry of `units`"""
     if float(cfg.get("dropout_rate", 0.0)) != 0.0:
-        raise ValueError("GRU dropout is not implemented")
+        raise ValueError("bidirectional_GRU_block: GRU dropout / recurrent_dropout masks exist on the fused path only (models.SeldNet), not among "
+                         "the composed path's Dropout operators: dropout_rate must be 0")
     if any(int(u) != 128 for u in cfg["units"]):
         raise ValueError("the recurrence kernels are built for 128 units")
 
@@ -1438,14 +1572,29 @@ SECOND_KINDS = {
 assert tuple(SECOND_KINDS) == COMPOSED_SECOND + CONFORMER_SECOND + ATTENTION_SECOND + RNN_SECOND
 
 
-def _build_second(kind: str, rt, cfg: dict, S: int, D: int, B: int, prefix=None) -> Stage:
+DROPOUT_KINDS = COMPOSED_SECOND[1:] + CONFORMER_SECOND + ATTENTION_SECOND      # the SECOND kinds whose Dropouts can draw (_Drop)
+
+
+def _check_second(kind: str, cfg: dict, D=None, dropout: bool = False) -> None:
+    _, check, _, stage, with_d = SECOND_KINDS[kind]
+    kw = {"dropout": True} if dropout and kind in DROPOUT_KINDS else {}
+    check(cfg, stage, D, **kw) if with_d else check(cfg, stage, **kw)
+
+
+def _build_second(kind: str, rt, cfg: dict, S: int, D: int, B: int, prefix=None, dropout: bool = False) -> Stage:
     """the SECOND stage `kind` on [B*S, D] (rt None: on a runtime of its own on the current device); the configuration errors, those that
-    need the width among them (pos_encoding 'basic' on an odd one, the FF width), are raised first, without a device"""
-    block, check, pre, stage, with_d = SECOND_KINDS[kind]
-    check(cfg, stage, D) if with_d else check(cfg, stage)
+    need the width among them (pos_encoding 'basic' on an odd one, the FF width), are raised first, without a device.  dropout: the caller
+    accepts the library's draws (_dropout_rate); a given rt carries its owner's choice"""
+    block, _, pre, stage, _ = SECOND_KINDS[kind]
+    dropout = bool(dropout) if rt is None else rt.dropout
+    _check_second(kind, cfg, D, dropout)
+    own = rt is None
     rt = rt or _Rt(torch.device("cuda", torch.cuda.current_device()))
+    rt.dropout = dropout
     depth = int(cfg["depth"]) if stage else len(cfg["units"]) if block is BidirectionalGRUBlock else 1
-    return Stage(rt, block, cfg, S, D, prefix or pre, B, depth)
+    st = Stage(rt, block, cfg, S, D, prefix or pre, B, depth)
+    st.model = own
+    return st
 
 
 class Head:
@@ -1500,6 +1649,7 @@ class ComposedSeldNet:
         self.input_shape = (B, T, Fq, Ch)
         self.n_classes = int(cfg.get("n_classes", 14))
         rt = self.rt = _Rt(self._dev)
+        rt.dropout = True      # a model trains on the library's Dropout draws (dropout_seed / dropout_step below), as the fused models do
         self.lib = rt.lib
         fa = cfg["FIRST_ARGS"]
         if cfg["FIRST"] == "mother_stage":
@@ -1524,7 +1674,8 @@ class ComposedSeldNet:
         for head, key, n_out, act in (("sed", "SED_ARGS", self.n_classes, "sigmoid"), ("doa", "DOA_ARGS", 3 * self.n_classes, "tanh")):
             ha = cfg[key]
             if int(ha.get("kernel_size", 1)) != 1 or float(ha.get("dropout_rate", 0)) != 0:
-                raise ValueError("composed heads: kernel_size 1, no dropout")
+                raise ValueError("composed heads: kernel_size 1 and no dropout — the heads' Dropout (simple_dense_block) is wired on the fused path only; "
+                                 "the composed path's Dropout covers the attention SECOND kinds")
             hact = ha.get("dense_activation", None)
             if hact not in ACT:
                 raise ValueError(f"dense_activation {hact!r}")
@@ -1646,9 +1797,30 @@ class ComposedSeldNet:
             raise ValueError(f"x shape {tuple(x.shape)}: a composed model built for {self.input_shape} runs batches of 1..{Bm} clips of {(T, Fq, Ch)}")
         return x
 
+    # the Dropout draws (attention SECOND kinds with dropout_rate > 0): masks are a function of (dropout_seed, step, layer, element); every
+    # training forward takes the next step.  Settable, as the fused models' options of the same names.
+    @property
+    def dropout_seed(self) -> int:
+        return self.rt.dropout_seed
+
+    @dropout_seed.setter
+    def dropout_seed(self, v: int) -> None:
+        self.rt.dropout_seed = int(v) & 0xffffffffffffffff
+
+    @property
+    def dropout_step(self) -> int:
+        """the step counter the NEXT training forward draws its masks with"""
+        return self.rt.dropout_step
+
+    @dropout_step.setter
+    def dropout_step(self, v: int) -> None:
+        self.rt.dropout_step = int(v) & 0xffffffff
+
     def _forward(self, x, training: bool):
         rt = self.rt
         B = x.shape[0]
+        if training:
+            rt.next_draws()
         h = x
         for blk in self.blocks:
             h = blk.forward(h, B, training)
@@ -1736,50 +1908,55 @@ def mother_block(model_config: dict):
     return build
 
 
-def _second_factory(kind: str, model_config: dict):
-    _, check, pre, stage, _ = SECOND_KINDS[kind]
-    check(model_config, stage)
+def _second_factory(kind: str, model_config: dict, dropout: bool = False):
+    """dropout (the transformer, conformer and attention kinds): the caller accepts the library's counter-based Dropout draws in place of
+    TensorFlow's, and dropout_rate may then be any rate in [0, 1), absent = the reference's 0.1; False: dropout_rate must be present and 0"""
+    pre = SECOND_KINDS[kind][2]
+    _check_second(kind, model_config, None, dropout)
 
     def build(input_shape, rt=None, prefix=pre):
         """input_shape [B, S, D] or [B, S, F, C] (layers.force_1d_inputs: D = F * C)"""
         sh = [int(v) for v in input_shape]
         if len(sh) not in (3, 4):
             raise ValueError(f"{kind.replace('_stage', '_block')}: input [B, S, D] or [B, S, F, C]")
-        return _build_second(kind, rt, model_config, sh[1], int(np.prod(sh[2:])), sh[0], prefix)
+        return _build_second(kind, rt, model_config, sh[1], int(np.prod(sh[2:])), sh[0], prefix, dropout)
     return build
 
 
-def transformer_encoder_block(model_config: dict):
+def transformer_encoder_block(model_config: dict, dropout: bool = False):
     """reference modules.transformer_encoder_block(model_config) (modules.py:379-407) -> a factory `(input_shape) -> a one-block Stage`
-    (forward(x, B, training) / backward(dy, B) on [B*S, D]); configuration errors are raised here, without a device."""
-    return _second_factory("transformer_encoder_block", model_config)
+    (forward(x, B, training) / backward(dy, B) on [B*S, D]); configuration errors are raised here, without a device.  dropout: accept the
+    library's Dropout draws (_second_factory); without it dropout_rate must be present and 0."""
+    return _second_factory("transformer_encoder_block", model_config, dropout)
 
 
-def transformer_encoder_stage(model_config: dict):
+def transformer_encoder_stage(model_config: dict, dropout: bool = False):
     """reference modules.transformer_encoder_stage(model_config) (modules.py:106-126): `depth` blocks"""
-    return _second_factory("transformer_encoder_stage", model_config)
+    return _second_factory("transformer_encoder_stage", model_config, dropout)
 
 
-def conformer_encoder_block(model_config: dict):
+def conformer_encoder_block(model_config: dict, dropout: bool = False):
     """reference modules.conformer_encoder_block(model_config) (modules.py:410-508) -> a factory `(input_shape) -> a one-block Stage`
-    (forward(x, B, training) / backward(dy, B) on [B*S, D]); configuration errors are raised here, without a device."""
-    return _second_factory("conformer_encoder_block", model_config)
+    (forward(x, B, training) / backward(dy, B) on [B*S, D]); configuration errors are raised here, without a device.  dropout: accept the
+    library's Dropout draws (_second_factory); without it dropout_rate must be present and 0."""
+    return _second_factory("conformer_encoder_block", model_config, dropout)
 
 
-def conformer_encoder_stage(model_config: dict):
+def conformer_encoder_stage(model_config: dict, dropout: bool = False):
     """reference modules.conformer_encoder_stage(model_config) (modules.py:129-152): `depth` blocks"""
-    return _second_factory("conformer_encoder_stage", model_config)
+    return _second_factory("conformer_encoder_stage", model_config, dropout)
 
 
-def attention_block(model_config: dict):
+def attention_block(model_config: dict, dropout: bool = False):
     """reference modules.attention_block(model_config) (modules.py:511-635) -> a factory `(input_shape) -> a one-block Stage`
-    (forward(x, B, training) / backward(dy, B) on [B*S, D]); configuration errors are raised here, without a device."""
-    return _second_factory("attention_block", model_config)
+    (forward(x, B, training) / backward(dy, B) on [B*S, D]); configuration errors are raised here, without a device.  dropout: accept the
+    library's Dropout draws (_second_factory); without it dropout_rate must be present and 0."""
+    return _second_factory("attention_block", model_config, dropout)
 
 
-def attention_stage(model_config: dict):
+def attention_stage(model_config: dict, dropout: bool = False):
     """reference modules.attention_stage(model_config) (modules.py:155-180): `depth` blocks"""
-    return _second_factory("attention_stage", model_config)
+    return _second_factory("attention_stage", model_config, dropout)
 
 
 def RNN_block(model_config: dict):
