@@ -8,17 +8,9 @@
 // (batch, head) streams 64-key tiles of K and V through LDS with an online softmax (running maximum m and sum l per query row), and the
 // backward recomputes the probabilities from the saved log-sum-exp m + ln l.  All products run on v_mfma_f32_32x32x2_f32 (exact fp32).
 //
-// Tile scheme (forward, and the dQ kernel of the backward): the logits are computed TRANSPOSED, S^T[key][query] = K Q^T, so that a lane
-// of the accumulator layout (common.h) holds ONE query (column l & 31) and 16 keys (rows (r & 3) + 8 (r >> 2) + 4 (l >> 5)); lane l ^ 32
-// holds the other 16.  The row maximum and sum of a query are then 16 in-lane operations and one cross-half shuffle, m / l / lse / delta are
-// per-lane scalars, and the accumulator registers p[r] ARE the B operand of the next product O^T[dd][query] += V^T[dd][key] P^T[key][query]
-// (step r contracts keys row(r, 0) and row(r, 1): a sum over keys has no order to respect), so P never crosses LDS.  The dK / dV kernel is
-// the mirror image: S[query][key] with the key on the lane and K, V of the wave's 32 keys in registers, Q and dO tiles through LDS, and
-// p[r] / ds[r] the B operands of dV^T += dO^T P and dK^T += Q^T dS.  Each output element is owned by exactly one lane of one workgroup:
-// no atomics, sums in a fixed order, two runs are bit-identical.
-//
-// LDS rows are d + 1 floats (odd): the [key = lane][dd] operand reads of a 32-lane half then hit 32 different banks, and the
-// [key = row][dd = lane] reads are consecutive addresses.  2 x 64 x 65 x 4 B = 33 KB per workgroup at d = 64 (4 workgroups per CU).
+// Tile scheme: attn_tile.h (logits transposed, a lane owns one query in the forward and the dQ kernel and one key in the dK / dV kernel, LDS rows
+// of d + 1 floats), whose steps the three kernels below are written in.  2 x 64 x 65 x 4 B = 33 KB of LDS per workgroup at d = 64 (4 workgroups
+// per CU).
 // Registers: Q (and dO) fragments d / 2 each, logits 16 (+16), outputs 16 ceil(d / 32) (twice that in the dK / dV kernel).
 //
 // Dropped probabilities (seld_attn_drop_*: tf.keras.layers.MultiHeadAttention(dropout = r), layers.MultiHeadAttention_, layers.py:253-257).
@@ -33,49 +25,11 @@
 // of one group and the SAME 16 queries: each lane draws the words of four of them (register 4 g + (lane & 3), g = 0 .. 3) and the quad exchanges
 // the keep bits by DPP — four Philox calls per 32 x 32 block and lane there too, in place of one per element.
 // (b H + h) S + n must fit 32 bits: B H S <= 2^32, checked by the entry points.
-#include "common.h"
-#include <cmath>
-#include "../../include/seld_hip.h"
-#include <math.h>
+#include "attn_tile.h"
 
 namespace {
 
-#define AT_TILE 64      // query rows per workgroup = keys per LDS tile (two 32-row MFMA blocks)
-
-__device__ __forceinline__ float xhalf(float v) { return __shfl_xor(v, 32, 64); }
-
-// rows k0 .. k0 + 63 of one head of a [B*S, ld] view -> LDS [64][D + 1], rows past S as zeros; `mul` scales (the query's 1 / sqrt(key_dim))
-template <int D>
-__device__ __forceinline__ void load_tile(const float* __restrict__ src, int ld, size_t row0, int k0, int S, int col0, float mul, float* dst) {
-    for (int e = threadIdx.x; e < AT_TILE * D; e += 128) {
-        const int kk = e / D, dd = e - kk * D;
-        const int key = k0 + kk;
-        dst[kk * (D + 1) + dd] = key < S ? src[(row0 + key) * (size_t)ld + col0 + dd] * mul : 0.f;
-    }
-}
-
-// the lane's fragment of row `row` (valid: ok) of a view: f[s] = row[2 s + hi] * mul
-template <int D>
-__device__ __forceinline__ void load_frag(const float* __restrict__ src, int ld, size_t row, int col0, bool ok, int hi, float mul, float (&f)[D / 2]) {
-    const float* p = src + row * (size_t)ld + col0 + hi;
-#pragma unroll
-    for (int s = 0; s < D / 2; ++s) f[s] = ok ? p[2 * s] * mul : 0.f;
-}
-
-// out^T[dd][lane's row] accumulators -> out[row][col0 + dd] * mul
-template <int D>
-__device__ __forceinline__ void store_t(const f32x16 (&acc)[(D + 31) / 32], float* __restrict__ out, int ld, size_t row, int col0, bool ok, int hi,
-                                        float mul) {
-    if (!ok) return;
-    float* p = out + row * (size_t)ld + col0;
-#pragma unroll
-    for (int nb = 0; nb < (D + 31) / 32; ++nb)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int dd = nb * 32 + mfma_row(r, hi);
-            if (dd < D) p[dd] = acc[nb][r] * mul;
-        }
-}
+using namespace attn_tile;
 
 // what the DROP instantiations read (the others ignore it): the fp32 rate, 1 / (1 - rate), the Philox key and the stream
 struct AttnDrop { float rate, keep; unsigned seed_lo, seed_hi, layer, step; };
@@ -113,58 +67,33 @@ __global__ __launch_bounds__(128) void attn_fwd_kernel(const float* __restrict__
                                                        int ldk, int ldv, float* __restrict__ O, float* __restrict__ lse, int S, int H, float scale,
                                                        int nqt, AttnDrop dr) {
     constexpr int LD = D + 1, NB = (D + 31) / 32;
-    __shared__ float Ks[AT_TILE * LD], Vs[AT_TILE * LD];
+    __shared__ float Ks[ATTN_TILE * LD], Vs[ATTN_TILE * LD];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 31, hi = lane >> 5;
     const int qt = blockIdx.x % nqt, bh = blockIdx.x / nqt, h = bh % H, b = bh / H;
-    const int q = qt * AT_TILE + wave * 32 + li;
+    const int q = qt * ATTN_TILE + wave * 32 + li;
     const bool qok = q < S;
     const size_t row0 = (size_t)b * S;
     float qf[D / 2];
-    load_frag<D>(Q, ldq, row0 + (qok ? q : 0), h * D, qok, hi, scale, qf);
+    load_frag<D>(Q, ldq, row0 + (qok ? q : 0), h * D, qok, hi, nullptr, scale, qf);
     f32x16 o[NB];
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) o[nb] = zero16();
     float m = -INFINITY, l = 0.f;
-    for (int k0 = 0; k0 < S; k0 += AT_TILE) {
+    for (int k0 = 0; k0 < S; k0 += ATTN_TILE) {
         __syncthreads();
-        load_tile<D>(K, ldk, row0, k0, S, h * D, 1.f, Ks);
-        load_tile<D>(V, ldv, row0, k0, S, h * D, 1.f, Vs);
+        load_rows<D>(K, ldk, row0, k0, ATTN_TILE, S, h * D, 1.f, Ks);
+        load_rows<D>(V, ldv, row0, k0, ATTN_TILE, S, h * D, 1.f, Vs);
         __syncthreads();
         for (int kb = 0; kb < 2 && k0 + kb * 32 < S; ++kb) {
-            f32x16 s = zero16();
-            const float* kr = Ks + (kb * 32 + li) * LD + hi;
-#pragma unroll
-            for (int st = 0; st < D / 2; ++st) s = MFMA_F32_32x32x2(kr[2 * st], qf[st], s);
-            float mx = m;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                if (k0 + kb * 32 + mfma_row(r, hi) >= S) s[r] = -INFINITY;      // the edge tile's keys past S
-                mx = fmaxf(mx, s[r]);
-            }
-            mx = fmaxf(mx, xhalf(mx));      // finite: the block's first key is < S
-            const float alpha = __expf(m - mx);
-            float ps = 0.f;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { s[r] = __expf(s[r] - mx); ps += s[r]; }
-            ps += xhalf(ps);
-            l = l * alpha + ps;
-            m = mx;
+            f32x16 s = logits<D>(Ks, kb * 32 + li, hi, qf);
+            const float alpha = softmax_step(s, k0 + kb * 32, S, hi, m, l);
             if constexpr (DROP) {      // after the sums: l and lse are the full softmax's
                 float mk[16];
                 attn_mask16(dr, k0 + kb * 32, hi, (unsigned)bh * (unsigned)S + (unsigned)q, mk);
 #pragma unroll
                 for (int r = 0; r < 16; ++r) s[r] *= mk[r];
             }
-#pragma unroll
-            for (int nb = 0; nb < NB; ++nb) {
-                const int dd = nb * 32 + li;
-                const bool dok = dd < D;
-                const float* vr = Vs + kb * 32 * LD + (dok ? dd : 0);
-#pragma unroll
-                for (int r = 0; r < 16; ++r) o[nb][r] *= alpha;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) o[nb] = MFMA_F32_32x32x2(dok ? vr[mfma_row(r, hi) * LD] : 0.f, s[r], o[nb]);
-            }
+            accum_t<D, true>(o, Vs + kb * 32 * LD, s, li, hi, alpha);
         }
     }
     store_t<D>(o, O, H * D, row0 + (qok ? q : 0), h * D, qok, hi, 1.f / l);
@@ -178,59 +107,37 @@ __global__ __launch_bounds__(128) void attn_bwd_dq_kernel(const float* __restric
                                                           const float* __restrict__ lse, float* __restrict__ dQ, int lddq, float* __restrict__ delta,
                                                           int S, int H, float scale, int nqt, AttnDrop dr) {
     constexpr int LD = D + 1, NB = (D + 31) / 32;
-    __shared__ float Ks[AT_TILE * LD], Vs[AT_TILE * LD];
+    __shared__ float Ks[ATTN_TILE * LD], Vs[ATTN_TILE * LD];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 31, hi = lane >> 5;
     const int qt = blockIdx.x % nqt, bh = blockIdx.x / nqt, h = bh % H, b = bh / H;
-    const int q = qt * AT_TILE + wave * 32 + li;
+    const int q = qt * ATTN_TILE + wave * 32 + li;
     const bool qok = q < S;
     const size_t row0 = (size_t)b * S, row = row0 + (qok ? q : 0);
     float qf[D / 2], dof[D / 2];
-    load_frag<D>(Q, ldq, row, h * D, qok, hi, scale, qf);
-    load_frag<D>(dO, H * D, row, h * D, qok, hi, 1.f, dof);
-    float dl = 0.f;
-    {
-        const float* op = O + row * (size_t)(H * D) + h * D + hi;
-#pragma unroll
-        for (int s = 0; s < D / 2; ++s) dl += qok ? dof[s] * op[2 * s] : 0.f;
-    }
-    dl += xhalf(dl);
+    load_frag<D>(Q, ldq, row, h * D, qok, hi, nullptr, scale, qf);
+    load_frag<D>(dO, H * D, row, h * D, qok, hi, nullptr, 1.f, dof);
+    const float dl = delta_rowsum<D>(dof, O, H * D, row, h * D, qok, hi);
     if (qok && hi == 0) delta[(size_t)bh * S + q] = dl;
     const float lq = qok ? lse[(size_t)bh * S + q] : INFINITY;      // a row past S: p = exp(-inf) = 0
     f32x16 dq[NB];
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) dq[nb] = zero16();
-    for (int k0 = 0; k0 < S; k0 += AT_TILE) {
+    for (int k0 = 0; k0 < S; k0 += ATTN_TILE) {
         __syncthreads();
-        load_tile<D>(K, ldk, row0, k0, S, h * D, 1.f, Ks);
-        load_tile<D>(V, ldv, row0, k0, S, h * D, 1.f, Vs);
+        load_rows<D>(K, ldk, row0, k0, ATTN_TILE, S, h * D, 1.f, Ks);
+        load_rows<D>(V, ldv, row0, k0, ATTN_TILE, S, h * D, 1.f, Vs);
         __syncthreads();
         for (int kb = 0; kb < 2 && k0 + kb * 32 < S; ++kb) {
-            f32x16 s = zero16(), dp = zero16();
-            const float* kr = Ks + (kb * 32 + li) * LD + hi;
-            const float* vr = Vs + (kb * 32 + li) * LD + hi;
-#pragma unroll
-            for (int st = 0; st < D / 2; ++st) s = MFMA_F32_32x32x2(kr[2 * st], qf[st], s);
-#pragma unroll
-            for (int st = 0; st < D / 2; ++st) dp = MFMA_F32_32x32x2(vr[2 * st], dof[st], dp);
+            f32x16 s = logits<D>(Ks, kb * 32 + li, hi, qf);
+            f32x16 dp = logits<D>(Vs, kb * 32 + li, hi, dof);
             if constexpr (DROP) {      // dPd = M (dO . V)
                 float mk[16];
                 attn_mask16(dr, k0 + kb * 32, hi, (unsigned)bh * (unsigned)S + (unsigned)q, mk);
 #pragma unroll
                 for (int r = 0; r < 16; ++r) dp[r] *= mk[r];
             }
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float p = k0 + kb * 32 + mfma_row(r, hi) < S ? __expf(s[r] - lq) : 0.f;
-                s[r] = p * (dp[r] - dl);
-            }
-#pragma unroll
-            for (int nb = 0; nb < NB; ++nb) {
-                const int dd = nb * 32 + li;
-                const bool dok = dd < D;
-                const float* kc = Ks + kb * 32 * LD + (dok ? dd : 0);
-#pragma unroll
-                for (int r = 0; r < 16; ++r) dq[nb] = MFMA_F32_32x32x2(dok ? kc[mfma_row(r, hi) * LD] : 0.f, s[r], dq[nb]);
-            }
+            prob_ds_q(s, dp, k0 + kb * 32, S, hi, lq, dl);
+            accum_t<D>(dq, Ks + kb * 32 * LD, s, li, hi);
         }
     }
     store_t<D>(dq, dQ, lddq, row, h * D, qok, hi, scale);
@@ -243,29 +150,27 @@ __global__ __launch_bounds__(128) void attn_bwd_dkv_kernel(const float* __restri
                                                            const float* __restrict__ delta, float* __restrict__ dK, float* __restrict__ dV, int lddk,
                                                            int lddv, int S, int H, float scale, int nkt, AttnDrop dr) {
     constexpr int LD = D + 1, NB = (D + 31) / 32;
-    __shared__ float Qs[AT_TILE * LD], Gs[AT_TILE * LD], ls[AT_TILE], ds_[AT_TILE];
+    __shared__ float Qs[ATTN_TILE * LD], Gs[ATTN_TILE * LD], ls[ATTN_TILE], ds_[ATTN_TILE];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 31, hi = lane >> 5;
     const int kt = blockIdx.x % nkt, bh = blockIdx.x / nkt, h = bh % H, b = bh / H;
-    const int key = kt * AT_TILE + wave * 32 + li;
+    const int key = kt * ATTN_TILE + wave * 32 + li;
     const bool kok = key < S;
     const size_t row0 = (size_t)b * S, row = row0 + (kok ? key : 0);
     float kf[D / 2], vf[D / 2];
-    load_frag<D>(K, ldk, row, h * D, kok, hi, 1.f, kf);
-    load_frag<D>(V, ldv, row, h * D, kok, hi, 1.f, vf);
+    load_frag<D>(K, ldk, row, h * D, kok, hi, nullptr, 1.f, kf);
+    load_frag<D>(V, ldv, row, h * D, kok, hi, nullptr, 1.f, vf);
     f32x16 dk[NB], dv[NB];
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) { dk[nb] = zero16(); dv[nb] = zero16(); }
-    for (int q0 = 0; q0 < S; q0 += AT_TILE) {
+    for (int q0 = 0; q0 < S; q0 += ATTN_TILE) {
         __syncthreads();
-        load_tile<D>(Q, ldq, row0, q0, S, h * D, scale, Qs);
-        load_tile<D>(dO, H * D, row0, q0, S, h * D, 1.f, Gs);
-        if (threadIdx.x < AT_TILE) {
-            const int q = q0 + threadIdx.x;
-            ls[threadIdx.x] = q < S ? lse[(size_t)bh * S + q] : INFINITY;      // a row past S: p = exp(-inf) = 0
-            ds_[threadIdx.x] = q < S ? delta[(size_t)bh * S + q] : 0.f;
-        }
+        load_rows<D>(Q, ldq, row0, q0, ATTN_TILE, S, h * D, scale, Qs);
+        load_rows<D>(dO, H * D, row0, q0, ATTN_TILE, S, h * D, 1.f, Gs);
+        load_lse_delta(lse, delta, (size_t)bh * S, q0, ATTN_TILE, S, ls, ds_);
         __syncthreads();
         for (int qb = 0; qb < 2 && q0 + qb * 32 < S; ++qb) {
+            // the block's body is written out, not built from attn_tile.h's logits / accum_t: the helpers cost the DROP form 1 us of 234 at d = 24
+            // and relattn.hip's twin of this kernel 11 % at d = 48; as it stands the kernel's code is the parent's, instruction for instruction
             f32x16 s = zero16(), dp = zero16();
             const float* qr = Qs + (qb * 32 + li) * LD + hi;
             const float* gr = Gs + (qb * 32 + li) * LD + hi;
@@ -385,32 +290,13 @@ __global__ __launch_bounds__(256) void ln_bwd_fold_kernel(const float* __restric
 }
 inline int ln_blocks(int64_t rows) { const int64_t b = (rows + 15) / 16; return (int)(b < LN_MAX_BLOCKS ? b : LN_MAX_BLOCKS); }
 
-inline int ok() { return hipGetLastError() == hipSuccess ? SELD_OK : SELD_ERR_HIP; }
-inline bool d_ok(int d) { return d >= 8 && d <= 64 && d % 8 == 0; }
-// a row stride covers the H * d columns of all heads; the product in 64 bits: H * d past INT_MAX fits no int stride (and the kernels' H * D stays an int)
-inline bool ld_ok(int ld, int H, int d) { return (int64_t)ld >= (int64_t)H * d; }
-// workgroups B * H * ceil(S / 64), or -1 where they do not fit a launch; every product in 64 bits and bounded before the next factor
-inline int64_t at_grid(int B, int S, int H) {
-    const int64_t bh = (int64_t)B * H, nt = ((int64_t)S + AT_TILE - 1) / AT_TILE;
-    return bh > 0x7fffffff || bh * nt > 0x7fffffff ? -1 : bh * nt;
-}
-
-// launch `kern`<d, drop> for d = 8, 16, ..., 64
-#define AT_DISPATCH(kern, drop, d, grid, st, ...)                                                                        \
-    switch (d) {                                                                                                     \
-        case 8: hipLaunchKernelGGL((kern<8, drop>), dim3(grid), dim3(128), 0, st, __VA_ARGS__); break;                     \
-        case 16: hipLaunchKernelGGL((kern<16, drop>), dim3(grid), dim3(128), 0, st, __VA_ARGS__); break;                   \
-        case 24: hipLaunchKernelGGL((kern<24, drop>), dim3(grid), dim3(128), 0, st, __VA_ARGS__); break;                   \
-        case 32: hipLaunchKernelGGL((kern<32, drop>), dim3(grid), dim3(128), 0, st, __VA_ARGS__); break;                   \
-        case 40: hipLaunchKernelGGL((kern<40, drop>), dim3(grid), dim3(128), 0, st, __VA_ARGS__); break;                   \
-        case 48: hipLaunchKernelGGL((kern<48, drop>), dim3(grid), dim3(128), 0, st, __VA_ARGS__); break;                   \
-        case 56: hipLaunchKernelGGL((kern<56, drop>), dim3(grid), dim3(128), 0, st, __VA_ARGS__); break;                   \
-        default: hipLaunchKernelGGL((kern<64, drop>), dim3(grid), dim3(128), 0, st, __VA_ARGS__); break;                   \
-    }
+// launch `kern`<D_, drop> on `grid` workgroups (static LDS)
+#define AT_LAUNCH(D_, kern, drop, grid, st, ...) hipLaunchKernelGGL((kern<D_, drop>), dim3(grid), dim3(128), 0, st, __VA_ARGS__)
+#define AT_DISPATCH(kern, drop, d, grid, st, ...) ATTN_DISPATCH_D(d, AT_LAUNCH, kern, drop, grid, st, __VA_ARGS__)
 
 inline bool rate_ok(float rate) { return rate >= 0.f && rate < 1.f; }      // (a NaN fails both)
 // the mask counter's last word (b H + h) S + n is 32 bits wide
-inline bool ctr_ok(int B, int S, int H) { return (int64_t)B * H * S <= ((int64_t)1 << 32); }      // B * H fits an int behind at_grid: no overflow
+inline bool ctr_ok(int B, int S, int H) { return (int64_t)B * H * S <= ((int64_t)1 << 32); }      // B * H fits an int behind tile_grid: no overflow
 inline AttnDrop at_drop(float rate, uint64_t seed, unsigned layer, unsigned step) {
     return AttnDrop{rate, 1.f / (1.f - rate), (unsigned)seed, (unsigned)(seed >> 32), layer, step};
 }
@@ -421,7 +307,7 @@ int attn_fwd_impl(const float* Q, const float* K, const float* V, int ldq, int l
     if (!d_ok(d)) return SELD_ERR_UNSUPPORTED;
     if (!Q || !K || !V || !O || B < 1 || S < 1 || H < 1 || !ld_ok(ldq, H, d) || !ld_ok(ldk, H, d) || !ld_ok(ldv, H, d) || !rate_ok(rate))
         return SELD_ERR_INVALID;
-    const int64_t grid = at_grid(B, S, H);
+    const int64_t grid = tile_grid(B, S, H);
     if (grid < 0) return SELD_ERR_UNSUPPORTED;
     const int nt = (int)(grid / B / H);
     const AttnDrop dr = at_drop(rate, seed, layer, step);
@@ -441,7 +327,7 @@ int attn_bwd_impl(const float* Q, const float* K, const float* V, int ldq, int l
     if (!Q || !K || !V || !O || !dO || !lse || !dQ || !dK || !dV || !scratch || B < 1 || S < 1 || H < 1 || !ld_ok(ldq, H, d) || !ld_ok(ldk, H, d) ||
         !ld_ok(ldv, H, d) || !ld_ok(lddq, H, d) || !ld_ok(lddk, H, d) || !ld_ok(lddv, H, d) || !rate_ok(rate))
         return SELD_ERR_INVALID;
-    const int64_t grid = at_grid(B, S, H);
+    const int64_t grid = tile_grid(B, S, H);
     if (grid < 0) return SELD_ERR_UNSUPPORTED;
     const int nt = (int)(grid / B / H);
     const AttnDrop dr = at_drop(rate, seed, layer, step);
@@ -471,7 +357,7 @@ int seld_attn_fwd(const float* Q, const float* K, const float* V, int ldq, int l
 
 /* floats of caller scratch seld_attn_bwd takes: delta[b][h][q] = rowsum(dO * O) */
 int64_t seld_attn_bwd_scratch(int B, int S, int H, int d) {
-    if (!d_ok(d) || B < 1 || S < 1 || H < 1 || (int64_t)H * d > 0x7fffffff || at_grid(B, S, H) < 0) return -1;      // what seld_attn_bwd refuses
+    if (!d_ok(d) || B < 1 || S < 1 || H < 1 || (int64_t)H * d > 0x7fffffff || tile_grid(B, S, H) < 0) return -1;      // what seld_attn_bwd refuses
     return (int64_t)B * H * S;      // B * H fits an int here: no overflow
 }
 

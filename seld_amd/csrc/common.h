@@ -2,6 +2,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "../../include/seld_hip.h"
+
+// what an entry point returns behind its launches: the status of the last one (asynchronous: the kernels have not run yet)
+inline int ok() { return hipGetLastError() == hipSuccess ? SELD_OK : SELD_ERR_HIP; }
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 

@@ -215,7 +215,6 @@ __global__ __launch_bounds__(256) void head_permute_kernel(const float* __restri
     dst[e] = src[from];
 }
 
-inline int ok() { return hipGetLastError() == hipSuccess ? SELD_OK : SELD_ERR_HIP; }
 inline bool dw_sizes_ok(int B, int S, int C, int k) { return B >= 1 && S >= 1 && C >= 1 && k >= 1 && k <= DW_KMAX; }
 // workgroups of the tile kernel, or -1 where they do not fit a launch; every product in 64 bits and bounded before the next factor
 inline int64_t dw_grid(int B, int S, int C) {

@@ -380,7 +380,6 @@ __global__ __launch_bounds__(256) void rnn_merge_bwd_kernel(const T* __restrict_
 inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 inline unsigned nblk(int64_t n) { return (unsigned)((n + 255) / 256); }
-inline int ok() { return hipGetLastError() == hipSuccess ? SELD_OK : SELD_ERR_HIP; }
 
 }  // namespace
 

@@ -12,7 +12,7 @@
 // band B[c] = P'[c mod (S + 1)], and the product of a 32-query block with 64 band rows, read back along the skewed diagonal, is the
 // positional term of a 32 x 32 logit block.  Blocks below the diagonal take it from qv_i, blocks above from qv_{i+1}, the diagonal block both.
 //
-// Forward and the dQ kernel keep attention.hip's tile scheme (a lane owns one query, logits transposed, online softmax); the band product
+// Forward and the dQ kernel keep attention.hip's tile scheme (attn_tile.h: a lane owns one query, logits transposed, online softmax); the band product
 // Gt[band row][query] goes through a per-wave LDS tile [64][32] and is read back at row (key - query + 31): both the write (lanes = queries of
 // one row) and the skewed read (row stride 32, lane stride -31 .. the addresses of a half-wave are 32 different banks) are conflict-free.  The
 // backward of the shift is the same map run backwards: dS of a block is scattered to band rows and contracted with the band on the MFMA.
@@ -24,34 +24,18 @@
 //   relattn_fold     dQv[i] += the scratch row i - 1;  dP = the batches' partials added in batch order
 // Every output element is owned by one lane or folded in a fixed order: no atomics, two runs give the same bits.  No [B,H,S,S] (nor S x (S+1))
 // tensor exists; scratch is B H S (1 + 2 d) floats.  All products run on v_mfma_f32_32x32x2_f32 (exact fp32).
-#include "common.h"
-#include "../../include/seld_hip.h"
-#include <math.h>
+#include "attn_tile.h"
 
 namespace {
 
-#define RA_TILE 64
+using namespace attn_tile;
 
-__device__ __forceinline__ float xhalf(float v) { return __shfl_xor(v, 32, 64); }
 // orders a wave's own LDS writes and reads of its private tile (LDS operations of one wave complete in order; the compiler must not move them)
 __device__ __forceinline__ void wave_lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 
 // the lane index again, opaque to the optimiser: the per-register lane masks of the skewed reads are then compared where they are used (one
 // v_cmp each) instead of being hoisted out of the tile loop into 32 - 48 mask pairs that no scalar register file holds
 __device__ __forceinline__ int opaque(int v) { asm volatile("" : "+v"(v)); return v; }
-
-// rows r0 .. r0 + n - 1 of one head of a [B*S, ld] view (+ bias[col0 + dd], then * mul) -> LDS [n][D + 1]; rows outside [0, S) as zeros
-template <int D>
-__device__ __forceinline__ void load_rows(const float* __restrict__ src, int ld, size_t row0, int r0, int n, int S, int col0,
-                                          const float* __restrict__ bias, float mul, float* dst) {
-    for (int e = threadIdx.x; e < n * D; e += 128) {
-        const int rr = e / D, dd = e - rr * D;
-        const int r = r0 + rr;
-        float v = 0.f;
-        if (r >= 0 && r < S) v = (src[(row0 + r) * (size_t)ld + col0 + dd] + (bias ? bias[col0 + dd] : 0.f)) * mul;
-        dst[rr * (D + 1) + dd] = v;
-    }
-}
 
 // band rows c0 .. c0 + n - 1 of one head: B[c] = P[c] (c < S), 0 (c = S), P[c - S - 1] (S < c <= 2 S), 0 elsewhere -> LDS [n][D + 1]
 template <int D>
@@ -62,30 +46,6 @@ __device__ __forceinline__ void load_band(const float* __restrict__ P, int ldp, 
         const int64_t m = c < S ? c : c - S - 1;
         dst[t * (D + 1) + dd] = c >= 0 && c != S && c <= 2 * (int64_t)S ? P[(size_t)m * ldp + col0 + dd] : 0.f;
     }
-}
-
-// the lane's fragment of row `row` (valid: ok) of a view: f[s] = (row[2 s + hi] + bias[2 s + hi]) * mul
-template <int D>
-__device__ __forceinline__ void load_frag(const float* __restrict__ src, int ld, size_t row, int col0, bool ok, int hi, const float* __restrict__ bias,
-                                          float mul, float (&f)[D / 2]) {
-    const float* p = src + row * (size_t)ld + col0 + hi;
-#pragma unroll
-    for (int s = 0; s < D / 2; ++s) f[s] = ok ? (p[2 * s] + (bias ? bias[col0 + hi + 2 * s] : 0.f)) * mul : 0.f;
-}
-
-// out^T[dd][lane's row] accumulators -> out[row][col0 + dd] * mul
-template <int D>
-__device__ __forceinline__ void store_t(const f32x16 (&acc)[(D + 31) / 32], float* __restrict__ out, int ld, size_t row, int col0, bool ok, int hi,
-                                        float mul) {
-    if (!ok) return;
-    float* p = out + row * (size_t)ld + col0;
-#pragma unroll
-    for (int nb = 0; nb < (D + 31) / 32; ++nb)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int dd = nb * 32 + mfma_row(r, hi);
-            if (dd < D) p[dd] = acc[nb][r] * mul;
-        }
 }
 
 // Gt[band row][query] of the wave's 32 queries (rows qrow .. of an LDS tile, lane li's row given) against 64 band rows -> Gw [64][32]
@@ -132,7 +92,7 @@ __device__ __forceinline__ void add_positional_t(f32x16& s, const float* pb, con
 }
 
 template <int D>
-constexpr int ra_lds_qtile() { return ((2 * RA_TILE + 2 * RA_TILE + RA_TILE + 1) * (D + 1) + 2 * 64 * 32) * (int)sizeof(float); }
+constexpr int ra_lds_qtile() { return ((2 * ATTN_TILE + 2 * ATTN_TILE + ATTN_TILE + 1) * (D + 1) + 2 * 64 * 32) * (int)sizeof(float); }
 
 // Workgroup = 64 queries of one (batch, head); LDS: K, V tiles [64][D+1], band [128][D+1], qv rows I0w .. I0w + 64 [65][D+1], Gw [2][64][32]
 template <int D>
@@ -143,59 +103,34 @@ __global__ __launch_bounds__(128) void relattn_fwd_kernel(const float* __restric
     constexpr int LD = D + 1, NB = (D + 31) / 32;
     extern __shared__ float sm[];
     float* Ks = sm;
-    float* Vs = Ks + RA_TILE * LD;
-    float* Pb = Vs + RA_TILE * LD;
-    float* Qv = Pb + 2 * RA_TILE * LD;
-    float* Gs = Qv + (RA_TILE + 1) * LD;
+    float* Vs = Ks + ATTN_TILE * LD;
+    float* Pb = Vs + ATTN_TILE * LD;
+    float* Qv = Pb + 2 * ATTN_TILE * LD;
+    float* Gs = Qv + (ATTN_TILE + 1) * LD;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), li = lane & 31, hi = lane >> 5;
     const int qt = blockIdx.x % nqt, bh = blockIdx.x / nqt, h = bh % H, b = bh / H;
-    const int I0w = qt * RA_TILE, I0 = I0w + wave * 32, q = I0 + li;
+    const int I0w = qt * ATTN_TILE, I0 = I0w + wave * 32, q = I0 + li;
     const bool qok = q < S;
     const size_t row0 = (size_t)b * S;
     float* Gw = Gs + wave * 64 * 32;
     float qf[D / 2];
     load_frag<D>(Q, ldq, row0 + (qok ? q : 0), h * D, qok, hi, u, scale, qf);
-    load_rows<D>(Q, ldq, row0, I0w, RA_TILE + 1, S, h * D, vb, scale, Qv);
+    load_rows<D>(Q, ldq, row0, I0w, ATTN_TILE + 1, S, h * D, vb, scale, Qv);
     f32x16 o[NB];
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) o[nb] = zero16();
     float m = -INFINITY, l = 0.f;
-    for (int k0 = 0; k0 < S; k0 += RA_TILE) {
+    for (int k0 = 0; k0 < S; k0 += ATTN_TILE) {
         __syncthreads();
-        load_rows<D>(K, ldk, row0, k0, RA_TILE, S, h * D, nullptr, 1.f, Ks);
-        load_rows<D>(V, ldv, row0, k0, RA_TILE, S, h * D, nullptr, 1.f, Vs);
-        load_band<D>(P, ldp, h * D, S, (int64_t)S - 1 + k0 - I0w - 63, 2 * RA_TILE, Pb);
+        load_rows<D>(K, ldk, row0, k0, ATTN_TILE, S, h * D, 1.f, Ks);
+        load_rows<D>(V, ldv, row0, k0, ATTN_TILE, S, h * D, 1.f, Vs);
+        load_band<D>(P, ldp, h * D, S, (int64_t)S - 1 + k0 - I0w - 63, 2 * ATTN_TILE, Pb);
         __syncthreads();
         for (int kb = 0; kb < 2 && k0 + kb * 32 < S; ++kb) {
-            f32x16 s = zero16();
-            const float* kr = Ks + (kb * 32 + li) * LD + hi;
-#pragma unroll
-            for (int st = 0; st < D / 2; ++st) s = MFMA_F32_32x32x2(kr[2 * st], qf[st], s);
+            f32x16 s = logits<D>(Ks, kb * 32 + li, hi, qf);
             add_positional_t<D>(s, Pb + (kb * 32 - wave * 32 + 32) * LD, Qv, Gw, I0, k0 + kb * 32, wave, li, hi);
-            float mx = m;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                if (k0 + kb * 32 + mfma_row(r, hi) >= S) s[r] = -INFINITY;      // the edge tile's keys past S
-                mx = fmaxf(mx, s[r]);
-            }
-            mx = fmaxf(mx, xhalf(mx));      // finite: the block's first key is < S
-            const float alpha = __expf(m - mx);
-            float ps = 0.f;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { s[r] = __expf(s[r] - mx); ps += s[r]; }
-            ps += xhalf(ps);
-            l = l * alpha + ps;
-            m = mx;
-#pragma unroll
-            for (int nb = 0; nb < NB; ++nb) {
-                const int dd = nb * 32 + li;
-                const bool dok = dd < D;
-                const float* vr = Vs + kb * 32 * LD + (dok ? dd : 0);
-#pragma unroll
-                for (int r = 0; r < 16; ++r) o[nb][r] *= alpha;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) o[nb] = MFMA_F32_32x32x2(dok ? vr[mfma_row(r, hi) * LD] : 0.f, s[r], o[nb]);
-            }
+            const float alpha = softmax_step(s, k0 + kb * 32, S, hi, m, l);
+            accum_t<D, true>(o, Vs + kb * 32 * LD, s, li, hi, alpha);
         }
     }
     store_t<D>(o, O, H * D, row0 + (qok ? q : 0), h * D, qok, hi, 1.f / l);
@@ -243,54 +178,41 @@ __global__ __launch_bounds__(128) void relattn_bwd_dq_kernel(const float* __rest
     constexpr int LD = D + 1, NB = (D + 31) / 32;
     extern __shared__ float sm[];
     float* Ks = sm;
-    float* Vs = Ks + RA_TILE * LD;
-    float* Pb = Vs + RA_TILE * LD;
-    float* Qv = Pb + 2 * RA_TILE * LD;
-    float* Gs = Qv + (RA_TILE + 1) * LD;
+    float* Vs = Ks + ATTN_TILE * LD;
+    float* Pb = Vs + ATTN_TILE * LD;
+    float* Qv = Pb + 2 * ATTN_TILE * LD;
+    float* Gs = Qv + (ATTN_TILE + 1) * LD;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), li = lane & 31, hi = lane >> 5;
     const int qt = blockIdx.x % nqt, bh = blockIdx.x / nqt, h = bh % H, b = bh / H;
-    const int I0w = qt * RA_TILE, I0 = I0w + wave * 32, q = I0 + li;
+    const int I0w = qt * ATTN_TILE, I0 = I0w + wave * 32, q = I0 + li;
     const bool qok = q < S;
     const size_t row0 = (size_t)b * S, row = row0 + (qok ? q : 0);
     float* Gw = Gs + wave * 64 * 32;
     float qf[D / 2], dof[D / 2];
     load_frag<D>(Q, ldq, row, h * D, qok, hi, u, scale, qf);
     load_frag<D>(dO, H * D, row, h * D, qok, hi, nullptr, 1.f, dof);
-    load_rows<D>(Q, ldq, row0, I0w, RA_TILE + 1, S, h * D, vb, scale, Qv);
-    float dl = 0.f;
-    {
-        const float* op = O + row * (size_t)(H * D) + h * D + hi;
-#pragma unroll
-        for (int s = 0; s < D / 2; ++s) dl += qok ? dof[s] * op[2 * s] : 0.f;
-    }
-    dl += xhalf(dl);
+    load_rows<D>(Q, ldq, row0, I0w, ATTN_TILE + 1, S, h * D, vb, scale, Qv);
+    const float dl = delta_rowsum<D>(dof, O, H * D, row, h * D, qok, hi);
     if (qok && hi == 0) delta[(size_t)bh * S + q] = dl;
     const float lq = qok ? lse[(size_t)bh * S + q] : INFINITY;      // a row past S: p = exp(-inf) = 0
     f32x16 dqu[NB], dqa[NB], dqb[NB];
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) { dqu[nb] = zero16(); dqa[nb] = zero16(); dqb[nb] = zero16(); }
-    for (int k0 = 0; k0 < S; k0 += RA_TILE) {
+    for (int k0 = 0; k0 < S; k0 += ATTN_TILE) {
         __syncthreads();
-        load_rows<D>(K, ldk, row0, k0, RA_TILE, S, h * D, nullptr, 1.f, Ks);
-        load_rows<D>(V, ldv, row0, k0, RA_TILE, S, h * D, nullptr, 1.f, Vs);
-        load_band<D>(P, ldp, h * D, S, (int64_t)S - 1 + k0 - I0w - 63, 2 * RA_TILE, Pb);
+        load_rows<D>(K, ldk, row0, k0, ATTN_TILE, S, h * D, 1.f, Ks);
+        load_rows<D>(V, ldv, row0, k0, ATTN_TILE, S, h * D, 1.f, Vs);
+        load_band<D>(P, ldp, h * D, S, (int64_t)S - 1 + k0 - I0w - 63, 2 * ATTN_TILE, Pb);
         __syncthreads();
         for (int kb = 0; kb < 2 && k0 + kb * 32 < S; ++kb) {
             const int J0 = k0 + kb * 32;
             const float* pb = Pb + (kb * 32 - wave * 32 + 32) * LD;
-            f32x16 s = zero16(), dp = zero16();
-            const float* kr = Ks + (kb * 32 + li) * LD + hi;
-            const float* vr = Vs + (kb * 32 + li) * LD + hi;
-#pragma unroll
-            for (int st = 0; st < D / 2; ++st) s = MFMA_F32_32x32x2(kr[2 * st], qf[st], s);
+            f32x16 s = logits<D>(Ks, kb * 32 + li, hi, qf);
             add_positional_t<D>(s, pb, Qv, Gw, I0, J0, wave, li, hi);
-#pragma unroll
-            for (int st = 0; st < D / 2; ++st) dp = MFMA_F32_32x32x2(vr[2 * st], dof[st], dp);
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float p = J0 + mfma_row(r, hi) < S ? __expf(s[r] - lq) : 0.f;
-                s[r] = p * (dp[r] - dl);
-            }
+            const f32x16 dp = logits<D>(Vs, kb * 32 + li, hi, dof);
+            prob_ds_q(s, dp, J0, S, hi, lq, dl);
+            // attn_tile.h's accum_t, spelled out: through the helper the d >= 32 instantiations of this kernel and of relattn_bwd_dp_kernel pair one
+            // more couple of LDS reads into a ds_read2_b32 — the same words, but not the parent's instruction counts
 #pragma unroll
             for (int nb = 0; nb < NB; ++nb) {
                 const int dd = nb * 32 + li;
@@ -309,7 +231,7 @@ __global__ __launch_bounds__(128) void relattn_bwd_dq_kernel(const float* __rest
 }
 
 template <int D>
-constexpr int ra_lds_ktile() { return ((RA_TILE + RA_TILE + 1 + RA_TILE + 2 * RA_TILE) * (D + 1) + 2 * RA_TILE + 2 * 32 * 64) * (int)sizeof(float); }
+constexpr int ra_lds_ktile() { return ((ATTN_TILE + ATTN_TILE + 1 + ATTN_TILE + 2 * ATTN_TILE) * (D + 1) + 2 * ATTN_TILE + 2 * 32 * 64) * (int)sizeof(float); }
 
 // dK and dV: a workgroup owns 64 keys of one (batch, head) (32 per wave, K and V fragments in registers) and sweeps the query tiles.
 // LDS: qu [64][D+1], qv rows q0 .. q0 + 64 [65][D+1], dO [64][D+1], band [128][D+1], lse / delta [64] each, Gw [2][32][64]
@@ -323,15 +245,15 @@ __global__ __launch_bounds__(128) void relattn_bwd_dkv_kernel(const float* __res
     constexpr int LD = D + 1, NB = (D + 31) / 32;
     extern __shared__ float sm[];
     float* Qu = sm;
-    float* Qv = Qu + RA_TILE * LD;
-    float* Gd = Qv + (RA_TILE + 1) * LD;
-    float* Pb = Gd + RA_TILE * LD;
-    float* ls = Pb + 2 * RA_TILE * LD;
-    float* ds_ = ls + RA_TILE;
-    float* Gs = ds_ + RA_TILE;
+    float* Qv = Qu + ATTN_TILE * LD;
+    float* Gd = Qv + (ATTN_TILE + 1) * LD;
+    float* Pb = Gd + ATTN_TILE * LD;
+    float* ls = Pb + 2 * ATTN_TILE * LD;
+    float* ds_ = ls + ATTN_TILE;
+    float* Gs = ds_ + ATTN_TILE;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), li = lane & 31, hi = lane >> 5;
     const int kt = blockIdx.x % nkt, bh = blockIdx.x / nkt, h = bh % H, b = bh / H;
-    const int J0w = kt * RA_TILE, J0 = J0w + wave * 32, key = J0 + li;
+    const int J0w = kt * ATTN_TILE, J0 = J0w + wave * 32, key = J0 + li;
     const bool kok = key < S;
     const size_t row0 = (size_t)b * S, row = row0 + (kok ? key : 0);
     float* Gw = Gs + wave * 32 * 64;
@@ -341,21 +263,19 @@ __global__ __launch_bounds__(128) void relattn_bwd_dkv_kernel(const float* __res
     f32x16 dk[NB], dv[NB];
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) { dk[nb] = zero16(); dv[nb] = zero16(); }
-    for (int q0 = 0; q0 < S; q0 += RA_TILE) {
+    for (int q0 = 0; q0 < S; q0 += ATTN_TILE) {
         __syncthreads();
-        load_rows<D>(Q, ldq, row0, q0, RA_TILE, S, h * D, u, scale, Qu);
-        load_rows<D>(Q, ldq, row0, q0, RA_TILE + 1, S, h * D, vb, scale, Qv);
-        load_rows<D>(dO, H * D, row0, q0, RA_TILE, S, h * D, nullptr, 1.f, Gd);
-        load_band<D>(P, ldp, h * D, S, (int64_t)S - 1 + J0w - q0 - 63, 2 * RA_TILE, Pb);
-        if (threadIdx.x < RA_TILE) {
-            const int q = q0 + threadIdx.x;
-            ls[threadIdx.x] = q < S ? lse[(size_t)bh * S + q] : INFINITY;      // a row past S: p = exp(-inf) = 0
-            ds_[threadIdx.x] = q < S ? delta[(size_t)bh * S + q] : 0.f;
-        }
+        load_rows<D>(Q, ldq, row0, q0, ATTN_TILE, S, h * D, u, scale, Qu);
+        load_rows<D>(Q, ldq, row0, q0, ATTN_TILE + 1, S, h * D, vb, scale, Qv);
+        load_rows<D>(dO, H * D, row0, q0, ATTN_TILE, S, h * D, 1.f, Gd);
+        load_band<D>(P, ldp, h * D, S, (int64_t)S - 1 + J0w - q0 - 63, 2 * ATTN_TILE, Pb);
+        load_lse_delta(lse, delta, (size_t)bh * S, q0, ATTN_TILE, S, ls, ds_);
         __syncthreads();
         for (int qb = 0; qb < 2 && q0 + qb * 32 < S; ++qb) {
             const int I0 = q0 + qb * 32;
             const float* pb = Pb + (wave * 32 - qb * 32 + 32) * LD;
+            // from here to the accumulations the parent's own text, not attn_tile.h's logits / accum_t: through the helpers this kernel ran 11 %
+            // slower at d = 48 (695 -> 774 us)
             f32x16 s = zero16(), dp = zero16();
             const float* qr = Qu + (qb * 32 + li) * LD + hi;
             const float* gr = Gd + (qb * 32 + li) * LD + hi;
@@ -456,7 +376,7 @@ __global__ __launch_bounds__(128) void relattn_bwd_dp_kernel(const float* __rest
     float* Gs = ds_ + 32;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), li = lane & 31, hi = lane >> 5;
     const int mt = blockIdx.x % nmt, bh = blockIdx.x / nmt, h = bh % H, b = bh / H;
-    const int M0w = mt * RA_TILE, m = M0w + wave * 32 + li;
+    const int M0w = mt * ATTN_TILE, m = M0w + wave * 32 + li;
     const bool mok = m < S;
     const size_t row0 = (size_t)b * S;
     float* Gw = Gs + wave * 32 * 64;
@@ -471,27 +391,16 @@ __global__ __launch_bounds__(128) void relattn_bwd_dp_kernel(const float* __rest
         for (int I0 = 0; I0 < S; I0 += 32) {
             if (I0 + d0 > S - 1 || I0 + 31 + d0 + 63 < 0) continue;      // the stripe's keys of this block lie outside [0, S)
             __syncthreads();
-            load_rows<D>(K, ldk, row0, (int)(I0 + d0), 96, S, h * D, nullptr, 1.f, Kb);
-            load_rows<D>(V, ldv, row0, (int)(I0 + d0), 96, S, h * D, nullptr, 1.f, Vb);
+            load_rows<D>(K, ldk, row0, (int)(I0 + d0), 96, S, h * D, 1.f, Kb);
+            load_rows<D>(V, ldv, row0, (int)(I0 + d0), 96, S, h * D, 1.f, Vb);
             load_rows<D>(Q, ldq, row0, I0, 32, S, h * D, u, scale, Qu);
             load_rows<D>(Q, ldq, row0, I0, 33, S, h * D, vb, scale, Qv);
-            load_rows<D>(dO, H * D, row0, I0, 32, S, h * D, nullptr, 1.f, Gd);
-            if (threadIdx.x < 32) {
-                const int q = I0 + threadIdx.x;
-                ls[threadIdx.x] = q < S ? lse[(size_t)bh * S + q] : INFINITY;
-                ds_[threadIdx.x] = q < S ? delta[(size_t)bh * S + q] : 0.f;
-            }
+            load_rows<D>(dO, H * D, row0, I0, 32, S, h * D, 1.f, Gd);
+            load_lse_delta(lse, delta, (size_t)bh * S, I0, 32, S, ls, ds_);
             __syncthreads();
             f32x16 s = stripe_product<D>(Qu + li * LD + hi, Kb + wave * 32 * LD, Gw, li, hi);
             f32x16 dp = stripe_product<D>(Gd + li * LD + hi, Vb + wave * 32 * LD, Gw, li, hi);
-            {
-                f32x16 t = zero16();
-                const float* ar = Qv + (li + up) * LD + hi;
-#pragma unroll
-                for (int st = 0; st < D / 2; ++st) t = MFMA_F32_32x32x2(ar[2 * st], pf[st], t);
-#pragma unroll
-                for (int r = 0; r < 16; ++r) s[r] += t[r];
-            }
+            s += logits<D>(Qv, li + up, hi, pf);
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int ii = mfma_row(r, hi);
@@ -499,6 +408,7 @@ __global__ __launch_bounds__(128) void relattn_bwd_dp_kernel(const float* __rest
                 const float p = mok && j >= 0 && j < S ? __expf(s[r] - ls[ii]) : 0.f;      // (a query past S: lse = inf)
                 s[r] = p * (dp[r] - ds_[ii]);
             }
+            // accum_t spelled out: see relattn_bwd_dq_kernel
 #pragma unroll
             for (int nb = 0; nb < NB; ++nb) {
                 const int dd = nb * 32 + li;
@@ -552,34 +462,17 @@ __global__ __launch_bounds__(256) void glu_bwd_kernel(const float* __restrict__ 
     du[r * lddu + C + c] = dy[e] * a * (ex * rr * rr);
 }
 
-inline int ok() { return hipGetLastError() == hipSuccess ? SELD_OK : SELD_ERR_HIP; }
-inline bool d_ok(int d) { return d >= 8 && d <= 64 && d % 8 == 0; }
-inline bool ld_ok(int ld, int H, int d) { return (int64_t)ld >= (int64_t)H * d; }
-// workgroups B * H * ceil(S / 64), or -1 where they do not fit a launch (every product in 64 bits and bounded before the next factor) or where
-// a band index 2 S leaves an int
-inline int64_t ra_grid(int B, int S, int H) {
-    const int64_t bh = (int64_t)B * H, nt = ((int64_t)S + RA_TILE - 1) / RA_TILE;
-    return S > 0x3fffff00 || bh > 0x7fffffff || bh * nt > 0x7fffffff ? -1 : bh * nt;
-}
+// attn_tile.h's grid, or -1 also where a band index 2 S leaves an int
+inline int64_t ra_grid(int B, int S, int H) { return S > 0x3fffff00 ? -1 : tile_grid(B, S, H); }
 
 // launch `kern`<D_> with `ldsfn`<D_>() bytes of dynamic LDS
-#define RA_LAUNCH(kern, ldsfn, D_, grid, st, ...)                                                                            \
+#define RA_LAUNCH(D_, kern, ldsfn, grid, st, ...)                                                                            \
     {                                                                                                                        \
         if (ldsfn<D_>() > 65536)                                                                                             \
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern<D_>), hipFuncAttributeMaxDynamicSharedMemorySize, ldsfn<D_>()); \
         hipLaunchKernelGGL((kern<D_>), dim3(grid), dim3(128), ldsfn<D_>(), st, __VA_ARGS__);                                 \
     }
-#define RA_DISPATCH(kern, ldsfn, d, grid, st, ...)                                  \
-    switch (d) {                                                                    \
-        case 8: RA_LAUNCH(kern, ldsfn, 8, grid, st, __VA_ARGS__) break;             \
-        case 16: RA_LAUNCH(kern, ldsfn, 16, grid, st, __VA_ARGS__) break;           \
-        case 24: RA_LAUNCH(kern, ldsfn, 24, grid, st, __VA_ARGS__) break;           \
-        case 32: RA_LAUNCH(kern, ldsfn, 32, grid, st, __VA_ARGS__) break;           \
-        case 40: RA_LAUNCH(kern, ldsfn, 40, grid, st, __VA_ARGS__) break;           \
-        case 48: RA_LAUNCH(kern, ldsfn, 48, grid, st, __VA_ARGS__) break;           \
-        case 56: RA_LAUNCH(kern, ldsfn, 56, grid, st, __VA_ARGS__) break;           \
-        default: RA_LAUNCH(kern, ldsfn, 64, grid, st, __VA_ARGS__) break;           \
-    }
+#define RA_DISPATCH(kern, ldsfn, d, grid, st, ...) ATTN_DISPATCH_D(d, RA_LAUNCH, kern, ldsfn, grid, st, __VA_ARGS__)
 
 }  // namespace
 

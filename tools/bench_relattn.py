@@ -52,7 +52,7 @@ def main():
         q, k, v, do = (torch.randn(R, HD, generator=g).cuda() for _ in range(4))
         P, u, vb = torch.randn(S, HD, generator=g).cuda(), torch.randn(HD, generator=g).cuda(), torch.randn(HD, generator=g).cuda()
         o, lse = torch.empty(R, HD).cuda(), torch.empty(B * H * S).cuda()
-        dqu, dqv, dk, dv, dP = (torch.empty(R, HD).cuda() for _ in range(4)) + (torch.empty(S, HD).cuda(),)
+        dqu, dqv, dk, dv, dP = tuple(torch.empty(R, HD).cuda() for _ in range(4)) + (torch.empty(S, HD).cuda(),)
         s_rel = torch.empty(int(lib.seld_relattn_bwd_scratch(B, S, H, d))).cuda()
         s_att = torch.empty(int(lib.seld_attn_bwd_scratch(B, S, H, d))).cuda()
 
