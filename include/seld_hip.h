@@ -133,8 +133,8 @@ int seld_sync(seld_ctx* ctx);
  * block's forward whenever its pre-BN tensor is not stored (conv_pool_sb.hip).  "conv1_pool_fused" / "conv1_gram" (default 1): first block's pooling inside the conv
  * epilogue / its kernel gradient from the patch Gram matrix.  "dropout_seed" / "dropout_step" (values): the key of the heads' dropout
  * draws and the step counter of the next training forward (seld_arch.sed_dropout / doa_dropout; INTEGRATION.md section 6 lists every key).
- * EVERY key is per context: the kernel choices the launchers read from library-wide variables ("bwd_four_products", "gru_var" 0..255,
- * "conv64_dbuf", "tn_tile_blocks", "tn_lds_floor", "gram_bg_blocks", "bf16_single") are stored in the context and copied into those
+ * EVERY key is per context: the kernel choices the launchers read from library-wide variables ("bwd_four_products",
+ * "conv64_dbuf", "tn_tile_blocks", "gram_bg_blocks", "bf16_single") are stored in the context and copied into those
  * variables at the start of each forward / backward pass, so a six-product context and a four-product context coexist in one process
  * (calls on one context are not thread-safe; two contexts driven from two threads at once are not supported for differing choices). */
 int seld_set_option(seld_ctx* ctx, const char* key, int value);
@@ -692,10 +692,6 @@ int seld_k_rn_bn(const float* z, const float* gamma, const float* beta, const fl
                  int64_t npix, int C, int relu);
 int seld_k_rn_bn_bwd(const float* z, const float* dy, const float* mask, const float* gamma, float* dz, float* dgamma, float* dbeta,
                      int64_t npix, int C);
-/* Diagnostic builds only (make CXXFLAGS+=-DGRU_TIMING; tools/tune_gru.py): shader-cycle sums per phase of the recurrence kernels'
- * last launch, wave 0 of every workgroup: cycles[blocks][4] = forward {h read + mat-vec, gate tail, barrier, chunk commit},
- * BPTT {gate gradients, barrier, coefficients + mat-vec + fold, -}.  SELD_ERR_UNSUPPORTED in the normal build. */
-int seld_k_gru_timing(int which, unsigned long long* cycles, int blocks);
 /* hipGetDeviceProperties of `device`: compute units, engine clock (kHz), memory clock (kHz), memory bus width (bits) —
  * bench.py prints the peaks they imply next to the constants its roofline fractions use. */
 int seld_device_clocks(int device, int* compute_units, int* clock_khz, int* mem_clock_khz, int* mem_bus_bits);

@@ -168,7 +168,6 @@ SIGNATURES = {
     "seld_debug_relu_output": (_I, [_P, _I, _I, _P, _L, C.POINTER(C.c_int64)]),
     "seld_debug_set_routing": (_I, [_P, _I, _L, _P, _P]),
     "seld_debug_set_relu_gates": (_I, [_P, _I, _I, _L, _P, _P]),
-    "seld_k_gru_timing": (_I, [_I, _P, _I]),
     "seld_m_conv_out": (_I, [_I, _I]),
     "seld_m_im2col": (_I, [_P, _P] + [_I] * 8 + [_P]),
     "seld_m_col2im": (_I, [_P, _P] + [_I] * 9 + [_P]),

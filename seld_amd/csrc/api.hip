@@ -81,10 +81,8 @@ bool rn_c1_direct(const RnBlock& R) {
 void apply_kernel_choices(const seld_ctx* c) {
     g_mfma_one = c->bf16_single;
     g_bwd_four = c->bwd_four_products;
-    g_gru_var = c->gru_var;
     g_conv64_dbuf = c->conv64_dbuf;
     g_tn_tile_blocks = c->tn_tile_blocks;
-    g_tn_lds_floor_kb = c->tn_lds_floor;
     g_gram_bg_blocks = c->gram_bg_blocks;
     g_xc_xcd_map = c->xc_xcd_map;
     g_xc_w16 = c->xc_w16;
@@ -504,7 +502,6 @@ int seld_set_option(seld_ctx* c, const char* key, int value) {
     if (!strcmp(key, "conv1_pool_fused")) { c->conv1_pool_fused = value != 0; return SELD_OK; }
     if (!strcmp(key, "conv1_gram")) { c->conv1_gram = value != 0; return SELD_OK; }
     if (!strcmp(key, "gru_wgrad_batch")) { c->gru_wgrad_batch = value != 0; return SELD_OK; }
-    if (!strcmp(key, "gru_din_first")) { c->gru_din_first = value != 0; return SELD_OK; }
     if (!strcmp(key, "conv2_pre_fused")) { c->conv2_pre_fused = value != 0; return SELD_OK; }
     if (!strcmp(key, "conv3_pre_fused")) { c->conv3_pre_fused = value != 0; return SELD_OK; }
     if (!strcmp(key, "gram_parts") && (value == 1 || value == 2)) { c->gram_parts = value; return SELD_OK; }
@@ -519,11 +516,6 @@ int seld_set_option(seld_ctx* c, const char* key, int value) {
     // per-context kernel choices (apply_kernel_choices copies them into the launchers' variables at the start of each pass)
     if (!strcmp(key, "bwd_four_products")) { c->bwd_four_products = value != 0; return SELD_OK; }
     if (!strcmp(key, "tn_tile_blocks") && value >= 64 && value <= 4096) { c->tn_tile_blocks = value; return SELD_OK; }     // gemm_tn_sb.hip
-    if (!strcmp(key, "gru_var")) {      // gru.hip: bit 0 forward VAR 1, bit 1 backward VAR 1, bit 3 falling priority, bits 4.. experimental bodies
-        if (value < 0 || value > 255) return fail(c, SELD_ERR_INVALID, "gru_var: 0..255");
-        c->gru_var = value; return SELD_OK;
-    }
-    if (!strcmp(key, "tn_lds_floor") && value >= 0 && value <= 100) { c->tn_lds_floor = value; return SELD_OK; }   // experiment: gemm_tn_sb.hip
     if (!strcmp(key, "conv64_dbuf")) { c->conv64_dbuf = value != 0; return SELD_OK; }     // conv_sb.hip
     if (!strcmp(key, "conv_wgrad_side")) { c->conv_wgrad_side = value != 0; return SELD_OK; }
     if (!strcmp(key, "dgrad_r8")) { c->dgrad_r8 = value != 0; return SELD_OK; }

@@ -184,9 +184,8 @@ static int backward_gru(seld_ctx* c, const float* dfeat, const float** din) {
             launch_gru_bwd(st, dout, G.h[0], G.h[1], G.sv[0], G.sv[1], c->params + G.u_off[0], c->params + G.u_off[1], c->dgx[i][0],
                            c->dgx[i][1], c->dgh[i][0], c->dgh[i][1], B, S);
         }
-        // the input gradient the next BPTT (or the conv backward) waits for: main stream.  Option "gru_din_first" (experiment, default 0) enqueues it BEFORE the
-        // side stream is released for this layer's weight gradients, so that they do not share the card with it: same box 2.651 / 2.650 ms per step with,
-        // 2.639 / 2.635 without — what the product gains the weight gradients lose under the next BPTT
+        // the input gradient the next BPTT (or the conv backward) waits for: main stream, enqueued AFTER the side stream is released for this layer's weight
+        // gradients (ahead of the release: same box 2.651 / 2.650 ms per step against 2.639 / 2.635 — what the product gains the weight gradients lose under the next BPTT)
         auto din_gemm = [&]() {
         {
             PROF2(c, "gru_bwd_gemms");   // main stream: the input gradient the next BPTT waits for
@@ -210,7 +209,6 @@ static int backward_gru(seld_ctx* c, const float* dfeat, const float** din) {
                                    G.din, G.in_feat, rows, G.in_feat, 384, 1, 0, 0);
         }
         };
-        if (c->gru_din_first) din_gemm();
         // weight gradients of this layer: side stream (they overlap with the next layer's BPTT, which uses 2B of the 256 CUs)
         fork_side(c);
         if (i == (int)c->gru.size() - 1 && heads_lin(c)) heads_lin_side(c, rows);
@@ -232,7 +230,7 @@ static int backward_gru(seld_ctx* c, const float* dfeat, const float** din) {
                 wgrad_dense(c, c->side, c->tn_slab_side, tj.A[j], tj.lda[j], tj.B[j], 384, rows, j & 1 ? 128 : G.in_feat, 384,
                             tj.out_w[j] - c->grads, tj.out_b[j] - c->grads, j & 1 ? S : 0, tj.shift[j]);
         hipEventRecord(c->ev_bucket[(int)c->gru.size() - 1 - i], c->side);   // this layer's (and, for the last layer, the heads') gradients are final
-        if (!c->gru_din_first) din_gemm();
+        din_gemm();
         dout = G.din;
     }
     *din = dout;

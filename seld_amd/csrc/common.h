@@ -27,12 +27,13 @@ __device__ __forceinline__ f32x16 zero16() {
 // a quarter of the kernel (tools/tune_conv64.py: the same bytes as dwordx4 stores cost an eighth of that).  A 4 x 4 transpose inside
 // each quad of lanes (two DPP butterfly stages) turns registers 4q..4q+3 (pixels 8q + 4hi + 0..3, channel li) into pixel 8q + 4hi +
 // (li & 3), channels 4 (li >> 2) .. + 3: one float4.
-__device__ __forceinline__ float dpp_quad_xor1(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1 /*quad_perm [1,0,3,2]*/, 0xF, 0xF, true));
+// one DPP move (VALU, no LDS round trip): lane l receives v of the lane that CTRL names, all rows and banks enabled
+template <int CTRL>
+__device__ __forceinline__ float dpp(float v) {
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
 }
-__device__ __forceinline__ float dpp_quad_xor2(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E /*quad_perm [2,3,0,1]*/, 0xF, 0xF, true));
-}
+__device__ __forceinline__ float dpp_quad_xor1(float v) { return dpp<0xB1 /*quad_perm [1,0,3,2]*/>(v); }
+__device__ __forceinline__ float dpp_quad_xor2(float v) { return dpp<0x4E /*quad_perm [2,3,0,1]*/>(v); }
 __device__ __forceinline__ float4 quad_transpose4(float x0, float x1, float x2, float x3, int lane) {
     const bool b0 = lane & 1, b1 = lane & 2;
     float r;
@@ -43,6 +44,12 @@ __device__ __forceinline__ float4 quad_transpose4(float x0, float x1, float x2, 
     return make_float4(x0, x1, x2, x3);
 }
 
+// ---- primitives of the recurrence kernels (gru.hip, lstm.hip) ----
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+// v_pk_fma_f32: two fp32 FMAs per lane per instruction.  The scalar v_fma_f32 issues a wave64 in 4 cycles
+// on gfx950, so the mat-vec of a recurrence (the step's longest phase) runs twice as fast packed.
+__device__ __forceinline__ f32x2 pk_fma(f32x2 a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(a, b, c); }
+constexpr float L2E = 1.4426950408889634f;      // log2(e): exp(x) = exp2(L2E x), folded into fma operands ahead of v_exp_f32
 
 // ---- Philox4x32-10 (Salmon et al., SC11; Random123): the counter-based generator behind every dropout mask of the library — a pure function
 // of (counter, key), so a backward pass recomputes a mask instead of storing it.  Users: loss_adam.hip::dropout_kernel, module_ops.hip
@@ -143,8 +150,6 @@ int launch_flip_weights(hipStream_t st, const float* w, float* wt);
 int launch_split_weights(hipStream_t st, const float* w, unsigned short* wsp);
 // up to 8 tensors in one launch; flip[i] != 0: the planes of the flipped (input-gradient) weights, from the unflipped tensor
 int launch_split_weights_batch(hipStream_t st, int n, const float* const* w, unsigned short* const* dst, const int* flip);
-extern int g_tn_lds_floor_kb;   // gemm_tn_sb.hip: extra dynamic LDS (KB) of the GRU weight-gradient batch launches (0 = none)
-extern int g_gru_var;       // gru.hip: step-body variants (bit 0 forward, bit 1 backward)
 extern int g_conv64_dbuf;   // conv_sb.hip: 1 = double-buffered-weights kernel (default)
 // two-plane split of two floats for the four-product form: hi = the truncated upper 16 bits, mid = the residual ROUNDED to bf16 (half up on the
 // magnitude: one integer add) — with a truncated mid the dropped remainder has the sign of x for every element, and the products it would have
@@ -352,15 +357,10 @@ int launch_colsum(hipStream_t st, const float* X, int ld, float* slab, int* nsla
 int launch_gru_fwd(hipStream_t st, const float* gx_f, const float* gx_b, const float* U_f, const float* U_b,
                    const float* brec_f, const float* brec_b, float* h_f, float* h_b, float* sv_f, float* sv_b,
                    int B, int S, const float* rm_f = nullptr, const float* rm_b = nullptr, float* hm_f = nullptr, float* hm_b = nullptr);
-// gru_df.hip: the same recurrences without a workgroup barrier between steps (two wave groups, LDS step counters); option "gru_var" bit 4 / 5
-int launch_gru_fwd_df(hipStream_t st, const float* gx_f, const float* gx_b, const float* U_f, const float* U_b,
-                      const float* brec_f, const float* brec_b, float* h_f, float* h_b, float* sv_f, float* sv_b, int B, int S);
-int gru_df_trace_read(int which, unsigned long long* out);
 int launch_gru_bwd(hipStream_t st, const float* dout, const float* h_f, const float* h_b, const float* sv_f,
                    const float* sv_b, const float* U_f, const float* U_b, float* dgx_f, float* dgx_b,
                    float* dgh_f, float* dgh_b, int B, int S, const float* rm_f = nullptr, const float* rm_b = nullptr, const float* hm_f = nullptr,
                    const float* hm_b = nullptr);
-int gru_timing_read(int which, unsigned long long* out, int blocks);
 // the same kernels for reference modules.RNN_block (seld_rnn_gru_*): one direction alone; output gradients per direction, used as given
 int launch_gru_fwd_uni(hipStream_t st, const float* gx, const float* U, const float* brec, float* h, float* sv, int B, int S);
 int launch_gru_bwd_dh(hipStream_t st, const float* dh_f, const float* dh_b, const float* h_f, const float* h_b, const float* sv_f, const float* sv_b,

@@ -36,7 +36,6 @@ int seld_k_set_option(const char* key, int value) {
     if (!key) return SELD_ERR_INVALID;
     if (!strcmp(key, "conv64_split_bf16")) { g_conv64_split_bf16 = value != 0; return SELD_OK; }
     if (!strcmp(key, "conv1_split_bf16")) { g_conv1_split_bf16 = value != 0; return SELD_OK; }
-    if (!strcmp(key, "gru_var")) { g_gru_var = value; return SELD_OK; }
     if (!strcmp(key, "conv64_dbuf")) { g_conv64_dbuf = value != 0; return SELD_OK; }
     if (!strcmp(key, "gemm_tn_split_bf16")) { g_gemm_tn_sb = value != 0; return SELD_OK; }
     if (!strcmp(key, "bf16_single")) { g_mfma_one = value != 0; return SELD_OK; }
@@ -527,12 +526,6 @@ int seld_k_rn_bn_bwd(const float* z, const float* dy, const float* mask, const f
     launch_rn_bn_bwd_finalize(0, part, nbx, (double)npix, dgamma, dbeta, coef, C);
     launch_rn_bn_bwd_dz(0, z, dy, mask, coef, dz, npix, C);
     return done();
-}
-
-int seld_k_gru_timing(int which, unsigned long long* cycles, int blocks) {
-    if (!cycles) return SELD_ERR_INVALID;
-    const int rc = gru_timing_read(which, cycles, blocks);
-    return rc == 0 ? SELD_OK : (rc == -2 ? SELD_ERR_UNSUPPORTED : SELD_ERR_INVALID);
 }
 
 int seld_device_clocks(int device, int* compute_units, int* clock_khz, int* mem_clock_khz, int* mem_bus_bits) {

@@ -18,14 +18,8 @@
 
 namespace {
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ f32x2 pk_fma(f32x2 a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(a, b, c); }      // v_pk_fma_f32
-template <int CTRL>
-__device__ __forceinline__ float dpp(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
-}
-constexpr float L2E = 1.4426950408889634f;
-// branch-free, saturating: exp2 -> inf gives rcp -> 0 (abs error ~1e-7, as gru.hip's)
+// f32x2, pk_fma, dpp<CTRL> and L2E: common.h, shared with gru.hip
+// branch-free, saturating: exp2 -> inf gives rcp -> 0 (abs error ~1e-7, the form gru.hip's step uses)
 __device__ __forceinline__ float tanh_(float x) { return fmaf(-2.f, __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(x * (2.f * L2E))), 1.f); }
 
 #define LSTM_U 128
@@ -73,7 +67,7 @@ __global__ __launch_bounds__(512) void lstm_fwd_kernel(const float* __restrict__
     float c_own = 0.f, pre_n = 0.f;
     const unsigned h_off = 4u * j, sv_off = 4u * tid;
     const int nchunks = (S + LSTMF_CH - 1) / LSTMF_CH;
-    float4 stg0, stg1, stg2, stg3;      // named registers: see gru_fwd_kernel
+    float4 stg0, stg1, stg2, stg3;      // named registers, not an array: see gru_fwd_kernel's staged chunk
     // chunk c = processing steps [c*CH, c*CH+n); its rows are contiguous in memory from row tlo
 #define LSTMF_CHUNK_ROWS(c, n, tlo)                    \
     {                                                  \
@@ -104,7 +98,7 @@ __global__ __launch_bounds__(512) void lstm_fwd_kernel(const float* __restrict__
     for (int c = 0; c < nchunks; ++c) {
         int n, tlo;
         LSTMF_CHUNK_ROWS(c, n, tlo)
-        LSTMF_ISSUE(min(c + 1, nchunks - 1))      // unconditional: see gru_fwd_kernel
+        LSTMF_ISSUE(min(c + 1, nchunks - 1))      // unconditional: see gru_fwd_kernel's chunk loop
         const float* gb = gxl + (c & 1) * LSTMF_CH * LSTM_G;
         // the step's input term is read from the staged chunk a step AHEAD, so the reads queued behind the barrier are the eight of h alone
         auto load_gx = [&](int i) {
@@ -138,7 +132,7 @@ __global__ __launch_bounds__(512) void lstm_fwd_kernel(const float* __restrict__
             c_own = fmaf(gf, c_own, gi * gg);
             const float rc = __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(c_own * (2.f * L2E)));
             const float hn = fmaf(-2.f * go, rc, go);      // o tanh(c')
-            // all four lanes of a quad hold the same hn and store it to the same word: the step body stays ONE basic block (gru_fwd_kernel)
+            // all four lanes of a quad hold the same hn and store it to the same word: the step body stays ONE basic block (gru_fwd_kernel's do_step)
             hl[((step + 1) & 1) * LSTM_HL + j + 4 * (j >> 5)] = hn;
             __builtin_amdgcn_sched_barrier(0);      // the exchange write leaves first; output stores and the next step's input term follow
             *reinterpret_cast<float*>(reinterpret_cast<char*>(H) + ((unsigned)t * (LSTM_U * 4u) + h_off)) = hn;
@@ -164,7 +158,7 @@ __global__ __launch_bounds__(512) void lstm_fwd_kernel(const float* __restrict__
 //   dh = dh[t] + dh_c;  dc = dh o (1 - tanh^2(c')) + dc_c;  dz_i = dc g i(1-i)  dz_f = dc c_prev f(1-f)  dz_c = dc i (1-g^2)  dz_o = dh tanh(c') o(1-o)
 //   dc_c = dc f;  dh_c = dz U^T;  dgx[t] = dz
 // Lane (grp = lane >> 4, cp = lane & 15) of wave w owns the outputs j0..j0+3 (j0 = 4 (4w + grp)) of the mat-vec over the 32 columns
-// [32cp, 32cp+32), U^T's four rows in the order a ^ (cp & 3) (gru_bwd_kernel VAR 1), and the gate gradient of (unit j0 + (cp & 3), gate cp >> 2).
+// [32cp, 32cp+32), U^T's four rows in the order a ^ (cp & 3) (as gru_bwd_kernel), and the gate gradient of (unit j0 + (cp & 3), gate cp >> 2).
 // Everything of a step except dh and dc is prepared by pre() for the NEXT step while this step's mat-vec runs: behind the carry sit one add, two
 // fma and one multiply.
 __global__ __launch_bounds__(512) void lstm_bwd_kernel(const float* __restrict__ dh_f, const float* __restrict__ dh_b,
@@ -247,7 +241,7 @@ __global__ __launch_bounds__(512) void lstm_bwd_kernel(const float* __restrict__
     const int gl_slot = 36 * (cidx / 32) + cidx % 32;
     const unsigned c_off = 4u * cidx;
     float k_do = 0.f, k_a = 0.f, k_c = 0.f, k_h = 0.f, k_f = 0.f;
-    // gate by 0 / 1 lane masks: plain multiply-adds, no exec-mask region in the step (gru_bwd_kernel VAR 1)
+    // gate by 0 / 1 lane masks: plain multiply-adds, no exec-mask region in the step (gru_bwd_kernel's pre())
     const float m_i = qr == 0 ? 1.f : 0.f, m_f = qr == 1 ? 1.f : 0.f, m_g = qr == 2 ? 1.f : 0.f, m_o = qr == 3 ? 1.f : 0.f;
     auto pre = [&](const float* sbuf, int row) {
         const float* rp = sbuf + row * LSTMB_ROW;
@@ -268,7 +262,7 @@ __global__ __launch_bounds__(512) void lstm_bwd_kernel(const float* __restrict__
     for (int c = 0; c < nchunks; ++c) {
         int n, tlo;
         chunk_rows(c, n, tlo);
-        issue(min(c + 1, nchunks - 1));   // unconditional: see gru_fwd_kernel
+        issue(min(c + 1, nchunks - 1));   // unconditional: see gru_fwd_kernel's chunk loop
         const float* sb = stage + (c & 1) * LSTMB_CH * LSTMB_ROW;
         float* gw = nullptr;
         auto part1 = [&](int i) {   // gate gradients of step i -> LDS vector + global
