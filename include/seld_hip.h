@@ -133,10 +133,10 @@ int seld_sync(seld_ctx* ctx);
  * block's forward whenever its pre-BN tensor is not stored (conv_pool_sb.hip).  "conv1_pool_fused" / "conv1_gram" (default 1): first block's pooling inside the conv
  * epilogue / its kernel gradient from the patch Gram matrix.  "dropout_seed" / "dropout_step" (values): the key of the heads' dropout
  * draws and the step counter of the next training forward (seld_arch.sed_dropout / doa_dropout; INTEGRATION.md section 6 lists every key).
- * EVERY key is per context: the kernel choices the launchers read from library-wide variables ("bwd_four_products",
- * "conv64_dbuf", "tn_tile_blocks", "gram_bg_blocks", "bf16_single") are stored in the context and copied into those
- * variables at the start of each forward / backward pass, so a six-product context and a four-product context coexist in one process
- * (calls on one context are not thread-safe; two contexts driven from two threads at once are not supported for differing choices). */
+ * EVERY key is per context: the kernel choices ("bwd_four_products", "conv64_dbuf", "tn_tile_blocks", "gram_bg_blocks",
+ * "bf16_single", ...) are stored in the context and handed to every kernel launch of its passes as an argument, so a six-product
+ * context and a four-product context coexist in one process, from one host thread or from two
+ * (calls on one context are not thread-safe). */
 int seld_set_option(seld_ctx* ctx, const char* key, int value);
 
 /* ---- variables: replaces model.trainable_variables / get_weights / set_weights
@@ -335,8 +335,8 @@ int seld_profile_reset(seld_ctx* ctx);
  * Each cites what it computes in the reference.  Shapes are checked; SELD_ERR_UNSUPPORTED if
  * the build has no kernel for them. */
 /* same keys as seld_set_option, for the seld_k_* entry points: PROCESS-WIDE (there is no context).  Defaults: the product's
- * ("bwd_four_products" 1: the unit entry points' backward products also run on four of the six split terms); a forward / backward pass of
- * any context overwrites them with that context's choices, so set them right before the seld_k_* calls they are meant for. */
+ * ("bwd_four_products" 1: the unit entry points' backward products also run on four of the six split terms).  A value holds until it is
+ * set again: no context reads these and no context's pass changes them, so a caller that sets one restores it when done. */
 int seld_k_set_option(const char* key, int value);
 /* Conv2D(64, 3, padding='same', use_bias=True) on NHWC (layers.py:27-32); x [B,H,W,Cin], w HWIO, z [B,H,W,64].
  * stats (may be NULL): [2*64] = per-channel sum(z), sum(z^2) over B*H*W (BatchNormalization batch statistics). */

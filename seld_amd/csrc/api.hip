@@ -77,18 +77,6 @@ bool rn_c1_direct(const RnBlock& R) {
     return R.c[1].wsp9 && (!R.c[1].w2 || (R.Wout & 1) == 0) && (W == 16 || W == 8 || W == 4);
 }
 
-// the launchers' kernel-choice variables (common.h) take THIS context's values for the pass that starts here
-void apply_kernel_choices(const seld_ctx* c) {
-    g_mfma_one = c->bf16_single;
-    g_bwd_four = c->bwd_four_products;
-    g_conv64_dbuf = c->conv64_dbuf;
-    g_tn_tile_blocks = c->tn_tile_blocks;
-    g_gram_bg_blocks = c->gram_bg_blocks;
-    g_xc_xcd_map = c->xc_xcd_map;
-    g_xc_w16 = c->xc_w16;
-    g_sbd_dgrad_r8 = c->dgrad_r8;
-}
-
 extern "C" {
 
 int seld_abi_sizes(int32_t* out, int n) {
@@ -152,7 +140,7 @@ int seld_create(const seld_arch* a, int B, int T, int dtype, int device, seld_ct
 
     seld_ctx* c = new seld_ctx();
     c->arch = *a; c->B = B; c->Bmax = B; c->T = T; c->S = S; c->device = device;
-    c->bf16_single = dtype == SELD_DTYPE_BF16;
+    c->kc.mfma_one = dtype == SELD_DTYPE_BF16;
 
     // ---- variable layout (Keras creation order; oracle/seldnet_oracle.py::variable_specs is the twin)
     int64_t off = 0, soff = 0;
@@ -498,7 +486,7 @@ int seld_set_option(seld_ctx* c, const char* key, int value) {
     if (!strcmp(key, "dropout_seed")) { c->dropout_seed = 0x5e1d5e1d00000000ull ^ (uint64_t)(unsigned)value; return SELD_OK; }      // the masks are a function of (seed, step, layer, element)
     if (!strcmp(key, "dropout_step")) { c->dropout_step = (unsigned)value; return SELD_OK; }                                         // the NEXT training forward's step counter
     if (!strcmp(key, "conv1_split_bf16")) { c->conv1_split_bf16 = value != 0; return SELD_OK; }
-    if (!strcmp(key, "gram_bg_blocks") && value >= 16 && value <= 512) { c->gram_bg_blocks = value; return SELD_OK; }   // tuning knob
+    if (!strcmp(key, "gram_bg_blocks") && value >= 16 && value <= 512) { c->kc.gram_bg_blocks = value; return SELD_OK; }   // tuning knob
     if (!strcmp(key, "conv1_pool_fused")) { c->conv1_pool_fused = value != 0; return SELD_OK; }
     if (!strcmp(key, "conv1_gram")) { c->conv1_gram = value != 0; return SELD_OK; }
     if (!strcmp(key, "gru_wgrad_batch")) { c->gru_wgrad_batch = value != 0; return SELD_OK; }
@@ -513,19 +501,19 @@ int seld_set_option(seld_ctx* c, const char* key, int value) {
     if (!strcmp(key, "rn_epi_add")) { c->rn_epi_add = value != 0; return SELD_OK; }
     if (!strcmp(key, "xc_wgrad_side")) { c->xc_wgrad_side = value != 0; return SELD_OK; }
     if (!strcmp(key, "xc_fused_pw_bwd")) { c->xc_fused_pw_bwd = value != 0; return SELD_OK; }
-    // per-context kernel choices (apply_kernel_choices copies them into the launchers' variables at the start of each pass)
-    if (!strcmp(key, "bwd_four_products")) { c->bwd_four_products = value != 0; return SELD_OK; }
-    if (!strcmp(key, "tn_tile_blocks") && value >= 64 && value <= 4096) { c->tn_tile_blocks = value; return SELD_OK; }     // gemm_tn_sb.hip
-    if (!strcmp(key, "conv64_dbuf")) { c->conv64_dbuf = value != 0; return SELD_OK; }     // conv_sb.hip
+    // the context's kernel choices (common.h KernelChoices): its passes hand c->kc to every launcher that chooses by one
+    if (!strcmp(key, "bwd_four_products")) { c->kc.bwd_four = value != 0; return SELD_OK; }
+    if (!strcmp(key, "tn_tile_blocks") && value >= 64 && value <= 4096) { c->kc.tn_tile_blocks = value; return SELD_OK; }     // gemm_tn_sb.hip
+    if (!strcmp(key, "conv64_dbuf")) { c->kc.conv64_dbuf = value != 0; return SELD_OK; }     // conv_sb.hip
     if (!strcmp(key, "conv_wgrad_side")) { c->conv_wgrad_side = value != 0; return SELD_OK; }
-    if (!strcmp(key, "dgrad_r8")) { c->dgrad_r8 = value != 0; return SELD_OK; }
+    if (!strcmp(key, "dgrad_r8")) { c->kc.dgrad_r8 = value != 0; return SELD_OK; }
     if (!strcmp(key, "prep_side")) { c->prep_side = value != 0; return SELD_OK; }
     if (!strcmp(key, "xc_nowait")) { c->xc_nowait = value != 0; return SELD_OK; }
     if (!strcmp(key, "xc_fused_bn_sums")) { c->xc_fused_bn_sums = value != 0; return SELD_OK; }
     if (!strcmp(key, "xc_fused_dw_bwd")) { c->xc_fused_dw_bwd = value != 0; return SELD_OK; }
-    if (!strcmp(key, "xc_w16")) { c->xc_w16 = value != 0; return SELD_OK; }               // xception.hip
-    if (!strcmp(key, "xc_xcd_map")) { c->xc_xcd_map = value != 0; return SELD_OK; }       // xception.hip
-    if (!strcmp(key, "bf16_single")) { c->bf16_single = value != 0; return SELD_OK; }     // = SELD_DTYPE_BF16 at seld_create
+    if (!strcmp(key, "xc_w16")) { c->kc.xc_w16 = value != 0; return SELD_OK; }               // xception.hip
+    if (!strcmp(key, "xc_xcd_map")) { c->kc.xc_xcd_map = value != 0; return SELD_OK; }       // xception.hip
+    if (!strcmp(key, "bf16_single")) { c->kc.mfma_one = value != 0; return SELD_OK; }     // = SELD_DTYPE_BF16 at seld_create
     return fail(c, SELD_ERR_INVALID, std::string("unknown option: ") + key);
 }
 int seld_sync(seld_ctx* c) {

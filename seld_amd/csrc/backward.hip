@@ -11,7 +11,7 @@ static void wgrad_dense(seld_ctx* c, hipStream_t st, float* slab, const float* A
     int ns = 0;
     // both slab buffers hold gemm_tn_max_splits() slabs of 384 x 384 + 384 floats: larger products (a 2048-feature GRU input) take fewer splits
     const int64_t cap = tn_slab_capacity() / ((int64_t)K1 * N + N);
-    if (c->gemm_split_bf16 && gemm_tn_sb_usable(A, lda, Bm, ldb, K1, N)) launch_gemm_tn_sb(st, A, lda, Bm, ldb, slab, &ns, M, N, S, shift, 1);
+    if (c->gemm_split_bf16 && gemm_tn_sb_usable(A, lda, Bm, ldb, K1, N)) launch_gemm_tn_sb(st, c->kc, A, lda, Bm, ldb, slab, &ns, M, N, S, shift, 1);
     else launch_gemm_tn(st, A, lda, Bm, ldb, slab, &ns, M, K1, N, S, shift, 1, (int)std::min<int64_t>(cap, gemm_tn_max_splits()));
     launch_reduce_slabs2(st, slab, ns, (int64_t)K1 * N + N, c->grads + w_off, (int64_t)K1 * N, c->grads + b_off, N);
 }
@@ -146,8 +146,7 @@ static int backward_heads(seld_ctx* c) {
         }
     }
     if (merged0 && heads_sb(c) && gemm_sb_usable(S0.dy, S0.out, S0.in, S0.out) && gemm_sb_usable(D0.dy, S0.out, S0.in, S0.out)) {
-        BwdFourScope four_;
-        launch_gemm_sb(st, S0.dy, D0.dy, S0.out, c->h0sp_bwd[0], c->h0sp_bwd[1], nullptr, nullptr, dfeat, nullptr, S0.in, rows, S0.in,
+        launch_gemm_sb(st, c->kc, true, GemmEpi(), S0.dy, D0.dy, S0.out, c->h0sp_bwd[0], c->h0sp_bwd[1], nullptr, nullptr, dfeat, nullptr, S0.in, rows, S0.in,
                        S0.out, 0, 2);
     } else if (merged0)
         launch_gemm_dual_k(st, S0.dy, D0.dy, S0.out, c->params + S0.w_off, c->params + D0.w_off, S0.out, nullptr, dfeat, S0.in, rows,
@@ -193,16 +192,14 @@ static int backward_gru(seld_ctx* c, const float* dfeat, const float** din) {
             if (gru_drop) {      // din = (dgx_f K_f^T) * imask_f + (dgx_b K_b^T) * imask_b: each direction's input rows had their own mask
                 for (int d = 0; d < 2; ++d) {
                     float* t_ = d == 0 ? G.din : G.dtmp;
-                    if (gru_sb(c, G)) {
-                        BwdFourScope four_;
-                        launch_gemm_sb(st, c->dgx[i][d], nullptr, 384, c->ksp_bwd[i][d], nullptr, nullptr, nullptr, t_, nullptr, G.in_feat, rows, G.in_feat, 384, 0, 0);
-                    } else
+                    if (gru_sb(c, G))
+                        launch_gemm_sb(st, c->kc, true, GemmEpi(), c->dgx[i][d], nullptr, 384, c->ksp_bwd[i][d], nullptr, nullptr, nullptr, t_, nullptr, G.in_feat, rows, G.in_feat, 384, 0, 0);
+                    else
                         launch_gemm(st, c->dgx[i][d], 384, c->params + G.k_off[d], 384, nullptr, t_, G.in_feat, rows, G.in_feat, 384, 1, 0, 0);
                     launch_mask_rows(st, t_, G.imask[d], G.din, rows, S, G.in_feat, d);
                 }
             } else if (gru_sb(c, G)) {
-                BwdFourScope four_;
-                launch_gemm_sb(st, c->dgx[i][0], c->dgx[i][1], 384, c->ksp_bwd[i][0], c->ksp_bwd[i][1], nullptr, nullptr, G.din, nullptr,
+                launch_gemm_sb(st, c->kc, true, GemmEpi(), c->dgx[i][0], c->dgx[i][1], 384, c->ksp_bwd[i][0], c->ksp_bwd[i][1], nullptr, nullptr, G.din, nullptr,
                                G.in_feat, rows, G.in_feat, 384, 0, 2);
             } else
                 launch_gemm_dual_k(st, c->dgx[i][0], c->dgx[i][1], 384, c->params + G.k_off[0], c->params + G.k_off[1], 384, nullptr,
@@ -222,7 +219,7 @@ static int backward_gru(seld_ctx* c, const float* dfeat, const float** din) {
             tj.out_w[2 * d + 1] = c->grads + G.u_off[d]; tj.out_b[2 * d + 1] = c->grads + G.b_off[d] + 384;
         }
         int ns4 = 0;
-        if (c->gru_wgrad_batch && c->gemm_split_bf16 && G.in_feat == 128 && launch_gemm_tn_sb_batch(c->side, tj, 4, 384, c->tn_slab_side, &ns4, rows, 384, S, 1) == 0) {
+        if (c->gru_wgrad_batch && c->gemm_split_bf16 && G.in_feat == 128 && launch_gemm_tn_sb_batch(c->side, c->kc, tj, 4, 384, c->tn_slab_side, &ns4, rows, 384, S, 1) == 0) {
             // the layer's four products in one launch, their slabs combined by one more
             launch_reduce_slabs2_batch(c->side, c->tn_slab_side, ns4, (int64_t)128 * 384 + 384, tj, 4, (int64_t)128 * 384, 384);
         } else
@@ -260,7 +257,7 @@ static int backward_resnet(seld_ctx* c, const float* dout, const float** dp) {
     auto done = [&](int slot) { if (aside) { hipEventRecord(c->ev_rn_free[slot], c->side); busy[slot] = true; } };
     auto wgrad = [&](int slot, const float* A, int lda, const float* dz, int M_, int K1, int N, int64_t w_off) {
         fork(slot);
-        launch_rn_product_wgrad(ws, A, lda, dz, c->tn_slab, tn_slab_capacity(), c->grads + w_off, M_, K1, N,
+        launch_rn_product_wgrad(ws, c->kc, A, lda, dz, c->tn_slab, tn_slab_capacity(), c->grads + w_off, M_, K1, N,
                                 c->rn_split_bf16);
         done(slot);
     };
@@ -278,32 +275,32 @@ static int backward_resnet(seld_ctx* c, const float* dout, const float** dp) {
         float* dz2 = take(0, 2, zi);
         { PROF3(c, "rn_bn_bwd"); rn_bn_bwd(c, st, R.c[2], g, R.gate, dz2, M); }
         wgrad(zi, R.y1, w, dz2, (int)M, w, 4 * w, R.c[2].w_off);
-        { PROF3(c, "rn_products_dgrad"); launch_rn_product_dgrad(st, dz2, c->params + R.c[2].w_off, sb ? R.c[2].wsp_t : nullptr, c->rn_ba, w, (int)M, w, 4 * w, 0); }
+        { PROF3(c, "rn_products_dgrad"); launch_rn_product_dgrad(st, c->kc, dz2, c->params + R.c[2].w_off, sb ? R.c[2].wsp_t : nullptr, c->rn_ba, w, (int)M, w, 4 * w, 0); }
         // BN1 (mask = y1), 3x3: stage 1 on the conv blocks' kernels, the other widths through im2col / col2im
         float* dz1 = take(2, 3, bbi);
         { PROF3(c, "rn_bn_bwd"); rn_bn_bwd(c, st, R.c[1], c->rn_ba, nullptr, dz1, M); }
         if (sb && rn_c1_direct(R)) {
             fork(bbi);
             int ns = 0;
-            launch_conv64_wgrad_sb(ws, R.y0, dz1, c->rn_w9_slab, &ns, B, S, rn_c1_width(R));
+            launch_conv64_wgrad_sb(ws, c->kc, R.y0, dz1, c->rn_w9_slab, &ns, B, S, rn_c1_width(R));
             if (R.c[1].w2) {
                 launch_reduce_slabs(ws, c->rn_w9_slab, ns, 9 * 4096 + 64, R.c[1].dw2, 9 * 4096, 0);
                 launch_rn_w32_extract(ws, R.c[1].dw2, c->grads + R.c[1].w_off);
             } else
                 launch_reduce_slabs(ws, c->rn_w9_slab, ns, 9 * 4096 + 64, c->grads + R.c[1].w_off, 9 * 4096, 0);
             done(bbi);
-            { PROF3(c, "rn_products_dgrad"); launch_conv64_dgrad_sb(st, dz1, R.c[1].wsp9_flip, c->rn_ba, B, S, rn_c1_width(R)); }
+            { PROF3(c, "rn_products_dgrad"); launch_conv64_dgrad_sb(st, c->kc, dz1, R.c[1].wsp9_flip, c->rn_ba, B, S, rn_c1_width(R)); }
         } else if (sb && rn_c1_implicit(c, R)) {
             fork(bbi);
-            launch_rn_conv3_wgrad(ws, R.y0, dz1, c->tn_slab, tn_slab_capacity(), c->grads + R.c[1].w_off, B, S,
+            launch_rn_conv3_wgrad(ws, c->kc, R.y0, dz1, c->tn_slab, tn_slab_capacity(), c->grads + R.c[1].w_off, B, S,
                                   R.Wout, w, w);
             done(bbi);
-            { PROF3(c, "rn_products_dgrad"); launch_rn_conv3_dgrad(st, dz1, R.c[1].wsp_t, c->rn_ba, B, S, R.Wout, w, w); }
+            { PROF3(c, "rn_products_dgrad"); launch_rn_conv3_dgrad(st, c->kc, dz1, R.c[1].wsp_t, c->rn_ba, B, S, R.Wout, w, w); }
         } else {
             if (!R.c[1].col) return fail(c, SELD_ERR_INVALID, "resnet50_block: the options changed between forward and backward");
             if (!c->rn_bcol && dalloc(c, &c->rn_bcol, c->rn_col_elems)) return fail(c, SELD_ERR_NOMEM, "col2im tensor");
             wgrad(bbi, R.c[1].col, 9 * w, dz1, (int)M, 9 * w, w, R.c[1].w_off);
-            { PROF3(c, "rn_products_dgrad"); launch_rn_product_dgrad(st, dz1, c->params + R.c[1].w_off, sb ? R.c[1].wsp_t : nullptr, c->rn_bcol, 9 * w, (int)M, 9 * w, w, 0); }
+            { PROF3(c, "rn_products_dgrad"); launch_rn_product_dgrad(st, c->kc, dz1, c->params + R.c[1].w_off, sb ? R.c[1].wsp_t : nullptr, c->rn_bcol, 9 * w, (int)M, 9 * w, w, 0); }
             launch_col2im3x3(st, c->rn_bcol, c->rn_ba, B, S, R.Wout, w);
         }
         // BN0 (mask = y0), 1x1 reduce; its input gradient lands on the strided rows of dX
@@ -315,7 +312,7 @@ static int backward_resnet(seld_ctx* c, const float* dout, const float** dp) {
         // fp32 GEMM and the separate pass below still runs)
         const bool epi_add = !R.proj && c->rn_epi_add && R.stride_f == 1;
         int added = 1;
-        { PROF3(c, "rn_products_dgrad"); added = launch_rn_product_dgrad(st, dz0, c->params + R.c[0].w_off, sb ? R.c[0].wsp_t : nullptr, dX, ldx, (int)M, R.Cin, w, 0,
+        { PROF3(c, "rn_products_dgrad"); added = launch_rn_product_dgrad(st, c->kc, dz0, c->params + R.c[0].w_off, sb ? R.c[0].wsp_t : nullptr, dX, ldx, (int)M, R.Cin, w, 0,
                                                                          epi_add ? g : nullptr, epi_add ? R.gate : nullptr); }
         if (added < 0) return fail(c, SELD_ERR_INVALID, "resnet50_block: reduce convolution's input-gradient product");
         // shortcut
@@ -323,7 +320,7 @@ static int backward_resnet(seld_ctx* c, const float* dout, const float** dp) {
             float* dzs = take(0, 2, zi);
             { PROF3(c, "rn_bn_bwd"); rn_bn_bwd(c, st, R.sc, g, R.gate, dzs, M); }
             wgrad(zi, X, ldx, dzs, (int)M, R.Cin, 4 * w, R.sc.w_off);
-            { PROF3(c, "rn_products_dgrad"); launch_rn_product_dgrad(st, dzs, c->params + R.sc.w_off, sb ? R.sc.wsp_t : nullptr, dX, ldx, (int)M, R.Cin, 4 * w, 1); }
+            { PROF3(c, "rn_products_dgrad"); launch_rn_product_dgrad(st, c->kc, dzs, c->params + R.sc.w_off, sb ? R.sc.wsp_t : nullptr, dX, ldx, (int)M, R.Cin, 4 * w, 1); }
         } else if (!epi_add || added == 1) {
             { PROF3(c, "rn_bn_bwd"); launch_rn_add_gated(st, dX, g, R.gate, M * 4 * w); }
         }
@@ -432,7 +429,7 @@ static int backward_xception(seld_ctx* c, const float* dout, const float** dp) {
                 // a folded unit's input is the previous unit's pre-BN tensor and gin that BatchNormalization's output gradient: its backward sums ride along
                 const bool sums = fold && c->xc_fused_bn_sums;
                 const XcUnit* Pv = sums ? &c->xc[(size_t)b * 3 + u - 1] : nullptr;
-                if (launch_dw3x3_bwd_fused(st, F1c, c->params + U.dw_off, uin, u == 0 ? X : nullptr, gin, sl, &ns, B, S, 16, aff,
+                if (launch_dw3x3_bwd_fused(st, c->kc, F1c, c->params + U.dw_off, uin, u == 0 ? X : nullptr, gin, sl, &ns, B, S, 16, aff,
                                            sums ? Pv->mean : nullptr, sums ? Pv->invstd : nullptr, sums ? c->xc_part_dw : nullptr))
                     return fail(c, SELD_ERR_UNSUPPORTED, "dw3x3_bwd_fused");
                 if (sums) { have_sums = true; n_dw_part = ns; }
@@ -459,7 +456,7 @@ static int backward_xception(seld_ctx* c, const float* dout, const float** dp) {
                 launch_dw3x3_bwd_w(ws, uin, F1c, c->xc_slab, &ns, B, S, 16, aff);
                 launch_reduce_slabs(ws, c->xc_slab, ns, 576, c->grads + U.dw_off, 576, 0);
                 done(sf);
-                launch_dw3x3_bwd_data(st, F1c, c->params + U.dw_off, uin, u == 0 ? X : nullptr, gin, B, S, 16, aff);
+                launch_dw3x3_bwd_data(st, c->kc, F1c, c->params + U.dw_off, uin, u == 0 ? X : nullptr, gin, B, S, 16, aff);
             }
             gY = gin;
         }
@@ -546,7 +543,7 @@ static int backward_conv_blocks(seld_ctx* c, const float* x, const float* dp) {
                 float* wsl = wside ? c->wgrad_slab_side : c->wgrad_slab;
                 if (wside) { hipEventRecord(c->ev_fork, st); hipStreamWaitEvent(c->side, c->ev_fork, 0); }      // dz (and the block's input) are final on the main stream
                 if (c->conv64_split_bf16 && conv64_wgrad_sb_usable(L.W)) {
-                    if (launch_conv64_wgrad_sb(wst, lin, dzb, wsl, &ns, B, L.H, L.W))
+                    if (launch_conv64_wgrad_sb(wst, c->kc, lin, dzb, wsl, &ns, B, L.H, L.W))
                         return fail(c, SELD_ERR_UNSUPPORTED, "conv64_wgrad_sb");
                 } else if (launch_conv64_wgrad(wst, lin, dzb, wsl, &ns, B, L.H, L.W))
                     return fail(c, SELD_ERR_UNSUPPORTED, "conv64_wgrad");
@@ -557,7 +554,7 @@ static int backward_conv_blocks(seld_ctx* c, const float* x, const float* dp) {
             {
                 PROF2(c, tn);
                 if (c->conv64_split_bf16) {   // flipped + split planes were made by the forward's weight pre-pass
-                    launch_conv64_dgrad_sb(st, dzb, c->wsp_bwd[i], c->conv[i - 1].dp, B, L.H, L.W);
+                    launch_conv64_dgrad_sb(st, c->kc, dzb, c->wsp_bwd[i], c->conv[i - 1].dp, B, L.H, L.W);
                 } else {
                     launch_flip_weights(st, c->params + L.w_off, c->wflip);
                     launch_conv64_fwd(st, dzb, c->wflip, nullptr, c->conv[i - 1].dp, nullptr, nullptr, B, L.H, L.W);
@@ -570,7 +567,6 @@ static int backward_conv_blocks(seld_ctx* c, const float* x, const float* dp) {
 }
 
 int backward_impl(seld_ctx* c, const float* x) {
-    apply_kernel_choices(c);
     const float *dout = nullptr, *dp = nullptr;      // gradient w.r.t. the first GRU layer's input / the conv blocks' output
     int rc = apply_overrides(c);
     if (!rc) rc = backward_heads(c);

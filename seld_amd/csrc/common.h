@@ -77,12 +77,27 @@ __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(
 
 // ---- per-step weight pre-passes: job descriptors (kernel arguments by value) and the merged launch (prep.hip) ----------------
 #define GSB_MAX_JOBS 16
-// bf16 single-product mode (SELD_DTYPE_BF16 / option "bf16_single"): the split-bf16 kernels that implement it take ONE bf16 MFMA product per
-// fp32 product, operands rounded to nearest-even bf16 (fp32 accumulation), instead of the six products of the exact 3-way split.  Set by
-// api.hip from the ctx before it enqueues a pass (process-wide: contexts of different modes must not enqueue concurrently from different
-// host threads); kernels without a single-product form keep the exact six products: the weight pre-split writes ALL three planes in both
-// modes (plane 0 = the rounded value in this mode, planes 1-2 the exact split of the rest, prep.h), so they compute with exact weights.
-extern int g_mfma_one;
+// What a launcher may choose its kernel by.  A context owns one (ctx.h seld_ctx::kc, written by seld_create / seld_set_option), the seld_k_* entry
+// points own one (kernels_api.hip, written by seld_k_set_option); every launcher that reads a field takes the struct as the argument after the
+// stream, so which instantiation a call takes depends on its arguments alone.  The defaults are the product's.
+struct KernelChoices {
+    // bf16 single-product mode (SELD_DTYPE_BF16 / option "bf16_single"): the split-bf16 kernels that implement it take ONE bf16 MFMA product per
+    // fp32 product, operands rounded to nearest-even bf16 (fp32 accumulation), instead of the six products of the exact 3-way split.  Kernels
+    // without a single-product form keep the exact six products: the weight pre-split writes ALL three planes in both modes (plane 0 = the
+    // rounded value in this mode, planes 1-2 the exact split of the rest, prep.h), so they compute with exact weights.
+    int mfma_one = 0;
+    int bwd_four = 1;          // option "bwd_four_products": backward-only products (input / kernel gradients) on four of the six split-bf16 terms
+    int conv64_dbuf = 1;       // conv_sb.hip: 1: conv64_fwd_sbd_kernel (double-buffered weights) for W = 16 / 4; 0: conv64_fwd_sbr_kernel
+    int dgrad_r8 = 1;          // option "dgrad_r8" (conv_sb.hip): the W = 16 four-product input gradient on 8-row tiles (4 waves, 74 KB of LDS instead of 8 waves, 107 KB: two
+                               // workgroups per CU, or one beside a kernel-gradient workgroup of the side stream; the same taps and k-steps per pixel: the same bits;
+                               // round 5: 2.510 -> 2.496 ms per step same box)
+    int tn_tile_blocks = 384;  // gemm_tn_sb.hip tile mode: workgroups per launch the split count aims at (option "tn_tile_blocks"; resnet50_gru same box: 14.709 / 14.752 ms per
+                               // step at 768, 14.646 at 384, 14.691 at 512, 14.87 at 256 and 1024)
+    int gram_bg_blocks = 192;  // conv_gram.hip: workgroups of a background launch
+    int xc_w16 = 1;            // option "xc_w16" (xception.hip): the row-per-workgroup depthwise kernels for W = 16 (0: the generic kernel, for A/B)
+    int xc_xcd_map = 1;        // option "xc_xcd_map" (xception.hip): XCD-contiguous row ranges in the depthwise kernels (0: identity map, for A/B)
+    int gsb_dbg = 0;           // seld_k_* only (a context's stays 0), tools/tune_gemm.py: 1 no loads in the 4-wave loop, 2 no stores, 4 force the 4-wave form, 8 the 16-wave form
+};
 // round-to-nearest-even bf16 of an fp32 value, as its 16 high bits (NaN stays a quiet NaN)
 __host__ __device__ __forceinline__ unsigned bf16_rne_bits(float x) {
     unsigned u;
@@ -100,17 +115,17 @@ struct GemmSplitJobs {
 struct SplitWeightJobs { const float* w[8]; unsigned short* dst[8]; int flip[8]; int one; };
 struct HeadsLin { const float *w1[2], *b1[2], *w2[2], *b2[2]; int n[2]; int K, Hd; };
 // one launch for all three kinds (any of them may be empty: na / nb = 0, weff = nullptr)
-int launch_weight_prep(hipStream_t st, const GemmSplitJobs& a, int na, const SplitWeightJobs& b, int nb, const HeadsLin& h, float* weff);
+int launch_weight_prep(hipStream_t st, const KernelChoices& kc, const GemmSplitJobs& a, int na, const SplitWeightJobs& b, int nb, const HeadsLin& h, float* weff);
 
 // ---- launcher prototypes (implemented in the .hip files; used by api.hip) -------------------
 struct ConvFirstArgs { const float* x; const float* w; const float* bias; float* z; float* stat_partial; int B, H; };
 
 int launch_conv_first_fwd(hipStream_t st, const float* x, const float* w, const float* bias, float* z,
                           float* stat_partial, int* n_partial, int B, int H, int Cin);
-int launch_conv_first_fwd_pool(hipStream_t st, const float* x, const float* w, const float* bias, const float* gamma,
+int launch_conv_first_fwd_pool(hipStream_t st, const KernelChoices& kc, const float* x, const float* w, const float* bias, const float* gamma,
                                float* z, float* zext, unsigned char* amax, float* stat_partial, int* n_partial, int B, int H,
                                int Cin, int split_bf16 = 1);
-int launch_conv_first_fwd_pool_sb(hipStream_t st, const float* x, const float* w, const float* bias, const float* gamma,
+int launch_conv_first_fwd_pool_sb(hipStream_t st, const KernelChoices& kc, const float* x, const float* w, const float* bias, const float* gamma,
                                   float* zext, unsigned char* amax, float* stat_partial, int* n_partial, int B, int H, int Cin);
 int conv_pool_sb_stat_capacity();
 int launch_pool_argext(hipStream_t st, const float* z, const float* gamma, unsigned char* amax, int B, int H, int W, int pt,
@@ -127,30 +142,25 @@ int launch_conv_first_wgrad_fused(hipStream_t st, const float* x, const float* z
                                   const unsigned char* amax, const float* coef, float* slab, int* n_slab, int B, int H,
                                   int Cin, int pt, int pf);
 int conv_gram_dim(int Cin);
-extern int g_gram_bg_blocks;
-extern int g_sbd_dgrad_r8;    // conv_sb.hip (experiment)
-extern int g_xc_w16;          // xception.hip: row-per-workgroup depthwise kernels for W = 16
-extern int g_xc_xcd_map;      // xception.hip: XCD-contiguous row ranges in the depthwise kernels
 int conv_gram_slab_capacity();
 int conv_msparse_slab_capacity();
-int launch_conv_first_gram(hipStream_t st, const float* x, float* slab, int* n_slab, int B, int H, int Cin, int background = 0, int part = 0, int nparts = 1);
+int launch_conv_first_gram(hipStream_t st, const KernelChoices& kc, const float* x, float* slab, int* n_slab, int B, int H, int Cin, int background = 0, int part = 0, int nparts = 1);
 int launch_conv_first_msparse(hipStream_t st, const float* x, const float* p, const float* dp, const unsigned char* amax,
                               const float* scale, float* slab, int* n_slab, int B, int H, int Cin);
 int launch_conv_first_assemble(hipStream_t st, const float* G, const float* M, const float* W, const float* bias, const float* coef,
                                float* dW, float* db, int Cin);
 // split-bf16 form with transposed LDS reads (conv_wgrad_sb.hip): W = 16, 8 or 4; same slab layout as launch_conv64_wgrad
 int conv64_wgrad_sb_usable(int W);
-int launch_conv64_wgrad_sb(hipStream_t st, const float* x, const float* dz, float* slab, int* n_slab, int B, int H, int W);
+int launch_conv64_wgrad_sb(hipStream_t st, const KernelChoices& kc, const float* x, const float* dz, float* slab, int* n_slab, int B, int H, int W);
 int launch_conv64_wgrad(hipStream_t st, const float* x, const float* dz, float* slab, int* n_slab,
                         int B, int H, int W);
 int conv_wgrad_slab_capacity();
 int conv_first_wgrad_slab_stride(int Cin);   // floats per first-layer wgrad slab: rows 0..9*Cin-1 kernel, row 9*Cin bias
 int launch_flip_weights(hipStream_t st, const float* w, float* wt);
 // split-bf16 conv (conv_sb.hip): w [9][in][out] fp32 -> planes [9][3][out][in] bf16; conv with 6 bf16 MFMAs per product
-int launch_split_weights(hipStream_t st, const float* w, unsigned short* wsp);
+int launch_split_weights(hipStream_t st, const KernelChoices& kc, const float* w, unsigned short* wsp);
 // up to 8 tensors in one launch; flip[i] != 0: the planes of the flipped (input-gradient) weights, from the unflipped tensor
-int launch_split_weights_batch(hipStream_t st, int n, const float* const* w, unsigned short* const* dst, const int* flip);
-extern int g_conv64_dbuf;   // conv_sb.hip: 1 = double-buffered-weights kernel (default)
+int launch_split_weights_batch(hipStream_t st, const KernelChoices& kc, int n, const float* const* w, unsigned short* const* dst, const int* flip);
 // two-plane split of two floats for the four-product form: hi = the truncated upper 16 bits, mid = the residual ROUNDED to bf16 (half up on the
 // magnitude: one integer add) — with a truncated mid the dropped remainder has the sign of x for every element, and the products it would have
 // carried bias every sum by the same ~2^-16 relative; rounded, it is zero-mean and the dropped terms average out over a sum
@@ -160,21 +170,14 @@ __device__ __forceinline__ void split2r_pair(float x0, float x1, unsigned& h, un
     const float r0 = x0 - __uint_as_float(u0 & 0xffff0000u), r1 = x1 - __uint_as_float(u1 & 0xffff0000u);
     m = __builtin_amdgcn_perm(__float_as_uint(r1) + 0x8000u, __float_as_uint(r0) + 0x8000u, 0x07060302);
 }
-extern thread_local int g_gsb_four_now;    // gemm_sb.hip
-extern int g_tn_tile_blocks;   // gemm_tn_sb.hip
-extern int g_bwd_four;        // conv_sb.hip: backward-only products on four of the six split-bf16 terms (option "bwd_four_products")
-// a backward-only launch_gemm_sb (input gradients: their B planes come from a transposed / flipped gemm_split_b job) inside this scope takes the four-product form
-struct BwdFourScope {
-    BwdFourScope() { g_gsb_four_now = g_bwd_four && !g_mfma_one; }
-    ~BwdFourScope() { g_gsb_four_now = 0; }
-};
-int launch_conv64_dgrad_sb(hipStream_t st, const float* dz, const unsigned short* wsp_flip, float* dx, int B, int H, int W);
-// pre_scale / pre_shift / pre_out (conv64_fwd_sb_takes_pre(W)): x holds the previous block's window extremes; its BatchNorm + ReLU are applied on load
+// the input gradient of a 64 -> 64 3x3 convolution: a backward-only product, on four products when kc.bwd_four allows
+int launch_conv64_dgrad_sb(hipStream_t st, const KernelChoices& kc, const float* dz, const unsigned short* wsp_flip, float* dx, int B, int H, int W);
+// pre_scale / pre_shift / pre_out (conv64_fwd_sb_takes_pre(kc, W)): x holds the previous block's window extremes; its BatchNorm + ReLU are applied on load
 // and the activated tensor is written to pre_out (!= x)
-int launch_conv64_fwd_sb(hipStream_t st, const float* x, const unsigned short* wsp, const float* bias, float* z,
+int launch_conv64_fwd_sb(hipStream_t st, const KernelChoices& kc, const float* x, const unsigned short* wsp, const float* bias, float* z,
                          float* stat_partial, int* n_partial, int B, int H, int W, const float* pre_scale = nullptr, const float* pre_shift = nullptr,
                          float* pre_out = nullptr, const float* ext_gamma = nullptr, float* ext_out = nullptr);      // ext_*: W = 16, with pre_*: the (1,4) windows' extremes of z
-int conv64_fwd_sb_takes_pre(int W);
+int conv64_fwd_sb_takes_pre(const KernelChoices& kc, int W);
 int conv_sb_partial_capacity();  // [3,3,64,64] -> dgrad weights
 int launch_reduce_slabs(hipStream_t st, const float* slab, int nslab, int64_t slab_stride, float* out,
                         int64_t n, int accumulate);
@@ -223,11 +226,11 @@ int launch_rn_add_masked(hipStream_t st, float* dst, const float* dy, const floa
 int rn_sb_fwd_ok(int K, int N);
 int rn_sb_dgrad_ok(int K, int N);
 int rn_sb_wgrad_ok(int K, int N);
-int launch_rn_product_fwd(hipStream_t st, const float* A, int lda, const float* w, const unsigned short* wsp, float* z, int M, int K, int N,
+int launch_rn_product_fwd(hipStream_t st, const KernelChoices& kc, const float* A, int lda, const float* w, const unsigned short* wsp, float* z, int M, int K, int N,
                           float* stat_part = nullptr, int* nbx = nullptr, size_t part_cap = 0);
-int launch_rn_product_dgrad(hipStream_t st, const float* dz, const float* w, const unsigned short* wsp_t, float* dA, int ldd, int M, int K, int N,
+int launch_rn_product_dgrad(hipStream_t st, const KernelChoices& kc, const float* dz, const float* w, const unsigned short* wsp_t, float* dA, int ldd, int M, int K, int N,
                             int accumulate, const float* addg = nullptr, const unsigned char* gate4 = nullptr);
-int launch_rn_product_wgrad(hipStream_t st, const float* A, int lda, const float* dz, float* slab, int64_t slab_cap, float* dw, int M, int K, int N,
+int launch_rn_product_wgrad(hipStream_t st, const KernelChoices& kc, const float* A, int lda, const float* dz, float* slab, int64_t slab_cap, float* dw, int M, int K, int N,
                             int split_bf16);
 // 3x3 'same' convolution [B*H*W][C] -> [B*H*W][N] with the im2col rows formed on load (C, N powers of two >= 128: rn_conv3_sb_ok);
 // wsp = split of w [9 C][N] (transb 0), wsp_flip = split with transb 2 (K = 9 N, N = C): the input-gradient convolution's matrix
@@ -235,22 +238,22 @@ int launch_rn_product_wgrad(hipStream_t st, const float* A, int lda, const float
 int launch_rn_w32_embed(hipStream_t st, const float* w, float* w2);
 int launch_rn_w32_extract(hipStream_t st, const float* dw2, float* dw);
 int rn_conv3_sb_ok(int C, int N);
-int launch_rn_conv3_fwd(hipStream_t st, const float* img, const unsigned short* wsp, float* z, int B, int H, int W, int C, int N,
+int launch_rn_conv3_fwd(hipStream_t st, const KernelChoices& kc, const float* img, const unsigned short* wsp, float* z, int B, int H, int W, int C, int N,
                         float* stat_part = nullptr, int* nbx = nullptr, size_t part_cap = 0);
-int launch_rn_conv3_dgrad(hipStream_t st, const float* dz, const unsigned short* wsp_flip, float* dimg, int B, int H, int W, int C, int N);
-int launch_rn_conv3_wgrad(hipStream_t st, const float* img, const float* dz, float* slab, int64_t slab_cap, float* dw, int B, int H, int W, int C, int N);
+int launch_rn_conv3_dgrad(hipStream_t st, const KernelChoices& kc, const float* dz, const unsigned short* wsp_flip, float* dimg, int B, int H, int W, int C, int N);
+int launch_rn_conv3_wgrad(hipStream_t st, const KernelChoices& kc, const float* img, const float* dz, float* slab, int64_t slab_cap, float* dw, int B, int H, int W, int C, int N);
 // xception.hip: middle flow of xception_block (spec/XCEPTION_BLOCK.md)
 int launch_xc_unit_fwd(hipStream_t st, const float* x, const float* kdw, const float* wpw, float* dwo, float* z, float* partial, int* npartial,
                        int B, int H, int W, const float* aff = nullptr);
 int xc_partial_capacity();
-int launch_dw3x3_fwd(hipStream_t st, const float* x, const float* k, float* y, int B, int H, int W, const float* aff = nullptr);
-int launch_dw3x3_bwd_data(hipStream_t st, const float* dy, const float* k, const float* xin, const float* add, float* dx, int B, int H, int W,
+int launch_dw3x3_fwd(hipStream_t st, const KernelChoices& kc, const float* x, const float* k, float* y, int B, int H, int W, const float* aff = nullptr);
+int launch_dw3x3_bwd_data(hipStream_t st, const KernelChoices& kc, const float* dy, const float* k, const float* xin, const float* add, float* dx, int B, int H, int W,
                           const float* aff = nullptr);
 int launch_dw3x3_bwd_w(hipStream_t st, const float* x, const float* dy, float* slab, int* nslab, int B, int H, int W, const float* aff = nullptr);
 // input gradient + kernel-gradient slabs in one pass (W = 16): slab [xc_dw_fused_slabs(B, H)][576]
 int xc_dw_fused_slabs(int B, int H);
 // bn_partial (aff units only): + the backward sums of the BatchNormalization whose pre-BN tensor is xin, [xc_dw_fused_slabs][128]; fold with launch_xc_fold_partials
-int launch_dw3x3_bwd_fused(hipStream_t st, const float* dy, const float* k, const float* xin, const float* add, float* dx, float* slab, int* nslab,
+int launch_dw3x3_bwd_fused(hipStream_t st, const KernelChoices& kc, const float* dy, const float* k, const float* xin, const float* add, float* dx, float* slab, int* nslab,
                            int B, int H, int W, const float* aff = nullptr, const float* bn_mean = nullptr, const float* bn_invstd = nullptr,
                            float* bn_partial = nullptr);
 int launch_xc_fold_partials(hipStream_t st, const float* partial, int n, float* out, int* nout);
@@ -283,22 +286,16 @@ int launch_bn_pool_bwd_dz(hipStream_t st, const float* z, const float* dp, const
                           int B, int H, int W, int C, int pt, int pf);
 int bn_partial_capacity();
 
-// Optional epilogue extras of the NEXT launch_gemm / launch_gemm_sb call of this host thread (resnet50_block, round 5), set by a GemmEpiScope
-// around the call the way BwdFourScope selects the four-product form:
+// Optional epilogue extras of a launch_gemm / launch_gemm_sb call (resnet50_block, round 5), passed as its `epi` argument; GemmEpi() = none:
 //   stat_part : the product's BatchNorm statistics leave with its epilogue — per (row block, column) [sum | sum of squares] in the layout
 //               rn_bn_finalize reads (partial[(chunk * nbx + row block) * 128 + {c, 64 + c}], chunk = column / 64, nbx = the launch's row
 //               blocks: gemm_epi_row_blocks) — instead of a separate pass over z.  Requires no bias, no activation, mode 0, no accumulate.
 //   addg, gate4: C += addg [gate bit]  (the identity shortcut's gated gradient added in the reduce convolution's input-gradient epilogue:
 //               gate4[(row * ldc + col) / 4] bit (col & 3), what rn_bn_apply wrote beside the block output; ldc % 4 == 0)
 struct GemmEpi { float* stat_part = nullptr; const float* addg = nullptr; const unsigned char* gate4 = nullptr; };
-extern thread_local GemmEpi g_gemm_epi;
-struct GemmEpiScope {
-    GemmEpiScope(float* stat_part, const float* addg = nullptr, const unsigned char* gate4 = nullptr) { g_gemm_epi.stat_part = stat_part; g_gemm_epi.addg = addg; g_gemm_epi.gate4 = gate4; }
-    ~GemmEpiScope() { g_gemm_epi = GemmEpi(); }
-};
 int gemm_epi_row_blocks(int M, int split_bf16);      // row blocks (= statistics partials per 64-channel chunk) of a launch: 128-row tiles (split-bf16) / 64-row tiles
 int launch_gemm(hipStream_t st, const float* A, int lda, const float* Bm, int ldb, const float* bias, float* C,
-                int ldc, int M, int N, int K, int transb, int act, int accumulate);
+                int ldc, int M, int N, int K, int transb, int act, int accumulate, const GemmEpi& epi = GemmEpi());
 int launch_gemm_dual_n(hipStream_t st, const float* A, int lda, const float* B0, const float* B1, int ldb, const float* bias0,
                        const float* bias1, float* C0, float* C1, int ldc, int M, int N, int K, int transb, int act);
 int launch_gemm_mirror(hipStream_t st, const float* A, int lda, const float* Bm, int ldb, const float* bias, float* C, float* mirror,
@@ -315,13 +312,14 @@ int launch_gemm_dual_k(hipStream_t st, const float* A0, const float* A1, int lda
 // split-bf16 GEMM (gemm_sb.hip): weights pre-split into bf16 planes by launch_gemm_split_b (up to 16 operands per launch),
 // then C = act(A B + bias) with mode 0 / 1 (two products sharing A) / 2 (one product over a concatenated K).
 // Usable when K % 32 == 0, N % 128 == 0, lda % 4 == 0 and A is 16-byte aligned (gemm_sb_usable).
-extern int g_gsb_dbg;   // tools/tune_gemm.py: 1 no loads in the 4-wave loop, 2 no stores, 4 force the 4-wave form, 8 the 16-wave form
 size_t gemm_sb_split_elems(int K, int N);
 int gemm_sb_usable(const void* A, int lda, int N, int K);
-int launch_gemm_split_b(hipStream_t st, int njobs, const float* const* src, unsigned short* const* dst, const int* ldb,
+int launch_gemm_split_b(hipStream_t st, const KernelChoices& kc, int njobs, const float* const* src, unsigned short* const* dst, const int* ldb,
                         const int* transb, const int* K, const int* N);
-int launch_gemm_sb(hipStream_t st, const float* A0, const float* A1, int lda, const unsigned short* Bs0, const unsigned short* Bs1,
-                   const float* bias0, const float* bias1, float* C0, float* C1, int ldc, int M, int N, int K, int act, int mode,
+// backward: a backward-only product (input gradients: their B planes come from a transposed / flipped gemm_split_b job), which takes the
+// four-product form when kc.bwd_four allows
+int launch_gemm_sb(hipStream_t st, const KernelChoices& kc, bool backward, const GemmEpi& epi, const float* A0, const float* A1, int lda,
+                   const unsigned short* Bs0, const unsigned short* Bs1, const float* bias0, const float* bias1, float* C0, float* C1, int ldc, int M, int N, int K, int act, int mode,
                    int accum = 0,       // accum: C += (the shortcut's input gradient lands on the reduce convolution's)
                    int conv_C = 0, int conv_H = 0, int conv_W = 0);   // conv_C > 0: A0 = NHWC image [M px][C], the product is its 3x3 'same'
                                                                        // convolution (K = 9 C, im2col rows formed on load, never stored)
@@ -340,12 +338,12 @@ struct TnJobs {
     float* out_w[TN_MAX_JOBS];      // combine targets (launch_reduce_slabs2_batch)
     float* out_b[TN_MAX_JOBS];
 };
-int launch_gemm_tn_sb_batch(hipStream_t st, const TnJobs& jobs, int njobs, int ldb, float* slab, int* nslab, int M, int N, int S, int want_bias);
+int launch_gemm_tn_sb_batch(hipStream_t st, const KernelChoices& kc, const TnJobs& jobs, int njobs, int ldb, float* slab, int* nslab, int M, int N, int S, int want_bias);
 int launch_reduce_slabs2_batch(hipStream_t st, const float* slab, int nslab, int64_t stride, const TnJobs& jobs, int njobs, int64_t n_w, int64_t n_b);
-int launch_gemm_tn_sb(hipStream_t st, const float* A, int lda, const float* Bm, int ldb, float* slab, int* nslab, int M, int N, int S,
+int launch_gemm_tn_sb(hipStream_t st, const KernelChoices& kc, const float* A, int lda, const float* Bm, int ldb, float* slab, int* nslab, int M, int N, int S,
                       int shift, int want_bias);
 // one product with K1 % 128 == 0 (resnet50_block's kernel gradients): slabs of K1 * N floats, `slab_cap` floats available
-int launch_gemm_tn_sb_tiles(hipStream_t st, const float* A, int lda, const float* Bm, int ldb, float* slab, int64_t slab_cap, int* nslab,
+int launch_gemm_tn_sb_tiles(hipStream_t st, const KernelChoices& kc, const float* A, int lda, const float* Bm, int ldb, float* slab, int64_t slab_cap, int* nslab,
                             int M, int K1, int N, int conv_C = 0, int conv_H = 0, int conv_W = 0);   // conv_C > 0: A = NHWC image, implicit im2col (K1 = 9 C)
 int launch_reduce_slabs2(hipStream_t st, const float* slab, int nslab, int64_t stride, float* out_w, int64_t n_w,
                          float* out_b, int64_t n_b);

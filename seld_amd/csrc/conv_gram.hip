@@ -149,15 +149,14 @@ __global__ __launch_bounds__(256, 2) void conv_first_gram_kernel(const float* __
 // recurrences, 192 blocks each: a half is done (~0.23 ms) before its recurrence is (0.29 ms), so the Gram product no longer shares the card with the second
 // layer's input projection, the heads and the losses (the heads' product took 44 us beside it, ~15 alone).  Same box: 2.652 / 2.645 ms per step with one
 // 128-block launch, 2.673 / 2.657 with two of 128, 2.631 / 2.633 with two of 192, 2.643 with two of 160.
-int g_gram_bg_blocks = 192;   // workgroups of a background launch
 // part / nparts: the launch covers the part-th of nparts equal shares of the tiles and writes its slabs behind those of the parts before it
 // (*n_slab = this part's slab count; the caller sums them)
-int launch_conv_first_gram(hipStream_t st, const float* x, float* slab, int* n_slab, int B, int H, int Cin, int background, int part, int nparts) {
+int launch_conv_first_gram(hipStream_t st, const KernelChoices& kc, const float* x, float* slab, int* n_slab, int B, int H, int Cin, int background, int part, int nparts) {
     if ((Cin != 7 && Cin != 10) || B <= 0 || H <= 0 || nparts < 1 || part < 0 || part >= nparts) return -2;
     const int all = B * ((H + 3) / 4);
     const int tile0 = (int)((int64_t)all * part / nparts), tile1 = (int)((int64_t)all * (part + 1) / nparts);
     const int ntiles = tile1 - tile0;
-    const int cap = background ? g_gram_bg_blocks : GRAM_MAX_BLOCKS;
+    const int cap = background ? kc.gram_bg_blocks : GRAM_MAX_BLOCKS;
     const int grid = ntiles < cap ? ntiles : cap;
     if (grid < 1) { *n_slab = 0; return 0; }
     const size_t lds_floor = background ? (size_t)112 * 1024 : 0;

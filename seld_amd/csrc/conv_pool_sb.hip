@@ -49,7 +49,7 @@ struct PoolSbGeom {
     static constexpr size_t SMEM = (size_t)(3 * PLANE + 3 * WPLANE) * 2 + 512 * sizeof(float);
 };
 
-// ONE: bf16 single-product mode (common.h g_mfma_one): operands rounded to nearest bf16, plane 0 only, one MFMA per (k-step, row, half)
+// ONE: bf16 single-product mode (common.h KernelChoices::mfma_one): operands rounded to nearest bf16, plane 0 only, one MFMA per (k-step, row, half)
 template <int CIN, bool WRITE_AMAX, bool ONE>
 __global__ __launch_bounds__(256, (CIN < 8 ? 2 : 1)) void conv_first_fwd_pool_sb_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                                         const float* __restrict__ bias,
@@ -298,14 +298,14 @@ __global__ __launch_bounds__(256, (CIN < 8 ? 2 : 1)) void conv_first_fwd_pool_sb
 }
 
 template <int CIN>
-static int launch_cpsb(hipStream_t st, const float* x, const float* w, const float* bias, const float* gamma, float* zext,
+static int launch_cpsb(hipStream_t st, const KernelChoices& kc, const float* x, const float* w, const float* bias, const float* gamma, float* zext,
                        unsigned char* amax, float* stat_partial, int* n_partial, int B, int H) {
     using G = PoolSbGeom<CIN>;
     const int ntiles = B * ((H + 9) / 10);
     const int grid = ntiles < CPSB_MAX_PERSISTENT ? ntiles : CPSB_MAX_PERSISTENT;
 #define CPSB_GO(A_)                                                                                                  \
     {                                                                                                                \
-        if (g_mfma_one) {                                                                                            \
+        if (kc.mfma_one) {                                                                                           \
         hipFuncSetAttribute(reinterpret_cast<const void*>(conv_first_fwd_pool_sb_kernel<CIN, A_, true>),             \
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::SMEM);                               \
         hipLaunchKernelGGL((conv_first_fwd_pool_sb_kernel<CIN, A_, true>), dim3(grid), dim3(256), G::SMEM, st, x, w, bias, \
@@ -325,10 +325,10 @@ static int launch_cpsb(hipStream_t st, const float* x, const float* w, const flo
 }
 
 // same contract as launch_conv_first_fwd_pool with z == nullptr (conv_pool.hip)
-int launch_conv_first_fwd_pool_sb(hipStream_t st, const float* x, const float* w, const float* bias, const float* gamma,
+int launch_conv_first_fwd_pool_sb(hipStream_t st, const KernelChoices& kc, const float* x, const float* w, const float* bias, const float* gamma,
                                   float* zext, unsigned char* amax, float* stat_partial, int* n_partial, int B, int H, int Cin) {
     if (H % 5 || H <= 0 || B <= 0) return -2;
-    if (Cin == 7) return launch_cpsb<7>(st, x, w, bias, gamma, zext, amax, stat_partial, n_partial, B, H);
-    if (Cin == 10) return launch_cpsb<10>(st, x, w, bias, gamma, zext, amax, stat_partial, n_partial, B, H);
+    if (Cin == 7) return launch_cpsb<7>(st, kc, x, w, bias, gamma, zext, amax, stat_partial, n_partial, B, H);
+    if (Cin == 10) return launch_cpsb<10>(st, kc, x, w, bias, gamma, zext, amax, stat_partial, n_partial, B, H);
     return -2;
 }

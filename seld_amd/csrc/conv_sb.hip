@@ -39,8 +39,6 @@ __device__ __forceinline__ void split3_pair(float x0, float x1, unsigned& h, uns
 // bf16 single-product mode: the two floats rounded to nearest-even bf16, packed like the planes above
 __device__ __forceinline__ unsigned rne_pair(float x0, float x1) { return bf16_rne_bits(x0) | (bf16_rne_bits(x1) << 16); }
 
-int g_mfma_one = 0;
-
 // w [9][in 64][out 64] fp32 -> planes [9][3][out 64][in 64] bf16 (transposed so a B fragment is 8 contiguous k)
 __global__ __launch_bounds__(256) void split_weights_kernel(const float* __restrict__ w, unsigned short* __restrict__ wsp, int one) {
     const int idx = blockIdx.x * 256 + threadIdx.x;
@@ -61,17 +59,17 @@ __global__ __launch_bounds__(256) void split_weights_kernel(const float* __restr
 // (wt[tap][co][ci] = w[8 - tap][ci][co], conv.hip flip_weights_kernel) split directly from the unflipped tensor
 __global__ __launch_bounds__(256) void split_weights_batch_kernel(SplitWeightJobs jobs) { split_weights_body(jobs, blockIdx.y, blockIdx.x); }
 
-int launch_split_weights_batch(hipStream_t st, int n, const float* const* w, unsigned short* const* dst, const int* flip) {
+int launch_split_weights_batch(hipStream_t st, const KernelChoices& kc, int n, const float* const* w, unsigned short* const* dst, const int* flip) {
     if (n <= 0 || n > 8) return -1;
     SplitWeightJobs j;
-    j.one = g_mfma_one;
+    j.one = kc.mfma_one;
     for (int i = 0; i < n; ++i) { j.w[i] = w[i]; j.dst[i] = dst[i]; j.flip[i] = flip[i]; }
     hipLaunchKernelGGL(split_weights_batch_kernel, dim3(9 * 4096 / 256, n), dim3(256), 0, st, j);
     return 0;
 }
 
-int launch_split_weights(hipStream_t st, const float* w, unsigned short* wsp) {
-    hipLaunchKernelGGL(split_weights_kernel, dim3(9 * 4096 / 256), dim3(256), 0, st, w, wsp, g_mfma_one);
+int launch_split_weights(hipStream_t st, const KernelChoices& kc, const float* w, unsigned short* wsp) {
+    hipLaunchKernelGGL(split_weights_kernel, dim3(9 * 4096 / 256), dim3(256), 0, st, w, wsp, kc.mfma_one);
     return 0;
 }
 
@@ -712,14 +710,9 @@ __global__ __launch_bounds__(32 * ((R << WLOG2) / 32) * 2) void conv64_fwd_sbd_k
     }
 }
 
-int g_bwd_four = 1;        // option "bwd_four_products": backward-only products (input / kernel gradients) on four of the six split-bf16 terms
-static thread_local int s_sbd_four = 0; // set around an input-gradient launch (launch_conv64_dgrad_sb); per host thread: two contexts driven by two threads must not see each other's
-int g_sbd_dgrad_r8 = 1;    // option "dgrad_r8": the W = 16 four-product input gradient on 8-row tiles (4 waves, 74 KB of LDS instead of 8 waves, 107 KB: two workgroups per
-                           // CU, or one beside a kernel-gradient workgroup of the side stream; the same taps and k-steps per pixel: the same bits)
-int g_conv64_dbuf = 1;     // 1: conv64_fwd_sbd_kernel (double-buffered weights) for W = 16 / 4; 0: conv64_fwd_sbr_kernel
-
+// four: the four-product form (an input gradient under kc.bwd_four: conv64_sb below)
 template <int WLOG2, int R>
-static int launch_sbd(hipStream_t st, const float* x, const unsigned short* wsp, const float* bias, float* z,
+static int launch_sbd(hipStream_t st, const KernelChoices& kc, bool four, const float* x, const unsigned short* wsp, const float* bias, float* z,
                       float* stat_partial, int* n_partial, int B, int H, const float* pre_scale = nullptr, const float* pre_shift = nullptr,
                       float* pre_out = nullptr, const float* ext_gamma = nullptr, float* ext_out = nullptr) {
     constexpr int W = 1 << WLOG2, NW = (R * W) / 32, NT = 64 * NW, NPIX = (R + 2) * W;
@@ -734,7 +727,7 @@ static int launch_sbd(hipStream_t st, const float* x, const unsigned short* wsp,
         hipLaunchKernelGGL((conv64_fwd_sbd_kernel<WLOG2, R, S_, O_>), dim3(grid), dim3(NT), smem, st, x, wsp, bias, z, stat_partial, B, H);   \
     }
     if (pre_scale) {      // BatchNorm + ReLU of the previous block on load (six-product forward; launch_conv64_fwd_sb checks the shapes)
-        if (g_mfma_one || !pre_shift || pre_out == x) return -3;      // pre_out == nullptr: inference (nobody reads the activated tensor)
+        if (kc.mfma_one || !pre_shift || pre_out == x) return -3;      // pre_out == nullptr: inference (nobody reads the activated tensor)
 #define SBD_PRE_GO(S_, E_)                                                                                                                  \
         {                                                                                                                                   \
             hipFuncSetAttribute(reinterpret_cast<const void*>(conv64_fwd_sbd_kernel<WLOG2, R, S_, false, false, true, E_>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem); \
@@ -756,8 +749,8 @@ static int launch_sbd(hipStream_t st, const float* x, const unsigned short* wsp,
         return 0;
     }
     if (ext_out) return -3;      // window extremes come with the PRE loader only (the training step's second block)
-    if (g_mfma_one) { if (stat_partial) SBD_GO(true, true) else SBD_GO(false, true) }
-    else if (s_sbd_four && !stat_partial) {
+    if (kc.mfma_one) { if (stat_partial) SBD_GO(true, true) else SBD_GO(false, true) }
+    else if (four && !stat_partial) {
         // two planes of region and weights: 106 KB at W = 16, 84 KB at W = 4 — at W = 4 a kernel-gradient workgroup of the side stream (70 KB, option
         // conv_wgrad_side) fits on the same CU beside it
         const size_t smem4 = (size_t)(2 * (NPIX + 1) * 64 + 2 * 2 * 64 * 64) * sizeof(unsigned short);
@@ -783,17 +776,19 @@ static int launch_sbd_four(hipStream_t st, const float* x, const unsigned short*
     return 0;
 }
 
-int conv64_fwd_sb_takes_pre(int W) { return (W == 16 || W == 4) && g_conv64_dbuf && !g_mfma_one; }
-int launch_conv64_fwd_sb(hipStream_t st, const float* x, const unsigned short* wsp, const float* bias, float* z,
-                         float* stat_partial, int* n_partial, int B, int H, int W, const float* pre_scale, const float* pre_shift, float* pre_out,
-                         const float* ext_gamma, float* ext_out) {
-    if ((pre_scale || ext_out) && !conv64_fwd_sb_takes_pre(W)) return -3;
-    if (W == 16 && g_conv64_dbuf && s_sbd_four && g_sbd_dgrad_r8 && !stat_partial && !pre_scale && !ext_out && !g_mfma_one)
+int conv64_fwd_sb_takes_pre(const KernelChoices& kc, int W) { return (W == 16 || W == 4) && kc.conv64_dbuf && !kc.mfma_one; }
+// the forward convolution and, on the flipped weights, its input gradient (backward: a backward-only product, on four products when the option allows)
+static int conv64_sb(hipStream_t st, const KernelChoices& kc, bool backward, const float* x, const unsigned short* wsp, const float* bias, float* z,
+                     float* stat_partial, int* n_partial, int B, int H, int W, const float* pre_scale, const float* pre_shift, float* pre_out,
+                     const float* ext_gamma, float* ext_out) {
+    const bool four = backward && kc.bwd_four && !kc.mfma_one;
+    if ((pre_scale || ext_out) && !conv64_fwd_sb_takes_pre(kc, W)) return -3;
+    if (W == 16 && kc.conv64_dbuf && four && kc.dgrad_r8 && !stat_partial && !pre_scale && !ext_out)
         return launch_sbd_four<4, 8>(st, x, wsp, bias, z, n_partial, B, H);      // option "dgrad_r8"
     // (W = 4 on 40-row tiles — 76 KB, two per CU, 480 tiles in one round — measured: 2.331 -> 2.346 ms per step, not kept: profiles/r05_gru_experiments.txt)
-    if (W == 16 && g_conv64_dbuf) return launch_sbd<4, 16>(st, x, wsp, bias, z, stat_partial, n_partial, B, H, pre_scale, pre_shift, pre_out, ext_gamma, ext_out);   // 8 waves, 156 KB
-    if (W == 4 && g_conv64_dbuf) return launch_sbd<2, 48>(st, x, wsp, bias, z, stat_partial, n_partial, B, H, pre_scale, pre_shift, pre_out);    // 6 waves
-    if (W == 8 && g_conv64_dbuf) return launch_sbd<3, 32>(st, x, wsp, bias, z, stat_partial, n_partial, B, H);    // 8 waves (resnet50_block stage 1)
+    if (W == 16 && kc.conv64_dbuf) return launch_sbd<4, 16>(st, kc, four, x, wsp, bias, z, stat_partial, n_partial, B, H, pre_scale, pre_shift, pre_out, ext_gamma, ext_out);   // 8 waves, 156 KB
+    if (W == 4 && kc.conv64_dbuf) return launch_sbd<2, 48>(st, kc, four, x, wsp, bias, z, stat_partial, n_partial, B, H, pre_scale, pre_shift, pre_out);    // 6 waves
+    if (W == 8 && kc.conv64_dbuf) return launch_sbd<3, 32>(st, kc, four, x, wsp, bias, z, stat_partial, n_partial, B, H);    // 8 waves (resnet50_block stage 1)
     if (W == 16) return launch_sbr<4, 16, true>(st, x, wsp, bias, z, stat_partial, n_partial, B, H);    // 8 waves, 153 KB
     if (W == 4) return launch_sbr<2, 48, false>(st, x, wsp, bias, z, stat_partial, n_partial, B, H);   // 6 waves (halo columns: no room for 8)
     const int npix = B * H * W;
@@ -811,11 +806,14 @@ int launch_conv64_fwd_sb(hipStream_t st, const float* x, const unsigned short* w
     return 0;
 }
 
+int launch_conv64_fwd_sb(hipStream_t st, const KernelChoices& kc, const float* x, const unsigned short* wsp, const float* bias, float* z,
+                         float* stat_partial, int* n_partial, int B, int H, int W, const float* pre_scale, const float* pre_shift, float* pre_out,
+                         const float* ext_gamma, float* ext_out) {
+    return conv64_sb(st, kc, false, x, wsp, bias, z, stat_partial, n_partial, B, H, W, pre_scale, pre_shift, pre_out, ext_gamma, ext_out);
+}
+
 // the input gradient of a 64 -> 64 3x3 convolution = the forward kernel on dz with the flipped, channel-swapped weights (wsp_flip); four products when
-// the option allows (the forward itself never takes that path: s_sbd_four is set here only)
-int launch_conv64_dgrad_sb(hipStream_t st, const float* dz, const unsigned short* wsp_flip, float* dx, int B, int H, int W) {
-    s_sbd_four = g_bwd_four && !g_mfma_one;
-    const int rc = launch_conv64_fwd_sb(st, dz, wsp_flip, nullptr, dx, nullptr, nullptr, B, H, W);
-    s_sbd_four = 0;
-    return rc;
+// the option allows (the forward itself never takes that path: only this caller passes backward = true)
+int launch_conv64_dgrad_sb(hipStream_t st, const KernelChoices& kc, const float* dz, const unsigned short* wsp_flip, float* dx, int B, int H, int W) {
+    return conv64_sb(st, kc, true, dz, wsp_flip, nullptr, dx, nullptr, nullptr, B, H, W, nullptr, nullptr, nullptr, nullptr, nullptr);
 }

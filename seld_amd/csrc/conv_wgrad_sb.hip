@@ -47,8 +47,8 @@ __device__ __forceinline__ bf16x8 wgsb_frag(const char* p0, const char* p1) {
 
 __device__ __forceinline__ unsigned wgsb_rne_pair(float x0, float x1) { return bf16_rne_bits(x0) | (bf16_rne_bits(x1) << 16); }
 
-// ONE: bf16 single-product mode (common.h g_mfma_one): operands rounded to nearest bf16, plane 0 only, one MFMA per (k-step, tap)
-// FOUR (option "bwd_four_products", conv_sb.hip g_bwd_four): the two products with a lo factor are dropped and the lo planes neither staged nor read
+// ONE: bf16 single-product mode (common.h KernelChoices::mfma_one): operands rounded to nearest bf16, plane 0 only, one MFMA per (k-step, tap)
+// FOUR (option "bwd_four_products", common.h KernelChoices::bwd_four): the two products with a lo factor are dropped and the lo planes neither staged nor read
 template <int WLOG2, bool ONE, bool FOUR = false>
 __global__ __launch_bounds__(256, 2) void conv64_wgrad_sb_kernel(const float* __restrict__ x, const float* __restrict__ dz,
                                                                  float* __restrict__ slab, int B, int H) {
@@ -226,7 +226,7 @@ __global__ __launch_bounds__(256, 2) void conv64_wgrad_sb_kernel(const float* __
 
 int conv64_wgrad_sb_usable(int W) { return W == 16 || W == 8 || W == 4; }
 
-int launch_conv64_wgrad_sb(hipStream_t st, const float* x, const float* dz, float* slab, int* n_slab, int B, int H, int W) {
+int launch_conv64_wgrad_sb(hipStream_t st, const KernelChoices& kc, const float* x, const float* dz, float* slab, int* n_slab, int B, int H, int W) {
     if (!conv64_wgrad_sb_usable(W) || B <= 0 || H <= 0) return -2;
     const int R = WGSB_PXC / W;
     const int nchunks = B * ((H + R - 1) / R);
@@ -238,11 +238,11 @@ int launch_conv64_wgrad_sb(hipStream_t st, const float* x, const float* dz, floa
     const size_t smem = (size_t)3 * WGSB_HALO * 128 + (size_t)3 * WGSB_PXC * 128 + 16 * 64 * sizeof(float);
 #define WGSB_GO(L)                                                                                            \
     {                                                                                                         \
-        if (g_mfma_one) {                                                                                     \
+        if (kc.mfma_one) {                                                                                    \
             hipFuncSetAttribute(reinterpret_cast<const void*>(conv64_wgrad_sb_kernel<L, true>),               \
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);                       \
             hipLaunchKernelGGL((conv64_wgrad_sb_kernel<L, true>), dim3(grid), dim3(256), smem, st, x, dz, slab, B, H);  \
-        } else if (g_bwd_four) {                                                                              \
+        } else if (kc.bwd_four) {                                                                             \
             hipFuncSetAttribute(reinterpret_cast<const void*>(conv64_wgrad_sb_kernel<L, false, true>),        \
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);                       \
             hipLaunchKernelGGL((conv64_wgrad_sb_kernel<L, false, true>), dim3(grid), dim3(256), smem, st, x, dz, slab, B, H); \

@@ -114,7 +114,6 @@ struct seld_ctx {
     float *wgrad_slab = nullptr, *tn_slab = nullptr, *cs_slab = nullptr, *wflip = nullptr;
     float *wgrad_slab_side = nullptr, *dzbuf_alt = nullptr;      // conv_wgrad_side: the side stream's own slabs, the second dz buffer (allocated when the option is set)
     int conv_wgrad_side = 1;
-    int dgrad_r8 = 1;      // conv_sb.hip g_sbd_dgrad_r8: the W = 16 four-product input gradient on 8-row tiles (round 5: 2.510 -> 2.496 ms same box)
     float *dgx[SELD_MAX_LAYERS][2] = {}, *dgh[SELD_MAX_LAYERS][2] = {};   // per GRU layer: the side stream reads them later
     float* tn_slab_side = nullptr;
     unsigned short* wsplit = nullptr;      // per 64->64 conv layer i: [2 i] forward, [2 i + 1] flipped; each [9][3][64][64] bf16 planes
@@ -148,14 +147,11 @@ struct seld_ctx {
     int sync_world = 1;
     double* sync_buf = nullptr;                   // [128] (resnet50_block: [16][128]) sums handed to sync_fn
     bool sync_failed = false;                     // the all-reduce callback failed inside a helper: reported at the end of the pass
-    int bf16_single = 0;                          // SELD_DTYPE_BF16 / option "bf16_single": one bf16 MFMA product per fp32 product (common.h g_mfma_one)
-    // kernel choices the launchers read from process-wide variables (common.h): kept PER CONTEXT here and copied into those variables at the
-    // start of every forward / backward pass (apply_kernel_choices), so that setting one on a context never changes another context's arithmetic
-    int bwd_four_products = 1, conv64_dbuf = 1, tn_tile_blocks = 384, gram_bg_blocks = 192;
+    // what the launchers choose their kernels by (common.h): seld_create (SELD_DTYPE_BF16 -> mfma_one) and seld_set_option write it, the passes hand it
+    // to every launcher that reads a field — a context's arithmetic depends on nothing outside the context and the call
+    KernelChoices kc;
     int xc_fused_bn_sums = 1;              // ... and, for a folded unit, the previous BatchNormalization's backward sums too (0: xc_reduce's pass over (z, gY))
     int xc_fused_dw_bwd = 1;               // xception_block: the depthwise kernel gradient's slabs come out of the input-gradient pass (round 5; 0: dw3x3_bwd_w on the side stream)
-    int xc_w16 = 1;                        // xception_block: the row-per-workgroup depthwise kernels for W = 16 (0: the generic kernel)
-    int xc_xcd_map = 1;                    // xception_block: XCD-contiguous row ranges in the depthwise kernels (xception.hip; 0: identity map, for A/B)
     int rn_epi_stats = 1;                  // resnet50_block: a convolution's BatchNorm statistics leave with its product's epilogue (round 5; 0: the separate pass over z)
     int rn_epi_add = 1;                    // ... and the identity shortcut's gated gradient is added in the reduce convolution's input-gradient epilogue
     // data parallelism inside the library (seld_dp_*): one RCCL communicator, a communication stream, two events
@@ -234,8 +230,6 @@ struct ProfScope {
 // ---- shared by the passes (api.hip)
 // side stream: everything enqueued on it after this call starts once the main stream has reached this point
 void fork_side(seld_ctx* c);
-// the launchers' kernel-choice variables (common.h) take THIS context's values for the pass that starts here
-void apply_kernel_choices(const seld_ctx* c);
 // which path a context takes (the forward pass, its backward pass and the loss gradients must agree)
 bool gru_sb(const seld_ctx* c, const GruL& G);
 bool heads_general(const seld_ctx* c);

@@ -19,7 +19,7 @@ static int prepare_heads_weff(seld_ctx* c, hipStream_t st) {
 static int prepare_gemm_splits(seld_ctx* c, hipStream_t st, bool with_grad_orientation) {
     const float* src[16]; unsigned short* dst[16]; int ldb[16], tb[16], K[16], N[16];
     int n = 0;
-    auto flush = [&]() { int rc = n ? launch_gemm_split_b(st, n, src, dst, ldb, tb, K, N) : 0; n = 0; return rc; };
+    auto flush = [&]() { int rc = n ? launch_gemm_split_b(st, c->kc, n, src, dst, ldb, tb, K, N) : 0; n = 0; return rc; };
     auto add = [&](const float* w, unsigned short* d, int ld, int transb, int k, int nn) {
         src[n] = w; dst[n] = d; ldb[n] = ld; tb[n] = transb; K[n] = k; N[n] = nn;
         return ++n == 16 ? flush() : 0;
@@ -74,7 +74,7 @@ static void rn_weight_prep(seld_ctx* c, hipStream_t st, bool save) {
     int n = 0;
     auto add = [&](const float* w, unsigned short* d, int ld, int transb, int k, int nn) {
         src[n] = w; dst[n] = d; ldb[n] = ld; tb[n] = transb; Ks[n] = k; Ns[n] = nn;
-        if (++n == 16) { launch_gemm_split_b(st, n, src, dst, ldb, tb, Ks, Ns); n = 0; }
+        if (++n == 16) { launch_gemm_split_b(st, c->kc, n, src, dst, ldb, tb, Ks, Ns); n = 0; }
     };
     for (auto& R : c->rn)
         for (RnConv* cv : {&R.c[0], &R.c[1], &R.c[2], &R.sc}) {
@@ -85,7 +85,7 @@ static void rn_weight_prep(seld_ctx* c, hipStream_t st, bool save) {
                 else add(c->params + cv->w_off, cv->wsp_t, N, 1, N, K);
             }
         }
-    if (n) launch_gemm_split_b(st, n, src, dst, ldb, tb, Ks, Ns);
+    if (n) launch_gemm_split_b(st, c->kc, n, src, dst, ldb, tb, Ks, Ns);
     const float* w9[8]; unsigned short* d9[8]; int f9[8];
     n = 0;
     for (auto& R : c->rn) {
@@ -94,9 +94,9 @@ static void rn_weight_prep(seld_ctx* c, hipStream_t st, bool save) {
         if (R.c[1].w2) { launch_rn_w32_embed(st, wsrc, R.c[1].w2); wsrc = R.c[1].w2; }
         w9[n] = wsrc; d9[n] = R.c[1].wsp9; f9[n++] = 0;
         if (save) { w9[n] = wsrc; d9[n] = R.c[1].wsp9_flip; f9[n++] = 1; }
-        if (n >= 7) { launch_split_weights_batch(st, n, w9, d9, f9); n = 0; }
+        if (n >= 7) { launch_split_weights_batch(st, c->kc, n, w9, d9, f9); n = 0; }
     }
-    if (n) launch_split_weights_batch(st, n, w9, d9, f9);
+    if (n) launch_split_weights_batch(st, c->kc, n, w9, d9, f9);
 }
 
 // BatchNormalization coefficients of a 64-channel layer (a conv block or an xception unit: the same field names) from `np` partial
@@ -136,7 +136,6 @@ static int forward_weight_prep(seld_ctx* c, bool save, bool* prep_on_side, bool*
     // every weight-only pre-pass of the step in ONE launch (prep.hip): the split-bf16 planes of the GEMM and 64 -> 64 conv
     // weights (with the gradient orientations / flipped taps when a backward follows) and the folded head weights
     GemmSplitJobs a; SplitWeightJobs b; HeadsLin h;
-    a.one = b.one = g_mfma_one;     // bf16 single-product mode: plane 0 = round-to-nearest bf16 (prep.h)
     int na = 0, nb = 0;
     bool fits = true;
     auto adda = [&](const float* w, unsigned short* d, int ld, int transb, int k, int nn) {
@@ -179,12 +178,12 @@ static int forward_weight_prep(seld_ctx* c, bool save, bool* prep_on_side, bool*
         // (the Gram launches, the kernel gradients) is ordered behind it by the stream itself.
         *prep_on_side = c->prep_side && c->ev_prep && c->xc.empty() && c->rn.empty() && c->conv.size() >= 2;
         if (*prep_on_side) fork_side(c);
-        if (launch_weight_prep(*prep_on_side ? c->side : st, a, na, b, nb, h, lin ? c->weff : nullptr)) return fail(c, SELD_ERR_UNSUPPORTED, "weight_prep");
+        if (launch_weight_prep(*prep_on_side ? c->side : st, c->kc, a, na, b, nb, h, lin ? c->weff : nullptr)) return fail(c, SELD_ERR_UNSUPPORTED, "weight_prep");
         if (*prep_on_side) hipEventRecord(c->ev_prep, c->side);
     } else {      // more jobs than one launch takes (not a seldnet.json shape): the stand-alone kernels
         if (prepare_gemm_splits(c, st, save)) return fail(c, SELD_ERR_UNSUPPORTED, "gemm_split_b");
         if (lin && prepare_heads_weff(c, st)) return fail(c, SELD_ERR_UNSUPPORTED, "heads_weff");
-        if (nb && launch_split_weights_batch(st, nb, b.w, b.dst, b.flip)) return fail(c, SELD_ERR_UNSUPPORTED, "split_weights");
+        if (nb && launch_split_weights_batch(st, c->kc, nb, b.w, b.dst, b.flip)) return fail(c, SELD_ERR_UNSUPPORTED, "split_weights");
     }
     return SELD_OK;
 }
@@ -211,10 +210,10 @@ static int forward_conv_blocks(seld_ctx* c, const FwdPass& p, bool prep_on_side,
         // the pooled tensor's BatchNorm + ReLU pass folded into the next block's loader (conv_sb.hip PRE): training with the Gram backward (zext kept
         // beside p), and inference (nobody reads p: the extremes go to zext and p is not written at all)
         const bool pre_next = fused_pool && (gram || !p.save) && c->conv2_pre_fused && !p.conv_drop && c->arch.first_kind == SELD_FIRST_SIMPLE_CONV &&
-                              i + 1 < c->conv.size() && c->conv64_split_bf16 && !g_mfma_one && conv64_fwd_sb_takes_pre(c->conv[i + 1].W);
+                              i + 1 < c->conv.size() && c->conv64_split_bf16 && !c->kc.mfma_one && conv64_fwd_sb_takes_pre(c->kc, c->conv[i + 1].W);
         if (fused_pool) {
             PROF(c, tn);   // level 1
-            if (launch_conv_first_fwd_pool(st, in, c->params + L.w_off, c->params + L.b_off, c->params + L.g_off,
+            if (launch_conv_first_fwd_pool(st, c->kc, in, c->params + L.w_off, c->params + L.b_off, c->params + L.g_off,
                                            (p.save && !gram) ? L.z : nullptr, (gram || pre_next) ? L.zext : L.p, p.save ? L.amax : nullptr, stat,
                                            &npart, B, L.H, L.Cin, c->conv1_split_bf16))
                 return fail(c, SELD_ERR_UNSUPPORTED, "conv_first_fwd_pool");
@@ -231,9 +230,9 @@ static int forward_conv_blocks(seld_ctx* c, const FwdPass& p, bool prep_on_side,
                 // ext_now (option "conv3_pre_fused"): this block's (1,4) pooling is split the same way — the epilogue keeps every window's extreme of z
                 // (EXT), the NEXT block's loader applies BatchNorm + ReLU to them and writes this block's pooled tensor: no pooling pass over z
                 ext_now = pre_pending && c->conv3_pre_fused && L.zext && L.W == 16 && L.pt == 1 && L.pf == 4 && !p.conv_drop && i + 1 < c->conv.size() &&
-                          c->conv[i + 1].W == 4 && conv64_fwd_sb_takes_pre(4);
+                          c->conv[i + 1].W == 4 && conv64_fwd_sb_takes_pre(c->kc, 4);
                 // (inference: the previous block's activated tensor is read by nobody -> not written)
-                if (launch_conv64_fwd_sb(st, pre_pending ? P.zext : in, c->wsp_fwd[i], c->params + L.b_off, L.z, stat, &npart, B, L.H, L.W,
+                if (launch_conv64_fwd_sb(st, c->kc, pre_pending ? P.zext : in, c->wsp_fwd[i], c->params + L.b_off, L.z, stat, &npart, B, L.H, L.W,
                                          pre_pending ? P.scale : nullptr, pre_pending ? P.shift : nullptr, (pre_pending && p.save) ? P.p : nullptr,
                                          ext_now ? c->params + L.g_off : nullptr, ext_now ? L.zext : nullptr))
                     return fail(c, SELD_ERR_UNSUPPORTED, "conv64_fwd_sb");
@@ -288,7 +287,7 @@ static int forward_xception(seld_ctx* c, const FwdPass& p, const float** feat) {
         } else {
         {
             PROF2(c, "xc_depthwise_fwd");
-            launch_dw3x3_fwd(st, uin, c->params + U.dw_off, U.dwo, B, S, 16);       // ReLU on load, no bias
+            launch_dw3x3_fwd(st, c->kc, uin, c->params + U.dw_off, U.dwo, B, S, 16);       // ReLU on load, no bias
         }
         {
             PROF2(c, "xc_pointwise_fwd");
@@ -333,7 +332,7 @@ static int forward_resnet(seld_ctx* c, const FwdPass& p, bool rn_prep_on_side, c
         if (sc_side) {
             hipEventRecord(c->ev_rn_ready, st); hipStreamWaitEvent(c->side, c->ev_rn_ready, 0);
             int nb_ = 0;
-            if (launch_rn_product_fwd(c->side, X, R.Cin * R.stride_f, c->params + R.sc.w_off, sb ? R.sc.wsp : nullptr, R.sc.z, (int)M, R.Cin, 4 * w,
+            if (launch_rn_product_fwd(c->side, c->kc, X, R.Cin * R.stride_f, c->params + R.sc.w_off, sb ? R.sc.wsp : nullptr, R.sc.z, (int)M, R.Cin, 4 * w,
                                       epi_stats ? c->rn_part_side : nullptr, &nb_, c->rn_part_floats))
                 return fail(c, SELD_ERR_INVALID, "resnet50_block: projection shortcut product refused");
             rn_bn(c, c->side, R.sc, M, p.training, nb_, c->rn_part_side);
@@ -341,7 +340,7 @@ static int forward_resnet(seld_ctx* c, const FwdPass& p, bool rn_prep_on_side, c
         }
         // 1x1 (frequency stride = doubled row stride of the operand), BN, ReLU
         int nb0 = 0;
-        { PROF3(c, "rn_products_fwd"); rc_ = launch_rn_product_fwd(st, X, R.Cin * R.stride_f, c->params + R.c[0].w_off, sb ? R.c[0].wsp : nullptr, R.c[0].z, (int)M, R.Cin, w,
+        { PROF3(c, "rn_products_fwd"); rc_ = launch_rn_product_fwd(st, c->kc, X, R.Cin * R.stride_f, c->params + R.c[0].w_off, sb ? R.c[0].wsp : nullptr, R.c[0].z, (int)M, R.Cin, w,
                                                                    epi_stats ? c->rn_part : nullptr, &nb0, c->rn_part_floats); }
         if (rc_) return fail(c, SELD_ERR_INVALID, "resnet50_block: reduce convolution's product refused");
         { PROF3(c, "rn_bn_fwd"); rn_bn(c, st, R.c[0], M, p.training, nb0); }
@@ -351,18 +350,18 @@ static int forward_resnet(seld_ctx* c, const FwdPass& p, bool rn_prep_on_side, c
         if (sb && rn_c1_direct(R)) {
             int npart = 0;
             if (R.c[1].w2) {      // stage 0: the epilogue's sums are per (bin parity, channel): the statistics pass instead
-                { PROF3(c, "rn_products_fwd"); launch_conv64_fwd_sb(st, R.y0, R.c[1].wsp9, nullptr, R.c[1].z, nullptr, nullptr, B, S, rn_c1_width(R)); }
+                { PROF3(c, "rn_products_fwd"); launch_conv64_fwd_sb(st, c->kc, R.y0, R.c[1].wsp9, nullptr, R.c[1].z, nullptr, nullptr, B, S, rn_c1_width(R)); }
                 { PROF3(c, "rn_bn_fwd"); rn_bn(c, st, R.c[1], M, p.training); }
             } else {
                 // the conv epilogue's partial sums land in rn_part: at most conv_sb_partial_capacity() [128]-float partials, which must fit before the launch
                 if (p.training && (size_t)conv_sb_partial_capacity() * 128 > c->rn_part_floats)
                     return fail(c, SELD_ERR_INVALID, "resnet50_block: more BatchNorm partials than rn_part holds");
-                { PROF3(c, "rn_products_fwd"); launch_conv64_fwd_sb(st, R.y0, R.c[1].wsp9, nullptr, R.c[1].z, p.training ? c->rn_part : nullptr, &npart, B, S, R.Wout); }
+                { PROF3(c, "rn_products_fwd"); launch_conv64_fwd_sb(st, c->kc, R.y0, R.c[1].wsp9, nullptr, R.c[1].z, p.training ? c->rn_part : nullptr, &npart, B, S, R.Wout); }
                 { PROF3(c, "rn_bn_fwd"); rn_bn(c, st, R.c[1], M, p.training, npart); }
             }
         } else if (sb && rn_c1_implicit(c, R)) {
             int nb1 = 0;
-            { PROF3(c, "rn_products_fwd"); rc_ = launch_rn_conv3_fwd(st, R.y0, R.c[1].wsp, R.c[1].z, B, S, R.Wout, w, w, epi_stats ? c->rn_part : nullptr, &nb1,
+            { PROF3(c, "rn_products_fwd"); rc_ = launch_rn_conv3_fwd(st, c->kc, R.y0, R.c[1].wsp, R.c[1].z, B, S, R.Wout, w, w, epi_stats ? c->rn_part : nullptr, &nb1,
                                                                      c->rn_part_floats); }
             if (rc_) return fail(c, SELD_ERR_INVALID, "resnet50_block: 3x3 convolution's product refused");
             { PROF3(c, "rn_bn_fwd"); rn_bn(c, st, R.c[1], M, p.training, nb1); }
@@ -371,7 +370,7 @@ static int forward_resnet(seld_ctx* c, const FwdPass& p, bool rn_prep_on_side, c
             if (!R.c[1].col && dalloc(c, &R.c[1].col, (size_t)M * 9 * w)) return fail(c, SELD_ERR_NOMEM, "im2col tensor");
             launch_im2col3x3(st, R.y0, R.c[1].col, B, S, R.Wout, w);
             int nb1 = 0;
-            { PROF3(c, "rn_products_fwd"); rc_ = launch_rn_product_fwd(st, R.c[1].col, 9 * w, c->params + R.c[1].w_off, sb ? R.c[1].wsp : nullptr, R.c[1].z, (int)M, 9 * w, w,
+            { PROF3(c, "rn_products_fwd"); rc_ = launch_rn_product_fwd(st, c->kc, R.c[1].col, 9 * w, c->params + R.c[1].w_off, sb ? R.c[1].wsp : nullptr, R.c[1].z, (int)M, 9 * w, w,
                                                                        epi_stats ? c->rn_part : nullptr, &nb1, c->rn_part_floats); }
             if (rc_) return fail(c, SELD_ERR_INVALID, "resnet50_block: 3x3 convolution's product refused");
             { PROF3(c, "rn_bn_fwd"); rn_bn(c, st, R.c[1], M, p.training, nb1); }
@@ -379,7 +378,7 @@ static int forward_resnet(seld_ctx* c, const FwdPass& p, bool rn_prep_on_side, c
         { PROF3(c, "rn_bn_fwd"); launch_rn_bn_apply(st, R.c[1].z, R.c[1].coef, nullptr, R.y1, M, w, 1); }
         // 1x1 expand, BN; shortcut; out = ReLU(y + r)
         int nb2 = 0;
-        { PROF3(c, "rn_products_fwd"); rc_ = launch_rn_product_fwd(st, R.y1, w, c->params + R.c[2].w_off, sb ? R.c[2].wsp : nullptr, R.c[2].z, (int)M, w, 4 * w,
+        { PROF3(c, "rn_products_fwd"); rc_ = launch_rn_product_fwd(st, c->kc, R.y1, w, c->params + R.c[2].w_off, sb ? R.c[2].wsp : nullptr, R.c[2].z, (int)M, w, 4 * w,
                                                                    epi_stats ? c->rn_part : nullptr, &nb2, c->rn_part_floats); }
         if (rc_) return fail(c, SELD_ERR_INVALID, "resnet50_block: expand convolution's product refused");
         { PROF3(c, "rn_bn_fwd"); rn_bn(c, st, R.c[2], M, p.training, nb2); }
@@ -387,7 +386,7 @@ static int forward_resnet(seld_ctx* c, const FwdPass& p, bool rn_prep_on_side, c
             if (sc_side) hipStreamWaitEvent(st, c->ev_rn_free[0], 0);
             else {
                 int nbs = 0;
-                { PROF3(c, "rn_products_fwd"); rc_ = launch_rn_product_fwd(st, X, R.Cin * R.stride_f, c->params + R.sc.w_off, sb ? R.sc.wsp : nullptr, R.sc.z, (int)M, R.Cin, 4 * w,
+                { PROF3(c, "rn_products_fwd"); rc_ = launch_rn_product_fwd(st, c->kc, X, R.Cin * R.stride_f, c->params + R.sc.w_off, sb ? R.sc.wsp : nullptr, R.sc.z, (int)M, R.Cin, 4 * w,
                                                                            epi_stats ? c->rn_part : nullptr, &nbs, c->rn_part_floats); }
                 if (rc_) return fail(c, SELD_ERR_INVALID, "resnet50_block: projection shortcut product refused");
                 { PROF3(c, "rn_bn_fwd"); rn_bn(c, st, R.sc, M, p.training, nbs); }
@@ -423,7 +422,7 @@ static int forward_gru(seld_ctx* c, const FwdPass& p, const float** feat_io) {
                 launch_dropout(st, c->ones, G.rmask[d], (int64_t)B * 128, rate, c->dropout_seed, 98u + 4u * (unsigned)i + d, c->dropout_cur);
                 launch_mask_rows(st, feat, G.imask[d], G.xm[d], rows, S, G.in_feat, 0);
                 if (gru_sb(c, G) && gemm_sb_usable(G.xm[d], G.in_feat, 384, G.in_feat))
-                    launch_gemm_sb(st, G.xm[d], nullptr, G.in_feat, c->ksp_fwd[i][d], nullptr, c->params + G.b_off[d], nullptr, G.gx[d], nullptr, 384, rows, 384,
+                    launch_gemm_sb(st, c->kc, false, GemmEpi(), G.xm[d], nullptr, G.in_feat, c->ksp_fwd[i][d], nullptr, c->params + G.b_off[d], nullptr, G.gx[d], nullptr, 384, rows, 384,
                                    G.in_feat, 0, 0);
                 else
                     launch_gemm(st, G.xm[d], G.in_feat, c->params + G.k_off[d], 384, c->params + G.b_off[d], G.gx[d], 384, rows, 384, G.in_feat, 0, 0, 0);
@@ -436,7 +435,7 @@ static int forward_gru(seld_ctx* c, const FwdPass& p, const float** feat_io) {
             PROF2(c, "gru_inproj_gemm");
             // both directions' projections of the same input in one launch
             if (gru_sb(c, G) && gemm_sb_usable(feat, G.in_feat, 384, G.in_feat))
-                launch_gemm_sb(st, feat, nullptr, G.in_feat, c->ksp_fwd[i][0], c->ksp_fwd[i][1], c->params + G.b_off[0],
+                launch_gemm_sb(st, c->kc, false, GemmEpi(), feat, nullptr, G.in_feat, c->ksp_fwd[i][0], c->ksp_fwd[i][1], c->params + G.b_off[0],
                                c->params + G.b_off[1], G.gx[0], G.gx[1], 384, rows, 384, G.in_feat, 0, 1);
             else
                 launch_gemm_dual_n(st, feat, G.in_feat, c->params + G.k_off[0], c->params + G.k_off[1], 384, c->params + G.b_off[0],
@@ -458,7 +457,7 @@ static int forward_gru(seld_ctx* c, const FwdPass& p, const float** feat_io) {
             int ns = 0;
             const int kp = conv_gram_dim(c->conv[0].Cin);
             if (i == 0) gram_ns = 0;
-            if (launch_conv_first_gram(c->side, p.x, c->gram_slab + (size_t)gram_ns * kp * kp, &ns, B, c->conv[0].H, c->conv[0].Cin, 1, (int)i, gparts))
+            if (launch_conv_first_gram(c->side, c->kc, p.x, c->gram_slab + (size_t)gram_ns * kp * kp, &ns, B, c->conv[0].H, c->conv[0].Cin, 1, (int)i, gparts))
                 return fail(c, SELD_ERR_UNSUPPORTED, "conv_first_gram");
             gram_ns += ns;
             if ((int)i == gparts - 1) {
@@ -515,7 +514,7 @@ static int forward_heads(seld_ctx* c, const FwdPass& p, const float* feat, float
                              c->heads[0].hidden_act == c->heads[1].hidden_act;      // one launch, one epilogue activation
         const int hact0 = c->heads[0].hidden_act;
         if (merged0 && heads_sb(c) && gemm_sb_usable(feat, S0.in, S0.out, S0.in))
-            launch_gemm_sb(st, feat, nullptr, S0.in, c->h0sp_fwd[0], c->h0sp_fwd[1], c->params + S0.b_off, c->params + D0.b_off, S0.y,
+            launch_gemm_sb(st, c->kc, false, GemmEpi(), feat, nullptr, S0.in, c->h0sp_fwd[0], c->h0sp_fwd[1], c->params + S0.b_off, c->params + D0.b_off, S0.y,
                            D0.y, S0.out, rows, S0.out, S0.in, hact0, 1);
         else if (merged0)
             launch_gemm_dual_n(st, feat, S0.in, c->params + S0.w_off, c->params + D0.w_off, S0.out, c->params + S0.b_off,
@@ -540,7 +539,6 @@ static int forward_heads(seld_ctx* c, const FwdPass& p, const float* feat, float
 }
 
 int forward_impl(seld_ctx* c, const float* x, float* sed, float* doa, int training, bool save) {
-    apply_kernel_choices(c);
     c->last_training = training;
     if (training) c->dropout_cur = c->dropout_step++;      // every training forward draws new masks (Keras), backward or not
     const FwdPass p = {x, training, save, training && c->arch.conv_dropout > 0.f, training && c->arch.gru_dropout > 0.f};

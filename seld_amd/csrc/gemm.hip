@@ -217,10 +217,9 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const float* __restrict__
 
 static int gemm_go(hipStream_t st, const float* A, int lda, const float* Bm, int ldb, const float* bias, float* C, int ldc, int M,
                    int N, int K, int transb, int act, int accumulate, const float* A1, const float* B1, const float* bias1, float* C1,
-                   int mode, float* M0 = nullptr, float* M1 = nullptr, int nsplit = 0) {
+                   int mode, float* M0 = nullptr, float* M1 = nullptr, int nsplit = 0, const GemmEpi& epi = GemmEpi()) {
     if (M <= 0 || N <= 0 || K <= 0) return -1;
     if (mode == 2 && (K & 31)) return -2;
-    const GemmEpi epi = g_gemm_epi;
     if (epi.stat_part && (bias || act || accumulate || mode)) return -3;
     if (epi.addg) return -3;      // the gated add lives in the split-bf16 kernels' epilogues only
     dim3 grid((N + 63) / 64 * (mode == 1 ? 2 : 1), (M + 63) / 64);
@@ -234,8 +233,8 @@ static int gemm_go(hipStream_t st, const float* A, int lda, const float* Bm, int
 }
 
 int launch_gemm(hipStream_t st, const float* A, int lda, const float* Bm, int ldb, const float* bias, float* C,
-                int ldc, int M, int N, int K, int transb, int act, int accumulate) {
-    return gemm_go(st, A, lda, Bm, ldb, bias, C, ldc, M, N, K, transb, act, accumulate, nullptr, nullptr, nullptr, nullptr, 0);
+                int ldc, int M, int N, int K, int transb, int act, int accumulate, const GemmEpi& epi) {
+    return gemm_go(st, A, lda, Bm, ldb, bias, C, ldc, M, N, K, transb, act, accumulate, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, epi);
 }
 
 // C = act(A B + bias), also stored to `mirror` (same ldc) when it is not null

@@ -48,12 +48,12 @@ int gemm_sb_usable(const void* A, int lda, int N, int K) {
     return (K % GSB_KC) == 0 && (N % GSB_BN) == 0 && (lda & 3) == 0 && (reinterpret_cast<uintptr_t>(A) & 15) == 0;
 }
 
-int launch_gemm_split_b(hipStream_t st, int njobs, const float* const* src, unsigned short* const* dst, const int* ldb,
+int launch_gemm_split_b(hipStream_t st, const KernelChoices& kc, int njobs, const float* const* src, unsigned short* const* dst, const int* ldb,
                         const int* transb, const int* K, const int* N) {
     if (njobs <= 0 || njobs > GSB_MAX_JOBS) return -1;
     GemmSplitJobs j;
     j.njobs = njobs;
-    j.one = g_mfma_one;
+    j.one = kc.mfma_one;
     for (int i = 0; i < njobs; ++i) {
         if (K[i] % GSB_KC) return -2;
         j.src[i] = src[i]; j.dst[i] = dst[i]; j.ldb[i] = ldb[i]; j.transb[i] = transb[i]; j.K[i] = K[i]; j.N[i] = N[i];
@@ -66,9 +66,9 @@ int launch_gemm_split_b(hipStream_t st, int njobs, const float* const* src, unsi
 // mode 0: C0 = act(A0 B0 + bias0).
 // mode 1 (two products sharing A): column groups >= N/128 compute C1 = act(A0 B1 + bias1).
 // mode 2 (one product over a concatenated K axis): C0 = act(A0 B0 + A1 B1 + bias0).
-// ONE: bf16 single-product mode (common.h g_mfma_one): A rounded to nearest bf16 in registers, B's plane 0 holds the rounded weights
+// ONE: bf16 single-product mode (common.h KernelChoices::mfma_one): A rounded to nearest bf16 in registers, B's plane 0 holds the rounded weights
 // (gemm_split_b with jobs.one); one MFMA per k-step and column tile.  The B staging still moves all three planes (untouched code path).
-// FOUR (option "bwd_four_products", set for a launch by BwdFourScope — backward products only): the two products with a lo factor are dropped, plane 2 of B is
+// FOUR (option "bwd_four_products", launch_gemm_sb's `backward` argument — backward products only): the two products with a lo factor are dropped, plane 2 of B is
 // not staged, A is split in two planes with a rounded mid (common.h split2r_pair; gemm_split_b rounds the mid plane of every transposed / flipped B likewise)
 template <int NG, bool ONE = false, bool FOUR = false>   // NG 4: K = 128, one product (or two sharing A): every A row of the tile is requested up front; 0: runtime loop
 __global__ __launch_bounds__(256, NG == 4 ? 2 : 3) void gemm_sb_kernel(const float* __restrict__ A0, const float* __restrict__ A1, int lda,
@@ -642,12 +642,9 @@ __global__ __launch_bounds__(512) void gemm_sbp_kernel(const float* __restrict__
     }
 }
 
-int g_gsb_dbg = 0;
-thread_local GemmEpi g_gemm_epi;
 int gemm_epi_row_blocks(int M, int split_bf16) { return split_bf16 ? (M + 127) / 128 : (M + 63) / 64; }
-thread_local int g_gsb_four_now = 0;       // set for the duration of a backward launch (common.h BwdFourScope); per host thread: another thread's forward launch must not read it
-int launch_gemm_sb(hipStream_t st, const float* A0, const float* A1, int lda, const unsigned short* Bs0, const unsigned short* Bs1,
-                   const float* bias0, const float* bias1, float* C0, float* C1, int ldc, int M, int N, int K, int act, int mode,
+int launch_gemm_sb(hipStream_t st, const KernelChoices& kc, bool backward, const GemmEpi& epi, const float* A0, const float* A1, int lda,
+                   const unsigned short* Bs0, const unsigned short* Bs1, const float* bias0, const float* bias1, float* C0, float* C1, int ldc, int M, int N, int K, int act, int mode,
                    int accum, int conv_C, int conv_H, int conv_W) {
     int cvs = 0;
     if (conv_C) {      // implicit 3x3: K = 9 C, C a power of two >= 32, M = B * H * W pixels, one product
@@ -657,7 +654,8 @@ int launch_gemm_sb(hipStream_t st, const float* A0, const float* A1, int lda, co
     }
     if (M <= 0 || N <= 0 || K <= 0 || !gemm_sb_usable(A0, lda, N, K)) return -1;
     if (mode == 2 && !gemm_sb_usable(A1, lda, N, K)) return -1;
-    const GemmEpi epi = g_gemm_epi;
+    const bool four = backward && kc.bwd_four && !kc.mfma_one;
+    const int dbg = kc.gsb_dbg;
     if (epi.stat_part && (bias0 || act || mode || accum)) return -3;
     if (epi.addg && (!epi.gate4 || (ldc & 3) || mode)) return -3;
     dim3 grid(N / GSB_BN * (mode == 1 ? 2 : 1), (M + 127) / 128);
@@ -665,44 +663,44 @@ int launch_gemm_sb(hipStream_t st, const float* A0, const float* A1, int lda, co
     const bool wide = grid.x >= 2;
     // (an implicit convolution always takes the 16-wave form: its per-chunk address work is shared by 4 column waves there — K = 9 x 256,
     // N = 256: 198 us against 264 for the 4-wave form)
-    if (cvs ? false : (g_gsb_dbg & 4) ? true : (g_gsb_dbg & 8) ? false : wide) {
-#define GSB_GO(NG_) { if (g_mfma_one) hipLaunchKernelGGL((gemm_sb_kernel<NG_, true>), grid, dim3(256), 0, st, A0, A1, lda, Bs0, Bs1, bias0, bias1, C0, C1, ldc, M, N, K, act, \
-                                       mode, g_gsb_dbg & 3, accum, epi);                                                                                            \
-                      else if (g_gsb_four_now) hipLaunchKernelGGL((gemm_sb_kernel<NG_, false, true>), grid, dim3(256), 0, st, A0, A1, lda, Bs0, Bs1, bias0, bias1, C0, C1, ldc, M, N, K, act, \
-                                       mode, g_gsb_dbg & 3, accum, epi);                                                                                            \
+    if (cvs ? false : (dbg & 4) ? true : (dbg & 8) ? false : wide) {
+#define GSB_GO(NG_) { if (kc.mfma_one) hipLaunchKernelGGL((gemm_sb_kernel<NG_, true>), grid, dim3(256), 0, st, A0, A1, lda, Bs0, Bs1, bias0, bias1, C0, C1, ldc, M, N, K, act, \
+                                       mode, dbg & 3, accum, epi);                                                                                            \
+                      else if (four) hipLaunchKernelGGL((gemm_sb_kernel<NG_, false, true>), grid, dim3(256), 0, st, A0, A1, lda, Bs0, Bs1, bias0, bias1, C0, C1, ldc, M, N, K, act, \
+                                       mode, dbg & 3, accum, epi);                                                                                            \
                       else hipLaunchKernelGGL((gemm_sb_kernel<NG_, false>), grid, dim3(256), 0, st, A0, A1, lda, Bs0, Bs1, bias0, bias1, C0, C1, ldc, M, N, K, act, \
-                                       mode, g_gsb_dbg & 3, accum, epi); }
+                                       mode, dbg & 3, accum, epi); }
         // K = 128, plain epilogue: B stationary in LDS, persistent workgroups (gemm_sbp_kernel) — an opt-in (gsb_dbg bit 6): measured equal to the tiled form
         // (31.6 against 32.6 us at the GRU input projections' shape, the same bits; profiles/r05_gru_experiments.txt)
-        if (K == 128 && mode != 2 && !act && !accum && !epi.stat_part && !epi.addg && !g_mfma_one && (g_gsb_dbg & 64) && !(g_gsb_dbg & 3) && /* bits 8-11: ablations */ (int)grid.x <= 128 &&
+        if (K == 128 && mode != 2 && !act && !accum && !epi.stat_part && !epi.addg && !kc.mfma_one && (dbg & 64) && !(dbg & 3) && /* bits 8-11: ablations */ (int)grid.x <= 128 &&
             !(ldc & 3) && !(reinterpret_cast<uintptr_t>(C0) & 15) && !(reinterpret_cast<uintptr_t>(C1) & 15)) {
             const int ngroups = (int)grid.x, wpg = 256 / ngroups;
             const int need = ((M + 31) / 32 + 7) / 8;      // workgroups per column group that still have a tile for every wave
             const int w = wpg < need ? wpg : need;
             const size_t smem = (size_t)4 * 3 * 4096 * sizeof(unsigned short);
-            if (g_gsb_four_now) {
+            if (four) {
                 hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_sbp_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-                hipLaunchKernelGGL((gemm_sbp_kernel<true>), dim3(ngroups * w), dim3(512), smem, st, A0, lda, Bs0, Bs1, bias0, bias1, C0, C1, ldc, M, N, ngroups, g_gsb_dbg >> 8);
+                hipLaunchKernelGGL((gemm_sbp_kernel<true>), dim3(ngroups * w), dim3(512), smem, st, A0, lda, Bs0, Bs1, bias0, bias1, C0, C1, ldc, M, N, ngroups, dbg >> 8);
             } else {
                 hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_sbp_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-                hipLaunchKernelGGL((gemm_sbp_kernel<false>), dim3(ngroups * w), dim3(512), smem, st, A0, lda, Bs0, Bs1, bias0, bias1, C0, C1, ldc, M, N, ngroups, g_gsb_dbg >> 8);
+                hipLaunchKernelGGL((gemm_sbp_kernel<false>), dim3(ngroups * w), dim3(512), smem, st, A0, lda, Bs0, Bs1, bias0, bias1, C0, C1, ldc, M, N, ngroups, dbg >> 8);
             }
             return 0;
         }
-        if (K == 128 && mode != 2 && !(g_gsb_dbg & 32)) GSB_GO(4)
+        if (K == 128 && mode != 2 && !(dbg & 32)) GSB_GO(4)
         else GSB_GO(0)
 #undef GSB_GO
     } else {
         const int ng = K / GSB_KC * (mode == 2 ? 2 : 1);
-#define G16_GO(NG_, CV_) { if (g_gsb_four_now) hipLaunchKernelGGL((gemm_sb16_kernel<NG_, CV_, false, true>), grid, dim3(1024), 0, st, A0, A1, lda, Bs0, Bs1, bias0, bias1, C0, C1, ldc, M, N, K, act, mode, accum, cvs, conv_H, conv_W, epi); \
+#define G16_GO(NG_, CV_) { if (four) hipLaunchKernelGGL((gemm_sb16_kernel<NG_, CV_, false, true>), grid, dim3(1024), 0, st, A0, A1, lda, Bs0, Bs1, bias0, bias1, C0, C1, ldc, M, N, K, act, mode, accum, cvs, conv_H, conv_W, epi); \
                            else hipLaunchKernelGGL((gemm_sb16_kernel<NG_, CV_>), grid, dim3(1024), 0, st, A0, A1, lda, Bs0, Bs1, bias0, bias1, C0, C1, ldc, M, N, K, act, mode, accum, cvs, conv_H, conv_W, epi); }
 #define G16_GO1(NG_) hipLaunchKernelGGL((gemm_sb16_kernel<NG_, false, true>), grid, dim3(1024), 0, st, A0, A1, lda, Bs0, Bs1, bias0, bias1, C0, C1, ldc, M, N, K, act, mode, accum, cvs, conv_H, conv_W, epi)
         // bf16 single-product mode: instantiated for the shapes of the headline model (the GRU input gradients, K = 128, and the generic loop);
         // the implicit-convolution and resnet50 shapes keep the exact products
-        if (g_mfma_one && !cvs && !(g_gsb_dbg & 16) && (ng == 24 || ng == 4)) { if (ng == 24) G16_GO1(24); else G16_GO1(4); return 0; }
-        if (g_mfma_one && !cvs && ng != 36 && ng != 16 && ng != 12 && ng != 8) { G16_GO1(0); return 0; }
+        if (kc.mfma_one && !cvs && !(dbg & 16) && (ng == 24 || ng == 4)) { if (ng == 24) G16_GO1(24); else G16_GO1(4); return 0; }
+        if (kc.mfma_one && !cvs && ng != 36 && ng != 16 && ng != 12 && ng != 8) { G16_GO1(0); return 0; }
         if (cvs) { if (ng == 36) G16_GO(36, true) else if (ng == 72) G16_GO(72, true) else G16_GO(0, true) }      // implicit 3x3: K = 9 x 128 / 9 x 256 unrolled
-        else if (g_gsb_dbg & 16) G16_GO(0, false)
+        else if (dbg & 16) G16_GO(0, false)
         else if (ng == 36) G16_GO(36, false)        // resnet50_block stage 2: the 3x3 product on im2col rows (K = 9 x 128)
         else if (ng == 24) G16_GO(24, false)        // the GRU input gradients: K = 2 x 384
         else if (ng == 16) G16_GO(16, false)        // ... its 1x1 products with K = 512

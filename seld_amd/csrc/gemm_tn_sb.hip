@@ -40,8 +40,8 @@ __device__ __forceinline__ bf16x8 tnsb_frag(const char* p0, const char* p1) {
 // cvs = log2 C > 0 (tile mode only): A is an NHWC image [M pixels][C] and the product's A matrix its virtual im2col [M][9 C] (3 x 3
 // 'same', zeros outside the H x W image): tile y covers columns 128 y .. of it, i.e. ONE tap (C % 128 == 0) at channel offset
 // (128 y) % C — the row of the image is the pixel shifted by the tap, masked at the image border.
-// ONE: bf16 single-product mode (common.h g_mfma_one): both operands rounded to nearest bf16, plane 0 only, one MFMA per tile pair
-// FOUR (option "bwd_four_products", conv_sb.hip g_bwd_four): weight gradients on four products — the two with a lo factor dropped, two planes per image
+// ONE: bf16 single-product mode (common.h KernelChoices::mfma_one): both operands rounded to nearest bf16, plane 0 only, one MFMA per tile pair
+// FOUR (option "bwd_four_products", common.h KernelChoices::bwd_four): weight gradients on four products — the two with a lo factor dropped, two planes per image
 template <bool CONV, bool ONE = false, bool FOUR = false>      // a template parameter: the GRU's instantiation (the headline step's side stream) must not carry the convolution's index work
 __global__ __launch_bounds__(256, 3) void gemm_tn_sb_kernel(TnJobs jobs, int ldb, float* __restrict__ slab, int M, int N, int rows_per_split,
                                                             int S, int want_bias, long long tile_stride, int cvs, int cvH, int cvW) {
@@ -185,12 +185,11 @@ __global__ __launch_bounds__(256, 3) void gemm_tn_sb_kernel(TnJobs jobs, int ldb
 }
 
 // K1 = 128, N % 128 == 0, 16-byte aligned operands with leading dimensions % 4 == 0; same slab layout / n_slab as launch_gemm_tn
-int g_tn_tile_blocks = 384;      // tile mode: workgroups per launch the split count aims at (option "tn_tile_blocks"; resnet50_gru same box: 14.709 / 14.752 ms per step at 768, 14.646 at 384, 14.691 at 512, 14.87 at 256 and 1024)
 int gemm_tn_sb_usable(const void* A, int lda, const void* Bm, int ldb, int K1, int N) {
     return K1 == 128 && (N % 128) == 0 && (lda & 3) == 0 && (ldb & 3) == 0 && (reinterpret_cast<uintptr_t>(A) & 15) == 0 &&
            (reinterpret_cast<uintptr_t>(Bm) & 15) == 0;
 }
-int launch_gemm_tn_sb_batch(hipStream_t st, const TnJobs& jobs, int njobs, int ldb, float* slab, int* nslab, int M, int N, int S, int want_bias) {
+int launch_gemm_tn_sb_batch(hipStream_t st, const KernelChoices& kc, const TnJobs& jobs, int njobs, int ldb, float* slab, int* nslab, int M, int N, int S, int want_bias) {
     if (M <= 0 || njobs < 1 || njobs > TN_MAX_JOBS) return -1;
     for (int j = 0; j < njobs; ++j)
         if (!gemm_tn_sb_usable(jobs.A[j], jobs.lda[j], jobs.B[j], ldb, 128, N)) return -1;
@@ -199,9 +198,9 @@ int launch_gemm_tn_sb_batch(hipStream_t st, const TnJobs& jobs, int njobs, int l
     int rps = (M + splits - 1) / splits;
     rps = (rps + 31) / 32 * 32;
     splits = (M + rps - 1) / rps;
-    if (g_mfma_one) {
+    if (kc.mfma_one) {
         hipLaunchKernelGGL((gemm_tn_sb_kernel<false, true>), dim3(N / 128, njobs, splits), dim3(256), 0, st, jobs, ldb, slab, M, N, rps, S > 0 ? S : M, want_bias, 0LL, 0, 0, 0);
-    } else if (g_bwd_four) {
+    } else if (kc.bwd_four) {
         hipLaunchKernelGGL((gemm_tn_sb_kernel<false, false, true>), dim3(N / 128, njobs, splits), dim3(256), 0, st, jobs, ldb, slab, M, N, rps, S > 0 ? S : M, want_bias, 0LL, 0, 0, 0);
     } else {
         hipLaunchKernelGGL((gemm_tn_sb_kernel<false, false>), dim3(N / 128, njobs, splits), dim3(256), 0, st, jobs, ldb, slab, M, N, rps, S > 0 ? S : M, want_bias, 0LL, 0, 0, 0);
@@ -210,8 +209,8 @@ int launch_gemm_tn_sb_batch(hipStream_t st, const TnJobs& jobs, int njobs, int l
     return 0;
 }
 // C[K1][N] = A^T B with K1 % 128 == 0: one launch, (K1/128) x (N/128) tiles x splits blocks; slabs of K1 * N floats each (no bias part).
-// The split count aims at g_tn_tile_blocks workgroups per launch (384: fewer slabs to write and combine than the 768 that fill every CU three times) within the slab buffer's capacity.
-int launch_gemm_tn_sb_tiles(hipStream_t st, const float* A, int lda, const float* Bm, int ldb, float* slab, int64_t slab_cap, int* nslab,
+// The split count aims at kc.tn_tile_blocks workgroups per launch (384: fewer slabs to write and combine than the 768 that fill every CU three times) within the slab buffer's capacity.
+int launch_gemm_tn_sb_tiles(hipStream_t st, const KernelChoices& kc, const float* A, int lda, const float* Bm, int ldb, float* slab, int64_t slab_cap, int* nslab,
                             int M, int K1, int N, int conv_C, int conv_H, int conv_W) {
     int cvs = 0;
     if (conv_C) {      // A = NHWC image, K1 = 9 C, C a power of two and a multiple of 128
@@ -221,7 +220,7 @@ int launch_gemm_tn_sb_tiles(hipStream_t st, const float* A, int lda, const float
     }
     if (M <= 0 || K1 <= 0 || (K1 % 128) || !gemm_tn_sb_usable(A, lda, Bm, ldb, 128, N)) return -1;
     const int tiles = (K1 / 128) * (N / 128);
-    int64_t splits = (g_tn_tile_blocks + tiles - 1) / tiles;
+    int64_t splits = (kc.tn_tile_blocks + tiles - 1) / tiles;
     splits = std::min<int64_t>(splits, slab_cap / ((int64_t)K1 * N));
     splits = std::min<int64_t>(splits, 128);
     splits = std::min<int64_t>(splits, (M + 127) / 128);         // at least four 32-row chunks per split
@@ -231,7 +230,7 @@ int launch_gemm_tn_sb_tiles(hipStream_t st, const float* A, int lda, const float
     splits = (M + rps - 1) / rps;
     TnJobs jobs = {};
     jobs.A[0] = A; jobs.B[0] = Bm; jobs.lda[0] = lda; jobs.shift[0] = 0;
-    const bool four = g_bwd_four && !g_mfma_one;      // a kernel gradient: backward only
+    const bool four = kc.bwd_four && !kc.mfma_one;      // a kernel gradient: backward only
     if (cvs && four) hipLaunchKernelGGL((gemm_tn_sb_kernel<true, false, true>), dim3(N / 128, K1 / 128, (unsigned)splits), dim3(256), 0, st, jobs, ldb, slab, M, N, rps, M, 0,
                                 (long long)K1 * N, cvs, conv_H, conv_W);
     else if (cvs) hipLaunchKernelGGL(gemm_tn_sb_kernel<true>, dim3(N / 128, K1 / 128, (unsigned)splits), dim3(256), 0, st, jobs, ldb, slab, M, N, rps, M, 0,
@@ -243,9 +242,9 @@ int launch_gemm_tn_sb_tiles(hipStream_t st, const float* A, int lda, const float
     *nslab = (int)splits;
     return 0;
 }
-int launch_gemm_tn_sb(hipStream_t st, const float* A, int lda, const float* Bm, int ldb, float* slab, int* nslab, int M, int N, int S,
+int launch_gemm_tn_sb(hipStream_t st, const KernelChoices& kc, const float* A, int lda, const float* Bm, int ldb, float* slab, int* nslab, int M, int N, int S,
                       int shift, int want_bias) {
     TnJobs jobs = {};
     jobs.A[0] = A; jobs.B[0] = Bm; jobs.lda[0] = lda; jobs.shift[0] = shift;
-    return launch_gemm_tn_sb_batch(st, jobs, 1, ldb, slab, nslab, M, N, S, want_bias);
+    return launch_gemm_tn_sb_batch(st, kc, jobs, 1, ldb, slab, nslab, M, N, S, want_bias);
 }

@@ -9,10 +9,13 @@
 #include <string.h>
 
 namespace {
-int g_conv64_split_bf16 = 1;
-int g_conv1_split_bf16 = 1;
-int g_rn_split_bf16 = 1;
-int g_gemm_tn_sb = 1;
+// the only process-wide choices of the library, all written by seld_k_set_option alone: what the seld_k_* entry points hand to the launchers, and
+// four switches between kernel families that only these entry points have (a context has its own of each)
+KernelChoices k_kc;
+int k_conv64_split_bf16 = 1;
+int k_conv1_split_bf16 = 1;
+int k_rn_split_bf16 = 1;
+int k_gemm_tn_split_bf16 = 1;
 struct Scratch {
     std::vector<void*> p;
     float* get(size_t n) { void* q = nullptr; if (hipMalloc(&q, n * sizeof(float) + 256) != hipSuccess) return nullptr; p.push_back(q); return (float*)q; }
@@ -34,16 +37,16 @@ extern "C" {
 
 int seld_k_set_option(const char* key, int value) {
     if (!key) return SELD_ERR_INVALID;
-    if (!strcmp(key, "conv64_split_bf16")) { g_conv64_split_bf16 = value != 0; return SELD_OK; }
-    if (!strcmp(key, "conv1_split_bf16")) { g_conv1_split_bf16 = value != 0; return SELD_OK; }
-    if (!strcmp(key, "conv64_dbuf")) { g_conv64_dbuf = value != 0; return SELD_OK; }
-    if (!strcmp(key, "gemm_tn_split_bf16")) { g_gemm_tn_sb = value != 0; return SELD_OK; }
-    if (!strcmp(key, "bf16_single")) { g_mfma_one = value != 0; return SELD_OK; }
-    if (!strcmp(key, "gsb_dbg")) { g_gsb_dbg = value; return SELD_OK; }
-    if (!strcmp(key, "xc_w16")) { g_xc_w16 = value != 0; return SELD_OK; }
-    if (!strcmp(key, "xc_xcd_map")) { g_xc_xcd_map = value != 0; return SELD_OK; }
-    if (!strcmp(key, "bwd_four_products")) { g_bwd_four = value != 0; return SELD_OK; }
-    if (!strcmp(key, "rn_split_bf16")) { g_rn_split_bf16 = value != 0; return SELD_OK; }
+    if (!strcmp(key, "conv64_split_bf16")) { k_conv64_split_bf16 = value != 0; return SELD_OK; }
+    if (!strcmp(key, "conv1_split_bf16")) { k_conv1_split_bf16 = value != 0; return SELD_OK; }
+    if (!strcmp(key, "conv64_dbuf")) { k_kc.conv64_dbuf = value != 0; return SELD_OK; }
+    if (!strcmp(key, "gemm_tn_split_bf16")) { k_gemm_tn_split_bf16 = value != 0; return SELD_OK; }
+    if (!strcmp(key, "bf16_single")) { k_kc.mfma_one = value != 0; return SELD_OK; }
+    if (!strcmp(key, "gsb_dbg")) { k_kc.gsb_dbg = value; return SELD_OK; }
+    if (!strcmp(key, "xc_w16")) { k_kc.xc_w16 = value != 0; return SELD_OK; }
+    if (!strcmp(key, "xc_xcd_map")) { k_kc.xc_xcd_map = value != 0; return SELD_OK; }
+    if (!strcmp(key, "bwd_four_products")) { k_kc.bwd_four = value != 0; return SELD_OK; }
+    if (!strcmp(key, "rn_split_bf16")) { k_rn_split_bf16 = value != 0; return SELD_OK; }
     return SELD_ERR_INVALID;
 }
 
@@ -54,11 +57,11 @@ int seld_k_conv3x3_fwd(const float* x, const float* w, const float* bias, float*
     float* part = stats ? s.get((size_t)conv_stat_partial_capacity() * 128) : nullptr;
     if (stats && !part) return SELD_ERR_NOMEM;
     int np = 0, rc;
-    if (Cin == 64 && g_conv64_split_bf16) {
+    if (Cin == 64 && k_conv64_split_bf16) {
         unsigned short* wsp = reinterpret_cast<unsigned short*>(s.get(9 * 3 * 4096 / 2 + 16));
         if (!wsp) return SELD_ERR_NOMEM;
-        launch_split_weights(0, w, wsp);
-        rc = launch_conv64_fwd_sb(0, x, wsp, bias, z, part, &np, B, H, W);
+        launch_split_weights(0, k_kc, w, wsp);
+        rc = launch_conv64_fwd_sb(0, k_kc, x, wsp, bias, z, part, &np, B, H, W);
     } else if (Cin == 64) rc = launch_conv64_fwd(0, x, w, bias, z, part, &np, B, H, W);
     else if (W == 64) rc = launch_conv_first_fwd(0, x, w, bias, z, part, &np, B, H, Cin);
     else return SELD_ERR_UNSUPPORTED;
@@ -74,7 +77,7 @@ int seld_k_conv_first_fwd_pool(const float* x, const float* w, const float* bias
     float* part = stats ? s.get((size_t)conv_pool_stat_capacity() * 128) : nullptr;
     if (stats && !part) return SELD_ERR_NOMEM;
     int np = 0;
-    if (launch_conv_first_fwd_pool(0, x, w, bias, gamma, z, zext, amax, part, &np, B, H, Cin, g_conv1_split_bf16)) return SELD_ERR_UNSUPPORTED;
+    if (launch_conv_first_fwd_pool(0, k_kc, x, w, bias, gamma, z, zext, amax, part, &np, B, H, Cin, k_conv1_split_bf16)) return SELD_ERR_UNSUPPORTED;
     if (stats) launch_reduce_slabs(0, part, np, 128, stats, 128, 0);
     return done();
 }
@@ -91,14 +94,14 @@ int seld_k_conv3x3_dgrad(const float* dz, const float* w, float* dx, int B, int 
     float* wt = s.get(9 * 4096);
     if (!wt) return SELD_ERR_NOMEM;
     launch_flip_weights(0, w, wt);
-    if (g_conv64_split_bf16) {
+    if (k_conv64_split_bf16) {
         unsigned short* wsp = reinterpret_cast<unsigned short*>(s.get(9 * 3 * 4096 / 2 + 16));
         if (!wsp) return SELD_ERR_NOMEM;
         // the model's own route: the flipped planes straight from w (prep.h split_weights_body, flip = 1) and the input-gradient launcher, which takes
         // the four-product form under option "bwd_four_products"
         const float* ws[1] = {w}; unsigned short* ds[1] = {wsp}; const int fl[1] = {1};
-        launch_split_weights_batch(0, 1, ws, ds, fl);
-        launch_conv64_dgrad_sb(0, dz, wsp, dx, B, H, W);
+        launch_split_weights_batch(0, k_kc, 1, ws, ds, fl);
+        launch_conv64_dgrad_sb(0, k_kc, dz, wsp, dx, B, H, W);
     } else
         launch_conv64_fwd(0, dz, wt, nullptr, dx, nullptr, nullptr, B, H, W);
     return done();
@@ -112,8 +115,8 @@ int seld_k_conv3x3_wgrad(const float* x, const float* dz, float* dw, float* db, 
     if (!slab || !tmp) return SELD_ERR_NOMEM;
     int ns = 0;
     if (Cin == 64) {
-        if (g_conv64_split_bf16 && conv64_wgrad_sb_usable(W)) {
-            if (launch_conv64_wgrad_sb(0, x, dz, slab, &ns, B, H, W)) return SELD_ERR_UNSUPPORTED;
+        if (k_conv64_split_bf16 && conv64_wgrad_sb_usable(W)) {
+            if (launch_conv64_wgrad_sb(0, k_kc, x, dz, slab, &ns, B, H, W)) return SELD_ERR_UNSUPPORTED;
         } else if (launch_conv64_wgrad(0, x, dz, slab, &ns, B, H, W)) return SELD_ERR_UNSUPPORTED;
         launch_reduce_slabs(0, slab, ns, 9 * 4096 + 64, tmp, 9 * 4096 + 64, 0);
         hipMemcpyAsync(dw, tmp, 9 * 4096 * 4, hipMemcpyDeviceToDevice, 0);
@@ -164,7 +167,7 @@ int seld_k_conv1_gram(const float* x, float* G, int B, int H, int Cin) {
     float* slab = s.get((size_t)conv_gram_slab_capacity() * kp * kp);
     if (!slab) return SELD_ERR_NOMEM;
     int ns = 0;
-    if (launch_conv_first_gram(0, x, slab, &ns, B, H, Cin)) return SELD_ERR_UNSUPPORTED;
+    if (launch_conv_first_gram(0, k_kc, x, slab, &ns, B, H, Cin)) return SELD_ERR_UNSUPPORTED;
     launch_reduce_slabs(0, slab, ns, (int64_t)(kp * kp), G, (int64_t)(kp * kp), 0);
     return done();
 }
@@ -191,14 +194,14 @@ int seld_k_conv1_train_gram(const float* x, const float* w, const float* bias, c
     hipMemsetAsync(mov, 0, 128 * sizeof(float), 0);
     int npart = 0, nb = 0, ns = 0;
     // forward without z: window extremes + positions + statistics; then BN coefficients and the pooled activation
-    if (launch_conv_first_fwd_pool(0, x, w, bias, gamma, nullptr, zext, amax, part, &npart, B, H, Cin, g_conv1_split_bf16)) return SELD_ERR_UNSUPPORTED;
+    if (launch_conv_first_fwd_pool(0, k_kc, x, w, bias, gamma, nullptr, zext, amax, part, &npart, B, H, Cin, k_conv1_split_bf16)) return SELD_ERR_UNSUPPORTED;
     launch_bn_finalize(0, part, npart, (double)B * H * W, gamma, beta, mov, mov + 64, coef, coef + 64, coef + 128, coef + 192, C, 1);
     launch_bn_relu_ext(0, zext, coef + 128, coef + 192, p, (int64_t)np);
     // backward: BN sums from the pooled tensors, then dW = ka (G W + g b) + g kb + M
     if (launch_bn_pool_bwd_reduce(0, zext, p, dp, coef, coef + 64, coef + 128, coef + 192, bpart, &nb, B, H, W, C, 5, 4, 1))
         return SELD_ERR_UNSUPPORTED;
     launch_bn_bwd_finalize(0, bpart, nb, (double)B * H * W, dgamma, dbeta, coef + 256, C);
-    if (launch_conv_first_gram(0, x, gslab, &ns, B, H, Cin)) return SELD_ERR_UNSUPPORTED;
+    if (launch_conv_first_gram(0, k_kc, x, gslab, &ns, B, H, Cin)) return SELD_ERR_UNSUPPORTED;
     launch_reduce_slabs(0, gslab, ns, (int64_t)(kp * kp), gm, (int64_t)(kp * kp), 0);
     if (launch_conv_first_msparse(0, x, p, dp, amax, coef + 128, mslab, &ns, B, H, Cin)) return SELD_ERR_UNSUPPORTED;
     launch_reduce_slabs(0, mslab, ns, (int64_t)(kp * 64), mm, (int64_t)(kp * 64), 0);
@@ -268,8 +271,8 @@ int seld_k_gemm_sb(const float* A0, const float* A1, const float* B0, const floa
     const float* src[2] = {B0, B1};
     unsigned short* dst[2] = {sp, sp + ne};
     const int ldb[2] = {transb ? K : N, transb ? K : N}, tb[2] = {transb, transb}, Ks[2] = {K, K}, Ns[2] = {N, N};
-    if (launch_gemm_split_b(0, mode ? 2 : 1, src, dst, ldb, tb, Ks, Ns)) return SELD_ERR_INVALID;
-    if (launch_gemm_sb(0, A0, A1, K, dst[0], dst[1], bias0, bias1, C0, C1, N, M, N, K, act, mode)) return SELD_ERR_INVALID;
+    if (launch_gemm_split_b(0, k_kc, mode ? 2 : 1, src, dst, ldb, tb, Ks, Ns)) return SELD_ERR_INVALID;
+    if (launch_gemm_sb(0, k_kc, false, GemmEpi(), A0, A1, K, dst[0], dst[1], bias0, bias1, C0, C1, N, M, N, K, act, mode)) return SELD_ERR_INVALID;
     return done();
 }
 
@@ -288,7 +291,7 @@ int seld_k_xc_dw_bwd(const float* dy, const float* k, const float* xin, const fl
         float* part = s.get((size_t)nb * 128);
         float* folded = s.get((size_t)xc_partial_capacity() * 128);
         if (!slab || !tmp || !part || !folded) return SELD_ERR_NOMEM;
-        if (launch_dw3x3_bwd_fused(0, dy, k, xin, add, dx, slab, &ns, B, H, 16, aff, bn_mean, bn_invstd, want_sums ? part : nullptr)) return SELD_ERR_UNSUPPORTED;
+        if (launch_dw3x3_bwd_fused(0, k_kc, dy, k, xin, add, dx, slab, &ns, B, H, 16, aff, bn_mean, bn_invstd, want_sums ? part : nullptr)) return SELD_ERR_UNSUPPORTED;
         launch_reduce_slabs_2stage(0, slab, ns, 576, dk, 576, tmp);
         if (want_sums) {
             launch_xc_fold_partials(0, part, ns, folded, &np);
@@ -298,7 +301,7 @@ int seld_k_xc_dw_bwd(const float* dy, const float* k, const float* xin, const fl
         float* slab = s.get((size_t)xc_partial_capacity() * 576);
         float* part = s.get((size_t)xc_partial_capacity() * 128);
         if (!slab || !part) return SELD_ERR_NOMEM;
-        launch_dw3x3_bwd_data(0, dy, k, xin, add, dx, B, H, 16, aff);
+        launch_dw3x3_bwd_data(0, k_kc, dy, k, xin, add, dx, B, H, 16, aff);
         launch_dw3x3_bwd_w(0, xin, dy, slab, &ns, B, H, 16, aff);
         launch_reduce_slabs(0, slab, ns, 576, dk, 576, 0);
         if (want_sums) {
@@ -315,8 +318,8 @@ int seld_k_gemm_tn(const float* A, const float* Bm, float* C, float* colsum, int
     float* slab = s.get((size_t)gemm_tn_max_splits() * ((size_t)K1 * N + N));
     if (!slab) return SELD_ERR_NOMEM;
     int ns = 0;
-    if (g_gemm_tn_sb && gemm_tn_sb_usable(A, K1, Bm, N, K1, N)) {
-        if (launch_gemm_tn_sb(0, A, K1, Bm, N, slab, &ns, M, N, 0, 0, colsum ? 1 : 0)) return SELD_ERR_INVALID;
+    if (k_gemm_tn_split_bf16 && gemm_tn_sb_usable(A, K1, Bm, N, K1, N)) {
+        if (launch_gemm_tn_sb(0, k_kc, A, K1, Bm, N, slab, &ns, M, N, 0, 0, colsum ? 1 : 0)) return SELD_ERR_INVALID;
     } else if (launch_gemm_tn(0, A, K1, Bm, N, slab, &ns, M, K1, N, 0, 0, colsum ? 1 : 0)) return SELD_ERR_INVALID;
     if (colsum) launch_reduce_slabs2(0, slab, ns, (int64_t)K1 * N + N, C, (int64_t)K1 * N, colsum, N);
     else launch_reduce_slabs(0, slab, ns, (int64_t)K1 * N + N, C, (int64_t)K1 * N, 0);
@@ -407,12 +410,12 @@ int seld_k_valu_clock_mhz(int blocks, double* mhz) {
 // split `w` ([K,N]; transposed: the planes of w^T) into scratch planes when the split-bf16 product takes the shape, as the model does per step
 // transposed == 2: the matrix of a 3x3 kernel's input-gradient convolution (K = 9 Cin: flipped taps, channels swapped)
 static unsigned short* rn_k_split(Scratch& s, const float* w, int K, int N, int transposed) {
-    if (!g_rn_split_bf16 || !(transposed ? rn_sb_dgrad_ok(K, N) : rn_sb_fwd_ok(K, N))) return nullptr;
+    if (!k_rn_split_bf16 || !(transposed ? rn_sb_dgrad_ok(K, N) : rn_sb_fwd_ok(K, N))) return nullptr;
     unsigned short* d = reinterpret_cast<unsigned short*>(s.get((gemm_sb_split_elems(K, N) + 1) / 2));
     if (!d) return nullptr;
     const float* src[1] = {w}; unsigned short* dst[1] = {d};
     const int ldb[1] = {N}, tb[1] = {transposed}, Ks[1] = {transposed == 2 ? 9 * N : transposed ? N : K}, Ns[1] = {transposed == 2 ? K / 9 : transposed ? K : N};
-    return launch_gemm_split_b(0, 1, src, dst, ldb, tb, Ks, Ns) ? nullptr : d;
+    return launch_gemm_split_b(0, k_kc, 1, src, dst, ldb, tb, Ks, Ns) ? nullptr : d;
 }
 
 // sums (optional, device, ceil(Cout / 64) * 128 + 1 doubles): the BatchNorm statistics from the product's epilogue as the model takes them (GemmEpi
@@ -430,14 +433,14 @@ int seld_k_rn_conv_stats(const float* x, const float* w, float* z, int B, int H,
     if (sums && !part) return SELD_ERR_NOMEM;
     int nbx = 0;
     if (ksize == 1) {
-        if (launch_rn_product_fwd(0, x, Cin * stride_f, w, wsp, z, M, K, Cout, part, &nbx, cap)) return SELD_ERR_INVALID;
+        if (launch_rn_product_fwd(0, k_kc, x, Cin * stride_f, w, wsp, z, M, K, Cout, part, &nbx, cap)) return SELD_ERR_INVALID;
     } else if (wsp && rn_conv3_sb_ok(Cin, Cout)) {      // im2col rows formed on load
-        if (launch_rn_conv3_fwd(0, x, wsp, z, B, H, W, Cin, Cout, part, &nbx, cap)) return SELD_ERR_INVALID;
+        if (launch_rn_conv3_fwd(0, k_kc, x, wsp, z, B, H, W, Cin, Cout, part, &nbx, cap)) return SELD_ERR_INVALID;
     } else {
         float* col = s.get((size_t)M * 9 * Cin);
         if (!col) return SELD_ERR_NOMEM;
         launch_im2col3x3(0, x, col, B, H, W, Cin);
-        if (launch_rn_product_fwd(0, col, K, w, wsp, z, M, K, Cout, part, &nbx, cap)) return SELD_ERR_INVALID;
+        if (launch_rn_product_fwd(0, k_kc, col, K, w, wsp, z, M, K, Cout, part, &nbx, cap)) return SELD_ERR_INVALID;
     }
     // phase 1 folds the partials and stops: gamma, beta, the moving statistics and the coefficients are not touched
     if (sums) launch_rn_bn_finalize(0, part, nbx, (double)M, nullptr, nullptr, nullptr, nullptr, nullptr, Cout, 1, sums, 1);
@@ -459,11 +462,11 @@ int seld_k_rn_conv_bwd_add(const float* x, const float* w, const float* dz, floa
     const int64_t cap = tn_slab_capacity();     // the model's slab buffer
     float* slab = s.get((size_t)cap);
     if (!slab) return SELD_ERR_NOMEM;
-    if (ksize == 3 && g_rn_split_bf16 && rn_conv3_sb_ok(Cin, Cout)) {      // both gradients with the im2col rows formed on load
+    if (ksize == 3 && k_rn_split_bf16 && rn_conv3_sb_ok(Cin, Cout)) {      // both gradients with the im2col rows formed on load
         const unsigned short* wsp_f = rn_k_split(s, w, K1, Cout, 2);
         if (!wsp_f) return SELD_ERR_NOMEM;
-        if (launch_rn_conv3_wgrad(0, x, dz, slab, cap, dw, B, H, W, Cin, Cout)) return SELD_ERR_INVALID;
-        if (launch_rn_conv3_dgrad(0, dz, wsp_f, dx, B, H, W, Cin, Cout)) return SELD_ERR_INVALID;
+        if (launch_rn_conv3_wgrad(0, k_kc, x, dz, slab, cap, dw, B, H, W, Cin, Cout)) return SELD_ERR_INVALID;
+        if (launch_rn_conv3_dgrad(0, k_kc, dz, wsp_f, dx, B, H, W, Cin, Cout)) return SELD_ERR_INVALID;
         return done();
     }
     float* col = ksize == 3 ? s.get((size_t)M * 9 * Cin) : nullptr;
@@ -472,14 +475,14 @@ int seld_k_rn_conv_bwd_add(const float* x, const float* w, const float* dz, floa
     const unsigned short* wsp_t = rn_k_split(s, w, K1, Cout, 1);
     if (ksize == 3) {
         launch_im2col3x3(0, x, col, B, H, W, Cin);
-        if (launch_rn_product_wgrad(0, col, K1, dz, slab, cap, dw, M, K1, Cout, g_rn_split_bf16)) return SELD_ERR_INVALID;
-        if (launch_rn_product_dgrad(0, dz, w, wsp_t, dcol, K1, M, K1, Cout, 0)) return SELD_ERR_INVALID;
+        if (launch_rn_product_wgrad(0, k_kc, col, K1, dz, slab, cap, dw, M, K1, Cout, k_rn_split_bf16)) return SELD_ERR_INVALID;
+        if (launch_rn_product_dgrad(0, k_kc, dz, w, wsp_t, dcol, K1, M, K1, Cout, 0)) return SELD_ERR_INVALID;
         launch_col2im3x3(0, dcol, dx, B, H, W, Cin);
     } else {
         const int ldx = Cin * stride_f;
-        if (launch_rn_product_wgrad(0, x, ldx, dz, slab, cap, dw, M, K1, Cout, g_rn_split_bf16)) return SELD_ERR_INVALID;
+        if (launch_rn_product_wgrad(0, k_kc, x, ldx, dz, slab, cap, dw, M, K1, Cout, k_rn_split_bf16)) return SELD_ERR_INVALID;
         if (stride_f > 1 && hipMemsetAsync(dx, 0, (size_t)B * H * W * Cin * sizeof(float), 0) != hipSuccess) return SELD_ERR_HIP;
-        const int added = launch_rn_product_dgrad(0, dz, w, wsp_t, dx, ldx, M, K1, Cout, 0, addg, gate4);
+        const int added = launch_rn_product_dgrad(0, k_kc, dz, w, wsp_t, dx, ldx, M, K1, Cout, 0, addg, gate4);
         if (added < 0) return SELD_ERR_INVALID;
         if (addg && added == 1) launch_rn_add_gated(0, dx, addg, gate4, (int64_t)M * Cin);
     }

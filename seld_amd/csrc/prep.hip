@@ -11,11 +11,13 @@ __global__ __launch_bounds__(256) void weight_prep_kernel(GemmSplitJobs a, int n
     else if (weff) heads_weff_body(h, weff, 4 * blockIdx.x + (threadIdx.x >> 6), threadIdx.x & 63);
 }
 
-int launch_weight_prep(hipStream_t st, const GemmSplitJobs& a, int na, const SplitWeightJobs& b, int nb, const HeadsLin& h, float* weff) {
+int launch_weight_prep(hipStream_t st, const KernelChoices& kc, const GemmSplitJobs& a_, int na, const SplitWeightJobs& b_, int nb, const HeadsLin& h, float* weff) {
     if (na < 0 || na > GSB_MAX_JOBS || nb < 0 || nb > 8) return -1;
     if (weff && (h.n[0] + h.n[1] > 64 || h.K + 1 > 4 * 144)) return -1;
     const int ny = na + nb + (weff ? 1 : 0);
     if (ny == 0) return 0;
+    GemmSplitJobs a = a_; SplitWeightJobs b = b_;
+    a.one = b.one = kc.mfma_one;     // bf16 single-product mode: plane 0 = round-to-nearest bf16 (prep.h)
     // 144 block columns: what a conv weight tensor needs (9 * 4096 / 256); the GEMM splits stride over them
     hipLaunchKernelGGL(weight_prep_kernel, dim3(144, ny), dim3(256), 0, st, a, na, b, nb, h, weff);
     return 0;

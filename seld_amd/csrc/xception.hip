@@ -279,41 +279,39 @@ int launch_xc_fold_partials(hipStream_t st, const float* partial, int n, float* 
 }
 
 int xc_dw_fused_slabs(int B, int H) { return (B * H + XD_R - 1) / XD_R; }
-int launch_dw3x3_bwd_fused(hipStream_t st, const float* dy, const float* k, const float* xin, const float* add, float* dx, float* slab, int* nslab,
+int launch_dw3x3_bwd_fused(hipStream_t st, const KernelChoices& kc, const float* dy, const float* k, const float* xin, const float* add, float* dx, float* slab, int* nslab,
                            int B, int H, int W, const float* aff, const float* bn_mean, const float* bn_invstd, float* bn_partial) {
     if (W != 16 || (int64_t)B * H >= (1 << 30)) return -3;
     if (bn_partial && (!aff || !bn_mean || !bn_invstd || add)) return -3;
     const int nb = xc_dw_fused_slabs(B, H);
-    if (bn_partial) hipLaunchKernelGGL((dw3x3_w16_bwd_fused_kernel<true, true>), dim3((unsigned)nb), dim3(256), 0, st, dy, k, xin, add, dx, slab, B * H, H, aff, g_xc_xcd_map, bn_mean, bn_invstd, bn_partial);
-    else if (aff) hipLaunchKernelGGL((dw3x3_w16_bwd_fused_kernel<true, false>), dim3((unsigned)nb), dim3(256), 0, st, dy, k, xin, add, dx, slab, B * H, H, aff, g_xc_xcd_map, nullptr, nullptr, nullptr);
-    else hipLaunchKernelGGL((dw3x3_w16_bwd_fused_kernel<false, false>), dim3((unsigned)nb), dim3(256), 0, st, dy, k, xin, add, dx, slab, B * H, H, aff, g_xc_xcd_map, nullptr, nullptr, nullptr);
+    if (bn_partial) hipLaunchKernelGGL((dw3x3_w16_bwd_fused_kernel<true, true>), dim3((unsigned)nb), dim3(256), 0, st, dy, k, xin, add, dx, slab, B * H, H, aff, kc.xc_xcd_map, bn_mean, bn_invstd, bn_partial);
+    else if (aff) hipLaunchKernelGGL((dw3x3_w16_bwd_fused_kernel<true, false>), dim3((unsigned)nb), dim3(256), 0, st, dy, k, xin, add, dx, slab, B * H, H, aff, kc.xc_xcd_map, nullptr, nullptr, nullptr);
+    else hipLaunchKernelGGL((dw3x3_w16_bwd_fused_kernel<false, false>), dim3((unsigned)nb), dim3(256), 0, st, dy, k, xin, add, dx, slab, B * H, H, aff, kc.xc_xcd_map, nullptr, nullptr, nullptr);
     *nslab = nb;
     return 0;
 }
 
-int g_xc_w16 = 1;          // option "xc_w16": the row-per-workgroup depthwise kernels for W = 16 (0: the generic kernel, for A/B)
-int g_xc_xcd_map = 1;      // option "xc_xcd_map": XCD-contiguous row ranges in the depthwise kernels (0: identity map, for A/B)
-int launch_dw3x3_fwd(hipStream_t st, const float* x, const float* k, float* y, int B, int H, int W, const float* aff) {
+int launch_dw3x3_fwd(hipStream_t st, const KernelChoices& kc, const float* x, const float* k, float* y, int B, int H, int W, const float* aff) {
     const int64_t npix = (int64_t)B * H * W;
-    if (W == 16 && g_xc_w16 && (int64_t)B * H < (1 << 30)) {
-        if (aff) hipLaunchKernelGGL((dw3x3_w16_kernel<false, true>), dim3((unsigned)(B * H)), dim3(256), 0, st, x, k, nullptr, nullptr, y, B * H, H, aff, g_xc_xcd_map);
-        else hipLaunchKernelGGL((dw3x3_w16_kernel<false, false>), dim3((unsigned)(B * H)), dim3(256), 0, st, x, k, nullptr, nullptr, y, B * H, H, aff, g_xc_xcd_map);
+    if (W == 16 && kc.xc_w16 && (int64_t)B * H < (1 << 30)) {
+        if (aff) hipLaunchKernelGGL((dw3x3_w16_kernel<false, true>), dim3((unsigned)(B * H)), dim3(256), 0, st, x, k, nullptr, nullptr, y, B * H, H, aff, kc.xc_xcd_map);
+        else hipLaunchKernelGGL((dw3x3_w16_kernel<false, false>), dim3((unsigned)(B * H)), dim3(256), 0, st, x, k, nullptr, nullptr, y, B * H, H, aff, kc.xc_xcd_map);
         return 0;
     }
-    if (aff) hipLaunchKernelGGL((dw3x3_kernel<false, true>), dim3((unsigned)((npix * 16 + 255) / 256)), dim3(256), 0, st, x, k, nullptr, nullptr, y, npix, H, W, aff, g_xc_xcd_map);
-    else hipLaunchKernelGGL((dw3x3_kernel<false, false>), dim3((unsigned)((npix * 16 + 255) / 256)), dim3(256), 0, st, x, k, nullptr, nullptr, y, npix, H, W, aff, g_xc_xcd_map);
+    if (aff) hipLaunchKernelGGL((dw3x3_kernel<false, true>), dim3((unsigned)((npix * 16 + 255) / 256)), dim3(256), 0, st, x, k, nullptr, nullptr, y, npix, H, W, aff, kc.xc_xcd_map);
+    else hipLaunchKernelGGL((dw3x3_kernel<false, false>), dim3((unsigned)((npix * 16 + 255) / 256)), dim3(256), 0, st, x, k, nullptr, nullptr, y, npix, H, W, aff, kc.xc_xcd_map);
     return 0;
 }
-int launch_dw3x3_bwd_data(hipStream_t st, const float* dy, const float* k, const float* xin, const float* add, float* dx, int B, int H,
+int launch_dw3x3_bwd_data(hipStream_t st, const KernelChoices& kc, const float* dy, const float* k, const float* xin, const float* add, float* dx, int B, int H,
                           int W, const float* aff) {
     const int64_t npix = (int64_t)B * H * W;
-    if (W == 16 && g_xc_w16 && (int64_t)B * H < (1 << 30)) {
-        if (aff) hipLaunchKernelGGL((dw3x3_w16_kernel<true, true>), dim3((unsigned)(B * H)), dim3(256), 0, st, dy, k, xin, add, dx, B * H, H, aff, g_xc_xcd_map);
-        else hipLaunchKernelGGL((dw3x3_w16_kernel<true, false>), dim3((unsigned)(B * H)), dim3(256), 0, st, dy, k, xin, add, dx, B * H, H, aff, g_xc_xcd_map);
+    if (W == 16 && kc.xc_w16 && (int64_t)B * H < (1 << 30)) {
+        if (aff) hipLaunchKernelGGL((dw3x3_w16_kernel<true, true>), dim3((unsigned)(B * H)), dim3(256), 0, st, dy, k, xin, add, dx, B * H, H, aff, kc.xc_xcd_map);
+        else hipLaunchKernelGGL((dw3x3_w16_kernel<true, false>), dim3((unsigned)(B * H)), dim3(256), 0, st, dy, k, xin, add, dx, B * H, H, aff, kc.xc_xcd_map);
         return 0;
     }
-    if (aff) hipLaunchKernelGGL((dw3x3_kernel<true, true>), dim3((unsigned)((npix * 16 + 255) / 256)), dim3(256), 0, st, dy, k, xin, add, dx, npix, H, W, aff, g_xc_xcd_map);
-    else hipLaunchKernelGGL((dw3x3_kernel<true, false>), dim3((unsigned)((npix * 16 + 255) / 256)), dim3(256), 0, st, dy, k, xin, add, dx, npix, H, W, aff, g_xc_xcd_map);
+    if (aff) hipLaunchKernelGGL((dw3x3_kernel<true, true>), dim3((unsigned)((npix * 16 + 255) / 256)), dim3(256), 0, st, dy, k, xin, add, dx, npix, H, W, aff, kc.xc_xcd_map);
+    else hipLaunchKernelGGL((dw3x3_kernel<true, false>), dim3((unsigned)((npix * 16 + 255) / 256)), dim3(256), 0, st, dy, k, xin, add, dx, npix, H, W, aff, kc.xc_xcd_map);
     return 0;
 }
 
