@@ -133,7 +133,7 @@ int seld_sync(seld_ctx* ctx);
  * block's forward whenever its pre-BN tensor is not stored (conv_pool_sb.hip).  "conv1_pool_fused" / "conv1_gram" (default 1): first block's pooling inside the conv
  * epilogue / its kernel gradient from the patch Gram matrix.  "dropout_seed" / "dropout_step" (values): the key of the heads' dropout
  * draws and the step counter of the next training forward (seld_arch.sed_dropout / doa_dropout; INTEGRATION.md section 6 lists every key).
- * EVERY key is per context: the kernel choices ("bwd_four_products", "conv64_dbuf", "tn_tile_blocks", "gram_bg_blocks",
+ * EVERY key is per context: the kernel choices ("bwd_four_products", "dgrad_r8", "tn_tile_blocks", "gram_bg_blocks",
  * "bf16_single", ...) are stored in the context and handed to every kernel launch of its passes as an argument, so a six-product
  * context and a four-product context coexist in one process, from one host thread or from two
  * (calls on one context are not thread-safe). */

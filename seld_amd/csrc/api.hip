@@ -504,7 +504,6 @@ int seld_set_option(seld_ctx* c, const char* key, int value) {
     // the context's kernel choices (common.h KernelChoices): its passes hand c->kc to every launcher that chooses by one
     if (!strcmp(key, "bwd_four_products")) { c->kc.bwd_four = value != 0; return SELD_OK; }
     if (!strcmp(key, "tn_tile_blocks") && value >= 64 && value <= 4096) { c->kc.tn_tile_blocks = value; return SELD_OK; }     // gemm_tn_sb.hip
-    if (!strcmp(key, "conv64_dbuf")) { c->kc.conv64_dbuf = value != 0; return SELD_OK; }     // conv_sb.hip
     if (!strcmp(key, "conv_wgrad_side")) { c->conv_wgrad_side = value != 0; return SELD_OK; }
     if (!strcmp(key, "dgrad_r8")) { c->kc.dgrad_r8 = value != 0; return SELD_OK; }
     if (!strcmp(key, "prep_side")) { c->prep_side = value != 0; return SELD_OK; }

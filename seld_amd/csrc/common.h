@@ -87,7 +87,6 @@ struct KernelChoices {
     // rounded value in this mode, planes 1-2 the exact split of the rest, prep.h), so they compute with exact weights.
     int mfma_one = 0;
     int bwd_four = 1;          // option "bwd_four_products": backward-only products (input / kernel gradients) on four of the six split-bf16 terms
-    int conv64_dbuf = 1;       // conv_sb.hip: 1: conv64_fwd_sbd_kernel (double-buffered weights) for W = 16 / 4; 0: conv64_fwd_sbr_kernel
     int dgrad_r8 = 1;          // option "dgrad_r8" (conv_sb.hip): the W = 16 four-product input gradient on 8-row tiles (4 waves, 74 KB of LDS instead of 8 waves, 107 KB: two
                                // workgroups per CU, or one beside a kernel-gradient workgroup of the side stream; the same taps and k-steps per pixel: the same bits;
                                // round 5: 2.510 -> 2.496 ms per step same box)
@@ -127,7 +126,6 @@ int launch_conv_first_fwd_pool(hipStream_t st, const KernelChoices& kc, const fl
                                int Cin, int split_bf16 = 1);
 int launch_conv_first_fwd_pool_sb(hipStream_t st, const KernelChoices& kc, const float* x, const float* w, const float* bias, const float* gamma,
                                   float* zext, unsigned char* amax, float* stat_partial, int* n_partial, int B, int H, int Cin);
-int conv_pool_sb_stat_capacity();
 int launch_pool_argext(hipStream_t st, const float* z, const float* gamma, unsigned char* amax, int B, int H, int W, int pt,
                        int pf);
 int conv_pool_stat_capacity();
@@ -157,19 +155,9 @@ int launch_conv64_wgrad(hipStream_t st, const float* x, const float* dz, float* 
 int conv_wgrad_slab_capacity();
 int conv_first_wgrad_slab_stride(int Cin);   // floats per first-layer wgrad slab: rows 0..9*Cin-1 kernel, row 9*Cin bias
 int launch_flip_weights(hipStream_t st, const float* w, float* wt);
-// split-bf16 conv (conv_sb.hip): w [9][in][out] fp32 -> planes [9][3][out][in] bf16; conv with 6 bf16 MFMAs per product
-int launch_split_weights(hipStream_t st, const KernelChoices& kc, const float* w, unsigned short* wsp);
-// up to 8 tensors in one launch; flip[i] != 0: the planes of the flipped (input-gradient) weights, from the unflipped tensor
+// split-bf16 conv (conv_sb.hip): w [9][in][out] fp32 -> planes [9][3][out][in] bf16; conv with 6 bf16 MFMAs per product.
+// Up to 8 tensors in one launch; flip[i] != 0: the planes of the flipped (input-gradient) weights, from the unflipped tensor
 int launch_split_weights_batch(hipStream_t st, const KernelChoices& kc, int n, const float* const* w, unsigned short* const* dst, const int* flip);
-// two-plane split of two floats for the four-product form: hi = the truncated upper 16 bits, mid = the residual ROUNDED to bf16 (half up on the
-// magnitude: one integer add) — with a truncated mid the dropped remainder has the sign of x for every element, and the products it would have
-// carried bias every sum by the same ~2^-16 relative; rounded, it is zero-mean and the dropped terms average out over a sum
-__device__ __forceinline__ void split2r_pair(float x0, float x1, unsigned& h, unsigned& m) {
-    const unsigned u0 = __float_as_uint(x0), u1 = __float_as_uint(x1);
-    h = __builtin_amdgcn_perm(u1, u0, 0x07060302);
-    const float r0 = x0 - __uint_as_float(u0 & 0xffff0000u), r1 = x1 - __uint_as_float(u1 & 0xffff0000u);
-    m = __builtin_amdgcn_perm(__float_as_uint(r1) + 0x8000u, __float_as_uint(r0) + 0x8000u, 0x07060302);
-}
 // the input gradient of a 64 -> 64 3x3 convolution: a backward-only product, on four products when kc.bwd_four allows
 int launch_conv64_dgrad_sb(hipStream_t st, const KernelChoices& kc, const float* dz, const unsigned short* wsp_flip, float* dx, int B, int H, int W);
 // pre_scale / pre_shift / pre_out (conv64_fwd_sb_takes_pre(kc, W)): x holds the previous block's window extremes; its BatchNorm + ReLU are applied on load
@@ -220,12 +208,10 @@ int launch_rn_bn_bwd_dz(hipStream_t st, const float* z, const float* dy, const f
                         int gate_z = 0);
 int launch_rn_bn_apply2(hipStream_t st, const float* z, const float* coef, const float* zr, const float* coef_r, float* out, int64_t npix, int C,
                         unsigned char* gate4 = nullptr);
-int launch_rn_add_masked(hipStream_t st, float* dst, const float* dy, const float* mask, int64_t n);
 // the three products of a convolution ([M,K] rows x [K,N] kernel): split-bf16 kernels when the shape allows and pre-split planes are
 // given (wsp: launch_gemm_split_b of w, wsp_t: of w^T), else the fp32 MFMA GEMM
 int rn_sb_fwd_ok(int K, int N);
 int rn_sb_dgrad_ok(int K, int N);
-int rn_sb_wgrad_ok(int K, int N);
 int launch_rn_product_fwd(hipStream_t st, const KernelChoices& kc, const float* A, int lda, const float* w, const unsigned short* wsp, float* z, int M, int K, int N,
                           float* stat_part = nullptr, int* nbx = nullptr, size_t part_cap = 0);
 int launch_rn_product_dgrad(hipStream_t st, const KernelChoices& kc, const float* dz, const float* w, const unsigned short* wsp_t, float* dA, int ldd, int M, int K, int N,
@@ -350,7 +336,6 @@ int launch_reduce_slabs2(hipStream_t st, const float* slab, int nslab, int64_t s
 int gemm_tn_max_splits();
 // floats of the kernel-gradient slab buffer a model context holds (the GRU's largest product, gemm_tn_max_splits() slabs of it)
 inline int64_t tn_slab_capacity() { return (int64_t)gemm_tn_max_splits() * (384 * 384 + 384); }
-int launch_colsum(hipStream_t st, const float* X, int ld, float* slab, int* nslab, int M, int N);
 
 int launch_gru_fwd(hipStream_t st, const float* gx_f, const float* gx_b, const float* U_f, const float* U_b,
                    const float* brec_f, const float* brec_b, float* h_f, float* h_b, float* sv_f, float* sv_b,

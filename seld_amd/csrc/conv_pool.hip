@@ -145,13 +145,7 @@ __global__ __launch_bounds__(256, 2) void conv_first_fwd_pool_kernel(const float
         }                                                                                               \
     }
     static_assert(NS >= 32, "the drain of half a tile is spread over 32 k-steps");
-#ifdef CPOOL_TIMING
-    long long tm_top = 0, tm_a = 0, tm_b = 0, tm_commit = 0, tm_epi = 0, tm_bar = 0;
-#endif
     for (; tile < ntiles; tile += gridDim.x) {
-#ifdef CPOOL_TIMING
-        const long long c0 = clock64();
-#endif
         const int b = tile / tiles_per_img, t0 = (tile - b * tiles_per_img) * 10;
         const int nxt = tile + gridDim.x;
         CP_ISSUE(nxt < ntiles ? nxt : tile)
@@ -164,9 +158,6 @@ __global__ __launch_bounds__(256, 2) void conv_first_fwd_pool_kernel(const float
         const size_t er = ((size_t)(b * HP + tg / 5) * 16 + 8 * strip) * 64;
         float best = 0.f;
         int bpos = 0;
-#ifdef CPOOL_TIMING
-        const long long c1 = clock64();
-#endif
         f32x16 accA0 = zero16(), accA1 = zero16(), accA2 = zero16(), accA3 = zero16(), accA4 = zero16();
         f32x16 accB0 = zero16(), accB1 = zero16(), accB2 = zero16(), accB3 = zero16(), accB4 = zero16();
         if constexpr (!WRITE_Z) {
@@ -219,13 +210,10 @@ __global__ __launch_bounds__(256, 2) void conv_first_fwd_pool_kernel(const float
                 a0 = n0; a1 = n1; a2 = n2; a3 = n3; a4 = n4; b0 = m0;
             }
         }
-#ifdef CPOOL_TIMING
-        const long long c2 = clock64();
-#endif
         // ---- phase B: channels 32..63, and under its MFMAs the results of phase A trickle out: one accumulator
         // register (5 stores) every second k-step.  A wave can have 64 vector-memory operations in flight
         // (vmcnt); the 160 stores of a whole tile issued in one burst stalled on HBM write acknowledgements
-        // for ~19k cycles per tile (measured with -DCPOOL_TIMING), longer than the other block's k-loop.
+        // for ~19k cycles per tile (measured with per-phase cycle counters), longer than the other block's k-loop.
         {
             float a0, a1, a2, a3, a4, b0;
             CP_LD(0, 1, a0, a1, a2, a3, a4, b0)
@@ -245,29 +233,16 @@ __global__ __launch_bounds__(256, 2) void conv_first_fwd_pool_kernel(const float
             }
         }
         }
-#ifdef CPOOL_TIMING
-        const long long c3 = clock64();
-#endif
         // Commit the prefetched patch BEFORE the remaining z stores: vmcnt counts loads and stores in one
         // in-order queue, so waiting for loads issued ahead of stores would wait for those stores too.
         CP_COMMIT(patch0 + (cur ^ 1) * G::PATCH)
         __builtin_amdgcn_sched_barrier(0);
-#ifdef CPOOL_TIMING
-        const long long c4 = clock64();
-#endif
         if (live) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) CP_DRAIN(r, 1, accB0, accB1, accB2, accB3, accB4)
         }
-#ifdef CPOOL_TIMING
-        const long long c5 = clock64();
-#endif
         lds_barrier();
         cur ^= 1;
-#ifdef CPOOL_TIMING
-        const long long c6 = clock64();
-        tm_top += c1 - c0; tm_a += c2 - c1; tm_b += c3 - c2; tm_commit += c4 - c3; tm_epi += c5 - c4; tm_bar += c6 - c5;
-#endif
     }
 #undef CP_DRAIN
 #undef CP_LD
@@ -289,13 +264,6 @@ __global__ __launch_bounds__(256, 2) void conv_first_fwd_pool_kernel(const float
         }
         __syncthreads();
         if (tid < 128) stat_partial[(size_t)blockIdx.x * 128 + tid] = (red[tid] + red[128 + tid]) + (red[256 + tid] + red[384 + tid]);
-#ifdef CPOOL_TIMING
-        __syncthreads();
-        if (tid == 0) {      // debug build: the first 6 statistics slots carry wave 0's phase cycles instead
-            float* o = stat_partial + (size_t)blockIdx.x * 128;
-            o[0] = (float)tm_top; o[1] = (float)tm_a; o[2] = (float)tm_b; o[3] = (float)tm_commit; o[4] = (float)tm_epi; o[5] = (float)tm_bar;
-        }
-#endif
     }
 }
 

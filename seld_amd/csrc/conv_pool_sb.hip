@@ -14,23 +14,9 @@
 // (w & 1), 5 row tiles x 2 channel halves = 10 accumulator tiles that share the 6 weight fragments of a k-step.
 // The patch (3 bf16 planes [12][66][CP]) is single-buffered: two workgroups share a CU and cover each other's staging.
 #include "common.h"
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+#include "sb_tile.h"
 
 #define CPSB_MAX_PERSISTENT 512
-int conv_pool_sb_stat_capacity() { return CPSB_MAX_PERSISTENT; }
-
-// exact 3-way truncation split of two floats, packed as bf16 pairs (element 0 in the low half) — as conv_sb.hip
-__device__ __forceinline__ void cpsb_split3_pair(float x0, float x1, unsigned& h, unsigned& m, unsigned& l) {
-    const unsigned u0 = __float_as_uint(x0), u1 = __float_as_uint(x1);
-    h = __builtin_amdgcn_perm(u1, u0, 0x07060302);
-    const float r0 = x0 - __uint_as_float(u0 & 0xffff0000u), r1 = x1 - __uint_as_float(u1 & 0xffff0000u);
-    const unsigned v0 = __float_as_uint(r0), v1 = __float_as_uint(r1);
-    m = __builtin_amdgcn_perm(v1, v0, 0x07060302);
-    const float s0 = r0 - __uint_as_float(v0 & 0xffff0000u), s1 = r1 - __uint_as_float(v1 & 0xffff0000u);
-    l = __builtin_amdgcn_perm(__float_as_uint(s1), __float_as_uint(s0), 0x07060302);
-}
 
 template <int CIN>
 struct PoolSbGeom {
@@ -115,18 +101,18 @@ __global__ __launch_bounds__(256, (CIN < 8 ? 2 : 1)) void conv_first_fwd_pool_sb
         unsigned short* d_ = patch + (((idx >> 6) * 66 + (idx & 63) + 1) * CP);                         \
         _Pragma("unroll") for (int q = 0; q < CP / 8; ++q) {                                            \
             if (ONE) {                                                                                  \
-                const u32x4 rv_ = {bf16_rne_bits(CPSB_SLOT(u, 8 * q + 0)) | (bf16_rne_bits(CPSB_SLOT(u, 8 * q + 1)) << 16), \
-                                   bf16_rne_bits(CPSB_SLOT(u, 8 * q + 2)) | (bf16_rne_bits(CPSB_SLOT(u, 8 * q + 3)) << 16), \
-                                   bf16_rne_bits(CPSB_SLOT(u, 8 * q + 4)) | (bf16_rne_bits(CPSB_SLOT(u, 8 * q + 5)) << 16), \
-                                   bf16_rne_bits(CPSB_SLOT(u, 8 * q + 6)) | (bf16_rne_bits(CPSB_SLOT(u, 8 * q + 7)) << 16)}; \
+                const u32x4 rv_ = {rne_pair(CPSB_SLOT(u, 8 * q + 0), CPSB_SLOT(u, 8 * q + 1)), \
+                                   rne_pair(CPSB_SLOT(u, 8 * q + 2), CPSB_SLOT(u, 8 * q + 3)), \
+                                   rne_pair(CPSB_SLOT(u, 8 * q + 4), CPSB_SLOT(u, 8 * q + 5)), \
+                                   rne_pair(CPSB_SLOT(u, 8 * q + 6), CPSB_SLOT(u, 8 * q + 7))}; \
                 *reinterpret_cast<u32x4*>(d_ + 8 * q) = rv_;                                            \
                 continue;                                                                               \
             }                                                                                           \
             unsigned h0_, h1_, h2_, h3_, m0_, m1_, m2_, m3_, l0_, l1_, l2_, l3_;                        \
-            cpsb_split3_pair(CPSB_SLOT(u, 8 * q + 0), CPSB_SLOT(u, 8 * q + 1), h0_, m0_, l0_);          \
-            cpsb_split3_pair(CPSB_SLOT(u, 8 * q + 2), CPSB_SLOT(u, 8 * q + 3), h1_, m1_, l1_);          \
-            cpsb_split3_pair(CPSB_SLOT(u, 8 * q + 4), CPSB_SLOT(u, 8 * q + 5), h2_, m2_, l2_);          \
-            cpsb_split3_pair(CPSB_SLOT(u, 8 * q + 6), CPSB_SLOT(u, 8 * q + 7), h3_, m3_, l3_);          \
+            split3_pair(CPSB_SLOT(u, 8 * q + 0), CPSB_SLOT(u, 8 * q + 1), h0_, m0_, l0_);          \
+            split3_pair(CPSB_SLOT(u, 8 * q + 2), CPSB_SLOT(u, 8 * q + 3), h1_, m1_, l1_);          \
+            split3_pair(CPSB_SLOT(u, 8 * q + 4), CPSB_SLOT(u, 8 * q + 5), h2_, m2_, l2_);          \
+            split3_pair(CPSB_SLOT(u, 8 * q + 6), CPSB_SLOT(u, 8 * q + 7), h3_, m3_, l3_);          \
             const u32x4 hv_ = {h0_, h1_, h2_, h3_}, mv_ = {m0_, m1_, m2_, m3_}, lv_ = {l0_, l1_, l2_, l3_}; \
             *reinterpret_cast<u32x4*>(d_ + 8 * q) = hv_;                                                \
             *reinterpret_cast<u32x4*>(d_ + PLANE + 8 * q) = mv_;                                        \
@@ -148,7 +134,6 @@ __global__ __launch_bounds__(256, (CIN < 8 ? 2 : 1)) void conv_first_fwd_pool_sb
     const unsigned short* pbase = patch + ((5 * grp) * 66 + 32 * strip + li) * CP;
     const unsigned short* wbase = Wl + li * KW + 8 * kg;
     const int lane_e = kg * 64 + li;
-#define CPSB_MFMA(A_, B_, ACC_) ACC_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A_, B_, ACC_, 0, 0, 0)
     // PACK: slot 7 of the fragment <- element (2 s + kg) of the tap-8 pixel (row + 2, bin + 2): dword s of its vector, half kg
 #define CPSB_FRAG(ptr_, p8_)                                                                            \
     ([&]() {                                                                                            \
@@ -161,12 +146,12 @@ __global__ __launch_bounds__(256, (CIN < 8 ? 2 : 1)) void conv_first_fwd_pool_sb
         const unsigned short* ap_ = pa + (j_) * 66 * CP;                                                \
         const unsigned short* p8_ = p8 + (j_) * 66 * CP;                                                \
         const bf16x8 ah = CPSB_FRAG(ap_, p8_);                                                          \
-        CPSB_MFMA(ah, bh0, ACCA_); CPSB_MFMA(ah, bh1, ACCB_);                                           \
+        ACCA_ = mfma_bf16(ah, bh0, ACCA_); ACCB_ = mfma_bf16(ah, bh1, ACCB_);                                           \
         if (!ONE) {                                                                                     \
         const bf16x8 am = CPSB_FRAG(ap_ + PLANE, p8_ + PLANE), al = CPSB_FRAG(ap_ + 2 * PLANE, p8_ + 2 * PLANE);   \
-        CPSB_MFMA(ah, bm0, ACCA_); CPSB_MFMA(ah, bm1, ACCB_);                                           \
-        CPSB_MFMA(am, bh0, ACCA_); CPSB_MFMA(am, bh1, ACCB_); CPSB_MFMA(ah, bl0, ACCA_); CPSB_MFMA(ah, bl1, ACCB_);   \
-        CPSB_MFMA(al, bh0, ACCA_); CPSB_MFMA(al, bh1, ACCB_); CPSB_MFMA(am, bm0, ACCA_); CPSB_MFMA(am, bm1, ACCB_);   \
+        ACCA_ = mfma_bf16(ah, bm0, ACCA_); ACCB_ = mfma_bf16(ah, bm1, ACCB_);                                           \
+        ACCA_ = mfma_bf16(am, bh0, ACCA_); ACCB_ = mfma_bf16(am, bh1, ACCB_); ACCA_ = mfma_bf16(ah, bl0, ACCA_); ACCB_ = mfma_bf16(ah, bl1, ACCB_);   \
+        ACCA_ = mfma_bf16(al, bh0, ACCA_); ACCB_ = mfma_bf16(al, bh1, ACCB_); ACCA_ = mfma_bf16(am, bm0, ACCA_); ACCB_ = mfma_bf16(am, bm1, ACCB_);   \
         }                                                                                               \
     }
     // window reduction of one accumulator register of one channel half: conv_pool.hip's CP_DRAIN without the z store
@@ -194,13 +179,7 @@ __global__ __launch_bounds__(256, (CIN < 8 ? 2 : 1)) void conv_first_fwd_pool_sb
         s1p[c_] += y2;                                                                                  \
         s2p[c_] = __builtin_elementwise_fma(y2, y2, s2p[c_]);                                           \
     }
-#ifdef CPSB_TIMING
-    long long tm_top = 0, tm_mfma = 0, tm_drain = 0, tm_commit = 0;
-#endif
     for (; tile < ntiles; tile += gridDim.x) {
-#ifdef CPSB_TIMING
-        const long long c0 = clock64();
-#endif
         const int b = tile / tiles_per_img, t0 = (tile - b * tiles_per_img) * 10;
         const int nxt = tile + gridDim.x;
         CPSB_ISSUE(nxt < ntiles ? nxt : tile)
@@ -210,9 +189,6 @@ __global__ __launch_bounds__(256, (CIN < 8 ? 2 : 1)) void conv_first_fwd_pool_sb
         const size_t er = ((size_t)(b * HP + tg / 5) * 16 + 8 * strip) * 64;
         float best = 0.f;
         int bpos = 0;
-#ifdef CPSB_TIMING
-        const long long c1 = clock64();
-#endif
         f32x16 accA0 = zero16(), accA1 = zero16(), accA2 = zero16(), accA3 = zero16(), accA4 = zero16();
         f32x16 accB0 = zero16(), accB1 = zero16(), accB2 = zero16(), accB3 = zero16(), accB4 = zero16();
 #pragma unroll
@@ -237,9 +213,6 @@ __global__ __launch_bounds__(256, (CIN < 8 ? 2 : 1)) void conv_first_fwd_pool_sb
             CPSB_ROW(3, accA3, accB3)
             CPSB_ROW(4, accA4, accB4)
         }
-#ifdef CPSB_TIMING
-        const long long c2 = clock64();
-#endif
         if (live) {
             CPSB_STATS(0, accA0) CPSB_STATS(0, accA1) CPSB_STATS(0, accA2) CPSB_STATS(0, accA3) CPSB_STATS(0, accA4)
             CPSB_STATS(1, accB0) CPSB_STATS(1, accB1) CPSB_STATS(1, accB2) CPSB_STATS(1, accB3) CPSB_STATS(1, accB4)
@@ -248,23 +221,15 @@ __global__ __launch_bounds__(256, (CIN < 8 ? 2 : 1)) void conv_first_fwd_pool_sb
 #pragma unroll
             for (int r = 0; r < 16; ++r) CPSB_DRAIN(r, 1, accB0, accB1, accB2, accB3, accB4)
         }
-#ifdef CPSB_TIMING
-        const long long c3 = clock64();
-#endif
         // single patch buffer: everyone is done reading it, then the prefetched tile replaces it
         lds_barrier();
         CPSB_COMMIT()
         lds_barrier();
-#ifdef CPSB_TIMING
-        const long long c4 = clock64();
-        tm_top += c1 - c0; tm_mfma += c2 - c1; tm_drain += c3 - c2; tm_commit += c4 - c3;
-#endif
     }
 #undef CPSB_DRAIN
 #undef CPSB_STATS
 #undef CPSB_ROW
 #undef CPSB_FRAG
-#undef CPSB_MFMA
 #undef CPSB_AOFF
 #undef CPSB_TAP
 #undef CPSB_ISSUE
@@ -287,13 +252,6 @@ __global__ __launch_bounds__(256, (CIN < 8 ? 2 : 1)) void conv_first_fwd_pool_sb
         }
         __syncthreads();
         if (tid < 128) stat_partial[(size_t)blockIdx.x * 128 + tid] = (red[tid] + red[128 + tid]) + (red[256 + tid] + red[384 + tid]);
-#ifdef CPSB_TIMING
-        __syncthreads();
-        if (tid == 0) {      // diagnostic build (tools/tune_conv1.py): the first statistics slots carry wave 0's phase cycles instead
-            float* o = stat_partial + (size_t)blockIdx.x * 128;
-            o[0] = (float)tm_top; o[1] = (float)tm_mfma; o[2] = (float)tm_drain; o[3] = (float)tm_commit;
-        }
-#endif
     }
 }
 

@@ -11,12 +11,12 @@
 // Tile: 256 pixels x 64 output channels per 512-thread block (8 waves, wave w = pixel rows 32w..32w+31 x both
 // co-tiles).  Per tap: the fp32 A tile [256 px][64 ci] is prefetched into registers during the previous tap's
 // MFMAs, split at commit time into three bf16 planes in LDS (row stride 144 B: conflict-free 16-B fragment
-// reads); the tap's weights come pre-split and pre-transposed ([co][ci]) from split_weights_kernel.
+// reads); the tap's weights come pre-split and pre-transposed ([co][ci]) from split_weights_batch_kernel.  That is the generic kernel
+// (conv64_fwd_sb_kernel, any W); the widths the models use (W = 16 / 8 / 4) take conv64_fwd_sbd_kernel, which stages a tile's input
+// region once for all nine taps.
 #include "common.h"
 #include "prep.h"
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+#include "sb_tile.h"
 
 #define SB_LD 72                    // bf16 elements per LDS row: 64 + 8 pad (144 B)
 #define SB_A_ELEMS (3 * 256 * SB_LD)
@@ -25,37 +25,8 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 int conv_sb_partial_capacity() { return SB_MAX_PERSISTENT; }
 
-// exact 3-way truncation split of two floats, packed as bf16 pairs (element 0 in the low half)
-__device__ __forceinline__ void split3_pair(float x0, float x1, unsigned& h, unsigned& m, unsigned& l) {
-    const unsigned u0 = __float_as_uint(x0), u1 = __float_as_uint(x1);
-    h = __builtin_amdgcn_perm(u1, u0, 0x07060302);
-    const float r0 = x0 - __uint_as_float(u0 & 0xffff0000u), r1 = x1 - __uint_as_float(u1 & 0xffff0000u);
-    const unsigned v0 = __float_as_uint(r0), v1 = __float_as_uint(r1);
-    m = __builtin_amdgcn_perm(v1, v0, 0x07060302);
-    const float s0 = r0 - __uint_as_float(v0 & 0xffff0000u), s1 = r1 - __uint_as_float(v1 & 0xffff0000u);
-    l = __builtin_amdgcn_perm(__float_as_uint(s1), __float_as_uint(s0), 0x07060302);
-}
-
-// bf16 single-product mode: the two floats rounded to nearest-even bf16, packed like the planes above
-__device__ __forceinline__ unsigned rne_pair(float x0, float x1) { return bf16_rne_bits(x0) | (bf16_rne_bits(x1) << 16); }
-
-// w [9][in 64][out 64] fp32 -> planes [9][3][out 64][in 64] bf16 (transposed so a B fragment is 8 contiguous k)
-__global__ __launch_bounds__(256) void split_weights_kernel(const float* __restrict__ w, unsigned short* __restrict__ wsp, int one) {
-    const int idx = blockIdx.x * 256 + threadIdx.x;
-    if (idx >= 9 * 4096) return;
-    const int tap = idx >> 12, rem = idx & 4095, out = rem >> 6, in = rem & 63;
-    const float x = w[tap * 4096 + in * 64 + out];
-    const unsigned u = one ? bf16_rne_bits(x) << 16 : __float_as_uint(x) & 0xffff0000u;      // all three planes in both modes: prep.h
-    const float r = x - __uint_as_float(u);
-    const unsigned v = __float_as_uint(r);
-    const float s = r - __uint_as_float(v & 0xffff0000u);
-    unsigned short* o = wsp + (size_t)tap * 3 * 4096 + out * 64 + in;
-    o[0] = (unsigned short)(u >> 16);
-    o[4096] = (unsigned short)(v >> 16);
-    o[2 * 4096] = (unsigned short)(__float_as_uint(s) >> 16);
-}
-
-// several weight tensors in one launch; flip = the input-gradient form: tap 8 - tap with in / out swapped
+// w [9][in 64][out 64] fp32 -> planes [9][3][out 64][in 64] bf16 (transposed so a B fragment is 8 contiguous k), several weight tensors in
+// one launch; flip = the input-gradient form: tap 8 - tap with in / out swapped
 // (wt[tap][co][ci] = w[8 - tap][ci][co], conv.hip flip_weights_kernel) split directly from the unflipped tensor
 __global__ __launch_bounds__(256) void split_weights_batch_kernel(SplitWeightJobs jobs) { split_weights_body(jobs, blockIdx.y, blockIdx.x); }
 
@@ -68,11 +39,8 @@ int launch_split_weights_batch(hipStream_t st, const KernelChoices& kc, int n, c
     return 0;
 }
 
-int launch_split_weights(hipStream_t st, const KernelChoices& kc, const float* w, unsigned short* wsp) {
-    hipLaunchKernelGGL(split_weights_kernel, dim3(9 * 4096 / 256), dim3(256), 0, st, w, wsp, kc.mfma_one);
-    return 0;
-}
-
+// The generic kernel: any image width.  A tile is 256 consecutive pixels of the [B*H*W] pixel axis, whatever rows and clips they fall in; every
+// tap stages its own shifted copy of the tile (border pixels masked per tap), so the A traffic is nine times the region kernel's below.
 template <bool STATS>
 __global__ __launch_bounds__(512) void conv64_fwd_sb_kernel(const float* __restrict__ x, const unsigned short* __restrict__ wsp,
                                                             const float* __restrict__ bias, float* __restrict__ z,
@@ -155,15 +123,17 @@ __global__ __launch_bounds__(512) void conv64_fwd_sb_kernel(const float* __restr
                 }
 #pragma unroll
                 for (int c = 0; c < 2; ++c) {
-                    acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0][c], acc[c], 0, 0, 0);   // hi*hi
-                    acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[1][c], acc[c], 0, 0, 0);   // hi*mid
-                    acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[0][c], acc[c], 0, 0, 0);   // mid*hi
-                    acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[2][c], acc[c], 0, 0, 0);   // hi*lo
-                    acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[0][c], acc[c], 0, 0, 0);   // lo*hi
-                    acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[1][c], acc[c], 0, 0, 0);   // mid*mid
+                    acc[c] = mfma_bf16(a[0], b[0][c], acc[c]);   // hi*hi
+                    acc[c] = mfma_bf16(a[0], b[1][c], acc[c]);   // hi*mid
+                    acc[c] = mfma_bf16(a[1], b[0][c], acc[c]);   // mid*hi
+                    acc[c] = mfma_bf16(a[0], b[2][c], acc[c]);   // hi*lo
+                    acc[c] = mfma_bf16(a[2], b[0][c], acc[c]);   // lo*hi
+                    acc[c] = mfma_bf16(a[1], b[1][c], acc[c]);   // mid*mid
                 }
             }
-            lds_barrier();      // unconditional commit (see conv64_fwd_sbr_kernel): tap 8 re-commits itself
+            // The commit is UNCONDITIONAL (tap 8 re-commits itself): when the staged registers were only used inside an `if (tap < 8)` block the
+            // compiler sank the global loads into that block, i.e. behind the barrier, and every tap paid a full L2 round trip.
+            lds_barrier();
             SB_COMMIT()
             lds_barrier();
         }
@@ -208,260 +178,17 @@ __global__ __launch_bounds__(512) void conv64_fwd_sb_kernel(const float* __restr
 }
 
 // ------------------------------------------------------------------------------------------------
-// Halo-region variant: a tile is R full image rows x W columns (TP = R*W pixels, one wave per 32 pixels).
-// The (R+2) x (W+2) input region is loaded ONCE per tile (prefetched into registers under the previous
-// tile's MFMAs), split into the three bf16 planes once, and all 9 taps read their A fragments from it at
-// shifted pixel rows; only the 27 KB of pre-split weights change per tap.
-template <int WLOG2, int R, bool SWZ, bool STATS>
-__global__ __launch_bounds__(32 * ((R << WLOG2) / 32) * 2) void conv64_fwd_sbr_kernel(
-    const float* __restrict__ x, const unsigned short* __restrict__ wsp, const float* __restrict__ bias,
-    float* __restrict__ z, float* __restrict__ stat_partial, int B, int H) {
-    constexpr int W = 1 << WLOG2, TP = R * W, NW = TP / 32, NT = 64 * NW;
-    constexpr int RW = W + 2, RR = R + 2, NPIX = RR * RW;
-    constexpr int NREG4 = NPIX * 16, NPF = (NREG4 + NT - 1) / NT;      // region float4 slots, per thread
-    constexpr int NW4 = 3 * 64 * 8, NWF = (NW4 + NT - 1) / NT;         // weight uint4 slots per tap, per thread
-    static_assert(TP % 32 == 0, "tile must be whole 32-pixel MFMA row tiles");
-    // LDS rows of 64 bf16 (128 B).  Padded layout: row stride 72 (SB_LD).  Swizzled layout (SWZ): stride 64 and
-    // the 16-byte chunk c of row p stored at chunk c ^ ((p >> 1) & 7): 16 consecutive rows x one chunk index
-    // still cover all 64 banks, with no padding — which is what lets a 256-pixel tile (8 waves, two per SIMD)
-    // fit the 160 KB of LDS next to a tap's weights.
-    constexpr int LD = SWZ ? 64 : SB_LD;
-    extern __shared__ __attribute__((aligned(16))) unsigned short sb_smem[];
-    unsigned short* Rp = sb_smem;                          // [3][NPIX][LD]
-    unsigned short* Wp = sb_smem + 3 * NPIX * LD;          // [3][64][LD]
-    float* red = reinterpret_cast<float*>(Wp + 3 * 64 * LD);  // [NW][128]
-#define SBR_CH(p_, c_) (SWZ ? ((c_) ^ (((p_) >> 1) & 7)) : (c_))      /* where chunk c_ of row p_ lives */
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int hi = lane >> 5, li = lane & 31;
-    const int tiles_per_img = (H + R - 1) / R;
-    const int ntiles = B * tiles_per_img;
-    // static part of this thread's region slots
-    int roff[NPF];        // float offset relative to the tile's first pixel (may be negative: halo)
-    int rrow[NPF];  // region row (image row = t0 - 1 + rrow), -1 = slot unused / outside the image columns
-#pragma unroll
-    for (int u = 0; u < NPF; ++u) {
-        const int idx = tid + NT * u;
-        const int pix = idx >> 4, g = idx & 15;
-        const int rr = pix / RW, cc = pix - rr * RW;
-        const bool ok = idx < NREG4 && cc >= 1 && cc <= W;
-        rrow[u] = ok ? rr : -1;
-        roff[u] = ((rr - 1) * W + (cc - 1)) * 64 + g * 4;
-    }
-    float4 rreg[NPF];
-    static_assert(NWF == 4 || NWF == 3, "weight staging is three or four named registers");
-    u32x4 wreg0, wreg1, wreg2, wreg3;      // named (an indexed array of these was demoted to scratch)
-    float s1[2] = {0.f, 0.f}, s2[2] = {0.f, 0.f};
-#define SBR_ISSUE_REGION(tile_)                                                                         \
-    {                                                                                                   \
-        const int tb_ = (tile_) / tiles_per_img, tt0_ = ((tile_) - tb_ * tiles_per_img) * R;            \
-        const float* org_ = x + (size_t)(tb_ * H + tt0_) * W * 64;                                      \
-        _Pragma("unroll") for (int u = 0; u < NPF; ++u) {                                               \
-            const int t_ = tt0_ - 1 + rrow[u];                                                          \
-            const bool ok_ = rrow[u] >= 0 && t_ >= 0 && t_ < H;                                         \
-            const float4 v_ = *reinterpret_cast<const float4*>(ok_ ? org_ + roff[u] : x);               \
-            rreg[u] = ok_ ? v_ : make_float4(0.f, 0.f, 0.f, 0.f);                                       \
-        }                                                                                               \
-    }
-#define SBR_COMMIT_REGION()                                                                             \
-    _Pragma("unroll") for (int u = 0; u < NPF; ++u) {                                                   \
-        const int idx = tid + NT * u;                                                                   \
-        if (idx < NREG4) {                                                                              \
-            unsigned h0, m0, l0, h1, m1, l1;                                                            \
-            split3_pair(rreg[u].x, rreg[u].y, h0, m0, l0);                                              \
-            split3_pair(rreg[u].z, rreg[u].w, h1, m1, l1);                                              \
-            unsigned short* d_ = Rp + (idx >> 4) * LD + SBR_CH(idx >> 4, (idx & 15) >> 1) * 8 + (idx & 1) * 4; \
-            *reinterpret_cast<uint2*>(d_) = make_uint2(h0, h1);                                         \
-            *reinterpret_cast<uint2*>(d_ + NPIX * LD) = make_uint2(m0, m1);                             \
-            *reinterpret_cast<uint2*>(d_ + 2 * NPIX * LD) = make_uint2(l0, l1);                         \
-        }                                                                                               \
-    }
-#define SBR_W_SRC(tap_, u_) \
-    reinterpret_cast<const u32x4*>(wsp + (size_t)(tap_) * 3 * 4096)[(tid + NT * (u_)) < NW4 ? (tid + NT * (u_)) : 0]
-#define SBR_ISSUE_W(tap_)                                                                               \
-    {                                                                                                   \
-        wreg0 = SBR_W_SRC(tap_, 0);                                                                     \
-        wreg1 = SBR_W_SRC(tap_, 1);                                                                     \
-        wreg2 = SBR_W_SRC(tap_, 2);                                                                     \
-        if (NWF > 3) wreg3 = SBR_W_SRC(tap_, 3);                                                        \
-    }
-#define SBR_W_DST(u_, v_)                                                                               \
-    {                                                                                                   \
-        const int idx = tid + NT * (u_);                                                                \
-        if (idx < NW4) {                                                                                \
-            const int pl = idx >> 9, rem = idx & 511;      /* 512 uint4 per plane: row = rem>>3 */      \
-            *reinterpret_cast<u32x4*>(Wp + pl * 64 * LD + (rem >> 3) * LD + SBR_CH(rem >> 3, rem & 7) * 8) = v_; \
-        }                                                                                               \
-    }
-#define SBR_COMMIT_W()                                                                                  \
-    {                                                                                                   \
-        SBR_W_DST(0, wreg0)                                                                             \
-        SBR_W_DST(1, wreg1)                                                                             \
-        SBR_W_DST(2, wreg2)                                                                             \
-        if (NWF > 3) SBR_W_DST(3, wreg3)                                                                \
-    }
-    int tile = blockIdx.x;
-    // region row of this lane's pixel for tap (0,0): pixel p = 32*wave + li of the tile -> (r, c)
-    const int pl_ = wave * 32 + li;
-    const int pbase = (pl_ >> WLOG2) * RW + (pl_ & (W - 1));       // region row of this lane's pixel at tap (0,0)
-    if (tile < ntiles) {
-        SBR_ISSUE_REGION(tile)
-        SBR_ISSUE_W(0)
-        SBR_COMMIT_REGION()
-        SBR_COMMIT_W()
-    }
-    lds_barrier();
-#ifdef SBR_TIMING
-    long long tm_mfma = 0, tm_b1 = 0, tm_cw = 0, tm_b2 = 0, tm_epi = 0, tm_top = 0, ttop = clock64();
-    int tm_n = 0;
-#endif
-    for (; tile < ntiles; tile += gridDim.x) {
-        const int b = tile / tiles_per_img, t0 = (tile - b * tiles_per_img) * R;
-        const int nxt = tile + gridDim.x;
-        SBR_ISSUE_REGION(nxt < ntiles ? nxt : tile)     // unconditional: no phi on the staged registers
-        __builtin_amdgcn_sched_barrier(0);
-        f32x16 acc[2] = {zero16(), zero16()}, accs[2] = {zero16(), zero16()};
-        const unsigned short* wrow0 = Wp + li * LD;
-        const int wsw = (li >> 1) & 7;        // swizzle key of weight rows li and li + 32 (the same)
-#ifdef SBR_TIMING
-        const long long tc0 = clock64();
-#endif
-#pragma unroll 1
-        for (int tap = 0; tap < 9; ++tap) {
-#ifdef SBR_TIMING
-            const long long ta = clock64();
-#endif
-            SBR_ISSUE_W(tap < 8 ? tap + 1 : 0)          // tap 8 prefetches tap 0 of the next tile
-            __builtin_amdgcn_sched_barrier(0);          // keep the prefetch loads ahead of the MFMA steps
-            const int prow = pbase + (tap / 3) * RW + (tap % 3);
-            const unsigned short* arow = Rp + prow * LD;
-            const int asw = (prow >> 1) & 7;
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                bf16x8 a[3], bb[3][2];
-#pragma unroll
-                for (int pl = 0; pl < 3; ++pl) {
-                    const int ca = SWZ ? ((2 * s + hi) ^ asw) : (2 * s + hi), cw = SWZ ? ((2 * s + hi) ^ wsw) : (2 * s + hi);
-                    a[pl] = *reinterpret_cast<const bf16x8*>(arow + pl * NPIX * LD + 8 * ca);
-                    bb[pl][0] = *reinterpret_cast<const bf16x8*>(wrow0 + pl * 64 * LD + 8 * cw);
-                    bb[pl][1] = *reinterpret_cast<const bf16x8*>(wrow0 + pl * 64 * LD + 32 * LD + 8 * cw);
-                }
-                // Four accumulator chains (channel half x {large, small} products), visited round-robin: a dependent
-                // v_mfma_f32_32x32x16_bf16 cannot issue before its predecessor has left the pipe, and runs of six
-                // MFMAs into one accumulator (the natural order) held the matrix pipe at about half rate.
-#define SBR_MFMA(A_, B_, ACC_) ACC_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A_, B_, ACC_, 0, 0, 0)
-                SBR_MFMA(a[0], bb[0][0], acc[0]);  SBR_MFMA(a[0], bb[0][1], acc[1]);     // hi*hi
-                SBR_MFMA(a[0], bb[1][0], accs[0]); SBR_MFMA(a[0], bb[1][1], accs[1]);    // hi*mid
-                SBR_MFMA(a[1], bb[0][0], acc[0]);  SBR_MFMA(a[1], bb[0][1], acc[1]);     // mid*hi
-                SBR_MFMA(a[0], bb[2][0], accs[0]); SBR_MFMA(a[0], bb[2][1], accs[1]);    // hi*lo
-                SBR_MFMA(a[2], bb[0][0], acc[0]);  SBR_MFMA(a[2], bb[0][1], acc[1]);     // lo*hi
-                SBR_MFMA(a[1], bb[1][0], accs[0]); SBR_MFMA(a[1], bb[1][1], accs[1]);    // mid*mid
-#undef SBR_MFMA
-            }
-            // The commit is UNCONDITIONAL (after tap 8 it stores tap 0 of the next tile): when the staged
-            // registers were only used inside an `if (tap < 8)` block the compiler sank the global loads
-            // into that block, i.e. behind the barrier, and every tap paid a full L2 round trip.
-#ifdef SBR_TIMING
-            const long long tb = clock64();
-#endif
-            lds_barrier();
-#ifdef SBR_TIMING
-            const long long tcc = clock64();
-#endif
-            SBR_COMMIT_W()
-#ifdef SBR_TIMING
-            const long long td = clock64();
-#endif
-            lds_barrier();
-#ifdef SBR_TIMING
-            const long long te = clock64();
-            tm_mfma += tb - ta; tm_b1 += tcc - tb; tm_cw += td - tcc; tm_b2 += te - td;
-#endif
-        }
-#ifdef SBR_TIMING
-        const long long tf = clock64();
-#endif
-        SBR_COMMIT_REGION()     // next tile's region (every wave passed the barrier after tap 8's reads)
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-            const float bv = bias ? bias[c * 32 + li] : 0.f;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int p = wave * 32 + mfma_row(r, hi);          // pixel of the tile
-                const int t = t0 + (p >> WLOG2);
-                if (t < H) {
-                    const float v = (acc[c][r] + accs[c][r]) + bv;
-                    z[((size_t)(b * H + t) * W + (p & (W - 1))) * 64 + c * 32 + li] = v;
-                    s1[c] += v;
-                    s2[c] = fmaf(v, v, s2[c]);
-                }
-            }
-        }
-        lds_barrier();          // the committed region is visible to every wave
-#ifdef SBR_TIMING
-        tm_epi += clock64() - tf; tm_top += tc0 - ttop; ttop = clock64(); ++tm_n;
-#endif
-    }
-#ifdef SBR_TIMING
-    if (tid == 0 && (blockIdx.x == 3 || blockIdx.x == 200))
-        printf("sbr W=%d block %d tiles %d: per tile top %lld  mfma+issue %lld  barrier1 %lld  commitW %lld  barrier2 %lld  epilogue+commitR %lld\n",
-               W, blockIdx.x, tm_n, tm_top / tm_n, tm_mfma / tm_n, tm_b1 / tm_n, tm_cw / tm_n, tm_b2 / tm_n, tm_epi / tm_n);
-#endif
-#undef SBR_ISSUE_REGION
-#undef SBR_COMMIT_REGION
-#undef SBR_ISSUE_W
-#undef SBR_COMMIT_W
-#undef SBR_CH
-#undef SBR_W_SRC
-#undef SBR_W_DST
-    if (STATS) {
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-            s1[c] += __shfl_xor(s1[c], 32);
-            s2[c] += __shfl_xor(s2[c], 32);
-        }
-        __syncthreads();
-        if (hi == 0) {
-            red[wave * 128 + li] = s1[0];
-            red[wave * 128 + 32 + li] = s1[1];
-            red[wave * 128 + 64 + li] = s2[0];
-            red[wave * 128 + 96 + li] = s2[1];
-        }
-        __syncthreads();
-        if (tid < 128) {
-            float t = 0.f;
-#pragma unroll
-            for (int w8 = 0; w8 < NW; ++w8) t += red[w8 * 128 + tid];
-            stat_partial[(size_t)blockIdx.x * 128 + tid] = t;
-        }
-    }
-}
-
-template <int WLOG2, int R, bool SWZ>
-static int launch_sbr(hipStream_t st, const float* x, const unsigned short* wsp, const float* bias, float* z,
-                      float* stat_partial, int* n_partial, int B, int H) {
-    constexpr int W = 1 << WLOG2, NW = (R * W) / 32, NT = 64 * NW, NPIX = (R + 2) * (W + 2), LD = SWZ ? 64 : SB_LD;
-    const int ntiles = B * ((H + R - 1) / R);
-    const int grid = ntiles < 256 ? ntiles : 256;      // one block per CU (LDS-limited), persistent
-    const size_t smem = (size_t)(3 * NPIX * LD + 3 * 64 * LD) * sizeof(unsigned short) + (size_t)NW * 128 * sizeof(float);
-    if (stat_partial) {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(conv64_fwd_sbr_kernel<WLOG2, R, SWZ, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        hipLaunchKernelGGL((conv64_fwd_sbr_kernel<WLOG2, R, SWZ, true>), dim3(grid), dim3(NT), smem, st, x, wsp, bias, z, stat_partial, B, H);
-    } else {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(conv64_fwd_sbr_kernel<WLOG2, R, SWZ, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        hipLaunchKernelGGL((conv64_fwd_sbr_kernel<WLOG2, R, SWZ, false>), dim3(grid), dim3(NT), smem, st, x, wsp, bias, z, stat_partial, B, H);
-    }
-    if (n_partial) *n_partial = grid;
-    return 0;
-}
-
-// ------------------------------------------------------------------------------------------------
-// Double-buffered-weights variant (the default for W = 16 and W = 4).  Two changes against conv64_fwd_sbr_kernel, both aimed at
-// the 18 barriers + 9 serialised weight commits per tile that held its matrix pipe at ~54 % busy:
-//  * the image is exactly W columns wide, so the region's two halo COLUMNS are always zero padding: they are not stored — a lane
-//    whose shifted column falls outside reads ONE shared all-zero row instead — and the LDS they occupied pays for
-//  * a SECOND weight buffer: tap t + 1's pre-split weights are committed while tap t's MFMAs run (they were loaded to registers a
-//    tap earlier), so a tap needs one barrier instead of commit-between-two-barriers.
-// Region = (R + 2) rows x W columns, three bf16 planes, rows XOR-swizzled; weights [2][3][64][64].
+// The region kernel (W = 16 / 8 / 4: every model's 64 -> 64 blocks).  A tile is R full image rows x W columns (TP = R * W pixels, one wave per 32
+// pixels).  The (R + 2) rows x W columns input region of a tile is loaded ONCE (prefetched into registers under the previous tile's MFMAs), split
+// into the bf16 planes once, and all nine taps read their A fragments from it at shifted pixel rows; only the pre-split weights change per tap.
+//  * The image is exactly W columns wide, so a tap's column shift never leaves the region except into zero padding: the padding columns are not
+//    stored — a lane whose shifted column falls outside the image reads ONE shared all-zero row instead.
+//  * TWO weight buffers: tap t + 1's pre-split weights are committed while tap t's MFMAs run (they were loaded to registers a tap earlier), so a
+//    tap costs one barrier, not a commit between two.
+//  * Four accumulator chains (channel half x {large, small} products), visited round-robin: a dependent v_mfma_f32_32x32x16_bf16 cannot issue
+//    before its predecessor has left the pipe, and runs of six MFMAs into one accumulator held the matrix pipe at about half rate.
+// LDS: region [planes][(R + 2) W + 1 rows][64] bf16 with the 16-byte chunk c of row p stored at chunk c ^ ((p >> 1) & 7) (16 consecutive rows x one
+// chunk index cover all 64 banks, no padding); weights [2][planes][64][64], swizzled likewise.
 // ONE: bf16 single-product mode — operands rounded to nearest bf16, plane 0 only (region, weights, fragments), one MFMA per k-step and
 // column tile instead of six.
 // FOUR (round 4, backward products only: option "bwd_four_products"): four of the six products — hi*hi, hi*mid, mid*hi, mid*mid; the two with a lo
@@ -632,18 +359,16 @@ __global__ __launch_bounds__(32 * ((R << WLOG2) / 32) * 2) void conv64_fwd_sbd_k
                     bb[pl][0] = *reinterpret_cast<const bf16x8*>(wrow0 + pl * 64 * LD + 8 * cw);
                     bb[pl][1] = *reinterpret_cast<const bf16x8*>(wrow0 + pl * 64 * LD + 32 * LD + 8 * cw);
                 }
-#define SBD_MFMA(A_, B_, ACC_) ACC_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A_, B_, ACC_, 0, 0, 0)
-                SBD_MFMA(a[0], bb[0][0], acc[0]);  SBD_MFMA(a[0], bb[0][1], acc[1]);     // hi*hi
+                acc[0] = mfma_bf16(a[0], bb[0][0], acc[0]);  acc[1] = mfma_bf16(a[0], bb[0][1], acc[1]);     // hi*hi
                 if (!ONE) {
-                SBD_MFMA(a[0], bb[1][0], accs[0]); SBD_MFMA(a[0], bb[1][1], accs[1]);    // hi*mid
-                SBD_MFMA(a[1], bb[0][0], acc[0]);  SBD_MFMA(a[1], bb[0][1], acc[1]);     // mid*hi
+                accs[0] = mfma_bf16(a[0], bb[1][0], accs[0]); accs[1] = mfma_bf16(a[0], bb[1][1], accs[1]);    // hi*mid
+                acc[0] = mfma_bf16(a[1], bb[0][0], acc[0]);  acc[1] = mfma_bf16(a[1], bb[0][1], acc[1]);     // mid*hi
                 if (!FOUR) {
-                SBD_MFMA(a[0], bb[2][0], accs[0]); SBD_MFMA(a[0], bb[2][1], accs[1]);    // hi*lo
-                SBD_MFMA(a[2], bb[0][0], acc[0]);  SBD_MFMA(a[2], bb[0][1], acc[1]);     // lo*hi
+                accs[0] = mfma_bf16(a[0], bb[2][0], accs[0]); accs[1] = mfma_bf16(a[0], bb[2][1], accs[1]);    // hi*lo
+                acc[0] = mfma_bf16(a[2], bb[0][0], acc[0]);  acc[1] = mfma_bf16(a[2], bb[0][1], acc[1]);     // lo*hi
                 }
-                SBD_MFMA(a[1], bb[1][0], accs[0]); SBD_MFMA(a[1], bb[1][1], accs[1]);    // mid*mid
+                accs[0] = mfma_bf16(a[1], bb[1][0], accs[0]); accs[1] = mfma_bf16(a[1], bb[1][1], accs[1]);    // mid*mid
                 }
-#undef SBD_MFMA
             }
             lds_barrier();      // tap + 1's weights are visible; everyone is done with this tap's buffer
             wb ^= 1;
@@ -687,6 +412,7 @@ __global__ __launch_bounds__(32 * ((R << WLOG2) / 32) * 2) void conv64_fwd_sbd_k
 #undef SBD_CH
 #undef SBD_W_SRC
 #undef SBD_W_DST
+    // BatchNorm statistics: the tail of conv64_fwd_sb_kernel over NW waves (a shared template changed the register allocation of the STATS forms)
     if (STATS) {
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
@@ -776,21 +502,20 @@ static int launch_sbd_four(hipStream_t st, const float* x, const unsigned short*
     return 0;
 }
 
-int conv64_fwd_sb_takes_pre(const KernelChoices& kc, int W) { return (W == 16 || W == 4) && kc.conv64_dbuf && !kc.mfma_one; }
+int conv64_fwd_sb_takes_pre(const KernelChoices& kc, int W) { return (W == 16 || W == 4) && !kc.mfma_one; }
 // the forward convolution and, on the flipped weights, its input gradient (backward: a backward-only product, on four products when the option allows)
 static int conv64_sb(hipStream_t st, const KernelChoices& kc, bool backward, const float* x, const unsigned short* wsp, const float* bias, float* z,
                      float* stat_partial, int* n_partial, int B, int H, int W, const float* pre_scale, const float* pre_shift, float* pre_out,
                      const float* ext_gamma, float* ext_out) {
     const bool four = backward && kc.bwd_four && !kc.mfma_one;
     if ((pre_scale || ext_out) && !conv64_fwd_sb_takes_pre(kc, W)) return -3;
-    if (W == 16 && kc.conv64_dbuf && four && kc.dgrad_r8 && !stat_partial && !pre_scale && !ext_out)
+    if (W == 16 && four && kc.dgrad_r8 && !stat_partial && !pre_scale && !ext_out)
         return launch_sbd_four<4, 8>(st, x, wsp, bias, z, n_partial, B, H);      // option "dgrad_r8"
     // (W = 4 on 40-row tiles — 76 KB, two per CU, 480 tiles in one round — measured: 2.331 -> 2.346 ms per step, not kept: profiles/r05_gru_experiments.txt)
-    if (W == 16 && kc.conv64_dbuf) return launch_sbd<4, 16>(st, kc, four, x, wsp, bias, z, stat_partial, n_partial, B, H, pre_scale, pre_shift, pre_out, ext_gamma, ext_out);   // 8 waves, 156 KB
-    if (W == 4 && kc.conv64_dbuf) return launch_sbd<2, 48>(st, kc, four, x, wsp, bias, z, stat_partial, n_partial, B, H, pre_scale, pre_shift, pre_out);    // 6 waves
-    if (W == 8 && kc.conv64_dbuf) return launch_sbd<3, 32>(st, kc, four, x, wsp, bias, z, stat_partial, n_partial, B, H);    // 8 waves (resnet50_block stage 1)
-    if (W == 16) return launch_sbr<4, 16, true>(st, x, wsp, bias, z, stat_partial, n_partial, B, H);    // 8 waves, 153 KB
-    if (W == 4) return launch_sbr<2, 48, false>(st, x, wsp, bias, z, stat_partial, n_partial, B, H);   // 6 waves (halo columns: no room for 8)
+    if (W == 16) return launch_sbd<4, 16>(st, kc, four, x, wsp, bias, z, stat_partial, n_partial, B, H, pre_scale, pre_shift, pre_out, ext_gamma, ext_out);   // 8 waves, 156 KB
+    if (W == 4) return launch_sbd<2, 48>(st, kc, four, x, wsp, bias, z, stat_partial, n_partial, B, H, pre_scale, pre_shift, pre_out);    // 6 waves
+    if (W == 8) return launch_sbd<3, 32>(st, kc, four, x, wsp, bias, z, stat_partial, n_partial, B, H);    // 8 waves (resnet50_block stage 1)
+    // every other width: the generic kernel
     const int npix = B * H * W;
     const int ntiles = (npix + 255) / 256;
     const int grid = ntiles < SB_MAX_PERSISTENT ? ntiles : SB_MAX_PERSISTENT;

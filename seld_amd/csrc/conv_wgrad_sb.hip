@@ -15,37 +15,12 @@
 // (any 4 consecutive pixels then cover the 64 banks exactly).
 // Output: the slab layout of conv64_wgrad_kernel ([9][64 ci][64 co] + [64] per workgroup), reduced by reduce_slabs.
 #include "common.h"
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
+#include "sb_tile.h"
 
 #define WGSB_MAX_BLOCKS 512
 #define WGSB_SLAB (9 * 4096 + 64)
 #define WGSB_PXC 64            // pixels per chunk
 #define WGSB_HALO 108          // (R + 2) * (W + 2) for W = 16 (6 x 18) and W = 4 (18 x 6); W = 8 uses 100 (10 x 10) of it
-
-__device__ __forceinline__ void wgsb_split3_pair(float x0, float x1, unsigned& h, unsigned& m, unsigned& l) {
-    const unsigned u0 = __float_as_uint(x0), u1 = __float_as_uint(x1);
-    h = __builtin_amdgcn_perm(u1, u0, 0x07060302);
-    const float r0 = x0 - __uint_as_float(u0 & 0xffff0000u), r1 = x1 - __uint_as_float(u1 & 0xffff0000u);
-    const unsigned v0 = __float_as_uint(r0), v1 = __float_as_uint(r1);
-    m = __builtin_amdgcn_perm(v1, v0, 0x07060302);
-    const float s0 = r0 - __uint_as_float(v0 & 0xffff0000u), s1 = r1 - __uint_as_float(v1 & 0xffff0000u);
-    l = __builtin_amdgcn_perm(__float_as_uint(s1), __float_as_uint(s0), 0x07060302);
-}
-
-// 4 pixels x 16 channels, transposed: this lane's address is (pixel row q of the block, 4 of its channels); it receives its
-// own channel column for the 4 pixels
-__device__ __forceinline__ s16x4 wgsb_tr(const char* p) {
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p));
-}
-__device__ __forceinline__ bf16x8 wgsb_frag(const char* p0, const char* p1) {
-    const s16x4 a = wgsb_tr(p0), b = wgsb_tr(p1);
-    return __builtin_bit_cast(bf16x8, __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7));
-}
-
-__device__ __forceinline__ unsigned wgsb_rne_pair(float x0, float x1) { return bf16_rne_bits(x0) | (bf16_rne_bits(x1) << 16); }
 
 // ONE: bf16 single-product mode (common.h KernelChoices::mfma_one): operands rounded to nearest bf16, plane 0 only, one MFMA per (k-step, tap)
 // FOUR (option "bwd_four_products", common.h KernelChoices::bwd_four): the two products with a lo factor are dropped and the lo planes neither staged nor read
@@ -78,7 +53,6 @@ __global__ __launch_bounds__(256, 2) void conv64_wgrad_sb_kernel(const float* __
     f32x16 acc0 = zero16(), acc1 = zero16(), acc2 = zero16(), acc3 = zero16(), acc4 = zero16(), acc5 = zero16(), acc6 = zero16(),
            acc7 = zero16(), acc8 = zero16();
     float4 brun = make_float4(0.f, 0.f, 0.f, 0.f);     // this thread's 4 channels (tid & 15) of the bias gradient
-#define WGSB_MFMA(A_, B_, ACC_) ACC_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A_, B_, ACC_, 0, 0, 0)
     // compile-time pixel offset of the x block of k-step s, half h (pixels 8 kg + 4 h ...), tap (dy, dx), kg part excluded
 #define WGSB_P0(s_, h_, dy_, dx_) (W == 16 ? ((s_) + (dy_)) * RW + 4 * (h_) + (dx_) : W == 8 ? (2 * (s_) + (dy_)) * RW + 4 * (h_) + (dx_) \
                                            : (4 * (s_) + (h_) + (dy_)) * RW + (dx_))
@@ -87,18 +61,18 @@ __global__ __launch_bounds__(256, 2) void conv64_wgrad_sb_kernel(const float* __
     // the order is pinned with sched_barrier: left alone, the scheduler hoists a whole k-step of transposed reads (108
     // registers) above the MFMAs and spills the accumulators.
 #define WGSB_LDA(s_, tap_, H_, M_, L_)                                                                                \
-    H_ = wgsb_frag(WGSB_AADDR(s_, 0, (tap_) / 3, (tap_) % 3, 0), WGSB_AADDR(s_, 1, (tap_) / 3, (tap_) % 3, 0));       \
+    H_ = frag(WGSB_AADDR(s_, 0, (tap_) / 3, (tap_) % 3, 0), WGSB_AADDR(s_, 1, (tap_) / 3, (tap_) % 3, 0));       \
     if (!ONE) {                                                                                                       \
-    M_ = wgsb_frag(WGSB_AADDR(s_, 0, (tap_) / 3, (tap_) % 3, 1), WGSB_AADDR(s_, 1, (tap_) / 3, (tap_) % 3, 1));       \
-    if (!FOUR) L_ = wgsb_frag(WGSB_AADDR(s_, 0, (tap_) / 3, (tap_) % 3, 2), WGSB_AADDR(s_, 1, (tap_) / 3, (tap_) % 3, 2)); \
+    M_ = frag(WGSB_AADDR(s_, 0, (tap_) / 3, (tap_) % 3, 1), WGSB_AADDR(s_, 1, (tap_) / 3, (tap_) % 3, 1));       \
+    if (!FOUR) L_ = frag(WGSB_AADDR(s_, 0, (tap_) / 3, (tap_) % 3, 2), WGSB_AADDR(s_, 1, (tap_) / 3, (tap_) % 3, 2)); \
     }
 #define WGSB_LDB(s_, H_, M_, L_)                                                                                      \
     {                                                                                                                 \
         const char* bp_ = dl + (16 * (s_)) * 128 + offB;                                                              \
-        H_ = wgsb_frag(bp_, bp_ + 4 * 128);                                                                           \
+        H_ = frag(bp_, bp_ + 4 * 128);                                                                           \
         if (!ONE) {                                                                                                   \
-        M_ = wgsb_frag(bp_ + DPL, bp_ + DPL + 4 * 128);                                                               \
-        if (!FOUR) L_ = wgsb_frag(bp_ + 2 * DPL, bp_ + 2 * DPL + 4 * 128);                                            \
+        M_ = frag(bp_ + DPL, bp_ + DPL + 4 * 128);                                                               \
+        if (!FOUR) L_ = frag(bp_ + 2 * DPL, bp_ + 2 * DPL + 4 * 128);                                            \
         }                                                                                                             \
     }
 #define WGSB_TAP(s_, tap_, ACC_)                                                                                      \
@@ -109,11 +83,11 @@ __global__ __launch_bounds__(256, 2) void conv64_wgrad_sb_kernel(const float* __
         if (!last_) { WGSB_LDA(ns_, nt_, nh, nm, nl) }                                                                \
         if (!last_ && (tap_) == 8) WGSB_LDB(ns_, nbh, nbm, nbl)                                                       \
         __builtin_amdgcn_sched_barrier(0);                                                                            \
-        if (!ONE && !FOUR) WGSB_MFMA(al, bh, ACC_);                                                                   \
-        if (!ONE) { WGSB_MFMA(am, bh, ACC_); WGSB_MFMA(am, bm, ACC_); }                                               \
-        WGSB_MFMA(ah, bh, ACC_);                                                                                      \
-        if (!ONE) WGSB_MFMA(ah, bm, ACC_);                                                                            \
-        if (!ONE && !FOUR) WGSB_MFMA(ah, bl, ACC_);                                                                   \
+        if (!ONE && !FOUR) ACC_ = mfma_bf16(al, bh, ACC_);                                                                   \
+        if (!ONE) { ACC_ = mfma_bf16(am, bh, ACC_); ACC_ = mfma_bf16(am, bm, ACC_); }                                               \
+        ACC_ = mfma_bf16(ah, bh, ACC_);                                                                                      \
+        if (!ONE) ACC_ = mfma_bf16(ah, bm, ACC_);                                                                            \
+        if (!ONE && !FOUR) ACC_ = mfma_bf16(ah, bl, ACC_);                                                                   \
         __builtin_amdgcn_sched_barrier(0);                                                                            \
         ah = nh; am = nm; al = nl;                                                                                    \
         if ((tap_) == 8) { bh = nbh; bm = nbm; bl = nbl; }                                                            \
@@ -153,7 +127,7 @@ __global__ __launch_bounds__(256, 2) void conv64_wgrad_sb_kernel(const float* __
     {                                                                                                                 \
         char* d = (base_) + (P_) * 128 + ((8 * (g_)) ^ (64 * (((P_) >> 1) & 1)));                                     \
         if (ONE) {                                                                                                    \
-            *reinterpret_cast<uint2*>(d) = make_uint2(wgsb_rne_pair(v_.x, v_.y), wgsb_rne_pair(v_.z, v_.w));          \
+            *reinterpret_cast<uint2*>(d) = make_uint2(rne_pair(v_.x, v_.y), rne_pair(v_.z, v_.w));          \
         } else if (FOUR) {                                                                                            \
         unsigned h0, m0, h1, m1;                                                                                      \
         split2r_pair(v_.x, v_.y, h0, m0);                                                                             \
@@ -162,8 +136,8 @@ __global__ __launch_bounds__(256, 2) void conv64_wgrad_sb_kernel(const float* __
         *reinterpret_cast<uint2*>(d + (PL_)) = make_uint2(m0, m1);                                                    \
         } else {                                                                                                      \
         unsigned h0, m0, l0, h1, m1, l1;                                                                              \
-        wgsb_split3_pair(v_.x, v_.y, h0, m0, l0);                                                                     \
-        wgsb_split3_pair(v_.z, v_.w, h1, m1, l1);                                                                     \
+        split3_pair(v_.x, v_.y, h0, m0, l0);                                                                     \
+        split3_pair(v_.z, v_.w, h1, m1, l1);                                                                     \
         *reinterpret_cast<uint2*>(d) = make_uint2(h0, h1);                                                            \
         *reinterpret_cast<uint2*>(d + (PL_)) = make_uint2(m0, m1);                                                    \
         *reinterpret_cast<uint2*>(d + 2 * (PL_)) = make_uint2(l0, l1);                                                \
@@ -203,7 +177,6 @@ __global__ __launch_bounds__(256, 2) void conv64_wgrad_sb_kernel(const float* __
 #undef WGSB_LDB
 #undef WGSB_AADDR
 #undef WGSB_P0
-#undef WGSB_MFMA
     float* out = slab + (size_t)blockIdx.x * WGSB_SLAB;
     const int hi = kg, li = lane & 31;
 #define WGSB_OUT(tap_, ACC_)                                                                   \

@@ -15,15 +15,10 @@ static int prepare_heads_weff(seld_ctx* c, hipStream_t st) {
     return launch_heads_weff(st, w1, b1, w2, b2, n, c->heads[0].layers[0].in, c->heads[0].layers[0].out, c->weff);
 }
 
-// one launch splits every weight operand the split-bf16 GEMMs of this step will read (the weights change every step)
-static int prepare_gemm_splits(seld_ctx* c, hipStream_t st, bool with_grad_orientation) {
-    const float* src[16]; unsigned short* dst[16]; int ldb[16], tb[16], K[16], N[16];
-    int n = 0;
-    auto flush = [&]() { int rc = n ? launch_gemm_split_b(st, c->kc, n, src, dst, ldb, tb, K, N) : 0; n = 0; return rc; };
-    auto add = [&](const float* w, unsigned short* d, int ld, int transb, int k, int nn) {
-        src[n] = w; dst[n] = d; ldb[n] = ld; tb[n] = transb; K[n] = k; N[n] = nn;
-        return ++n == 16 ? flush() : 0;
-    };
+// The GEMM weight operands a step pre-splits (gemm_sb.hip's planes; the weights change every step): the GRU input projections and the heads'
+// first layer, each with its gradient orientation when a backward follows.  add(w, planes, ldb, transb, K, N) != 0 stops the walk.
+template <typename Add>
+static int gemm_split_jobs(seld_ctx* c, bool with_grad_orientation, Add add) {
     for (size_t i = 0; i < c->gru.size(); ++i) {
         const GruL& G = c->gru[i];
         if (!gru_sb(c, G)) continue;
@@ -38,7 +33,26 @@ static int prepare_gemm_splits(seld_ctx* c, hipStream_t st, bool with_grad_orien
             if (add(c->params + D.w_off, c->h0sp_fwd[hd], D.out, 0, D.in, D.out)) return -1;
             if (with_grad_orientation && add(c->params + D.w_off, c->h0sp_bwd[hd], D.out, 1, D.out, D.in)) return -1;
         }
-    return flush();
+    return 0;
+}
+
+// launch_gemm_split_b jobs gathered 16 to a launch (the stand-alone kernel: resnet50_block's planes, and the fallback of forward_weight_prep)
+struct GemmSplitBatch {
+    seld_ctx* c;
+    hipStream_t st;
+    const float* src[16]; unsigned short* dst[16]; int ldb[16], tb[16], K[16], N[16];
+    int n = 0;
+    int flush() { const int rc = n ? launch_gemm_split_b(st, c->kc, n, src, dst, ldb, tb, K, N) : 0; n = 0; return rc; }
+    int add(const float* w, unsigned short* d, int ld, int transb, int k, int nn) {
+        src[n] = w; dst[n] = d; ldb[n] = ld; tb[n] = transb; K[n] = k; N[n] = nn;
+        return ++n == 16 ? flush() : 0;
+    }
+};
+
+static int prepare_gemm_splits(seld_ctx* c, hipStream_t st, bool with_grad_orientation) {
+    GemmSplitBatch b{c, st};
+    if (gemm_split_jobs(c, with_grad_orientation, [&](const float* w, unsigned short* d, int ld, int transb, int k, int nn) { return b.add(w, d, ld, transb, k, nn); })) return -1;
+    return b.flush();
 }
 
 // BatchNormalization of a resnet50_block convolution: statistics (training) or moving statistics -> cv.coef
@@ -70,12 +84,8 @@ static int heads_couple(seld_ctx* c, float* doa, int rows) {
 // resnet50_block: this step's pre-split weight planes (16 operands per launch), on `st`.  They depend on the parameters only: with `prep_side` they are made
 // on the side stream beside the entry convolution and taken back (ev_prep) in front of the first stage (round 5: 0.15 ms of the 14.4-ms step).
 static void rn_weight_prep(seld_ctx* c, hipStream_t st, bool save) {
-    const float* src[16]; unsigned short* dst[16]; int ldb[16], tb[16], Ks[16], Ns[16];
-    int n = 0;
-    auto add = [&](const float* w, unsigned short* d, int ld, int transb, int k, int nn) {
-        src[n] = w; dst[n] = d; ldb[n] = ld; tb[n] = transb; Ks[n] = k; Ns[n] = nn;
-        if (++n == 16) { launch_gemm_split_b(st, c->kc, n, src, dst, ldb, tb, Ks, Ns); n = 0; }
-    };
+    GemmSplitBatch sb{c, st};
+    auto add = [&](const float* w, unsigned short* d, int ld, int transb, int k, int nn) { sb.add(w, d, ld, transb, k, nn); };
     for (auto& R : c->rn)
         for (RnConv* cv : {&R.c[0], &R.c[1], &R.c[2], &R.sc}) {
             const int K = cv->k * cv->k * cv->Cin, N = cv->Cout;
@@ -85,9 +95,9 @@ static void rn_weight_prep(seld_ctx* c, hipStream_t st, bool save) {
                 else add(c->params + cv->w_off, cv->wsp_t, N, 1, N, K);
             }
         }
-    if (n) launch_gemm_split_b(st, c->kc, n, src, dst, ldb, tb, Ks, Ns);
+    sb.flush();
     const float* w9[8]; unsigned short* d9[8]; int f9[8];
-    n = 0;
+    int n = 0;
     for (auto& R : c->rn) {
         if (!rn_c1_direct(R)) continue;
         const float* wsrc = c->params + R.c[1].w_off;
@@ -138,24 +148,11 @@ static int forward_weight_prep(seld_ctx* c, bool save, bool* prep_on_side, bool*
     GemmSplitJobs a; SplitWeightJobs b; HeadsLin h;
     int na = 0, nb = 0;
     bool fits = true;
-    auto adda = [&](const float* w, unsigned short* d, int ld, int transb, int k, int nn) {
-        if (na == GSB_MAX_JOBS) { fits = false; return; }
+    gemm_split_jobs(c, save, [&](const float* w, unsigned short* d, int ld, int transb, int k, int nn) {
+        if (na == GSB_MAX_JOBS) { fits = false; return 1; }
         a.src[na] = w; a.dst[na] = d; a.ldb[na] = ld; a.transb[na] = transb; a.K[na] = k; a.N[na] = nn; ++na;
-    };
-    for (size_t i = 0; i < c->gru.size(); ++i) {
-        const GruL& G = c->gru[i];
-        if (!gru_sb(c, G)) continue;
-        for (int d = 0; d < 2; ++d) {
-            adda(c->params + G.k_off[d], c->ksp_fwd[i][d], 384, 0, G.in_feat, 384);                // gx = feat K
-            if (save) adda(c->params + G.k_off[d], c->ksp_bwd[i][d], 384, 1, 384, G.in_feat);      // din = dgx K^T
-        }
-    }
-    if (heads_sb(c) && !heads_lin(c))
-        for (int hd = 0; hd < 2; ++hd) {
-            const DenseL& D = c->heads[hd].layers[0];
-            adda(c->params + D.w_off, c->h0sp_fwd[hd], D.out, 0, D.in, D.out);
-            if (save) adda(c->params + D.w_off, c->h0sp_bwd[hd], D.out, 1, D.out, D.in);
-        }
+        return 0;
+    });
     a.njobs = na;
     // the 64 -> 64 conv blocks' planes (forward, and flipped taps when a backward follows): one list for either form below
     static_assert(2 * (SELD_MAX_LAYERS - 1) <= 8, "the conv64 weight planes of a step fit one SplitWeightJobs");

@@ -15,25 +15,10 @@
 // multiplied.  Column groups are the fast grid index so the blocks that share rows of A run together.
 #include "common.h"
 #include "prep.h"
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+#include "sb_tile.h"
 
 #define GSB_KC 32
 #define GSB_BN 128
-
-// exact 3-way truncation split of two floats, packed as bf16 pairs (element 0 in the low half) — as conv_sb.hip
-__device__ __forceinline__ void gsb_split3_pair(float x0, float x1, unsigned& h, unsigned& m, unsigned& l) {
-    const unsigned u0 = __float_as_uint(x0), u1 = __float_as_uint(x1);
-    h = __builtin_amdgcn_perm(u1, u0, 0x07060302);
-    const float r0 = x0 - __uint_as_float(u0 & 0xffff0000u), r1 = x1 - __uint_as_float(u1 & 0xffff0000u);
-    const unsigned v0 = __float_as_uint(r0), v1 = __float_as_uint(r1);
-    m = __builtin_amdgcn_perm(v1, v0, 0x07060302);
-    const float s0 = r0 - __uint_as_float(v0 & 0xffff0000u), s1 = r1 - __uint_as_float(v1 & 0xffff0000u);
-    l = __builtin_amdgcn_perm(__float_as_uint(s1), __float_as_uint(s0), 0x07060302);
-}
-
-__device__ __forceinline__ unsigned gsb_rne_pair(float x0, float x1) { return bf16_rne_bits(x0) | (bf16_rne_bits(x1) << 16); }
 
 // ---- weight pre-pass ---------------------------------------------------------------------------
 // B fp32 ([K,N] if !transb, [N,K] if transb) -> planes [chunk c = k/32][plane][n][piece'][8] bf16 with
@@ -69,7 +54,7 @@ int launch_gemm_split_b(hipStream_t st, const KernelChoices& kc, int njobs, cons
 // ONE: bf16 single-product mode (common.h KernelChoices::mfma_one): A rounded to nearest bf16 in registers, B's plane 0 holds the rounded weights
 // (gemm_split_b with jobs.one); one MFMA per k-step and column tile.  The B staging still moves all three planes (untouched code path).
 // FOUR (option "bwd_four_products", launch_gemm_sb's `backward` argument — backward products only): the two products with a lo factor are dropped, plane 2 of B is
-// not staged, A is split in two planes with a rounded mid (common.h split2r_pair; gemm_split_b rounds the mid plane of every transposed / flipped B likewise)
+// not staged, A is split in two planes with a rounded mid (sb_tile.h split2r_pair; gemm_split_b rounds the mid plane of every transposed / flipped B likewise)
 template <int NG, bool ONE = false, bool FOUR = false>   // NG 4: K = 128, one product (or two sharing A): every A row of the tile is requested up front; 0: runtime loop
 __global__ __launch_bounds__(256, NG == 4 ? 2 : 3) void gemm_sb_kernel(const float* __restrict__ A0, const float* __restrict__ A1, int lda,
                                                          const unsigned short* __restrict__ Bs0,
@@ -121,15 +106,14 @@ __global__ __launch_bounds__(256, NG == 4 ? 2 : 3) void gemm_sb_kernel(const flo
     // fragment of column (nt*32 + li), k-step s: piece (2 kg + s) ^ ((li >> 2) & 3) of its 64-B row
     const int swz = (li >> 2) & 3;
     const int boff0 = li * GSB_KC + (((2 * kg) ^ swz) << 3), boff1 = li * GSB_KC + (((2 * kg + 1) ^ swz) << 3);
-#define GSB_MFMA(A_, B_, ACC_) ACC_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A_, B_, ACC_, 0, 0, 0)
 #define GSB_STEP(x0_, x1_, boff_)                                                                     \
     if (ONE) {                                                                                        \
-        const u32x4 h_ = {gsb_rne_pair(x0_.x, x0_.y), gsb_rne_pair(x0_.z, x0_.w), gsb_rne_pair(x1_.x, x1_.y), gsb_rne_pair(x1_.z, x1_.w)}; \
+        const u32x4 h_ = {rne_pair(x0_.x, x0_.y), rne_pair(x0_.z, x0_.w), rne_pair(x1_.x, x1_.y), rne_pair(x1_.z, x1_.w)}; \
         const bf16x8 ah = __builtin_bit_cast(bf16x8, h_);                                             \
         const unsigned short* bb_ = bl + boff_;                                                       \
         const bf16x8 bh0 = *reinterpret_cast<const bf16x8*>(bb_), bh1 = *reinterpret_cast<const bf16x8*>(bb_ + 32 * GSB_KC), \
                      bh2 = *reinterpret_cast<const bf16x8*>(bb_ + 64 * GSB_KC), bh3 = *reinterpret_cast<const bf16x8*>(bb_ + 96 * GSB_KC); \
-        GSB_MFMA(ah, bh0, acc0); GSB_MFMA(ah, bh1, acc1); GSB_MFMA(ah, bh2, acc2); GSB_MFMA(ah, bh3, acc3);   \
+        acc0 = mfma_bf16(ah, bh0, acc0); acc1 = mfma_bf16(ah, bh1, acc1); acc2 = mfma_bf16(ah, bh2, acc2); acc3 = mfma_bf16(ah, bh3, acc3);   \
     } else if (FOUR) {                                                                                \
         unsigned h0_, h1_, h2_, h3_, m0_, m1_, m2_, m3_;                                              \
         split2r_pair(x0_.x, x0_.y, h0_, m0_);                                                         \
@@ -144,17 +128,17 @@ __global__ __launch_bounds__(256, NG == 4 ? 2 : 3) void gemm_sb_kernel(const flo
         const unsigned short* bm_ = bb_ + GSB_BN * GSB_KC;                                            \
         const bf16x8 bm0 = *reinterpret_cast<const bf16x8*>(bm_), bm1 = *reinterpret_cast<const bf16x8*>(bm_ + 32 * GSB_KC), \
                      bm2 = *reinterpret_cast<const bf16x8*>(bm_ + 64 * GSB_KC), bm3 = *reinterpret_cast<const bf16x8*>(bm_ + 96 * GSB_KC); \
-        GSB_MFMA(ah, bh0, acc0); GSB_MFMA(ah, bh1, acc1); GSB_MFMA(ah, bh2, acc2); GSB_MFMA(ah, bh3, acc3);   /* hi*hi  */ \
-        GSB_MFMA(ah, bm0, acc0); GSB_MFMA(ah, bm1, acc1); GSB_MFMA(ah, bm2, acc2); GSB_MFMA(ah, bm3, acc3);   /* hi*mid */ \
-        GSB_MFMA(am, bh0, acc0); GSB_MFMA(am, bh1, acc1); GSB_MFMA(am, bh2, acc2); GSB_MFMA(am, bh3, acc3);   /* mid*hi */ \
-        GSB_MFMA(am, bm0, acc0); GSB_MFMA(am, bm1, acc1); GSB_MFMA(am, bm2, acc2); GSB_MFMA(am, bm3, acc3);   /* mid*mid */ \
+        acc0 = mfma_bf16(ah, bh0, acc0); acc1 = mfma_bf16(ah, bh1, acc1); acc2 = mfma_bf16(ah, bh2, acc2); acc3 = mfma_bf16(ah, bh3, acc3);   /* hi*hi  */ \
+        acc0 = mfma_bf16(ah, bm0, acc0); acc1 = mfma_bf16(ah, bm1, acc1); acc2 = mfma_bf16(ah, bm2, acc2); acc3 = mfma_bf16(ah, bm3, acc3);   /* hi*mid */ \
+        acc0 = mfma_bf16(am, bh0, acc0); acc1 = mfma_bf16(am, bh1, acc1); acc2 = mfma_bf16(am, bh2, acc2); acc3 = mfma_bf16(am, bh3, acc3);   /* mid*hi */ \
+        acc0 = mfma_bf16(am, bm0, acc0); acc1 = mfma_bf16(am, bm1, acc1); acc2 = mfma_bf16(am, bm2, acc2); acc3 = mfma_bf16(am, bm3, acc3);   /* mid*mid */ \
     } else                                                                                            \
     {                                                                                                 \
         unsigned h0_, h1_, h2_, h3_, m0_, m1_, m2_, m3_, l0_, l1_, l2_, l3_;                          \
-        gsb_split3_pair(x0_.x, x0_.y, h0_, m0_, l0_);                                                 \
-        gsb_split3_pair(x0_.z, x0_.w, h1_, m1_, l1_);                                                 \
-        gsb_split3_pair(x1_.x, x1_.y, h2_, m2_, l2_);                                                 \
-        gsb_split3_pair(x1_.z, x1_.w, h3_, m3_, l3_);                                                 \
+        split3_pair(x0_.x, x0_.y, h0_, m0_, l0_);                                                 \
+        split3_pair(x0_.z, x0_.w, h1_, m1_, l1_);                                                 \
+        split3_pair(x1_.x, x1_.y, h2_, m2_, l2_);                                                 \
+        split3_pair(x1_.z, x1_.w, h3_, m3_, l3_);                                                 \
         const u32x4 h_ = {h0_, h1_, h2_, h3_}, m_ = {m0_, m1_, m2_, m3_}, l_ = {l0_, l1_, l2_, l3_};  \
         const bf16x8 ah = __builtin_bit_cast(bf16x8, h_), am = __builtin_bit_cast(bf16x8, m_),        \
                      al = __builtin_bit_cast(bf16x8, l_);                                             \
@@ -167,12 +151,12 @@ __global__ __launch_bounds__(256, NG == 4 ? 2 : 3) void gemm_sb_kernel(const flo
         const unsigned short* bl_ = bm_ + GSB_BN * GSB_KC;                                            \
         const bf16x8 bl0 = *reinterpret_cast<const bf16x8*>(bl_), bl1 = *reinterpret_cast<const bf16x8*>(bl_ + 32 * GSB_KC), \
                      bl2 = *reinterpret_cast<const bf16x8*>(bl_ + 64 * GSB_KC), bl3 = *reinterpret_cast<const bf16x8*>(bl_ + 96 * GSB_KC); \
-        GSB_MFMA(ah, bh0, acc0); GSB_MFMA(ah, bh1, acc1); GSB_MFMA(ah, bh2, acc2); GSB_MFMA(ah, bh3, acc3);   /* hi*hi  */ \
-        GSB_MFMA(ah, bm0, acc0); GSB_MFMA(ah, bm1, acc1); GSB_MFMA(ah, bm2, acc2); GSB_MFMA(ah, bm3, acc3);   /* hi*mid */ \
-        GSB_MFMA(am, bh0, acc0); GSB_MFMA(am, bh1, acc1); GSB_MFMA(am, bh2, acc2); GSB_MFMA(am, bh3, acc3);   /* mid*hi */ \
-        GSB_MFMA(ah, bl0, acc0); GSB_MFMA(ah, bl1, acc1); GSB_MFMA(ah, bl2, acc2); GSB_MFMA(ah, bl3, acc3);   /* hi*lo  */ \
-        GSB_MFMA(al, bh0, acc0); GSB_MFMA(al, bh1, acc1); GSB_MFMA(al, bh2, acc2); GSB_MFMA(al, bh3, acc3);   /* lo*hi  */ \
-        GSB_MFMA(am, bm0, acc0); GSB_MFMA(am, bm1, acc1); GSB_MFMA(am, bm2, acc2); GSB_MFMA(am, bm3, acc3);   /* mid*mid */ \
+        acc0 = mfma_bf16(ah, bh0, acc0); acc1 = mfma_bf16(ah, bh1, acc1); acc2 = mfma_bf16(ah, bh2, acc2); acc3 = mfma_bf16(ah, bh3, acc3);   /* hi*hi  */ \
+        acc0 = mfma_bf16(ah, bm0, acc0); acc1 = mfma_bf16(ah, bm1, acc1); acc2 = mfma_bf16(ah, bm2, acc2); acc3 = mfma_bf16(ah, bm3, acc3);   /* hi*mid */ \
+        acc0 = mfma_bf16(am, bh0, acc0); acc1 = mfma_bf16(am, bh1, acc1); acc2 = mfma_bf16(am, bh2, acc2); acc3 = mfma_bf16(am, bh3, acc3);   /* mid*hi */ \
+        acc0 = mfma_bf16(ah, bl0, acc0); acc1 = mfma_bf16(ah, bl1, acc1); acc2 = mfma_bf16(ah, bl2, acc2); acc3 = mfma_bf16(ah, bl3, acc3);   /* hi*lo  */ \
+        acc0 = mfma_bf16(al, bh0, acc0); acc1 = mfma_bf16(al, bh1, acc1); acc2 = mfma_bf16(al, bh2, acc2); acc3 = mfma_bf16(al, bh3, acc3);   /* lo*hi  */ \
+        acc0 = mfma_bf16(am, bm0, acc0); acc1 = mfma_bf16(am, bm1, acc1); acc2 = mfma_bf16(am, bm2, acc2); acc3 = mfma_bf16(am, bm3, acc3);   /* mid*mid */ \
     }
     if constexpr (NG == 4) {
         // K = 128 = 4 chunks.  A chunk's 48 MFMAs (0.64 us) are shorter than a global load's round trip (~2 us under load),
@@ -354,7 +338,7 @@ __global__ __launch_bounds__(1024) void gemm_sb16_kernel(const float* __restrict
     {                                                                                                           \
         unsigned short* ad_ = Al[buf_] + a_dst;                                                                 \
         if (ONE) {                                                                                              \
-            *reinterpret_cast<uint2*>(ad_) = make_uint2(gsb_rne_pair(na.x, na.y), gsb_rne_pair(na.z, na.w));    \
+            *reinterpret_cast<uint2*>(ad_) = make_uint2(rne_pair(na.x, na.y), rne_pair(na.z, na.w));    \
         } else if (FOUR) {                                                                                      \
         unsigned h0_, m0_, h1_, m1_;                                                                            \
         split2r_pair(na.x, na.y, h0_, m0_);                                                                     \
@@ -363,8 +347,8 @@ __global__ __launch_bounds__(1024) void gemm_sb16_kernel(const float* __restrict
         *reinterpret_cast<uint2*>(ad_ + 128 * GSB_KC) = make_uint2(m0_, m1_);                                   \
         } else {                                                                                                \
         unsigned h0_, m0_, l0_, h1_, m1_, l1_;                                                                  \
-        gsb_split3_pair(na.x, na.y, h0_, m0_, l0_);                                                             \
-        gsb_split3_pair(na.z, na.w, h1_, m1_, l1_);                                                             \
+        split3_pair(na.x, na.y, h0_, m0_, l0_);                                                             \
+        split3_pair(na.z, na.w, h1_, m1_, l1_);                                                             \
         *reinterpret_cast<uint2*>(ad_) = make_uint2(h0_, h1_);                                                  \
         *reinterpret_cast<uint2*>(ad_ + 128 * GSB_KC) = make_uint2(m0_, m1_);                                   \
         *reinterpret_cast<uint2*>(ad_ + 2 * 128 * GSB_KC) = make_uint2(l0_, l1_);                               \
@@ -386,18 +370,18 @@ __global__ __launch_bounds__(1024) void gemm_sb16_kernel(const float* __restrict
         const unsigned short* ap_ = al + aofs + foff_;                                                          \
         const unsigned short* bp_ = bl + bofs + foff_;                                                          \
         const bf16x8 ah = *reinterpret_cast<const bf16x8*>(ap_), bh = *reinterpret_cast<const bf16x8*>(bp_);    \
-        GSB_MFMA(ah, bh, acc0);                                                                                 \
+        acc0 = mfma_bf16(ah, bh, acc0);                                                                                 \
         if (FOUR) {                                                                                             \
         const bf16x8 am = *reinterpret_cast<const bf16x8*>(ap_ + 128 * GSB_KC);                                 \
         const bf16x8 bm = *reinterpret_cast<const bf16x8*>(bp_ + GSB_BN * GSB_KC);                              \
-        GSB_MFMA(ah, bm, acc1); GSB_MFMA(am, bh, acc0); GSB_MFMA(am, bm, acc1);                                 \
+        acc1 = mfma_bf16(ah, bm, acc1); acc0 = mfma_bf16(am, bh, acc0); acc1 = mfma_bf16(am, bm, acc1);                                 \
         } else if (!ONE) {                                                                                      \
         const bf16x8 am = *reinterpret_cast<const bf16x8*>(ap_ + 128 * GSB_KC),                                 \
                      al_ = *reinterpret_cast<const bf16x8*>(ap_ + 2 * 128 * GSB_KC);                            \
         const bf16x8 bm = *reinterpret_cast<const bf16x8*>(bp_ + GSB_BN * GSB_KC),                              \
                      bl_ = *reinterpret_cast<const bf16x8*>(bp_ + 2 * GSB_BN * GSB_KC);                         \
-        GSB_MFMA(ah, bm, acc1); GSB_MFMA(am, bh, acc0);                                                         \
-        GSB_MFMA(ah, bl_, acc1); GSB_MFMA(al_, bh, acc0); GSB_MFMA(am, bm, acc1);                               \
+        acc1 = mfma_bf16(ah, bm, acc1); acc0 = mfma_bf16(am, bh, acc0);                                                         \
+        acc1 = mfma_bf16(ah, bl_, acc1); acc0 = mfma_bf16(al_, bh, acc0); acc1 = mfma_bf16(am, bm, acc1);                               \
         }                                                                                                       \
     }
     if constexpr (NG == 0) {
@@ -527,7 +511,6 @@ __global__ __launch_bounds__(1024) void gemm_sb16_kernel(const float* __restrict
 // overlap nothing: base 5.3 + B 1.6 + A 7 + MFMA 11 + stores 11 us add up almost serially in BOTH forms.  Kept as an opt-in (gsb_dbg bit 6).
 template <bool FOUR>
 __device__ __forceinline__ void sbp_step(const float4& x0, const float4& x1, const unsigned short* bb, f32x16& acc0, f32x16& acc1, f32x16& acc2, f32x16& acc3) {
-#define SBP_MFMA(A_, B_, ACC_) ACC_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A_, B_, ACC_, 0, 0, 0)
 #define SBP_B4(p_, n0_, n1_, n2_, n3_)                                                                                           \
     const bf16x8 n0_ = *reinterpret_cast<const bf16x8*>(bb + (p_) * 4096), n1_ = *reinterpret_cast<const bf16x8*>(bb + (p_) * 4096 + 1024), \
                  n2_ = *reinterpret_cast<const bf16x8*>(bb + (p_) * 4096 + 2048), n3_ = *reinterpret_cast<const bf16x8*>(bb + (p_) * 4096 + 3072);
@@ -539,28 +522,27 @@ __device__ __forceinline__ void sbp_step(const float4& x0, const float4& x1, con
         const bf16x8 ah = __builtin_bit_cast(bf16x8, h_), am = __builtin_bit_cast(bf16x8, m_);
         SBP_B4(0, bh0, bh1, bh2, bh3)
         SBP_B4(1, bm0, bm1, bm2, bm3)
-        SBP_MFMA(ah, bh0, acc0); SBP_MFMA(ah, bh1, acc1); SBP_MFMA(ah, bh2, acc2); SBP_MFMA(ah, bh3, acc3);
-        SBP_MFMA(ah, bm0, acc0); SBP_MFMA(ah, bm1, acc1); SBP_MFMA(ah, bm2, acc2); SBP_MFMA(ah, bm3, acc3);
-        SBP_MFMA(am, bh0, acc0); SBP_MFMA(am, bh1, acc1); SBP_MFMA(am, bh2, acc2); SBP_MFMA(am, bh3, acc3);
-        SBP_MFMA(am, bm0, acc0); SBP_MFMA(am, bm1, acc1); SBP_MFMA(am, bm2, acc2); SBP_MFMA(am, bm3, acc3);
+        acc0 = mfma_bf16(ah, bh0, acc0); acc1 = mfma_bf16(ah, bh1, acc1); acc2 = mfma_bf16(ah, bh2, acc2); acc3 = mfma_bf16(ah, bh3, acc3);
+        acc0 = mfma_bf16(ah, bm0, acc0); acc1 = mfma_bf16(ah, bm1, acc1); acc2 = mfma_bf16(ah, bm2, acc2); acc3 = mfma_bf16(ah, bm3, acc3);
+        acc0 = mfma_bf16(am, bh0, acc0); acc1 = mfma_bf16(am, bh1, acc1); acc2 = mfma_bf16(am, bh2, acc2); acc3 = mfma_bf16(am, bh3, acc3);
+        acc0 = mfma_bf16(am, bm0, acc0); acc1 = mfma_bf16(am, bm1, acc1); acc2 = mfma_bf16(am, bm2, acc2); acc3 = mfma_bf16(am, bm3, acc3);
     } else {
         unsigned h0, h1, h2, h3, m0, m1, m2, m3, l0, l1, l2, l3;
-        gsb_split3_pair(x0.x, x0.y, h0, m0, l0); gsb_split3_pair(x0.z, x0.w, h1, m1, l1);
-        gsb_split3_pair(x1.x, x1.y, h2, m2, l2); gsb_split3_pair(x1.z, x1.w, h3, m3, l3);
+        split3_pair(x0.x, x0.y, h0, m0, l0); split3_pair(x0.z, x0.w, h1, m1, l1);
+        split3_pair(x1.x, x1.y, h2, m2, l2); split3_pair(x1.z, x1.w, h3, m3, l3);
         const u32x4 h_ = {h0, h1, h2, h3}, m_ = {m0, m1, m2, m3}, l_ = {l0, l1, l2, l3};
         const bf16x8 ah = __builtin_bit_cast(bf16x8, h_), am = __builtin_bit_cast(bf16x8, m_), al = __builtin_bit_cast(bf16x8, l_);
         SBP_B4(0, bh0, bh1, bh2, bh3)
         SBP_B4(1, bm0, bm1, bm2, bm3)
         SBP_B4(2, bl0, bl1, bl2, bl3)
-        SBP_MFMA(ah, bh0, acc0); SBP_MFMA(ah, bh1, acc1); SBP_MFMA(ah, bh2, acc2); SBP_MFMA(ah, bh3, acc3);   // hi*hi
-        SBP_MFMA(ah, bm0, acc0); SBP_MFMA(ah, bm1, acc1); SBP_MFMA(ah, bm2, acc2); SBP_MFMA(ah, bm3, acc3);   // hi*mid
-        SBP_MFMA(am, bh0, acc0); SBP_MFMA(am, bh1, acc1); SBP_MFMA(am, bh2, acc2); SBP_MFMA(am, bh3, acc3);   // mid*hi
-        SBP_MFMA(ah, bl0, acc0); SBP_MFMA(ah, bl1, acc1); SBP_MFMA(ah, bl2, acc2); SBP_MFMA(ah, bl3, acc3);   // hi*lo
-        SBP_MFMA(al, bh0, acc0); SBP_MFMA(al, bh1, acc1); SBP_MFMA(al, bh2, acc2); SBP_MFMA(al, bh3, acc3);   // lo*hi
-        SBP_MFMA(am, bm0, acc0); SBP_MFMA(am, bm1, acc1); SBP_MFMA(am, bm2, acc2); SBP_MFMA(am, bm3, acc3);   // mid*mid
+        acc0 = mfma_bf16(ah, bh0, acc0); acc1 = mfma_bf16(ah, bh1, acc1); acc2 = mfma_bf16(ah, bh2, acc2); acc3 = mfma_bf16(ah, bh3, acc3);   // hi*hi
+        acc0 = mfma_bf16(ah, bm0, acc0); acc1 = mfma_bf16(ah, bm1, acc1); acc2 = mfma_bf16(ah, bm2, acc2); acc3 = mfma_bf16(ah, bm3, acc3);   // hi*mid
+        acc0 = mfma_bf16(am, bh0, acc0); acc1 = mfma_bf16(am, bh1, acc1); acc2 = mfma_bf16(am, bh2, acc2); acc3 = mfma_bf16(am, bh3, acc3);   // mid*hi
+        acc0 = mfma_bf16(ah, bl0, acc0); acc1 = mfma_bf16(ah, bl1, acc1); acc2 = mfma_bf16(ah, bl2, acc2); acc3 = mfma_bf16(ah, bl3, acc3);   // hi*lo
+        acc0 = mfma_bf16(al, bh0, acc0); acc1 = mfma_bf16(al, bh1, acc1); acc2 = mfma_bf16(al, bh2, acc2); acc3 = mfma_bf16(al, bh3, acc3);   // lo*hi
+        acc0 = mfma_bf16(am, bm0, acc0); acc1 = mfma_bf16(am, bm1, acc1); acc2 = mfma_bf16(am, bm2, acc2); acc3 = mfma_bf16(am, bm3, acc3);   // mid*mid
     }
 #undef SBP_B4
-#undef SBP_MFMA
 }
 
 template <bool FOUR>

@@ -11,25 +11,8 @@
 // the 64-B unit u of row m is stored at u ^ (m & 3): the 4 rows of a transposed-read block then cover the 64 banks.
 // Splits over rows write slabs in gemm_tn's layout ([128*N | N] per split), combined by reduce_slabs2 in a fixed order.
 #include "common.h"
+#include "sb_tile.h"
 #include <algorithm>
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void tnsb_split3_pair(float x0, float x1, unsigned& h, unsigned& m, unsigned& l) {
-    const unsigned u0 = __float_as_uint(x0), u1 = __float_as_uint(x1);
-    h = __builtin_amdgcn_perm(u1, u0, 0x07060302);
-    const float r0 = x0 - __uint_as_float(u0 & 0xffff0000u), r1 = x1 - __uint_as_float(u1 & 0xffff0000u);
-    const unsigned v0 = __float_as_uint(r0), v1 = __float_as_uint(r1);
-    m = __builtin_amdgcn_perm(v1, v0, 0x07060302);
-    const float s0 = r0 - __uint_as_float(v0 & 0xffff0000u), s1 = r1 - __uint_as_float(v1 & 0xffff0000u);
-    l = __builtin_amdgcn_perm(__float_as_uint(s1), __float_as_uint(s0), 0x07060302);
-}
-__device__ __forceinline__ bf16x8 tnsb_frag(const char* p0, const char* p1) {
-    const s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p0));
-    const s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p1));
-    return __builtin_bit_cast(bf16x8, __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7));
-}
 
 #define TNSB_PL (32 * 256)     // bytes per plane: 32 rows x 128 bf16
 
@@ -95,7 +78,7 @@ __global__ __launch_bounds__(256, 3) void gemm_tn_sb_kernel(TnJobs jobs, int ldb
     {                                                                                                        \
         char* d = (img_) + (m_) * 256 + ((((c4 >> 3) ^ ((m_) & 3)) << 6) | (8 * (c4 & 7)));                  \
         if (ONE) {                                                                                           \
-            *reinterpret_cast<uint2*>(d) = make_uint2(bf16_rne_bits(v_.x) | (bf16_rne_bits(v_.y) << 16), bf16_rne_bits(v_.z) | (bf16_rne_bits(v_.w) << 16)); \
+            *reinterpret_cast<uint2*>(d) = make_uint2(rne_pair(v_.x, v_.y), rne_pair(v_.z, v_.w)); \
         } else if (FOUR) {                                                                                   \
         unsigned h0, m0, h1, m1;                                                                             \
         split2r_pair(v_.x, v_.y, h0, m0);                                                                    \
@@ -104,8 +87,8 @@ __global__ __launch_bounds__(256, 3) void gemm_tn_sb_kernel(TnJobs jobs, int ldb
         *reinterpret_cast<uint2*>(d + TNSB_PL) = make_uint2(m0, m1);                                         \
         } else {                                                                                             \
         unsigned h0, m0, l0, h1, m1, l1;                                                                     \
-        tnsb_split3_pair(v_.x, v_.y, h0, m0, l0);                                                            \
-        tnsb_split3_pair(v_.z, v_.w, h1, m1, l1);                                                            \
+        split3_pair(v_.x, v_.y, h0, m0, l0);                                                            \
+        split3_pair(v_.z, v_.w, h1, m1, l1);                                                            \
         *reinterpret_cast<uint2*>(d) = make_uint2(h0, h1);                                                   \
         *reinterpret_cast<uint2*>(d + TNSB_PL) = make_uint2(m0, m1);                                         \
         *reinterpret_cast<uint2*>(d + 2 * TNSB_PL) = make_uint2(l0, l1);                                     \
@@ -118,29 +101,28 @@ __global__ __launch_bounds__(256, 3) void gemm_tn_sb_kernel(TnJobs jobs, int ldb
         bsum.x += vb[u].x; bsum.y += vb[u].y; bsum.z += vb[u].z; bsum.w += vb[u].w;                          \
     }
     f32x16 c00 = zero16(), c01 = zero16(), c10 = zero16(), c11 = zero16();      // [k1 tile][n tile] of this wave
-#define TNSB_MFMA(A_, B_, ACC_) ACC_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A_, B_, ACC_, 0, 0, 0)
 #define TNSB_PAIR(AH, AM, AL, BH, BM_, BL, ACC_)                                                             \
-    if (!FOUR) TNSB_MFMA(AL, BH, ACC_);                                                                      \
-    TNSB_MFMA(AM, BH, ACC_); TNSB_MFMA(AM, BM_, ACC_);                                                       \
-    TNSB_MFMA(AH, BH, ACC_); TNSB_MFMA(AH, BM_, ACC_);                                                       \
-    if (!FOUR) TNSB_MFMA(AH, BL, ACC_);
+    if (!FOUR) ACC_ = mfma_bf16(AL, BH, ACC_);                                                                      \
+    ACC_ = mfma_bf16(AM, BH, ACC_); ACC_ = mfma_bf16(AM, BM_, ACC_);                                                       \
+    ACC_ = mfma_bf16(AH, BH, ACC_); ACC_ = mfma_bf16(AH, BM_, ACC_);                                                       \
+    if (!FOUR) ACC_ = mfma_bf16(AH, BL, ACC_);
 #define TNSB_KSTEP(s_)                                                                                       \
     if (ONE) {                                                                                               \
         constexpr int o_ = (16 * (s_)) * 256;                                                                \
-        const bf16x8 a0h = tnsb_frag(Al + o_ + oa0, Al + o_ + oa0 + 4 * 256), a1h = tnsb_frag(Al + o_ + oa1, Al + o_ + oa1 + 4 * 256); \
-        const bf16x8 b0h = tnsb_frag(Bl + o_ + ob0, Bl + o_ + ob0 + 4 * 256), b1h = tnsb_frag(Bl + o_ + ob1, Bl + o_ + ob1 + 4 * 256); \
-        TNSB_MFMA(a0h, b0h, c00); TNSB_MFMA(a0h, b1h, c01); TNSB_MFMA(a1h, b0h, c10); TNSB_MFMA(a1h, b1h, c11);                        \
+        const bf16x8 a0h = frag(Al + o_ + oa0, Al + o_ + oa0 + 4 * 256), a1h = frag(Al + o_ + oa1, Al + o_ + oa1 + 4 * 256); \
+        const bf16x8 b0h = frag(Bl + o_ + ob0, Bl + o_ + ob0 + 4 * 256), b1h = frag(Bl + o_ + ob1, Bl + o_ + ob1 + 4 * 256); \
+        c00 = mfma_bf16(a0h, b0h, c00); c01 = mfma_bf16(a0h, b1h, c01); c10 = mfma_bf16(a1h, b0h, c10); c11 = mfma_bf16(a1h, b1h, c11);                        \
     } else                                                                                                   \
     {                                                                                                        \
         constexpr int o_ = (16 * (s_)) * 256;                                                                \
-        const bf16x8 a0h = tnsb_frag(Al + o_ + oa0, Al + o_ + oa0 + 4 * 256), a0m = tnsb_frag(Al + TNSB_PL + o_ + oa0, Al + TNSB_PL + o_ + oa0 + 4 * 256), \
-                     a0l = FOUR ? a0m : tnsb_frag(Al + 2 * TNSB_PL + o_ + oa0, Al + 2 * TNSB_PL + o_ + oa0 + 4 * 256);    \
-        const bf16x8 a1h = tnsb_frag(Al + o_ + oa1, Al + o_ + oa1 + 4 * 256), a1m = tnsb_frag(Al + TNSB_PL + o_ + oa1, Al + TNSB_PL + o_ + oa1 + 4 * 256), \
-                     a1l = FOUR ? a1m : tnsb_frag(Al + 2 * TNSB_PL + o_ + oa1, Al + 2 * TNSB_PL + o_ + oa1 + 4 * 256);    \
-        const bf16x8 b0h = tnsb_frag(Bl + o_ + ob0, Bl + o_ + ob0 + 4 * 256), b0m = tnsb_frag(Bl + TNSB_PL + o_ + ob0, Bl + TNSB_PL + o_ + ob0 + 4 * 256), \
-                     b0l = FOUR ? b0m : tnsb_frag(Bl + 2 * TNSB_PL + o_ + ob0, Bl + 2 * TNSB_PL + o_ + ob0 + 4 * 256);    \
-        const bf16x8 b1h = tnsb_frag(Bl + o_ + ob1, Bl + o_ + ob1 + 4 * 256), b1m = tnsb_frag(Bl + TNSB_PL + o_ + ob1, Bl + TNSB_PL + o_ + ob1 + 4 * 256), \
-                     b1l = FOUR ? b1m : tnsb_frag(Bl + 2 * TNSB_PL + o_ + ob1, Bl + 2 * TNSB_PL + o_ + ob1 + 4 * 256);    \
+        const bf16x8 a0h = frag(Al + o_ + oa0, Al + o_ + oa0 + 4 * 256), a0m = frag(Al + TNSB_PL + o_ + oa0, Al + TNSB_PL + o_ + oa0 + 4 * 256), \
+                     a0l = FOUR ? a0m : frag(Al + 2 * TNSB_PL + o_ + oa0, Al + 2 * TNSB_PL + o_ + oa0 + 4 * 256);    \
+        const bf16x8 a1h = frag(Al + o_ + oa1, Al + o_ + oa1 + 4 * 256), a1m = frag(Al + TNSB_PL + o_ + oa1, Al + TNSB_PL + o_ + oa1 + 4 * 256), \
+                     a1l = FOUR ? a1m : frag(Al + 2 * TNSB_PL + o_ + oa1, Al + 2 * TNSB_PL + o_ + oa1 + 4 * 256);    \
+        const bf16x8 b0h = frag(Bl + o_ + ob0, Bl + o_ + ob0 + 4 * 256), b0m = frag(Bl + TNSB_PL + o_ + ob0, Bl + TNSB_PL + o_ + ob0 + 4 * 256), \
+                     b0l = FOUR ? b0m : frag(Bl + 2 * TNSB_PL + o_ + ob0, Bl + 2 * TNSB_PL + o_ + ob0 + 4 * 256);    \
+        const bf16x8 b1h = frag(Bl + o_ + ob1, Bl + o_ + ob1 + 4 * 256), b1m = frag(Bl + TNSB_PL + o_ + ob1, Bl + TNSB_PL + o_ + ob1 + 4 * 256), \
+                     b1l = FOUR ? b1m : frag(Bl + 2 * TNSB_PL + o_ + ob1, Bl + 2 * TNSB_PL + o_ + ob1 + 4 * 256);    \
         TNSB_PAIR(a0h, a0m, a0l, b0h, b0m, b0l, c00) TNSB_PAIR(a0h, a0m, a0l, b1h, b1m, b1l, c01)            \
         TNSB_PAIR(a1h, a1m, a1l, b0h, b0m, b0l, c10) TNSB_PAIR(a1h, a1m, a1l, b1h, b1m, b1l, c11)            \
     }
@@ -156,7 +138,6 @@ __global__ __launch_bounds__(256, 3) void gemm_tn_sb_kernel(TnJobs jobs, int ldb
     }
 #undef TNSB_KSTEP
 #undef TNSB_PAIR
-#undef TNSB_MFMA
 #undef TNSB_COMMIT
 #undef TNSB_PUT
 #undef TNSB_LOAD

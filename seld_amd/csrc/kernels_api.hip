@@ -39,7 +39,6 @@ int seld_k_set_option(const char* key, int value) {
     if (!key) return SELD_ERR_INVALID;
     if (!strcmp(key, "conv64_split_bf16")) { k_conv64_split_bf16 = value != 0; return SELD_OK; }
     if (!strcmp(key, "conv1_split_bf16")) { k_conv1_split_bf16 = value != 0; return SELD_OK; }
-    if (!strcmp(key, "conv64_dbuf")) { k_kc.conv64_dbuf = value != 0; return SELD_OK; }
     if (!strcmp(key, "gemm_tn_split_bf16")) { k_gemm_tn_split_bf16 = value != 0; return SELD_OK; }
     if (!strcmp(key, "bf16_single")) { k_kc.mfma_one = value != 0; return SELD_OK; }
     if (!strcmp(key, "gsb_dbg")) { k_kc.gsb_dbg = value; return SELD_OK; }
@@ -60,7 +59,8 @@ int seld_k_conv3x3_fwd(const float* x, const float* w, const float* bias, float*
     if (Cin == 64 && k_conv64_split_bf16) {
         unsigned short* wsp = reinterpret_cast<unsigned short*>(s.get(9 * 3 * 4096 / 2 + 16));
         if (!wsp) return SELD_ERR_NOMEM;
-        launch_split_weights(0, k_kc, w, wsp);
+        const float* ws[1] = {w}; unsigned short* ds[1] = {wsp}; const int fl[1] = {0};
+        launch_split_weights_batch(0, k_kc, 1, ws, ds, fl);
         rc = launch_conv64_fwd_sb(0, k_kc, x, wsp, bias, z, part, &np, B, H, W);
     } else if (Cin == 64) rc = launch_conv64_fwd(0, x, w, bias, z, part, &np, B, H, W);
     else if (W == 64) rc = launch_conv_first_fwd(0, x, w, bias, z, part, &np, B, H, Cin);

@@ -3,6 +3,7 @@
 // (conv_sb.hip), and the folded head weights W1 W2 (gemm.hip).
 #pragma once
 #include "common.h"
+#include "sb_tile.h"
 
 // B fp32 ([K,N] if !transb, [N,K] if transb) -> planes [chunk c = k/32][plane][n][piece'][8] bf16, piece' = piece ^ ((n >> 2) & 3).
 // transb == 2: src is a 3x3 kernel [9][N = Cin][ldb = Cout] (HWIO) and B the matrix of its INPUT-GRADIENT convolution,
@@ -20,21 +21,13 @@ __device__ __forceinline__ void gemm_split_b_body(const GemmSplitJobs& jobs, int
             x = src[((size_t)(8 - tap) * N + n) * ldb + co];
         } else
             x = transb ? src[(size_t)n * ldb + k] : src[(size_t)k * ldb + n];
-        // plane 0: the truncated high part — in bf16 single-product mode the value ROUNDED to nearest bf16, which is all a ONE-form
-        // consumer reads.  Planes 1, 2 split the residual x - plane0 exactly either way (|residual| <= an ulp of plane 0: 16
-        // significant bits, 8 + 8), so a consumer WITHOUT a ONE form (six products over all three planes) computes with the exact
-        // weights in both modes — it never reads an unwritten plane.
-        const unsigned u = jobs.one ? bf16_rne_bits(x) << 16 : __float_as_uint(x) & 0xffff0000u;
-        const float r = x - __uint_as_float(u);
-        // a transposed / flipped B is a backward operand: its mid plane is rounded (common.h split2r_pair) for the four-product form; plane 2 completes
-        // the split exactly either way
-        const unsigned v = __float_as_uint(r) + (transb ? 0x8000u : 0u);
-        const float s = r - __uint_as_float(v & 0xffff0000u);
+        // a transposed / flipped B is a backward operand: its mid plane is rounded for the four-product form (sb_tile.h split3)
+        const Planes3 p = split3(x, jobs.one, transb != 0);
         const int c = k >> 5, kk = k & 31, piece = (kk >> 3) ^ ((n >> 2) & 3);
         unsigned short* o = dst + ((size_t)c * 3 * N + n) * 32 + piece * 8 + (kk & 7);
-        o[0] = (unsigned short)(u >> 16);
-        o[(size_t)N * 32] = (unsigned short)(v >> 16);
-        o[(size_t)2 * N * 32] = (unsigned short)(__float_as_uint(s) >> 16);
+        o[0] = p.p0;
+        o[(size_t)N * 32] = p.p1;
+        o[(size_t)2 * N * 32] = p.p2;
     }
 }
 
@@ -46,16 +39,12 @@ __device__ __forceinline__ void split_weights_body(const SplitWeightJobs& jobs, 
     if (idx >= 9 * 4096) return;
     const int tap = idx >> 12, rem = idx & 4095, out = rem >> 6, in = rem & 63;
     const float x = jobs.flip[job] ? w[(8 - tap) * 4096 + out * 64 + in] : w[tap * 4096 + in * 64 + out];
-    const unsigned u = jobs.one ? bf16_rne_bits(x) << 16 : __float_as_uint(x) & 0xffff0000u;      // see gemm_split_b_body
-    const float r = x - __uint_as_float(u);
-    // the flipped (input-gradient) form rounds its mid plane (common.h split2r_pair: the four-product kernel reads planes 0, 1 only and wants a
-    // zero-mean remainder); plane 2 still completes the exact split, so the six-product kernel sees the same weights either way
-    const unsigned v = __float_as_uint(r) + (jobs.flip[job] ? 0x8000u : 0u);
-    const float s = r - __uint_as_float(v & 0xffff0000u);
+    // the flipped (input-gradient) form rounds its mid plane; the six-product kernel sees the same weights either way (sb_tile.h split3)
+    const Planes3 p = split3(x, jobs.one, jobs.flip[job] != 0);
     unsigned short* o = wsp + (size_t)tap * 3 * 4096 + out * 64 + in;
-    o[0] = (unsigned short)(u >> 16);
-    o[4096] = (unsigned short)(v >> 16);
-    o[2 * 4096] = (unsigned short)(__float_as_uint(s) >> 16);
+    o[0] = p.p0;
+    o[4096] = p.p1;
+    o[2 * 4096] = p.p2;
 }
 
 // row k of Weff = [W1s W2s | W1d W2d] (k == K: the bias row b1 W2 + b2); one thread per column

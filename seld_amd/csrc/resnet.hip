@@ -11,7 +11,7 @@
 //   rn_bn_finalize / rn_bn_bwd_finalize   the per-channel finalisation of bn_pool.hip for any C (one workgroup per 64 channels)
 //   rn_bn_apply / rn_bn_apply2   out = [relu](z scale + shift [+ res])  /  relu(BN(z) + BN_r(z_r)) for a projection block
 //   rn_bn_bwd_dz              dz = scale (dy' - c1 - xhat c2)   (GATEZ forms of both backward kernels: the gate recomputed from z)
-//   rn_add_masked             dst += dy [mask > 0]
+//   rn_add_gated              dst += dy [gate bit]   (identity shortcut: the block input receives the gradient behind the block's final ReLU)
 #include "common.h"
 #include <algorithm>
 
@@ -361,15 +361,6 @@ int launch_rn_bn_bwd_dz(hipStream_t st, const float* z, const float* dy, const f
     return 0;
 }
 
-// dst += dy [mask > 0]   (identity shortcut: the block input receives the gradient behind the block's final ReLU)
-__global__ __launch_bounds__(256) void rn_add_masked_kernel(float* __restrict__ dst, const float* __restrict__ dy, const float* __restrict__ mask, int64_t n4) {
-    const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (gid >= n4) return;
-    const float4 d = reinterpret_cast<const float4*>(dy)[gid], m = reinterpret_cast<const float4*>(mask)[gid];
-    float4 o = reinterpret_cast<float4*>(dst)[gid];
-    o = make_float4(o.x + (m.x > 0.f ? d.x : 0.f), o.y + (m.y > 0.f ? d.y : 0.f), o.z + (m.z > 0.f ? d.z : 0.f), o.w + (m.w > 0.f ? d.w : 0.f));
-    reinterpret_cast<float4*>(dst)[gid] = o;
-}
 __global__ __launch_bounds__(256) void rn_add_gated_kernel(float* __restrict__ dst, const float* __restrict__ dy, const unsigned char* __restrict__ gate4,
                                                            int64_t n4) {
     const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -384,10 +375,6 @@ int launch_rn_add_gated(hipStream_t st, float* dst, const float* dy, const unsig
     hipLaunchKernelGGL(rn_add_gated_kernel, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, st, dst, dy, gate4, n / 4);
     return 0;
 }
-int launch_rn_add_masked(hipStream_t st, float* dst, const float* dy, const float* mask, int64_t n) {
-    hipLaunchKernelGGL(rn_add_masked_kernel, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, st, dst, dy, mask, n / 4);
-    return 0;
-}
 
 // ---- the products of a resnet50_block convolution ---------------------------------------------------------------------
 // A convolution here is a product on [M = B*S*Wout] rows (1x1: the input rows, a frequency stride is a doubled row stride; 3x3: the
@@ -396,7 +383,7 @@ int launch_rn_add_masked(hipStream_t st, float* dst, const float* dy, const floa
 // shape (the 32- and 64-channel products of the first two stages) takes the fp32 MFMA GEMM.
 int rn_sb_fwd_ok(int K, int N) { return (K % 32) == 0 && (N % 128) == 0; }               // z = A w           [M,K] x [K,N]
 int rn_sb_dgrad_ok(int K, int N) { return (N % 32) == 0 && (K % 128) == 0; }             // dA = dz w^T       [M,N] x [N,K]
-int rn_sb_wgrad_ok(int K, int N) { return (K % 128) == 0 && (N % 128) == 0; }            // dw = A^T dz       [K,M] x [M,N]
+static int rn_sb_wgrad_ok(int K, int N) { return (K % 128) == 0 && (N % 128) == 0; }            // dw = A^T dz       [K,M] x [M,N]
 
 // stat_part (may be null) + nbx: the convolution's BatchNorm statistics leave with the product's epilogue (common.h GemmEpi) — *nbx receives the
 // number of [sum | sum of squares] partials per 64-channel chunk that rn_bn_finalize has to fold.  part_cap: the floats stat_part holds; a launch

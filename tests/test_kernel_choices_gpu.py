@@ -51,7 +51,7 @@ SINGLE_SIX = {"bf16_single": 1, "bwd_four_products": 0}       # what a default c
 def test_a_contexts_choices_do_not_reach_the_kernel_entry_points(seld_lib, seldnet_config, batch):
     """seld_k_gemm_sb (M = 33, N = 128, K = 128, mode 0), seld_k_conv3x3_dgrad (B = 1, H = 3, W = 4) and seld_k_gemm_tn (M = 64, K1 = 128,
     N = 128) — launchers that branch on the single-product, four-product and tile-block choices — give the same bits before and after a
-    context with bf16_single = 1, bwd_four_products = 0, conv64_dbuf = 0, tn_tile_blocks = 64 has run a training step."""
+    context with bf16_single = 1, bwd_four_products = 0, dgrad_r8 = 0, tn_tile_blocks = 64 has run a training step."""
     rng = np.random.default_rng(71)
     A = dev(rng.standard_normal((33, 128)))
     Bm = dev(rng.standard_normal((128, 128)) / np.sqrt(128))
@@ -72,12 +72,31 @@ def test_a_contexts_choices_do_not_reach_the_kernel_entry_points(seld_lib, seldn
         return out
 
     before = entry_points()
-    model = _context(seldnet_config, {**SINGLE_SIX, "conv64_dbuf": 0, "tn_tile_blocks": 64})
+    model = _context(seldnet_config, {**SINGLE_SIX, "dgrad_r8": 0, "tn_tile_blocks": 64})
     _step_grads(model, batch)
     after = entry_points()
     model.close()
     for a, b in zip(before, after):
         np.testing.assert_array_equal(a, b)
+
+
+def test_the_retired_conv64_dbuf_key_is_refused(seld_lib, seldnet_config):
+    """"conv64_dbuf" chose between two region kernels of conv_sb.hip; one of them is gone and so is the key: a context's set_option and
+    seld_k_set_option refuse it like any unknown key, and still take the keys that stayed."""
+    from seld_amd import _lib
+    model = _context(seldnet_config)
+    try:
+        with pytest.raises(_lib.SeldError) as e:
+            model.set_option("conv64_dbuf", 1)
+        assert e.value.code != 0
+        assert seld_lib.seld_set_option(model.ctx, b"conv64_dbuf", 0) != 0
+        model.set_option("dgrad_r8", 1)
+        model.set_option("bwd_four_products", 1)
+    finally:
+        model.close()
+    assert seld_lib.seld_k_set_option(b"conv64_dbuf", 1) != 0
+    assert seld_lib.seld_k_set_option(b"conv64_dbuf", 0) != 0
+    assert seld_lib.seld_k_set_option(b"bwd_four_products", 1) == 0
 
 
 def test_kernel_entry_point_options_do_not_reach_a_context(seld_lib, seldnet_config, batch):

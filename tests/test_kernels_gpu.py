@@ -20,7 +20,10 @@ def _conv_ref(x, w, b):
 
 
 @pytest.mark.parametrize("B,H,W,Cin", [(2, 50, 64, 7), (1, 7, 64, 7), (2, 30, 64, 10), (2, 20, 16, 64), (3, 10, 4, 64), (1, 37, 16, 64), (2, 45, 8, 64),
-                                       (3, 70, 8, 64)])
+                                       (3, 70, 8, 64),
+                                       # widths other than 16 / 8 / 4: the generic kernel (two 256-pixel tiles, the last one partial, a clip boundary inside a
+                                       # tile; one partial tile with a clip boundary every 18 pixels)
+                                       (2, 5, 32, 64), (3, 9, 2, 64)])
 def test_conv_fwd(seld_lib, B, H, W, Cin):
     rng = np.random.default_rng(1)
     x = rng.standard_normal((B, H, W, Cin)).astype(np.float32)
@@ -40,7 +43,7 @@ def test_conv_fwd(seld_lib, B, H, W, Cin):
     seld_lib.seld_k_set_option(b"conv64_split_bf16", 1)
 
 
-@pytest.mark.parametrize("B,H,W", [(2, 20, 16), (3, 10, 4), (1, 37, 16), (4, 100, 16), (3, 70, 8)])
+@pytest.mark.parametrize("B,H,W", [(2, 20, 16), (3, 10, 4), (1, 37, 16), (4, 100, 16), (3, 70, 8), (2, 5, 32), (3, 9, 2)])      # the last two: the generic kernel
 def test_conv_dgrad(seld_lib, B, H, W):
     rng = np.random.default_rng(2)
     dz = rng.standard_normal((B, H, W, 64)).astype(np.float32)

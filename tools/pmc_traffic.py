@@ -24,7 +24,6 @@ GROUPS = {  # bench.py timer group -> kernel-name substring
     "conv1_wgrad_fused": "conv_first_wgrad_fused_kernel",
     "gru_fwd": "gru_fwd_kernel", "gru_bwd": "gru_bwd_kernel",
     "conv64_fwd_dgrad_W16": "conv64_fwd_sbd_kernel<4", "conv64_fwd_dgrad_W4": "conv64_fwd_sbd_kernel<2",
-    "conv64_fwd_dgrad_W16_sbr": "conv64_fwd_sbr_kernel<4", "conv64_fwd_dgrad_W4_sbr": "conv64_fwd_sbr_kernel<2",
     "feat_dft": "feat_dft_kernel", "feat_frame": "feat_wave_kernel", "feat_frame_workgroup": "feat_frame_kernel", "feat_topdb": "feat_topdb_kernel",
     "conv2_wgrad": "conv64_wgrad_sb_kernel<4", "conv3_wgrad": "conv64_wgrad_sb_kernel<2",
     "conv2_wgrad_f32": "conv64_wgrad_kernel<4>", "conv3_wgrad_f32": "conv64_wgrad_kernel<2>",

@@ -1,5 +1,5 @@
 """Time the first-layer conv(+pool) kernels through their seld_k_* entry points at the headline shape
-(B=32, T=3000); with a -DCPOOL_TIMING build of the library, the per-phase cycle counts of conv_pool.hip.  Wall clock around a synchronous call: good to ~10 us."""
+(B=32, T=3000).  Wall clock around a synchronous call: good to ~10 us."""
 import ctypes as C
 import sys
 import time
@@ -52,12 +52,3 @@ for _ in range(2):
     t2 = timeit(lambda: lib.seld_k_conv_first_fwd_pool(P(x), P(w), P(b), P(gamma), None, P(ze), None, P(st), B, H, Cin))
     print("conv_first_fwd_pool          %.4f ms (z stored)   %.4f ms (z not stored)" % (t1, t2))
 print("conv_first_fwd (unfused)      %.4f ms" % timeit(unfused))
-if os.environ.get("CPOOL_TIMING"):      # library built with -DCPOOL_TIMING: stats slots 0..5 = summed phase cycles of wave 0
-    for zz in (z, None):
-        lib.seld_k_conv_first_fwd_pool(P(x), P(w), P(b), P(gamma), P(zz) if zz is not None else None, P(ze), P(am) if zz is not None else None, P(st), B, H, Cin)
-        v = st[:6].cpu().numpy() / 512 / 18.75
-        print("z stored    " if zz is not None else "z not stored", "cycles per tile (wave 0 mean): top %.0f  phaseA %.0f  phaseB+drainA %.0f  commit %.0f  drainB %.0f  barrier %.0f  total %.0f" % (*v, v.sum()))
-if os.environ.get("CPSB_TIMING"):       # library built with -DCPSB_TIMING (conv_pool_sb.hip): phase cycles of wave 0, z not stored
-    lib.seld_k_conv_first_fwd_pool(P(x), P(w), P(b), P(gamma), None, P(ze), P(am), P(st), B, H, Cin)
-    v = st[:4].cpu().numpy() / 512 / 18.75
-    print("split-bf16, z not stored: cycles per tile (wave 0 mean): top %.0f  mfma loop %.0f  window reduction %.0f  barrier+commit+barrier %.0f  total %.0f" % (*v, v.sum()))

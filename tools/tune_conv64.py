@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""conv2 / conv3 forward (= input-gradient) kernels at the headline shapes through seld_k_conv3x3_fwd, each kernel choice in turn;
+"""conv2 / conv3 forward (= input-gradient) kernels at the headline shapes through seld_k_conv3x3_fwd;
 run under `rocprofv3 --kernel-trace --stats` (durations come from the trace)."""
 import ctypes as C
 import os
@@ -20,11 +20,7 @@ for W in (16, 4):
     b = torch.randn(64, device="cuda", generator=g)
     z = torch.empty(B, H, W, 64, device="cuda")
     st = torch.empty(2, 64, device="cuda")
-    for opts in ({"conv64_dbuf": 1}, {"conv64_dbuf": 0}):
-        for k, v in opts.items():
-            assert lib.seld_k_set_option(k.encode(), v) == 0
-        for _ in range(6):
-            rc = lib.seld_k_conv3x3_fwd(P(x), P(w), P(b), P(z), P(st), B, H, W, 64, 64)
-            assert rc == 0, rc
-lib.seld_k_set_option(b"conv64_dbuf", 1)
+    for _ in range(6):
+        rc = lib.seld_k_conv3x3_fwd(P(x), P(w), P(b), P(z), P(st), B, H, W, 64, 64)
+        assert rc == 0, rc
 print("ok")
