@@ -664,6 +664,29 @@ int seld_relattn_bwd(const float* Q, const float* K, const float* V, int ldq, in
                      int lddqu, int lddqv, int lddk, int lddv, int lddp, float* scratch, int B, int S, int H, int d, float scale, void* stream);
 int seld_glu_fwd(const float* u, int ldu, float* y, int64_t rows, int C, void* stream);
 int seld_glu_bwd(const float* u, int ldu, const float* dy, float* du, int lddu, int64_t rows, int C, void* stream);
+/* ---- the front of models.conv_temporal (stem.hip; reference models.py:54-66): conv2d_bn(filters, first_kernel_size, 'same') and
+ * MaxPooling2D(first_pool_size, padding).  Under the seld_m_* contract: NHWC fp32, asynchronous on `stream`, no allocation;
+ * SELD_ERR_INVALID, before anything is enqueued, for a NULL required pointer or a size < 1.
+ *   seld_stem_conv_fwd     z [B,H,W,F] = Conv2D(F, k, strides 1, 'same')(x [B,H,W,Cin]) + bias, kernel [k,k,Cin,F] (Keras).  k odd, 1 .. 7, Cin
+ *                          1 .. 16, any F, H, W, B; SELD_ERR_UNSUPPORTED outside that.  No im2col buffer: the halo patch of a 16 x 32 pixel
+ *                          tile sits in LDS and the products run on the split-bf16 MFMA (six bf16 products per fp32 product, fp32 sums).
+ *   seld_stem_conv_wgrad   dkernel [k,k,Cin,F] = sum over (b,h,w) of x[b,h+dy,w+dx,c] dz[b,h,w,f], dbias [F] = the column sums of dz; exact
+ *                          fp32 MFMA.  Two stages in a fixed order, no atomics: two runs give the same bits.  scratch:
+ *                          seld_stem_conv_wgrad_scratch(...) floats (a negative error code for arguments the kernel refuses).  There is no
+ *                          input gradient: the stem's input is the data.
+ *   seld_pool2d_fwd        y [B,Ho,Wo,C] = MaxPooling2D((ph,pw), strides = pool)(x [B,H,W,C]).  same != 0: TensorFlow 'SAME' — Ho = ceil(H / ph),
+ *                          pad_total = Ho ph - H, pad_before = pad_total / 2, the surplus behind; padding never wins: a window takes the maximum
+ *                          of its in-bounds elements.  same == 0: 'valid', Ho = H / ph (SELD_ERR_INVALID where that is 0).  idx (may be NULL:
+ *                          inference, y is bit-identical): the uint8 position i pw + j of the first maximum in row-major window order;
+ *                          SELD_ERR_UNSUPPORTED for ph pw > 255.  float4 over the channels where C % 4 == 0 and the pointers are aligned.
+ *   seld_pool2d_bwd        dx [B,H,W,C], all of it (no pre-zeroing, no atomics: strides == pool, so an element lies in at most one window):
+ *                          dy of its window where the element is the recorded maximum, 0 elsewhere and in the rows / columns 'valid' leaves out. */
+int seld_stem_conv_fwd(const float* x, const float* kernel, const float* bias, float* z, int B, int H, int W, int Cin, int k, int F, void* stream);
+int64_t seld_stem_conv_wgrad_scratch(int B, int H, int W, int Cin, int k, int F);
+int seld_stem_conv_wgrad(const float* x, const float* dz, float* dkernel, float* dbias, float* scratch, int B, int H, int W, int Cin, int k, int F,
+                         void* stream);
+int seld_pool2d_fwd(const float* x, float* y, unsigned char* idx, int B, int H, int W, int C, int ph, int pw, int same, void* stream);
+int seld_pool2d_bwd(const float* dy, const unsigned char* idx, float* dx, int B, int H, int W, int C, int ph, int pw, int same, void* stream);
 /* Measurement aid (bench.py, SURVEY.md §8(d) "state the step-latency floor"): the shader clock the card holds while `blocks`
  * workgroups of 512 threads run a VALU-only loop (the load shape of the GRU recurrence: 2B workgroups, no MFMA), from
  * s_memtime / s_memrealtime (100 MHz) inside the kernel.  No reference counterpart. */

@@ -217,6 +217,11 @@ SIGNATURES = {
     "seld_relattn_bwd": (_I, [_P, _P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P] + [_P] * 5 + [_I] * 5 + [_P, _I, _I, _I, _I, _F, _P]),
     "seld_glu_fwd": (_I, [_P, _I, _P, _L, _I, _P]),
     "seld_glu_bwd": (_I, [_P, _I, _P, _P, _I, _L, _I, _P]),
+    "seld_stem_conv_fwd": (_I, [_P, _P, _P, _P] + [_I] * 6 + [_P]),
+    "seld_stem_conv_wgrad_scratch": (_L, [_I] * 6),
+    "seld_stem_conv_wgrad": (_I, [_P, _P, _P, _P, _P] + [_I] * 6 + [_P]),
+    "seld_pool2d_fwd": (_I, [_P, _P, _P] + [_I] * 7 + [_P]),
+    "seld_pool2d_bwd": (_I, [_P, _P, _P] + [_I] * 7 + [_P]),
     "seld_k_rn_conv": (_I, [_P, _P, _P] + [_I] * 7),
     "seld_k_rn_conv_stats": (_I, [_P, _P, _P] + [_I] * 7 + [_P]),
     "seld_k_rn_conv_bwd": (_I, [_P, _P, _P, _P, _P] + [_I] * 7),

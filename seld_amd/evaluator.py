@@ -71,3 +71,15 @@ def ensemble_outputs(model: SeldNet, xs: list, win_size: int = 300, step_size: i
     if fused:
         _lib.check(lib.seld_set_batch(model.ctx, Bm), model.ctx)      # leave the context at the batch it was built for, as it was found
     return out
+
+
+def load_conv_temporal_model(input_shape, model_config, weights, device=None):
+    """reference load_conv_temporal_model (evaluator.py:53-58): `model_config` is the path of a JSON settings file (model_config/SS5.json),
+    `weights` a file in the format load_weights reads (an .npz keyed by variable name); ensemble_outputs takes the model it returns"""
+    import json
+    from . import models
+    with open(model_config, "r") as o:
+        cfg = json.load(o)
+    model = models.conv_temporal(input_shape, cfg, device)
+    model.load_weights(weights)
+    return model

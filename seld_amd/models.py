@@ -293,6 +293,15 @@ def seldnet(input_shape, model_config, device=None, dtype: str = "float32"):
     return SeldNet(input_shape, model_config, device, dtype)
 
 
+def conv_temporal(input_shape, model_config, device=None):
+    """reference models.conv_temporal (models.py:54-78; model_config/SS5.json): conv2d_bn(filters, first_kernel_size) + MaxPooling2D(
+    first_pool_size, 'same'), the BLOCK* chain in string order, and a SED and a DOA head that are blocks themselves — a
+    modules.ConvTemporalNet, composed from module operators like every composed model (float32; train.trainstep / teststep take it; agc and
+    the trainv2 recipe stay refused for composed models).  Configuration errors are ValueErrors raised without a device."""
+    from .modules import ConvTemporalNet
+    return ConvTemporalNet(input_shape, model_config, device)
+
+
 def seldnet_v1(input_shape, model_config, device=None, dtype: str = "float32") -> SeldNet:
     """reference models.seldnet_v1 (models.py:36-52; model_config/seldnet_v1.json): seldnet whose DOA output is coupled to the SED
     output, doa_out = tanh(doa * Concatenate([sed] * 3)) (seld_arch.output_coupling)."""

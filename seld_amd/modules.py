@@ -22,6 +22,10 @@ else).  There is no CPU or PyTorch fallback.
   RNN_block / RNN_stage (modules.py:64-83, 322-347)                  GRU or LSTM (units 128: the recurrence kernels of gru.hip / lstm.hip), one direction or
                                                   Bidirectional with merge_mode mul | concat | ave | sum (seld_rnn_*)
 
+  models.conv_temporal (models.py:54-78)                              ConvTemporalNet: StemConv2D (seld_stem_conv_* of stem.hip) + BatchNormalization + relu +
+                                                  MaxPool2D (seld_pool2d_*), the BLOCK* chain (mother blocks, then every 3-D kind, DenseBlock =
+                                                  simple_dense_block as a body block) and a block or stage as each head (_StageHead)
+
 The shared pieces, each in one place:
   Linear               GEMM + bias with its backward: Dense, Conv1D and Conv2D (im2col in front of it where the window is wider than one
                        sample), the heads' layers (Head) and the squeeze-and-excitation pair (_SqueezeExcite)
@@ -341,6 +345,88 @@ class Conv2D(Linear):
                                    int(accumulate), rt.st()))
 
 
+class StemConv2D(Linear):
+    """models.conv_temporal's first layer (reference models.py:62: Conv2D(filters, first_kernel_size, 'same') on the input channels): variables
+    `kernel` (k, k, Cin, F) and `bias`, the output buffer `z`, as Conv2D has them.  Inside the stem kernels' contract (k odd, 1 .. 7, Cin <= 16)
+    the forward is seld_stem_conv_fwd (no im2col buffer) and the kernel / bias gradients are seld_stem_conv_wgrad; outside it (an even k, more
+    channels) both are what Conv2D does: seld_m_im2col + the GEMMs.  DIRECT names the passes that run on the stem kernels where the contract
+    allows (tools/bench_conv_temporal.py measured both against im2col: DESIGN.md section 3o).  There is no input gradient: the input is the data."""
+    DIRECT = {"fwd": True, "wgrad": True}
+
+    def __init__(self, rt: _Rt, name: str, in_shape, filters: int, k: int, B: int = 1, direct=None):
+        self.k = int(k)
+        self.H, self.W, self.Cin = (int(v) for v in in_shape)
+        if self.k < 1 or int(filters) < 1:
+            raise ValueError(f"StemConv2D: filters {filters!r} and kernel size {k!r} must be >= 1")
+        super().__init__(rt, name, B * self.H * self.W, self.k * self.k * self.Cin, filters, (self.k, self.k, self.Cin, int(filters)))
+        self.out_shape = (self.H, self.W, self.N)
+        inside = self.k % 2 == 1 and self.k <= 7 and self.Cin <= 16
+        direct = dict(self.DIRECT, **(direct or {}))
+        self.direct_fwd, self.direct_wgrad = inside and bool(direct["fwd"]), inside and bool(direct["wgrad"])
+        self.col = None if (self.direct_fwd and self.direct_wgrad) or self.k == 1 else rt.empty(B * self.H * self.W, self.K)
+        self.scratch = rt.empty(int(rt.lib.seld_stem_conv_wgrad_scratch(B, self.H, self.W, self.Cin, self.k, self.N))) if self.direct_wgrad else None
+
+    def _im2col(self, x, B):
+        rt = self.rt
+        if self.k == 1:
+            return x
+        rt.ck(rt.lib.seld_m_im2col(rt.p(x), rt.p(self.col), B, self.H, self.W, self.Cin, self.k, self.k, 1, 1, rt.st()))
+        return self.col
+
+    def forward(self, x, B):
+        rt, n = self.rt, self.name
+        self.x = x
+        if self.direct_fwd:
+            rt.ck(rt.lib.seld_stem_conv_fwd(rt.p(x), rt.p(rt.w(f"{n}.kernel")), rt.p(rt.w(f"{n}.bias")), rt.p(self.z), B, self.H, self.W, self.Cin,
+                                            self.k, self.N, rt.st()))
+            return self.z[:B * self.H * self.W].view(B, *self.out_shape)
+        return Linear.forward(self, self._im2col(x, B), B * self.H * self.W).view(B, *self.out_shape)
+
+    def backward(self, dz, B):
+        """dz [B,H,W,F] -> the kernel's and the bias's gradients"""
+        rt, n = self.rt, self.name
+        if self.direct_wgrad:
+            rt.ck(rt.lib.seld_stem_conv_wgrad(rt.p(self.x), rt.p(dz), rt.p(rt.g(f"{n}.kernel")), rt.p(rt.g(f"{n}.bias")), rt.p(self.scratch), B, self.H,
+                                              self.W, self.Cin, self.k, self.N, rt.st()))
+            return
+        if self.direct_fwd:
+            self.a = self._im2col(self.x, B)      # the forward did not form the columns
+        Linear.backward(self, dz, None, B * self.H * self.W)
+
+
+class MaxPool2D:
+    """tf.keras.layers.MaxPooling2D(pool, strides = pool, padding 'same' | 'valid') on [B, H, W, C]: seld_pool2d_fwd / _bwd.  Owns the
+    positions `idx` of the maxima (written in training only), the output and the input gradient."""
+
+    def __init__(self, rt: _Rt, in_shape, pool, B: int, padding: str = "same"):
+        self.rt = rt
+        self.H, self.W, self.C = (int(v) for v in in_shape)
+        self.ph, self.pw = safe_tuple(pool)
+        if padding not in ("same", "valid"):
+            raise ValueError(f"MaxPool2D: padding {padding!r}: 'same' or 'valid'")
+        self.same = int(padding == "same")
+        if self.ph < 1 or self.pw < 1 or self.ph * self.pw > 255:
+            raise ValueError(f"MaxPool2D: pool {pool!r}: sizes >= 1 whose product is at most 255 (the maximum's position is a uint8)")
+        Ho, Wo = (-(-self.H // self.ph), -(-self.W // self.pw)) if self.same else (self.H // self.ph, self.W // self.pw)
+        if Ho < 1 or Wo < 1:
+            raise ValueError(f"MaxPool2D: pool {pool!r} with padding 'valid' leaves nothing of {tuple(in_shape)}")
+        self.out_shape = (Ho, Wo, self.C)
+        self.y = rt.empty(B, *self.out_shape)
+        self.idx = torch.empty((B,) + self.out_shape, dtype=torch.uint8, device=rt.dev)
+        self.dx = rt.empty(B, self.H, self.W, self.C)
+
+    def forward(self, x, B, training):
+        rt = self.rt
+        rt.ck(rt.lib.seld_pool2d_fwd(rt.p(x), rt.p(self.y), rt.p(self.idx) if training else None, B, self.H, self.W, self.C, self.ph, self.pw,
+                                     self.same, rt.st()))
+        return self.y[:B]
+
+    def backward(self, dy, B):
+        rt = self.rt
+        rt.ck(rt.lib.seld_pool2d_bwd(rt.p(dy), rt.p(self.idx), rt.p(self.dx), B, self.H, self.W, self.C, self.ph, self.pw, self.same, rt.st()))
+        return self.dx[:B]
+
+
 class BatchNorm:
     """tf.keras.layers.BatchNormalization() on the channel axis: batch statistics in training (moving statistics updated), the moving ones
     otherwise."""
@@ -567,7 +653,9 @@ class Stage:
     block is `block(rt, cfg, S, D, prefix + index, B)` with forward(x, B, training) / backward(dy, B) on [B*S, D] -> [B*S, out_dim], and
     reads the width the one in front of it gives (behind an RNN_block with merge_mode 'concat': 256)."""
 
-    def __init__(self, rt: _Rt, block, cfg: dict, S: int, D: int, prefix: str, B: int, depth: int):
+    def __init__(self, rt: _Rt, block, cfg: dict, S: int, D: int, prefix: str, B: int, depth: int, first_block: int = 0):
+        """first_block: the blocks a chain of stages built in front of this one (ConvTemporalNet); its blocks draw from the streams
+        DROP_STREAM0 + 32 * (first_block + index), so that two stages of one model never share masks.  models.seldnet has one stage: 0."""
         self.blocks = []
         self.rt, self.S, self.D = rt, int(S), int(D)
         self.model = False      # True: this stage IS the model (a factory built it on a runtime of its own), so its training forwards count the draws
@@ -575,7 +663,7 @@ class Stage:
             self.blocks.append(block(rt, cfg, S, D, f"{prefix}{i}", B))
             D = self.blocks[-1].out_dim
             if getattr(self.blocks[-1], "drop", None) is not None:
-                self.blocks[-1].drop.base = DROP_STREAM0 + 32 * i
+                self.blocks[-1].drop.base = DROP_STREAM0 + 32 * (int(first_block) + i)
         self.out_dim, self.out_shape = int(D), (self.S, int(D))
 
     def forward(self, x, B, training):
@@ -1581,7 +1669,7 @@ def _check_second(kind: str, cfg: dict, D=None, dropout: bool = False) -> None:
     check(cfg, stage, D, **kw) if with_d else check(cfg, stage, **kw)
 
 
-def _build_second(kind: str, rt, cfg: dict, S: int, D: int, B: int, prefix=None, dropout: bool = False) -> Stage:
+def _build_second(kind: str, rt, cfg: dict, S: int, D: int, B: int, prefix=None, dropout: bool = False, first_block: int = 0) -> Stage:
     """the SECOND stage `kind` on [B*S, D] (rt None: on a runtime of its own on the current device); the configuration errors, those that
     need the width among them (pos_encoding 'basic' on an odd one, the FF width), are raised first, without a device.  dropout: the caller
     accepts the library's draws (_dropout_rate); a given rt carries its owner's choice"""
@@ -1592,9 +1680,54 @@ def _build_second(kind: str, rt, cfg: dict, S: int, D: int, B: int, prefix=None,
     rt = rt or _Rt(torch.device("cuda", torch.cuda.current_device()))
     rt.dropout = dropout
     depth = int(cfg["depth"]) if stage else len(cfg["units"]) if block is BidirectionalGRUBlock else 1
-    st = Stage(rt, block, cfg, S, D, prefix or pre, B, depth)
+    st = Stage(rt, block, cfg, S, D, prefix or pre, B, depth, first_block)
     st.model = own
     return st
+
+
+def check_dense_config(cfg: dict) -> None:
+    """reference modules.simple_dense_block (modules.py:350-376) as a body block"""
+    if "units" not in cfg or not isinstance(cfg["units"], (list, tuple)):
+        raise ValueError("simple_dense_block: `units` is a list, one entry per layer")
+    if any(int(u) < 1 for u in cfg["units"]) or int(cfg.get("kernel_size", 1)) < 1:
+        raise ValueError("simple_dense_block: units and kernel_size >= 1")
+    _check_activation(cfg, None, "dense_activation")
+    if float(cfg.get("dropout_rate", 0) or 0) != 0.0:
+        raise ValueError("simple_dense_block: dropout_rate must be 0 — its Dropout layers are wired on the fused path only (models.SeldNet), as for "
+                         "the composed heads; the composed path's Dropout covers the attention kinds")
+
+
+class DenseBlock:
+    """reference modules.simple_dense_block (modules.py:350-376) as a body block on [B*S, D]: one Conv1D(units, kernel_size, 'same') +
+    dense_activation per entry of `units` (variables `{prefix}.dense{j}`), out_dim = the last width; `units` = []: the identity (which is
+    also what identity_block is, modules.py:639-642)."""
+
+    def __init__(self, rt: _Rt, cfg: dict, S: int, D: int, prefix: str, B: int):
+        check_dense_config(cfg)
+        self.rt, self.S, self.D = rt, int(S), int(D)
+        self.act = ACT[cfg.get("dense_activation", None)]
+        k, R = int(cfg.get("kernel_size", 1)), B * self.S
+        self.layers = []      # (layer, its activation y, the gradient of its pre-activation, the gradient of its input)
+        for j, u in enumerate(int(u) for u in cfg["units"]):
+            self.layers.append((Conv1D(rt, f"{prefix}.dense{j}", B, self.S, D, u, k), rt.empty(R, u), rt.empty(R, u), rt.empty(R, D)))
+            D = u
+        self.out_dim, self.out_shape = int(D), (self.S, int(D))
+
+    def forward(self, x, B, training):
+        R = B * self.S
+        x = x.reshape(R, self.D)
+        for lin, y, _, _ in self.layers:
+            self.rt.act(lin.forward(x, R), y[:R], self.act)
+            x = y[:R]
+        return x
+
+    def backward(self, dy, B):
+        R = B * self.S
+        for lin, _, dpre, dx in reversed(self.layers):
+            self.rt.act_bwd(lin.z[:R], dy, dpre[:R], self.act)
+            lin.backward(dpre[:R], dx[:R], R)
+            dy = dx[:R]
+        return dy
 
 
 class Head:
@@ -1894,6 +2027,198 @@ class ComposedSeldNet:
         sed, doa = self._forward(x, False)
         sloss, dloss = self._losses(sed, doa, ys, yd, cfg, False)
         return [sed, doa], sloss, dloss
+
+
+CHAIN_4D = ("mother_block", "mother_stage")
+# the kinds that take [B, S, D] (each applies layers.force_1d_inputs to a 4-D input: a free reshape in NHWC, D = F * C)
+CHAIN_3D = tuple(SECOND_KINDS) + ("bidirectional_GRU_stage", "simple_dense_block", "simple_dense_stage", "identity_block")
+
+
+def chain_blocks(model_config: dict):
+    """models.conv_temporal's block keys in the reference's order (models.py:66-68): the BLOCK* keys that do not end in _ARGS, sorted as
+    STRINGS (BLOCK10 comes before BLOCK2)"""
+    return sorted(k for k in model_config if k.startswith("BLOCK") and not k.endswith("_ARGS"))
+
+
+def canonical_kind(kind: str, args: dict):
+    """one block of a chain through models.canonical_config's rules: bidirectional_GRU_stage -> bidirectional_GRU_block (depth x [units]),
+    simple_dense_stage -> simple_dense_block (depth x [units], dense_activation = args.get('activation'): whatever dense_activation the
+    configuration holds is overwritten, reference modules.py:101), identity_block -> simple_dense_block without layers"""
+    from .models import canonical_config
+    if kind == "bidirectional_GRU_stage":
+        c = canonical_config({"SECOND": kind, "SECOND_ARGS": args})
+        return c["SECOND"], c["SECOND_ARGS"]
+    if kind in ("simple_dense_stage", "identity_block"):
+        c = canonical_config({"SED": kind, "SED_ARGS": args})
+        return c["SED"], c["SED_ARGS"]
+    return kind, copy.deepcopy(args)
+
+
+class _StageHead:
+    """A head of models.conv_temporal (models.py:73-76): any 3-D kind applied to the chain's output, then Dense(n_out) + `act`.  `dpre`: the
+    gradient of the output layer's pre-activation, which the loss kernel writes (the interface of Head)."""
+
+    def __init__(self, rt: _Rt, name: str, body, rows: int, n_out: int, act: int):
+        self.rt, self.body, self.act = rt, body, act
+        self.out = Linear(rt, f"{name}_out", rows, body.out_dim, n_out)
+        self.dpre = rt.empty(rows, n_out)
+        self.dbody = rt.empty(rows, body.out_dim)
+
+    def forward(self, x, y, B, rows, training):
+        self.rt.act(self.out.forward(self.body.forward(x, B, training), rows), y, self.act)
+
+    def backward(self, B, rows):
+        """dpre -> every variable's gradient; returns the gradient of the head's input (a buffer of the head's)"""
+        self.out.backward(self.dpre, self.dbody, rows)
+        return self.body.backward(self.dbody[:rows], B)
+
+
+class ConvTemporalNet(ComposedSeldNet):
+    """models.conv_temporal(input_shape, model_config) (reference models.py:54-78) composed from module operators:
+
+      stem    StemConv2D(filters, first_kernel_size) -> BatchNormalization -> relu -> MaxPool2D(first_pool_size, 'same')
+      blocks  the BLOCK* keys in string order (chain_blocks): mother_block / mother_stage while the tensor is 4-D; the first 3-D kind
+              (CHAIN_3D) flattens it to [B, S, F * C], and a 4-D kind behind a 3-D one is a ValueError
+      heads   SED and DOA: any 3-D kind on the chain's output, then Dense(n_classes, sigmoid) / Dense(3 n_classes, tanh)
+
+    Variables in the reference's creation order: stem.conv, stem.bn, b{i}.*, sed.*, sed_out, doa.*, doa_out; the BatchNormalization
+    statistics in `state_variables` in the same order.  Weights I/O, the losses, train_step / test_step, profile and batches of 1 .. B are
+    ComposedSeldNet's.  Every stage of the chain draws its Dropout masks from streams of its own (Stage: first_block).  device='meta': the
+    plan alone — variables and shapes without a device (nothing can be run)."""
+
+    def __init__(self, input_shape, model_config: dict, device=None):
+        cfg = copy.deepcopy(model_config)
+        meta = device == "meta"
+        if not meta and not torch.cuda.is_available():
+            ConvTemporalNet(input_shape, cfg, "meta")      # the configuration errors first, as the factories raise them without a device
+            raise RuntimeError("seld_amd needs a HIP device: there is no CPU fallback")
+        self._dev = torch.device("meta") if meta else torch.device("cuda", torch.cuda.current_device() if device is None else int(device))
+        B, T, Fq, Ch = (int(v) for v in input_shape)
+        self.input_shape = (B, T, Fq, Ch)
+        self.n_classes = int(cfg.get("n_classes", 14))
+        rt = self.rt = _Rt(self._dev)
+        rt.dropout = True
+        self.lib = rt.lib
+        # ---- stem (layers.conv2d_bn + MaxPooling2D, models.py:62-64)
+        self.stem_conv = StemConv2D(rt, "stem.conv", (T, Fq, Ch), int(cfg.get("filters", 32)), int(cfg.get("first_kernel_size", 7)), B)
+        self.stem_bn = BatchNorm(rt, "stem.bn", self.stem_conv.out_shape, B)
+        self.stem_pre, self.stem_act = rt.empty(B, *self.stem_conv.out_shape), rt.empty(B, *self.stem_conv.out_shape)
+        self.stem_dact, self.stem_dz = rt.empty(B, *self.stem_conv.out_shape), rt.empty(B, *self.stem_conv.out_shape)
+        self.pool = MaxPool2D(rt, self.stem_conv.out_shape, cfg.get("first_pool_size", [5, 1]), B, "same")
+        shape = self.pool.out_shape
+        # ---- the chain
+        self.blocks, self.body = [], []      # 4-D blocks (MotherBlock), 3-D blocks (Stage / DenseBlock)
+        self.stream_bases = {}                # prefix of a Stage -> its first Dropout stream
+        self.n_built = 0
+        D = None
+        for i, key in enumerate(chain_blocks(cfg)):
+            kind, args = cfg[key], cfg.get(f"{key}_ARGS")
+            if args is None:
+                raise ValueError(f"conv_temporal: {key} has no {key}_ARGS")
+            if kind in CHAIN_4D:
+                if D is not None:
+                    raise ValueError(f"conv_temporal: {key} = {kind!r} takes a 4-D tensor, but a block in front of it has made it 3-D")
+                cfgs, c = [], copy.deepcopy(args)
+                for _ in range(int(args["depth"]) if kind == "mother_stage" else 1):
+                    cfgs.append(copy.deepcopy(c))
+                    c["strides"] = (1, 1)       # modules.py:41
+                for d, c in enumerate(cfgs):
+                    blk = MotherBlock(rt, c, shape, f"b{i}.mb{d}", B)
+                    self.blocks.append(blk)
+                    shape = blk.out_shape
+                    self.n_built += 1
+            elif kind in CHAIN_3D:
+                if D is None:
+                    D = shape[1] * shape[2]      # layers.force_1d_inputs (layers.py:41-47): feature = f * C + c
+                blk = self._build_3d(kind, args, shape[0], D, B, f"b{i}")
+                self.body.append(blk)
+                D = blk.out_dim
+            else:
+                raise ValueError(f"conv_temporal: {key} = {kind!r}: one of {CHAIN_4D + CHAIN_3D}")
+        self.shape4 = shape                   # the tensor behind the last 4-D block
+        self.S = shape[0]
+        four_d = D is None
+        if four_d:
+            D = shape[1] * shape[2]
+        R = B * self.S
+        self.heads = []
+        for head, n_out, act in (("sed", self.n_classes, "sigmoid"), ("doa", 3 * self.n_classes, "tanh")):
+            kind, args = cfg.get(head.upper()), cfg.get(f"{head.upper()}_ARGS", {})
+            if kind not in CHAIN_3D:
+                raise ValueError(f"conv_temporal: {head.upper()} = {kind!r}: one of {CHAIN_3D}")
+            if four_d and kind == "identity_block":
+                raise ValueError(f"conv_temporal: {head.upper()} = identity_block on a 4-D tensor: the reference's Dense would give a 4-D output")
+            self.heads.append(_StageHead(rt, head, self._build_3d(kind, args, self.S, D, B, head), R, n_out, ACT[act]))
+        rt.finalize()
+        self.variables, self.state_variables = rt.variables, rt.state_variables
+        self.n_params, self.n_state = rt.n_params, rt.n_state
+        self.dfeat = rt.empty(R, D)
+        self.loss_scratch = rt.empty(int(rt.lib.seld_m_losses_scratch(R)))
+        self.adam_step = 0
+        self._marks = None
+        if not meta:
+            self._init_weights()
+
+    def _build_3d(self, kind: str, args: dict, S: int, D: int, B: int, prefix: str):
+        kind, args = canonical_kind(kind, args)
+        if kind == "simple_dense_block":
+            blk = DenseBlock(self.rt, args, S, D, prefix, B)
+            self.n_built += 1
+            return blk
+        pre = SECOND_KINDS[kind][2]
+        st = _build_second(kind, self.rt, args, S, D, B, prefix=f"{prefix}.{pre}", first_block=self.n_built)
+        self.stream_bases[f"{prefix}.{pre}"] = DROP_STREAM0 + 32 * self.n_built
+        self.n_built += len(st.blocks)
+        return st
+
+    def summary(self) -> str:
+        return super().summary().replace("ComposedSeldNet", "ConvTemporalNet", 1)
+
+    def _forward(self, x, training: bool):
+        rt = self.rt
+        B = x.shape[0]
+        if training:
+            rt.next_draws()
+        z = self.stem_conv.forward(x, B)
+        self.stem_bn.forward(z, self.stem_pre[:B], B, training, 0)
+        rt.act(self.stem_pre[:B], self.stem_act[:B], ACT["relu"])
+        h = self.pool.forward(self.stem_act[:B], B, training)
+        for blk in self.blocks:
+            h = blk.forward(h, B, training)
+        self._mark("first_fwd")
+        R = B * self.S
+        h = h.reshape(R, -1)
+        for blk in self.body:
+            h = blk.forward(h, B, training)
+        sed = rt.empty(B, self.S, self.n_classes)
+        doa = rt.empty(B, self.S, 3 * self.n_classes)
+        for head, out in zip(self.heads, (sed, doa)):
+            head.forward(h, out.view(R, -1), B, R, training)
+        self._mark("gru_heads_fwd")
+        return sed, doa
+
+    def _backward(self, B):
+        """from the heads' pre-activation gradients (written by seld_m_losses) to every variable's gradient"""
+        rt = self.rt
+        R = B * self.S
+        dy = self.dfeat[:R]
+        for i, head in enumerate(self.heads):
+            d = head.backward(B, R)
+            if i == 0:
+                dy.copy_(d.reshape(R, -1))
+            else:
+                rt.axpy(dy, d)      # the second head's gradient adds to the first one's
+        for blk in reversed(self.body):
+            dy = blk.backward(dy, B)
+        self._mark("heads_gru_bwd")
+        dy = dy[:R].reshape(B, *self.shape4)
+        for blk in reversed(self.blocks):
+            dy = blk.backward(dy, None, B)
+        dact = self.pool.backward(dy, B)
+        rt.act_bwd(self.stem_pre[:B], dact, self.stem_dact[:B], ACT["relu"])
+        self.stem_bn.backward(self.stem_dact[:B], self.stem_dz[:B], B)
+        self.stem_conv.backward(self.stem_dz[:B], B)
+        self._mark("first_bwd")
 
 
 def mother_block(model_config: dict):
