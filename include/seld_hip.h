@@ -313,6 +313,17 @@ int seld_overlap_average(const float* y, float* out, int n_windows, int L, int D
 int seld_aug_mask(float* x, int B, int T, int F, int C, int period, const int* t_off, const int* t_size, const int* f_off,
                   const int* f_size, void* stream);
 int seld_aug_gather_sign(float* x, int B, int64_t outer, int R, int64_t inner, const int* src, const float* sgn, void* stream);
+/* seld_aug_v2: the sample transforms of trainv2.get_dataset (trainv2.py:120-140) in ONE pass over x [B,T,F,C], in place: shift[b] is
+ *   added to the channels < n_shift_ch (random_ups_and_downs; shift float [B], may be NULL), then, per sample and per `period`-frame
+ *   segment, the union of n_t frame runs and the union of n_f bin runs is stored as +0.0f — the bits of the add followed by n_t + n_f
+ *   seld_aug_mask calls.  Tables: int32 [n_t][B * T/period] and [n_f][B * T/period]; n_t / n_f may be 0 (that axis's pointers may then be
+ *   NULL).  The four tables are read by the host, for the checks below, AND by the kernel: they must be host memory the device can read
+ *   (hipHostMalloc / a pinned torch tensor), alive until the kernel has run; shift is read by the kernel only.  Asynchronous on `stream`,
+ *   no allocation, no copy, no host synchronisation.  SELD_ERR_INVALID, before the first HIP call, for T % period != 0, n_t or n_f above
+ *   16, n_shift_ch > C, a negative size or offset, or a run that reaches outside its axis (offset + size > period, or > F);
+ *   SELD_ERR_UNSUPPORTED for F * C > 16384. */
+int seld_aug_v2(float* x, int B, int T, int F, int C, int period, const float* shift, int n_shift_ch, const int* t_off, const int* t_size,
+                int n_t, const int* f_off, const int* f_size, int n_f, void* stream);
 
 /* ---- SELD metrics on the device: SELDMetrics.update_states (metrics.py:60-154), which the reference runs in TF
  * eager mode on the host after every step (train.py:82-83).  `state` = seld_metrics_state_size(nc) doubles
@@ -561,6 +572,27 @@ int64_t seld_m_losses_scratch(int rows);
 int seld_m_losses(const float* sed, const float* doa, const float* y_sed, const float* y_doa, const seld_loss_cfg* cfg, float* sloss, float* dloss,
                   float* dsed_pre, float* ddoa_pre, float* scratch, int B, int S, int nc, void* stream);
 int seld_m_adam(float* theta, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps, int64_t step, void* stream);
+/* The v2 recipe (trainv2.py:23-56, swa.py) for composed models, as stream operators under the seld_m_* contract: asynchronous on `stream`,
+ * no host synchronisation, every argument check before the first HIP call.  They carry the recipe's seld_v2_ prefix, not seld_m_: like the
+ * attention, LayerNorm and recurrence operators below they are not part of the mother-block operator set that
+ * tests/test_module_ops_gpu.py enumerates by that prefix.
+ * seld_v2_losses: seld_k_losses_v2 (same refusals, same bits) on caller scratch of seld_v2_losses_scratch(B * S) floats, 8-byte aligned
+ *   (the denominator of the weighted MMSE sits behind the partials); dense gradient rows.
+ * seld_v2_plan_create: the device tables of the optimizer stage for n_vars variables in flat buffers of n floats — the arguments and
+ *   refusals of seld_k_reg_agc_adabelief (HOST arrays) — built once: the one call of this group that allocates and copies (on the current
+ *   device).  *plan is NULL on failure.  seld_v2_plan_destroy frees it (NULL: nothing).
+ * seld_v2_opt: regulariser + AGC (clip_factor <= 0: none) + AdaBelief in two launches, the bits of seld_k_reg_agc_adabelief on the same
+ *   buffers; g is overwritten with the gradient the optimizer consumed; step is 1-based.
+ * seld_v2_swa: swa = (swa cnt + w) / (cnt + 1), each operation rounded to float32 as numpy evaluates swa.py:29-31; cnt == 0 copies. */
+int64_t seld_v2_losses_scratch(int rows);
+int seld_v2_losses(const float* sed, const float* doa, const float* y_sed, const float* y_doa, const seld_v2_cfg* cfg, float* sloss, float* dloss,
+                     float* dsed_pre, float* ddoa_pre, float* scratch, int B, int S, int nc, void* stream);
+int seld_v2_plan_create(int64_t n, int n_vars, const int64_t* off_host, const int32_t* rows_host, const int32_t* cols_host,
+                          const int32_t* reg_host, void** plan);
+void seld_v2_plan_destroy(void* plan);
+int seld_v2_opt(void* plan, float* theta, float* g, float* m, float* v, float lr, float beta1, float beta2, float eps, float l2,
+                  float clip_factor, int64_t step, void* stream);
+int seld_v2_swa(float* swa, const float* w, int64_t n, int cnt, void* stream);
 /* ---- attention operators (attention.hip): the shared core of the reference's attention blocks — modules.transformer_encoder_block / _stage
  * (modules.py:106-126, 379-407), and of conformer_encoder_block / attention_block (modules.py:410-635, layers.py:268-287).  fp32 device
  * tensors, asynchronous on `stream`, no allocation.  Not seld_m_*: seld_amd/modules.py composes the transformer and conformer blocks from these and seld_m_*.

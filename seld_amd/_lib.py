@@ -134,6 +134,7 @@ SIGNATURES = {
     "seld_overlap_average": (_I, [_P, _P, _I, _I, _I, _P]),
     "seld_aug_mask": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "seld_aug_gather_sign": (_I, [_P, _I, _L, _I, _L, _P, _P, _P]),
+    "seld_aug_v2": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _I, _P, _P, _I, _P]),
     "seld_metrics_state_size": (_I, [_I]),
     "seld_metrics_scratch_floats": (_L, [_I, _I, _I, _I]),
     "seld_metrics_update": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P]),
@@ -199,6 +200,12 @@ SIGNATURES = {
     "seld_m_losses_scratch": (_L, [_I]),
     "seld_m_losses": (_I, [_P, _P, _P, _P, C.POINTER(LossCfg), _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "seld_m_adam": (_I, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _L, _P]),
+    "seld_v2_losses_scratch": (_L, [_I]),
+    "seld_v2_losses": (_I, [_P, _P, _P, _P, C.POINTER(V2Cfg), _P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "seld_v2_plan_create": (_I, [_L, _I, C.POINTER(_L), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(_P)]),
+    "seld_v2_plan_destroy": (None, [_P]),
+    "seld_v2_opt": (_I, [_P, _P, _P, _P, _P, _F, _F, _F, _F, _F, _F, _L, _P]),
+    "seld_v2_swa": (_I, [_P, _P, _L, _I, _P]),
     "seld_attn_fwd": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _I, _I, _I, _I, _F, _P]),
     "seld_attn_bwd_scratch": (_L, [_I, _I, _I, _I]),
     "seld_attn_bwd": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _I, _I, _I, _I, _F, _P]),

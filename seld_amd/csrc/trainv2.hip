@@ -7,11 +7,13 @@
 //   adabelief_kernel       utils.AdaBelief (utils.py:99-194, amsgrad=False) over the flat buffers, regulariser and clip folded in
 //   swa_kernel             swa.SWA.update_swa_weights (swa.py:25-32)
 // and the C ABI around them (include/seld_hip.h: seld_k_losses_v2, seld_k_reg_agc_adabelief, seld_train_fwd_bwd_v2, seld_set_regularized,
-// seld_v2_opt_step, seld_swa_*).  Nothing here is library-wide state: the tables live in the context.
+// seld_v2_opt_step, seld_swa_*; for composed models the stream operators seld_v2_losses, seld_v2_plan_*, seld_v2_opt, seld_v2_swa).
+// Nothing here is library-wide state: the tables live in the context, or in the plan a composed model owns.
 #include "ctx.h"
 
 #include <algorithm>
 #include <math.h>
+#include <stdint.h>
 #include <vector>
 
 #define V2_EPS 1e-7f      // K.epsilon() of K.binary_crossentropy, eps of losses.focal_loss
@@ -459,6 +461,74 @@ int seld_swa_apply(seld_ctx* c) {
     HIPCHK(c, hipMemcpyAsync(c->params, c->swa_w, (size_t)c->nparam * 4, hipMemcpyDeviceToDevice, c->stream));
     if (c->nstate) HIPCHK(c, hipMemcpyAsync(c->state, c->swa_s, (size_t)c->nstate * 4, hipMemcpyDeviceToDevice, c->stream));
     return SELD_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ the stream operators (composed models)
+/* floats of caller scratch seld_v2_losses needs for `rows` = B * S label frames: the partials and the denominator slot behind them */
+int64_t seld_v2_losses_scratch(int rows) { return rows > 0 ? (int64_t)loss_scratch_floats(rows) + 4 : -1; }
+
+int seld_v2_losses(const float* sed, const float* doa, const float* y_sed, const float* y_doa, const seld_v2_cfg* cfg, float* sloss, float* dloss,
+                     float* dsed_pre, float* ddoa_pre, float* scratch, int B, int S, int nc, void* stream) {
+    if (!sed || !doa || !y_sed || !y_doa || !cfg || !sloss || !dloss || !scratch || B < 1 || S < 1 || !v2_cfg_ok(cfg, nc)) return SELD_ERR_INVALID;
+    if ((uintptr_t)scratch & 7) return SELD_ERR_INVALID;      // the partials are doubles
+    const int rows = B * S;
+    launch_losses_v2((hipStream_t)stream, sed, doa, y_sed, y_doa, cfg, scratch + loss_scratch_floats(rows), sloss, dloss, dsed_pre, ddoa_pre, scratch,
+                     rows, nc, 0, 0);
+    return hipGetLastError() == hipSuccess ? SELD_OK : SELD_ERR_HIP;
+}
+
+namespace {
+// v2_build's tables, the flags and the scale array in one device allocation
+struct V2Plan { char* buf; const V2Tile* tiles; const V2Seg* segs; const int32_t* reg; float* scale; int ntiles, nsegs; };
+}  // namespace
+
+int seld_v2_plan_create(int64_t n, int n_vars, const int64_t* off, const int32_t* rows, const int32_t* cols, const int32_t* reg, void** plan) {
+    if (!plan) return SELD_ERR_INVALID;
+    *plan = nullptr;
+    if (!off || !rows || !cols || !reg || n <= 0 || n_vars < 1) return SELD_ERR_INVALID;
+    V2Host H;
+    if (!v2_build(n_vars, off, rows, cols, n, H)) return SELD_ERR_INVALID;
+    std::vector<int32_t> f(n_vars);
+    for (int i = 0; i < n_vars; ++i) f[i] = reg[i] != 0;
+    const size_t bt = H.tiles.size() * sizeof(V2Tile), bs = H.segs.size() * sizeof(V2Seg), br = (size_t)n_vars * sizeof(int32_t);
+    const size_t o1 = (bt + 255) & ~(size_t)255, o2 = o1 + ((bs + 255) & ~(size_t)255), o3 = o2 + ((br + 255) & ~(size_t)255);
+    char* buf = nullptr;
+    if (hipMalloc(&buf, o3 + (size_t)H.nunits * sizeof(float) + 256) != hipSuccess) return SELD_ERR_NOMEM;
+    if (hipMemcpy(buf, H.tiles.data(), bt, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(buf + o1, H.segs.data(), bs, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(buf + o2, f.data(), br, hipMemcpyHostToDevice) != hipSuccess) {
+        hipFree(buf);
+        return SELD_ERR_HIP;
+    }
+    *plan = new V2Plan{buf, reinterpret_cast<const V2Tile*>(buf), reinterpret_cast<const V2Seg*>(buf + o1), reinterpret_cast<const int32_t*>(buf + o2),
+                       reinterpret_cast<float*>(buf + o3), (int)H.tiles.size(), (int)H.segs.size()};
+    return SELD_OK;
+}
+
+void seld_v2_plan_destroy(void* plan) {
+    V2Plan* p = static_cast<V2Plan*>(plan);
+    if (!p) return;
+    hipFree(p->buf);
+    delete p;
+}
+
+int seld_v2_opt(void* plan, float* theta, float* g, float* m, float* v, float lr, float beta1, float beta2, float eps, float l2, float clip_factor,
+                  int64_t step, void* stream) {
+    const V2Plan* p = static_cast<const V2Plan*>(plan);
+    if (!p || !theta || !g || !m || !v || step < 1 || !(l2 >= 0.f)) return SELD_ERR_INVALID;
+    launch_v2_opt((hipStream_t)stream, theta, g, m, v, p->tiles, p->ntiles, p->segs, p->nsegs, p->reg, p->scale, (float)v2_lr_t(lr, beta1, beta2, step),
+                  beta1, beta2, eps, l2, clip_factor);
+    return hipGetLastError() == hipSuccess ? SELD_OK : SELD_ERR_HIP;
+}
+
+int seld_v2_swa(float* swa, const float* w, int64_t n, int cnt, void* stream) {
+    if (!swa || !w || n <= 0 || cnt < 0) return SELD_ERR_INVALID;
+    if (n > (int64_t)0x7fffffff * 256) return SELD_ERR_UNSUPPORTED;
+    if (cnt == 0) {      // swa.py:26-27: the first update copies
+        if (hipMemcpyAsync(swa, w, (size_t)n * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) return SELD_ERR_HIP;
+        return SELD_OK;
+    }
+    hipLaunchKernelGGL(swa_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, swa, w, n, (float)cnt);
+    return hipGetLastError() == hipSuccess ? SELD_OK : SELD_ERR_HIP;
 }
 
 }  // extern "C"

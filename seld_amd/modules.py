@@ -1761,6 +1761,20 @@ class Head:
         lin.backward(dz, dx, rows, accumulate)
 
 
+def v2_unit_shape(shape):
+    """utils.unitwise_norm (utils.py:71-83) as [rows][cols] with one clip unit per column, launch_agc's mapping: rank <= 1 one unit; rank 2 and
+    3 the norm over axis 0 alone (a head-major (H, D, dk) kernel is H rows of D * dk units: the reference as written); rank 4 over the
+    first three axes.  A higher rank raises, as the reference does."""
+    sh = tuple(int(v) for v in shape)
+    if len(sh) <= 1:
+        return int(np.prod(sh)), 1
+    if len(sh) in (2, 3):
+        return sh[0], int(np.prod(sh[1:]))
+    if len(sh) == 4:
+        return int(np.prod(sh[:3])), sh[3]
+    raise ValueError(f"Got a parameter with shape not in [1, 2, 4]! {sh}")
+
+
 class ComposedSeldNet:
     """models.seldnet(input_shape, model_config) (reference models.py:18-32) composed from module operators: FIRST = mother_block |
     mother_stage, SECOND = bidirectional_GRU_block (units 128: the recurrence kernels) | transformer_encoder_block | transformer_encoder_stage |
@@ -1883,7 +1897,16 @@ class ComposedSeldNet:
         self.set_weights(w, s)
 
     def close(self) -> None:
-        pass
+        """frees what the model holds outside torch's allocator: the v2 optimizer plan"""
+        plan, self._v2_plan = getattr(self, "_v2_plan", None), None
+        if plan is not None:
+            self.rt.lib.seld_v2_plan_destroy(plan)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
     # ---------------------------------------------------------------- measurement aid
     def profile(self, on: bool) -> None:
@@ -2027,6 +2050,89 @@ class ComposedSeldNet:
         sed, doa = self._forward(x, False)
         sloss, dloss = self._losses(sed, doa, ys, yd, cfg, False)
         return [sed, doa], sloss, dloss
+
+    # ---------------------------------------------------------------- the trainv2 recipe (trainv2.py:23-56, swa.py)
+    def set_regularized(self, flags) -> None:
+        """one flag per trainable variable: the variables the L2 kernel regulariser covers (trainv2.apply_kernel_regularizer sets them);
+        the optimizer plan is rebuilt at the next step when they changed"""
+        flags = [int(bool(f)) for f in flags]
+        if len(flags) != len(self.variables):
+            raise ValueError("set_regularized: one flag per trainable variable")
+        if flags != getattr(self, "_v2_flags", None):
+            self.close()
+            self._v2_flags = flags
+
+    def _v2_get_plan(self):
+        if getattr(self, "_v2_plan", None) is None:
+            nv = len(self.variables)
+            flags = getattr(self, "_v2_flags", None) or [0] * nv
+            rc = [v2_unit_shape(sh) for _, _, sh in self.variables]
+            plan = C.c_void_p()
+            self.rt.ck(self.rt.lib.seld_v2_plan_create(self.n_params, nv, (C.c_int64 * nv)(*[off for _, off, _ in self.variables]),
+                                                         (C.c_int32 * nv)(*[r for r, _ in rc]), (C.c_int32 * nv)(*[c for _, c in rc]),
+                                                         (C.c_int32 * nv)(*flags), C.byref(plan)))
+            self._v2_plan = plan
+        return self._v2_plan
+
+    def _v2_fwd_bwd(self, x, y, v2cfg):
+        """forward, the weighted losses (seld_v2_losses writes the heads' dpre), backward -> ([sed, doa], sloss, dloss); rt.grads holds
+        every variable's raw gradient"""
+        rt = self.rt
+        x = self._prep(x)
+        B = x.shape[0]
+        ys, yd = self._labels(y, B)
+        if self.n_classes > _lib.V2_MAX_CLASSES:
+            raise ValueError(f"the v2 losses take at most {_lib.V2_MAX_CLASSES} classes")
+        self._mark("step_start")
+        sed, doa = self._forward(x, True)
+        sloss = torch.empty((), dtype=torch.float32, device=self._dev)
+        dloss = torch.empty((), dtype=torch.float32, device=self._dev)
+        rt.ck(rt.lib.seld_v2_losses(rt.p(sed), rt.p(doa), rt.p(ys), rt.p(yd), C.byref(v2cfg), rt.p(sloss), rt.p(dloss), rt.p(self.heads[0].dpre),
+                                      rt.p(self.heads[1].dpre), rt.p(self.loss_scratch), B, self.S, self.n_classes, rt.st()))
+        self._mark("losses")
+        self._backward(B)
+        return [sed, doa], sloss, dloss
+
+    def _v2_opt(self, optimizer, l2: float = 0.0, clip_factor: float = 0.01):
+        """regulariser + AGC + AdaBelief on the flat buffers, two launches; the AdaBelief slots are the Adam slots, as on the fused path"""
+        rt = self.rt
+        plan = self._v2_get_plan()
+        self.adam_step += 1
+        rt.ck(rt.lib.seld_v2_opt(plan, rt.p(rt.params), rt.p(rt.grads), rt.p(rt.adam_m), rt.p(rt.adam_v), optimizer.learning_rate, optimizer.beta_1,
+                                   optimizer.beta_2, optimizer.epsilon, float(l2), float(clip_factor), self.adam_step, rt.st()))
+        self._mark("v2_opt")
+
+    def train_step_v2(self, x, y, v2cfg, optimizer, l2: float = 0.0, clip_factor: float = 0.01):
+        """trainv2.trainstep (trainv2.py:33-56) -> ([sed, doa], sloss, dloss); v2cfg: _lib.V2Cfg; no host synchronisation"""
+        if l2 < 0:
+            raise ValueError("l2 must be >= 0")
+        self._v2_get_plan()      # its one-time allocation and copies come before the step's first launch
+        out = self._v2_fwd_bwd(x, y, v2cfg)
+        self._v2_opt(optimizer, l2, clip_factor)
+        return out
+
+    @property
+    def swa_count(self) -> int:
+        return getattr(self, "_swa_cnt", 0)
+
+    def swa_update(self) -> None:
+        """swa.SWA.update_swa_weights (swa.py:25-32) over the weights and the BatchNormalization statistics; the buffers are allocated at the
+        first update"""
+        rt = self.rt
+        if getattr(self, "_swa_w", None) is None:
+            self._swa_w, self._swa_s, self._swa_cnt = rt.empty(max(self.n_params, 1)), rt.empty(max(self.n_state, 1)), 0
+        rt.ck(rt.lib.seld_v2_swa(rt.p(self._swa_w), rt.p(rt.params), self.n_params, self._swa_cnt, rt.st()))
+        if self.n_state:
+            rt.ck(rt.lib.seld_v2_swa(rt.p(self._swa_s), rt.p(rt.state), self.n_state, self._swa_cnt, rt.st()))
+        self._swa_cnt += 1
+
+    def swa_apply(self) -> None:
+        """swa.SWA.on_train_end: the averages become the model's weights and statistics"""
+        if self.swa_count == 0:
+            raise ValueError("swa_apply before the first swa_update")
+        self.rt.params[:self.n_params].copy_(self._swa_w[:self.n_params])
+        if self.n_state:
+            self.rt.state[:self.n_state].copy_(self._swa_s[:self.n_state])
 
 
 CHAIN_4D = ("mother_block", "mother_stage")

@@ -1,6 +1,8 @@
 """Host-side mirror of the reference's trainv2.py step functions (trainv2.py:23-66), utils.AdaBelief / apply_kernel_regularizer
 (utils.py:99-194, 343-350) and swa.SWA (swa.py).  The arithmetic — weighted losses, L2 regulariser, AGC, AdaBelief, the running
-average — runs in libseld_hip.so (seld_amd/csrc/trainv2.hip); these objects select and sequence it."""
+average — runs in libseld_hip.so (seld_amd/csrc/trainv2.hip); these objects select and sequence it.  Two kinds of model take the recipe: a
+fused context (models.SeldNet: the seld_*_v2 entry points) and a composed model (modules.ComposedSeldNet, models.conv_temporal's
+ConvTemporalNet among them: the stream operators seld_v2_losses / seld_v2_opt / seld_v2_swa on the model's flat buffers)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -11,6 +13,7 @@ import torch
 
 from . import _lib, losses, train
 from .models import SeldNet
+from .modules import ComposedSeldNet
 
 # "These are statistics from the train dataset" (trainv2.py:24-29): frames per class
 TRAIN_SAMPLES = (58193, 32794, 29801, 21478, 14822, 9174, 66527, 6740, 9342, 6498, 22218, 49758)
@@ -24,7 +27,8 @@ def default_cls_weights() -> np.ndarray:
 
 
 class AdaBelief:
-    """utils.AdaBelief(learning_rate) (utils.py:99-116; amsgrad is not built): the slots live in the HIP ctx, in the Adam slots."""
+    """utils.AdaBelief(learning_rate) (utils.py:99-116; amsgrad is not built): the slots are the model's Adam slots (the HIP ctx's, or a
+    composed model's flat buffers)."""
 
     def __init__(self, learning_rate: float = 1e-3, beta_1: float = 0.9, beta_2: float = 0.999, epsilon: float = 1e-7):
         self.learning_rate, self.beta_1, self.beta_2, self.epsilon = learning_rate, beta_1, beta_2, epsilon
@@ -38,13 +42,49 @@ def is_regularized(name: str) -> bool:
     return name.endswith(".kernel") and not name.startswith("gru")
 
 
-def apply_kernel_regularizer(model: SeldNet, l2: float = 0.001) -> SeldNet:
-    """utils.apply_kernel_regularizer(model, l1_l2(l1=0, l2=l2)) (trainv2.py:247, 289): marks the regularised variables in the ctx and
-    remembers l2 for the v2 trainstep.  Returns the model, as the reference does."""
-    if not isinstance(model, SeldNet):
-        raise ValueError("the v2 recipe is wired for models.seldnet / seldnet_v1 contexts, not composed models")
+_HEAD_MAJOR = ("query_kernel", "key_kernel", "value_kernel", "projection_kernel", "pos_kernel", "pos_bias_u", "pos_bias_v")
+_KERAS_MHA = ("query", "key", "value", "attention_output")
+
+
+def is_regularized_composed(name: str) -> bool:
+    """The same question for a composed model's variable names (modules.py; DESIGN.md §3i has the reasoning).  utils.apply_kernel_regularizer
+    sets the regulariser on every layer with a public `kernel_regularizer` attribute, so regularised are
+      * `*.kernel` of a Dense / Conv1D / Conv2D layer — the stem, the mother blocks' convolutions, projections and squeeze-and-excite
+        pair, the conformer's feed-forward, pointwise and depthwise (a grouped Conv1D) layers, the transformer's Conv1D pair, the dense
+        blocks, sed_out / doa_out — and the input `kernel` of a one-direction RNN_block (a bare GRU / LSTM layer has the attribute; its
+        recurrent_kernel reads recurrent_regularizer);
+      * the head-major attention layers' query_ / key_ / value_ / projection_kernel, pos_kernel, pos_bias_u and pos_bias_v
+        (layers.py:123, 150-175, 336-356 pass kernel_regularizer to all of them).
+    Not: biases, gamma / beta; everything under a Bidirectional wrapper (`.fwd.` / `.bwd.`: the wrapper has no such attribute); the Keras
+    MultiHeadAttention of transformer_encoder_block (`mha.query|key|value|attention_output.kernel`: it keeps the regulariser in a private
+    attribute under the TensorFlow the reference requires)."""
+    parts = name.split(".")
+    leaf = parts[-1]
+    if "fwd" in parts[:-1] or "bwd" in parts[:-1]:
+        return False
+    if leaf in _HEAD_MAJOR:
+        return True
+    if leaf != "kernel":
+        return False
+    return not (len(parts) >= 3 and parts[-3] == "mha" and parts[-2] in _KERAS_MHA)
+
+
+def _not_wired(what: str) -> ValueError:
+    return ValueError(f"{what} is wired for models.seldnet / seldnet_v1 contexts and for composed models (modules.ComposedSeldNet, "
+                      "models.conv_temporal), not for this object")
+
+
+def apply_kernel_regularizer(model, l2: float = 0.001):
+    """utils.apply_kernel_regularizer(model, l1_l2(l1=0, l2=l2)) (trainv2.py:247, 289): marks the regularised variables (in the ctx, or in
+    the composed model's optimizer plan) and remembers l2 for the v2 trainstep.  Returns the model, as the reference does."""
+    if not isinstance(model, (SeldNet, ComposedSeldNet)):
+        raise _not_wired("the v2 recipe")
     if l2 < 0:
         raise ValueError("l2 must be >= 0")
+    if isinstance(model, ComposedSeldNet):
+        model.set_regularized([is_regularized_composed(n) for n, _, _ in model.variables])
+        model._v2_l2 = float(l2)
+        return model
     flags = (C.c_int32 * len(model.variables))(*[int(is_regularized(n)) for n, _, _ in model.variables])
     _lib.check(model.lib.seld_set_regularized(model.ctx, flags, len(model.variables)), model.ctx)
     model._v2_l2 = float(l2)
@@ -83,8 +123,11 @@ def generate_trainstep(sed_loss, doa_loss, loss_weights, label_smoothing: float 
         w = default_cls_weights() if given is None else given
         if w.size != nc or nc > _lib.V2_MAX_CLASSES:
             raise ValueError(f"cls_weights has {w.size} entries, the model {nc} classes (at most {_lib.V2_MAX_CLASSES})")
+        if isinstance(model, ComposedSeldNet):
+            return model.train_step_v2(x, y, _v2_cfg(sed_loss, loss_weights, label_smoothing, w), optimizer, float(getattr(model, "_v2_l2", 0.0)),
+                                       CLIP_FACTOR)
         if not isinstance(model, SeldNet):
-            raise ValueError("the v2 trainstep is wired for models.seldnet / seldnet_v1 contexts; composed models are a follow-up")
+            raise _not_wired("the v2 trainstep")
         x = model._prep(x)
         B = x.shape[0]
         ys, yd = train._labels(model, y, B)
@@ -110,21 +153,26 @@ def generate_teststep(sed_loss, doa_loss):
         raise ValueError("doa_loss must be seld_amd.losses.MMSE_with_cls_weights")
 
     def teststep(model, x, y, optimizer=None):
+        if not isinstance(model, (SeldNet, ComposedSeldNet)):
+            raise _not_wired("the v2 test step")
         return train.teststep(model, x, y, sed_loss, losses.MMSE)
     return teststep
 
 
 class SWA:
-    """swa.SWA (swa.py): the running average lives in the HIP ctx (weights and BatchNorm moving statistics, as model.get_weights()
-    holds both)."""
+    """swa.SWA (swa.py): the running average lives in the HIP ctx, or in a composed model's own buffers (weights and BatchNorm moving
+    statistics, as model.get_weights() holds both)."""
 
-    def __init__(self, model: SeldNet, start_epoch: int, swa_freq: int = 2, verbose: bool = False):
-        if not isinstance(model, SeldNet):
-            raise ValueError("SWA is wired for models.seldnet / seldnet_v1 contexts")
+    def __init__(self, model, start_epoch: int, swa_freq: int = 2, verbose: bool = False):
+        if not isinstance(model, (SeldNet, ComposedSeldNet)):
+            raise _not_wired("SWA")
         self.model, self.start_epoch, self.swa_freq, self.verbose = model, start_epoch - 1, swa_freq, verbose
+        self._composed = isinstance(model, ComposedSeldNet)
 
     @property
     def cnt(self) -> int:
+        if self._composed:
+            return self.model.swa_count
         return int(self.model.lib.seld_swa_count(self.model.ctx))
 
     def on_epoch_end(self, epoch: int) -> None:
@@ -135,7 +183,11 @@ class SWA:
             self.update_swa_weights()
 
     def update_swa_weights(self) -> None:
+        if self._composed:
+            return self.model.swa_update()
         _lib.check(self.model.lib.seld_swa_update(self.model.ctx), self.model.ctx)
 
     def on_train_end(self) -> None:
+        if self._composed:
+            return self.model.swa_apply()
         _lib.check(self.model.lib.seld_swa_apply(self.model.ctx), self.model.ctx)

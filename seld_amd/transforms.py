@@ -10,9 +10,13 @@ flip ~ U{0,1}^3, swap ~ U{0,2}, acs index ~ U{0..7}) and only the small tables g
   acs_aug(x, y, rng)                                       transforms.py:159-207
   mic_gcc_perm(mic_perm)                                   transforms.py:122-140
   split_total_labels_to_sed_doa(x, y)                      transforms.py:117-119
+  random_ups_and_downs(x, rng)                             trainv2.py:120-124   one N(0, 0.2^2) shift per sample on the first 4 channels
+  v2_sample_transforms(x, rng, time, freq, period)         trainv2.py:133-140   that shift, 10 time masks and 6 frequency masks in ONE
+                                                                               pass (seld_aug_v2)
 mcs_aug (CGMM mask estimation in float64, transforms.py:237-292) is outside the accelerated path."""
 from __future__ import annotations
 
+import collections
 import ctypes as C
 
 import numpy as np
@@ -85,6 +89,83 @@ def mask(specs, axis, max_mask_size=None, period=100, n_mask=1, rng=None, draws=
         if rc:
             raise _lib.SeldError(f"seld_aug_mask failed ({rc})")
     return specs
+
+
+# seld_aug_v2 reads its tables where the host wrote them (pinned memory): they stay alive here until the kernel that reads them has run
+_v2_in_flight = collections.deque()
+UPS_AND_DOWNS_CHANNELS = 4      # trainv2.py:122: x[..., :4]
+UPS_AND_DOWNS_STDDEV = 0.2
+
+
+def _pinned(a, dtype):
+    """a host array -> a pinned tensor the device can read (one host copy)"""
+    a = np.ascontiguousarray(a, dtype)
+    t = torch.empty(a.shape, dtype=torch.float32 if dtype == np.float32 else torch.int32, pin_memory=True)
+    t.numpy()[...] = a
+    return t
+
+
+def draw_v2(rng, B, nseg, F, time=(6, 10), freq=(8, 6), period=100):
+    """the draws of one batch: (shift float32 [B], (t_size, t_off) int32 [n_t][B * nseg] each, (f_size, f_off) [n_f][B * nseg] each)"""
+    shift = (rng.standard_normal(B) * UPS_AND_DOWNS_STDDEV).astype(np.float32)
+    tm = [draw_mask(rng, B * nseg, period, time[0]) for _ in range(time[1])]
+    fm = [draw_mask(rng, B * nseg, F, freq[0]) for _ in range(freq[1])]
+    pack = lambda m, k: np.stack([d[k] for d in m]).astype(np.int32) if m else np.zeros((0, B * nseg), np.int32)
+    return shift, (pack(tm, 0), pack(tm, 1)), (pack(fm, 0), pack(fm, 1))
+
+
+def _aug_v2(x, shift, tmask, fmask, period):
+    x = _dev_tensor(x, "x")
+    if x.dim() != 4:
+        raise ValueError("x must be [B,T,F,C]")
+    B, T, F, Cc = x.shape
+    if T % period != 0:
+        raise ValueError("(spec time length / period)' rest must be 0")
+    N = B * (T // period)
+    keep, args = [], []
+    if shift is not None:
+        sh = _pinned(np.asarray(shift).reshape(B), np.float32)
+        keep.append(sh)
+    for m in (tmask, fmask):
+        size, off = (np.asarray(a).reshape(-1, N) for a in m) if m is not None else (np.zeros((0, N)), np.zeros((0, N)))
+        n = size.shape[0]
+        if n:
+            tab = _pinned(np.stack([off, size]), np.int32)       # [2][n][N]: one copy per axis
+            keep.append(tab)
+            args += [C.c_void_p(tab[0].data_ptr()), C.c_void_p(tab[1].data_ptr()), n]
+        else:
+            args += [None, None, 0]
+    rc = _lib.load().seld_aug_v2(_ptr(x), B, T, F, Cc, period, _ptr(sh) if shift is not None else None, min(UPS_AND_DOWNS_CHANNELS, Cc), *args,
+                                 _stream())
+    if rc:
+        raise _lib.SeldError(rc, "seld_aug_v2 refused its arguments")
+    while _v2_in_flight and _v2_in_flight[0][0].query():
+        _v2_in_flight.popleft()
+    if keep:
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(x.device))
+        _v2_in_flight.append((ev, keep))
+    return x
+
+
+def random_ups_and_downs(x, rng=None, draws=None):
+    """trainv2.random_ups_and_downs (trainv2.py:120-124) on a device batch [B,T,F,C], in place: one N(0, 0.2^2) float32 per sample added to
+    the first 4 channels.  `draws` = shift [B] overrides the generator (tests)."""
+    rng = rng or np.random.default_rng()
+    shift = draws if draws is not None else (rng.standard_normal(x.shape[0]) * UPS_AND_DOWNS_STDDEV).astype(np.float32)
+    return _aug_v2(x, shift, None, None, int(x.shape[1]))      # no masks: one segment per sample
+
+
+def v2_sample_transforms(x, rng=None, draws=None, time=(6, 10), freq=(8, 6), period=100):
+    """trainv2.get_dataset's sample transforms (trainv2.py:133-140) on a device batch [B,T,F,C], in place, in one kernel: random_ups_and_downs,
+    then mask(axis=-3, max_mask_size=time[0], n_mask=time[1]) and mask(axis=-2, max_mask_size=freq[0], n_mask=freq[1]).  The host makes the
+    draws (draw_v2) and writes three tables: the shifts, the time runs, the frequency runs.  `draws` = what draw_v2 returns (tests)."""
+    if x.dim() != 4 or x.shape[1] % period != 0:
+        raise ValueError("x must be [B,T,F,C] with (spec time length / period)' rest 0")
+    B, T, F, _ = x.shape
+    rng = rng or np.random.default_rng()
+    shift, tmask, fmask = draws if draws is not None else draw_v2(rng, B, T // period, F, time, freq, period)
+    return _aug_v2(x, shift, tmask, fmask, period)
 
 
 def _gather_sign(t, B, outer, R, inner, src, sgn):
