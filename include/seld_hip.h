@@ -334,6 +334,34 @@ int64_t seld_metrics_scratch_floats(int B, int S, int n_classes, int block_size)
 int seld_metrics_update(const float* sed_true, const float* doa_true, const float* sed_pred, const float* doa_pred, int B, int S,
                         int n_classes, int block_size, float doa_threshold, double* state, float* scratch, void* stream);
 
+/* ---- the segment-based, location-aware DCASE score on the device: SELDMetrics_.update_seld_scores
+ * (SELD_evaluation_metrics.py:63-154) with distance_between_cartesian_coordinates (:171-188), which trainv2.evaluate_fn
+ * (trainv2.py:195-237) reaches per file through a csv file, nested dicts and a Hungarian assignment per (frame, class).
+ * Inputs are concatenated over n_files files; file_off [n_files + 1] is a HOST array, file_off[0] = 0, strictly ascending,
+ * N = file_off[n_files].  A block_size-frame segment never spans two files; a file's last segment may be ragged.
+ *   sed [N, nc], doa [N, 3nc] fp32 (class c's vector: columns c, nc + c, 2nc + c); sed_thresh [nc] (active iff sed > thresh);
+ *   gt_xyz [N, nc, K, 3] fp64; gt_slot [N, nc, K] uint8: dense index (< SELD_DCASE_MAX_SLOTS) of the entry's track id among the
+ *   distinct ids of its (segment, class) in order of first appearance; gt_n [N, nc] int32 entries per (frame, class), 0..K.
+ * `state` = seld_dcase_state_size() doubles (device, zero to reset): TP FP FN S D I Nref total_DE DE_TP DE_FP DE_FN; the call
+ * adds to it.  `scratch` = seld_dcase_update_scratch_bytes(N, n_files, block_size) bytes (device, 8-byte aligned).  Two stages
+ * in a fixed order, no atomics: equal inputs give equal bits.  SELD_ERR_INVALID before the first HIP call for a NULL pointer,
+ * offsets that do not ascend from 0, nc < 1, K outside 1..SELD_DCASE_MAX_SLOTS, block_size outside 1..32, N nc > INT32_MAX.  The
+ * segment table is built on the host and copied once; the call waits for that copy, then returns with the kernels enqueued. */
+#define SELD_DCASE_MAX_SLOTS 8
+int seld_dcase_state_size(void);
+int64_t seld_dcase_update_scratch_bytes(int64_t N, int n_files, int block_size);
+int seld_dcase_update(const float* sed, const float* doa, const float* sed_thresh, const double* gt_xyz, const uint8_t* gt_slot,
+                      const int32_t* gt_n, const int32_t* file_off, int n_files, int n_classes, int K, int block_size, double doa_threshold,
+                      double* state, void* scratch, void* stream);
+/* the tf.where + gather of utils.write_answer (utils.py:249-264) for every file at once: the active (frame-in-file, class) pairs in
+ * row-major order, file after file, and class c's DOA vector beside each.  row_fc int32 [cap, 2], row_xyz fp32 [cap, 3] with
+ * cap = N nc; row_off int32 [n_files + 1]: file f's rows are [row_off[f], row_off[f + 1]).  All three on the device.  `scratch` =
+ * seld_answer_rows_scratch_bytes(N, n_files, nc) bytes.  An ordered compaction (count per chunk, scan, write) without atomics.  Same
+ * refusals and the same one copy (file_off) as seld_dcase_update. */
+int64_t seld_answer_rows_scratch_bytes(int64_t N, int n_files, int n_classes);
+int seld_answer_rows(const float* sed, const float* doa, const float* sed_thresh, const int32_t* file_off, int n_files, int n_classes,
+                     int32_t* row_fc, float* row_xyz, int32_t* row_off, void* scratch, void* stream);
+
 /* ---- measurement: HIP-event timing of named kernel groups on the ctx stream (bench.py roofline).
  * seld_profile_enable(ctx, level): 0 off, 1 the largest groups (conv1 fwd / conv1 wgrad / GRU fwd / GRU BPTT, the resnet stages), 2 every group,
  * 3 additionally one scope per product / BatchNorm launch of resnet50_block (hundreds of event pairs per step: a profile pass, not a timed one) */

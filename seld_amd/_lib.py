@@ -138,6 +138,11 @@ SIGNATURES = {
     "seld_metrics_state_size": (_I, [_I]),
     "seld_metrics_scratch_floats": (_L, [_I, _I, _I, _I]),
     "seld_metrics_update": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P]),
+    "seld_dcase_state_size": (_I, []),
+    "seld_dcase_update_scratch_bytes": (_L, [_L, _I, _I]),
+    "seld_dcase_update": (_I, [_P, _P, _P, _P, _P, _P, C.POINTER(C.c_int32), _I, _I, _I, _I, C.c_double, _P, _P, _P]),
+    "seld_answer_rows_scratch_bytes": (_L, [_L, _I, _I]),
+    "seld_answer_rows": (_I, [_P, _P, _P, C.POINTER(C.c_int32), _I, _I, _P, _P, _P, _P, _P]),
     "seld_profile_enable": (_I, [_P, _I]),
     "seld_profile_count": (_I, [_P]),
     "seld_profile_get": (_I, [_P, _I, C.c_char_p, _I, C.POINTER(_L), C.POINTER(C.c_double)]),

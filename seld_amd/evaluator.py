@@ -73,6 +73,27 @@ def ensemble_outputs(model: SeldNet, xs: list, win_size: int = 300, step_size: i
     return out
 
 
+def ensemble_models(models, xs: list, **kw):
+    """The model average of evaluator.py:88-103 and make_answer.py:125-140: the mean over `models` of ensemble_outputs(model, xs, **kw),
+    file by file, accumulated on the device (seld_m_axpy with alpha = 1 / len(models) into a zeroed pair) -> [(sed, doa), ...]."""
+    models = list(models)
+    if not models:
+        raise ValueError("ensemble_models: no models")
+    alpha = 1.0 / len(models)
+    acc = None
+    for model in models:
+        outs = ensemble_outputs(model, xs, **kw)
+        if acc is None:
+            acc = [(torch.zeros_like(s), torch.zeros_like(d)) for s, d in outs]
+        st = C.c_void_p(torch.cuda.current_stream(model._dev).cuda_stream)
+        for (a_s, a_d), (s, d) in zip(acc, outs):
+            if a_s.shape != s.shape or a_d.shape != d.shape or a_s.device != s.device:
+                raise ValueError("ensemble_models: the models' outputs differ in shape or device")
+            _lib.check(model.lib.seld_m_axpy(a_s.data_ptr(), s.data_ptr(), a_s.numel(), alpha, st))
+            _lib.check(model.lib.seld_m_axpy(a_d.data_ptr(), d.data_ptr(), a_d.numel(), alpha, st))
+    return acc
+
+
 def load_conv_temporal_model(input_shape, model_config, weights, device=None):
     """reference load_conv_temporal_model (evaluator.py:53-58): `model_config` is the path of a JSON settings file (model_config/SS5.json),
     `weights` a file in the format load_weights reads (an .npz keyed by variable name); ensemble_outputs takes the model it returns"""

@@ -2,7 +2,11 @@
 (utils.py:99-194, 343-350) and swa.SWA (swa.py).  The arithmetic — weighted losses, L2 regulariser, AGC, AdaBelief, the running
 average — runs in libseld_hip.so (seld_amd/csrc/trainv2.hip); these objects select and sequence it.  Two kinds of model take the recipe: a
 fused context (models.SeldNet: the seld_*_v2 entry points) and a composed model (modules.ComposedSeldNet, models.conv_temporal's
-ConvTemporalNet among them: the stream operators seld_v2_losses / seld_v2_opt / seld_v2_swa on the model's flat buffers)."""
+ConvTemporalNet among them: the stream operators seld_v2_losses / seld_v2_opt / seld_v2_swa on the model's flat buffers).
+
+Around the step: get_dataset (trainv2.py:127-155), generate_iterloop (:69-117), generate_evaluate_fn (:195-237; the DCASE score of the
+sliding-window outputs on the device, SELD_evaluation_metrics.SELDMetrics_) and main (:240-369):
+    python -m seld_amd.trainv2 --name x --model conv_temporal --model_config SS5 --abspath DATA/ --ans_path METADATA_DEV/"""
 from __future__ import annotations
 
 import ctypes as C
@@ -191,3 +195,202 @@ class SWA:
         if self._composed:
             return self.model.swa_apply()
         _lib.check(self.model.lib.seld_swa_apply(self.model.ctx), self.model.ctx)
+
+
+# ---------------------------------------------------------------------------------------------------
+WIN_SIZE, STEP_SIZE = 300, 5      # ensemble_outputs' defaults (trainv2.py:158-159): 300-frame windows every 5 frames, one label frame per 5
+
+
+def get_dataset(config, mode: str = 'train', device=None):
+    """reference trainv2.get_dataset (trainv2.py:127-155).  --use_tfm: random_ups_and_downs, ten time masks and six frequency masks in one
+    kernel (transforms.v2_sample_transforms); --use_acs: foa_intensity_vec_aug — both on the device batch of the train set, in the
+    reference's order, applied by the step loop as train.get_dataset wires its transforms.  `device`: keep the windowed dataset in that
+    GPU's HBM."""
+    import os
+    from . import data_loader as dl, transforms as tfm
+    path = os.path.join(config.abspath, 'DCASE2021/feat_label/')
+    x, y = dl.load_seldnet_data(os.path.join(path, 'foa_dev_norm'), os.path.join(path, 'foa_dev_label'), mode=mode, n_freq_bins=64)
+    device_transforms = []
+    if getattr(config, 'use_tfm', False) and mode == 'train':
+        device_transforms.append(lambda x, y, rng: (tfm.v2_sample_transforms(x, rng=rng), y))
+    if getattr(config, 'use_acs', False) and mode == 'train':
+        device_transforms.append(lambda x, y, rng: tfm.foa_intensity_vec_aug(x, y, rng=rng))
+    ds = dl.seldnet_data_to_dataloader(x, y, train=mode == 'train', label_window_size=60, batch_size=config.batch,
+                                       loop_time=config.loop_time, device_transforms=device_transforms)
+    return ds.to_device(device) if device is not None else ds
+
+
+def generate_iterloop(sed_loss, doa_loss, evaluator, mode, loss_weights=None, label_smoothing=0.):
+    """reference trainv2.generate_iterloop (trainv2.py:69-117) -> iterloop(model, dataset, epoch, optimizer=None) -> (mean sed loss, mean
+    doa loss, seld score).  `evaluator` (seld_amd.metrics.SELDMetrics) is reset, then updated on the device after every step; the losses
+    are summed on the device: one host synchronisation per epoch.  The progress bar and the tensorboard writer are left out."""
+    from . import metrics as _metrics
+    if mode == 'train':
+        if loss_weights is None:
+            raise ValueError("the train loop needs loss_weights")
+        step = generate_trainstep(sed_loss, doa_loss, loss_weights, label_smoothing)
+    else:
+        step = generate_teststep(sed_loss, doa_loss)
+
+    def iterloop(model, dataset, epoch, optimizer=None):
+        evaluator.reset_states()
+        tot_s = torch.zeros((), device=model._dev)
+        tot_d = torch.zeros((), device=model._dev)
+        n = 0
+        dev_tf = getattr(dataset, 'device_transforms', None)
+        for x, y in dataset:
+            if dev_tf:        # augmentation on the device batch; labels arrive unsplit [b,60,4C] (data_loader.SeldDataset)
+                x = torch.as_tensor(x, dtype=torch.float32).to(model._dev).contiguous()
+                y = torch.as_tensor(y, dtype=torch.float32).to(model._dev).contiguous()
+                for f in dev_tf:
+                    x, y = f(x, y, dataset.rng)
+                nc = y.shape[-1] // 4
+                y = (y[..., :nc].contiguous(), y[..., nc:].contiguous())
+            preds, sloss, dloss = step(model, x, y, optimizer)
+            evaluator.update_states(y, preds)
+            tot_s += sloss
+            tot_d += dloss.mean()
+            n += 1
+        score = _metrics.calculate_seld_score(evaluator.result())
+        return float(tot_s.item()) / max(n, 1), float(tot_d.item()) / max(n, 1), score
+    return iterloop
+
+
+def _label_frames(n_frames: int, win_size: int = WIN_SIZE, step_size: int = STEP_SIZE) -> int:
+    """label frames ensemble_outputs returns for a clip of n_frames feature frames: (windows - 1) + win_size // step_size"""
+    return (n_frames - win_size) // step_size + win_size // step_size
+
+
+def generate_evaluate_fn(test_xs, test_labels, write_path, ans_path=None, batch_size=256, doa_threshold=20, nb_classes=12):
+    """reference trainv2.generate_evaluate_fn (trainv2.py:195-237) -> evaluate_fn(model, epoch) -> (seld_score, (ER, F, LE, LR)).
+
+    evaluate_fn: ensemble_outputs on every test clip, then — when `write_path` is not None — utils.write_answer of `sed > 0.5` per file,
+    then ONE SELDMetrics_.update_seld_scores over all files (the reference scores file by file from the csv it has just written), then
+    compute_seld_scores and metrics.calculate_seld_score.  The reference's SELDMetrics_() keeps its default of 11 classes and so never looks
+    at the twelfth; `nb_classes` is explicit here.
+
+    Ground truth, with `ans_path`: as trainv2.py:202-213 reads it — sorted `ans_path/dev-test/*`, the files whose name carries fold digit 6
+    at index 4, polar -> cartesian, paired by position with `test_xs` (the two lists must be equally long, which the reference does not
+    check).  Without it, `test_labels` holds the already loaded cartesian dicts.  Either way the labels are packed once, here."""
+    import os
+    from glob import glob
+    from . import utils
+    if ans_path is not None:
+        files = sorted(glob(os.path.join(ans_path, 'dev-test', '*')))
+        files = [f for f in files if int(os.path.basename(f)[4]) in [6]]
+        names = [os.path.splitext(os.path.basename(f))[0] for f in files]
+        dicts = [utils.convert_output_format_polar_to_cartesian(utils.load_output_format_file(f)) for f in files]
+    else:
+        if test_labels is None:
+            raise ValueError("generate_evaluate_fn needs ans_path or the loaded label dicts")
+        dicts = list(test_labels)
+        names = [f'fold6_file{i:03d}' for i in range(len(dicts))]
+    if len(dicts) != len(test_xs):
+        raise AssertionError(f"{len(test_xs)} test clips but {len(dicts)} label files: they are paired by position")
+    packed = utils.concat_labels([utils.pack_labels(d, _label_frames(int(np.shape(x)[0])), nb_classes) for d, x in zip(dicts, test_xs)])
+
+    def evaluate_fn(model, epoch):
+        from . import evaluator as _evaluator, metrics as _metrics
+        from .SELD_evaluation_metrics import SELDMetrics_
+        e_outs = _evaluator.ensemble_outputs(model, test_xs, win_size=WIN_SIZE, step_size=STEP_SIZE, batch_size=batch_size)
+        if write_path is not None:
+            os.makedirs(write_path, exist_ok=True)
+            for name, (sed, doa) in zip(names, e_outs):
+                utils.write_answer(write_path, name + '.csv', sed > 0.5, doa)
+        seld_ = SELDMetrics_(doa_threshold=doa_threshold, nb_classes=nb_classes, device=model._dev)
+        seld_.update_seld_scores(e_outs, packed, sed_thresh=0.5)
+        metric_values = seld_.compute_seld_scores()
+        seld_score = float(_metrics.calculate_seld_score(metric_values))
+        er, f, der, derf = metric_values
+        print(f'ensemble outputs (epoch {epoch})  ER: {er:4f}, F: {f:4f}, DER: {der:4f}, DERF: {derf:4f}, SELD: {seld_score:4f}')
+        return seld_score, metric_values
+    evaluate_fn.names = names
+    return evaluate_fn
+
+
+def main(config, model_config=None, max_epochs=None, swa_start_epoch=80, swa_freq=2, eval_every=10, l2=0.001, label_smoothing=0.):
+    """reference trainv2.main (trainv2.py:240-369): datasets, a model with n_classes = 12 built for the largest batch any pass uses, L2
+    flags, AdaBelief, BCE + MMSE_with_cls_weights, SWA, `--resume` from the saved .npz weights, then per epoch: halve the learning rate at
+    `swa_start_epoch`, evaluate_fn every `eval_every` epochs, the train / val / test loops, swa.on_epoch_end, best model by validation
+    score, early stop on config.patience (the reference's LR-on-plateau block is commented out and is left out); at the end
+    swa.on_train_end(), a last evaluate_fn and `SWA_best_{score:.5f}.npz`.  -> (model, history)."""
+    import os
+    from . import data_loader as dl, metrics as _metrics, models
+    if isinstance(config, tuple):
+        config, model_config = config
+    if config.sed_loss != 'BCE':
+        raise ValueError("trainv2.main: sed_loss must be 'BCE' (generate_teststep has no focal test kernel)")
+    if model_config is None:
+        raise ValueError("trainv2.main needs the model configuration")
+    if not callable(getattr(models, config.model, None)) or config.model.startswith('_'):
+        raise ValueError(f"seld_amd.models has no model {config.model!r}")
+    if swa_freq < 1 or eval_every < 1 or swa_start_epoch < 1:
+        raise ValueError("swa_start_epoch, swa_freq and eval_every must be at least 1")
+    loss_weights = [int(i) for i in config.loss_weight.split(',')]
+    if len(loss_weights) != 2:
+        raise ValueError("--loss_weight takes two comma-separated integers")
+    n_classes = 12                                                  # trainv2.py:244
+    dev = torch.device('cuda', torch.cuda.current_device())
+    trainset, valset, testset = (get_dataset(config, m, dev) for m in ('train', 'val', 'test'))      # HBM-resident
+    path = os.path.join(config.abspath, 'DCASE2021/feat_label/')
+    test_xs, _ = dl.load_seldnet_data(os.path.join(path, 'foa_dev_norm'), os.path.join(path, 'foa_dev_label'), mode='test', n_freq_bins=64)
+    x, y = next(iter(trainset.take(1)))
+    input_shape = (max(config.batch, valset.batch_size, testset.batch_size),) + tuple(x.shape[1:])
+    model_config = dict(model_config)
+    model_config['n_classes'] = n_classes
+    model = getattr(models, config.model)(input_shape, model_config)
+    model.summary()
+    model = apply_kernel_regularizer(model, l2)
+    optimizer = AdaBelief(config.lr)
+    sed_loss = losses.BinaryCrossentropy()
+    doa_loss = losses.MMSE_with_cls_weights                         # trainv2.py:296-297
+    swa = SWA(model, swa_start_epoch, swa_freq)
+    model_path = os.path.join('./saved_model', config.name)
+    os.makedirs(model_path, exist_ok=True)
+    if getattr(config, 'resume', False):                           # trainv2.py:302-306: the saved model's weights
+        from glob import glob
+        saved = sorted(glob(os.path.join(model_path, '*.npz')))
+        if len(saved) == 0:
+            raise ValueError('the model does not exist, cannot be resumed')
+        model.load_weights(saved[0])
+    evaluator = _metrics.SELDMetrics(doa_threshold=config.lad_doa_thresh, n_classes=n_classes)
+    train_iterloop = generate_iterloop(sed_loss, doa_loss, evaluator, 'train', loss_weights=loss_weights, label_smoothing=label_smoothing)
+    val_iterloop = generate_iterloop(sed_loss, doa_loss, evaluator, 'val')
+    test_iterloop = generate_iterloop(sed_loss, doa_loss, evaluator, 'test')
+    evaluate_fn = generate_evaluate_fn(test_xs, None, config.output_path, config.ans_path, config.batch * 4,
+                                       doa_threshold=config.lad_doa_thresh, nb_classes=n_classes)
+    best, early, history, epoch = float('inf'), 0, [], 0
+    for epoch in range(config.epoch if max_epochs is None else min(config.epoch, max_epochs)):
+        if epoch == swa_start_epoch:
+            optimizer.learning_rate = config.lr * 0.5              # trainv2.py:325-326
+        ev = evaluate_fn(model, epoch) if epoch % eval_every == 0 else None
+        tr = train_iterloop(model, trainset, epoch, optimizer)
+        va = val_iterloop(model, valset, epoch)
+        te = test_iterloop(model, testset, epoch)
+        score = va[2]
+        swa.on_epoch_end(epoch)
+        history.append({'epoch': epoch, 'train': tr, 'val': va, 'test': te, 'score': score, 'lr': optimizer.learning_rate, 'eval': ev})
+        print(f'epoch {epoch}: train sed/doa/seld {tr[0]:.4f}/{tr[1]:.5f}/{tr[2]:.4f}  val {va[0]:.4f}/{va[1]:.5f}/{va[2]:.4f}'
+              f'  test {te[0]:.4f}/{te[1]:.5f}/{te[2]:.4f}')
+        if best > score:                                            # trainv2.py:338-346
+            old = os.path.join(model_path, f'bestscore_{best}.npz')
+            if os.path.exists(old):
+                os.remove(old)
+            best, early = score, 0
+            model.save_weights(os.path.join(model_path, f'bestscore_{best}.npz'))
+        else:                                                       # trainv2.py:347-358
+            if early == config.patience:
+                print(f'Early Stopping at {epoch}, score is {score}')
+                break
+            early += 1
+    print(f'epoch: {epoch}')
+    if swa.cnt > 0:
+        swa.on_train_end()
+    seld_score, _ = evaluate_fn(model, epoch)
+    model.save_weights(os.path.join(model_path, f'SWA_best_{seld_score:.5f}.npz'))
+    return model, history
+
+
+if __name__ == '__main__':
+    from . import params
+    main(params.get_param())
