@@ -130,10 +130,12 @@ int seld_sync(seld_ctx* ctx);
  * 0 selects the f32-input MFMA kernels.  "gemm_split_bf16" (default 1): the same scheme for the GRU input projections,
  * the heads' first Conv1D and their input gradients (gemm_sb.hip) where K % 32 == 0 and N % 128 == 0; 0 keeps them on
  * the f32-input MFMA GEMM.  "conv1_split_bf16" (default 1): the same scheme for the first
- * block's forward whenever its pre-BN tensor is not stored (conv_pool_sb.hip).  "conv1_pool_fused" / "conv1_gram" (default 1): first block's pooling inside the conv
+ * block's forward whenever its pre-BN tensor is not stored (conv_pool_sb.hip).  "conv1_pingpong" (default 1): that kernel for 7 input channels as one
+ * 8-wave workgroup per CU whose two wave groups alternate matrix and vector segments (the same bits; 0: the 4-wave kernel, which 10 channels
+ * always take).  "conv1_pool_fused" / "conv1_gram" (default 1): first block's pooling inside the conv
  * epilogue / its kernel gradient from the patch Gram matrix.  "dropout_seed" / "dropout_step" (values): the key of the heads' dropout
  * draws and the step counter of the next training forward (seld_arch.sed_dropout / doa_dropout; INTEGRATION.md section 6 lists every key).
- * EVERY key is per context: the kernel choices ("bwd_four_products", "dgrad_r8", "tn_tile_blocks", "gram_bg_blocks",
+ * EVERY key is per context: the kernel choices ("bwd_four_products", "dgrad_r8", "conv1_pingpong", "tn_tile_blocks", "gram_bg_blocks",
  * "bf16_single", ...) are stored in the context and handed to every kernel launch of its passes as an argument, so a six-product
  * context and a four-product context coexist in one process, from one host thread or from two
  * (calls on one context are not thread-safe). */

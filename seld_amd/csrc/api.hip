@@ -506,6 +506,7 @@ int seld_set_option(seld_ctx* c, const char* key, int value) {
     if (!strcmp(key, "tn_tile_blocks") && value >= 64 && value <= 4096) { c->kc.tn_tile_blocks = value; return SELD_OK; }     // gemm_tn_sb.hip
     if (!strcmp(key, "conv_wgrad_side")) { c->conv_wgrad_side = value != 0; return SELD_OK; }
     if (!strcmp(key, "dgrad_r8")) { c->kc.dgrad_r8 = value != 0; return SELD_OK; }
+    if (!strcmp(key, "conv1_pingpong")) { c->kc.conv1_pingpong = value != 0; return SELD_OK; }
     if (!strcmp(key, "prep_side")) { c->prep_side = value != 0; return SELD_OK; }
     if (!strcmp(key, "xc_nowait")) { c->xc_nowait = value != 0; return SELD_OK; }
     if (!strcmp(key, "xc_fused_bn_sums")) { c->xc_fused_bn_sums = value != 0; return SELD_OK; }

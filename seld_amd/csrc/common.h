@@ -90,6 +90,8 @@ struct KernelChoices {
     int dgrad_r8 = 1;          // option "dgrad_r8" (conv_sb.hip): the W = 16 four-product input gradient on 8-row tiles (4 waves, 74 KB of LDS instead of 8 waves, 107 KB: two
                                // workgroups per CU, or one beside a kernel-gradient workgroup of the side stream; the same taps and k-steps per pixel: the same bits;
                                // round 5: 2.510 -> 2.496 ms per step same box)
+    int conv1_pingpong = 1;    // option "conv1_pingpong" (conv_pool_sb.hip): the z-free first-block forward for Cin = 7 as ONE 8-wave workgroup per CU whose two wave groups alternate
+                               // matrix and vector segments (same bits; Cin = 10 keeps the 4-wave kernel; profiles/conv1_pingpong.json: 2.538 -> 2.500 ms per step same box)
     int tn_tile_blocks = 384;  // gemm_tn_sb.hip tile mode: workgroups per launch the split count aims at (option "tn_tile_blocks"; resnet50_gru same box: 14.709 / 14.752 ms per
                                // step at 768, 14.646 at 384, 14.691 at 512, 14.87 at 256 and 1024)
     int gram_bg_blocks = 192;  // conv_gram.hip: workgroups of a background launch

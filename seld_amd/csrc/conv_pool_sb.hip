@@ -13,8 +13,14 @@
 // conv_first_fwd_pool_kernel<CIN, false, *>: tile = 10 image rows x 64 bins, wave = pooling row (w >> 1) x 32-bin strip
 // (w & 1), 5 row tiles x 2 channel halves = 10 accumulator tiles that share the 6 weight fragments of a k-step.
 // The patch (3 bf16 planes [12][66][CP]) is single-buffered: two workgroups share a CU and cover each other's staging.
+//
+// Two kernels: conv_first_fwd_pool_sb_kernel (4 waves, two workgroups per CU, each wave runs a tile's MFMAs and then its vector epilogue) and, for
+// CIN = 7 and by default (option "conv1_pingpong"), conv_first_fwd_pool_sbpp_kernel: one 8-wave workgroup per CU whose two wave groups alternate
+// matrix and vector segments across workgroup barriers, with the matrix segment software-pipelined over its LDS reads.  Same tiles per (virtual)
+// workgroup in the same order, same MFMA order per accumulator: the same bits.  The schedule arithmetic is conv1_pp_sched.h.
 #include "common.h"
 #include "sb_tile.h"
+#include "conv1_pp_sched.h"
 
 #define CPSB_MAX_PERSISTENT 512
 
@@ -35,28 +41,13 @@ struct PoolSbGeom {
     static constexpr size_t SMEM = (size_t)(3 * PLANE + 3 * WPLANE) * 2 + 512 * sizeof(float);
 };
 
-// ONE: bf16 single-product mode (common.h KernelChoices::mfma_one): operands rounded to nearest bf16, plane 0 only, one MFMA per (k-step, row, half)
-template <int CIN, bool WRITE_AMAX, bool ONE>
-__global__ __launch_bounds__(256, (CIN < 8 ? 2 : 1)) void conv_first_fwd_pool_sb_kernel(const float* __restrict__ x, const float* __restrict__ w,
-                                                                        const float* __restrict__ bias,
-                                                                        const float* __restrict__ gamma, float* __restrict__ zext,
-                                                                        unsigned char* __restrict__ amax,
-                                                                        float* __restrict__ stat_partial, int B, int H) {
+// weights: w [9*CIN][64] fp32 (k = tap*CIN + c) -> planes [co][tap*CP + c] of the (zeroed) Wl; bias on (centre tap, slot CIN).  NT threads.
+template <int CIN, bool ONE, int NT>
+__device__ __forceinline__ void cpsb_stage_weights(unsigned short* Wl, const float* __restrict__ w, const float* __restrict__ bias,
+                                                   const float* __restrict__ gamma, int tid) {
     using G = PoolSbGeom<CIN>;
-    constexpr int CP = G::CP, NS = G::NS, KW = G::KW, PLANE = G::PLANE, WPLANE = G::WPLANE;
-    extern __shared__ __attribute__((aligned(16))) unsigned short cpsb_smem[];
-    unsigned short* patch = cpsb_smem;                 // [3][12][66][CP]
-    unsigned short* Wl = patch + 3 * PLANE;            // [3][64][KW]
-    float* red = reinterpret_cast<float*>(Wl + 3 * WPLANE);   // [4][128]
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int kg = lane >> 5, li = lane & 31;
-    const int grp = wave >> 1, strip = wave & 1;
-    // ---- weights: w [9*CIN][64] fp32 (k = tap*CIN + c) -> planes [co][tap*CP + c]; bias on (centre tap, slot CIN)
-    for (int idx = tid; idx < 3 * WPLANE / 2; idx += 256) reinterpret_cast<unsigned*>(Wl)[idx] = 0u;
-    for (int idx = tid; idx < 3 * PLANE / 2; idx += 256) reinterpret_cast<unsigned*>(patch)[idx] = 0u;   // halo columns stay zero
-    __syncthreads();
-    for (int idx = tid; idx < (9 * CIN + 1) * 64; idx += 256) {
+    constexpr int CP = G::CP, KW = G::KW, WPLANE = G::WPLANE;
+    for (int idx = tid; idx < (9 * CIN + 1) * 64; idx += NT) {
         const int k = idx >> 6, co = idx & 63;
         const bool isb = k == 9 * CIN;
         // output channels with gamma < 0 are computed NEGATED (weights and bias): their window extreme is then a maximum like
@@ -75,6 +66,29 @@ __global__ __launch_bounds__(256, (CIN < 8 ? 2 : 1)) void conv_first_fwd_pool_sb
         o[WPLANE] = (unsigned short)(vv >> 16);
         o[2 * WPLANE] = (unsigned short)(__float_as_uint(s) >> 16);
     }
+}
+
+// ONE: bf16 single-product mode (common.h KernelChoices::mfma_one): operands rounded to nearest bf16, plane 0 only, one MFMA per (k-step, row, half)
+template <int CIN, bool WRITE_AMAX, bool ONE>
+__global__ __launch_bounds__(256, (CIN < 8 ? 2 : 1)) void conv_first_fwd_pool_sb_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                                        const float* __restrict__ bias,
+                                                                        const float* __restrict__ gamma, float* __restrict__ zext,
+                                                                        unsigned char* __restrict__ amax,
+                                                                        float* __restrict__ stat_partial, int B, int H) {
+    using G = PoolSbGeom<CIN>;
+    constexpr int CP = G::CP, NS = G::NS, KW = G::KW, PLANE = G::PLANE, WPLANE = G::WPLANE;
+    extern __shared__ __attribute__((aligned(16))) unsigned short cpsb_smem[];
+    unsigned short* patch = cpsb_smem;                 // [3][12][66][CP]
+    unsigned short* Wl = patch + 3 * PLANE;            // [3][64][KW]
+    float* red = reinterpret_cast<float*>(Wl + 3 * WPLANE);   // [4][128]
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int kg = lane >> 5, li = lane & 31;
+    const int grp = wave >> 1, strip = wave & 1;
+    for (int idx = tid; idx < 3 * WPLANE / 2; idx += 256) reinterpret_cast<unsigned*>(Wl)[idx] = 0u;
+    for (int idx = tid; idx < 3 * PLANE / 2; idx += 256) reinterpret_cast<unsigned*>(patch)[idx] = 0u;   // halo columns stay zero
+    __syncthreads();
+    cpsb_stage_weights<CIN, ONE, 256>(Wl, w, bias, gamma, tid);
     // gamma < 0: the window extreme that survives BN+ReLU+MaxPool is the minimum of z -> flip the sign, take the maximum
     const unsigned smask[2] = {gamma[li] < 0.f ? 0x80000000u : 0u, gamma[32 + li] < 0.f ? 0x80000000u : 0u};
     const int tiles_per_img = (H + 9) / 10;
@@ -179,6 +193,38 @@ __global__ __launch_bounds__(256, (CIN < 8 ? 2 : 1)) void conv_first_fwd_pool_sb
         s1p[c_] += y2;                                                                                  \
         s2p[c_] = __builtin_elementwise_fma(y2, y2, s2p[c_]);                                           \
     }
+    // the matrix segment of a tile: NS k-steps x 5 rows into the ten accumulator tiles accA0 .. accB4.
+    // p8o: elements 2 s, 2 s + 1 of the tap-8 pixel.  The offset is laundered through an empty asm: seen as consecutive, the four k-steps' dwords
+    // were merged into one ds_read_b128 per (row, plane) that stayed live for the whole tile — 60 registers, 84 spill instructions, 462 us.
+    // psel: tap 7 keeps its 1.0 (the bias).  bm / bl: unused in single-product mode.
+#define CPSB_TILE_MFMA()                                                                                \
+    _Pragma("unroll") for (int s = 0; s < NS; ++s) {                                                    \
+        const unsigned short* pa = pbase + (kg ? CPSB_AOFF(s, 1) : CPSB_AOFF(s, 0));                    \
+        int p8o = 2 * s;                                                                                \
+        asm volatile("" : "+s"(p8o));                                                                   \
+        const unsigned short* p8 = pbase + (2 * 66 + 2) * CP + p8o;                                     \
+        const unsigned psel = s == 3 ? (kg ? 0x03020100u : 0x05040100u) : (kg ? 0x07060100u : 0x05040100u); \
+        const unsigned short* wp = wbase + 16 * s;                                                      \
+        const bf16x8 bh0 = *reinterpret_cast<const bf16x8*>(wp), bh1 = *reinterpret_cast<const bf16x8*>(wp + 32 * KW); \
+        bf16x8 bm0 = bh0, bm1 = bh1, bl0 = bh0, bl1 = bh1;                                              \
+        if (!ONE) {                                                                                     \
+            bm0 = *reinterpret_cast<const bf16x8*>(wp + WPLANE); bm1 = *reinterpret_cast<const bf16x8*>(wp + WPLANE + 32 * KW); \
+            bl0 = *reinterpret_cast<const bf16x8*>(wp + 2 * WPLANE); bl1 = *reinterpret_cast<const bf16x8*>(wp + 2 * WPLANE + 32 * KW); \
+        }                                                                                               \
+        CPSB_ROW(0, accA0, accB0)                                                                       \
+        CPSB_ROW(1, accA1, accB1)                                                                       \
+        CPSB_ROW(2, accA2, accB2)                                                                       \
+        CPSB_ROW(3, accA3, accB3)                                                                       \
+        CPSB_ROW(4, accA4, accB4)                                                                       \
+    }
+    // the vector segment of a live pooling row: statistics, then the window extremes and their positions
+#define CPSB_TILE_DRAIN()                                                                               \
+    {                                                                                                   \
+        CPSB_STATS(0, accA0) CPSB_STATS(0, accA1) CPSB_STATS(0, accA2) CPSB_STATS(0, accA3) CPSB_STATS(0, accA4) \
+        CPSB_STATS(1, accB0) CPSB_STATS(1, accB1) CPSB_STATS(1, accB2) CPSB_STATS(1, accB3) CPSB_STATS(1, accB4) \
+        _Pragma("unroll") for (int r = 0; r < 16; ++r) CPSB_DRAIN(r, 0, accA0, accA1, accA2, accA3, accA4) \
+        _Pragma("unroll") for (int r = 0; r < 16; ++r) CPSB_DRAIN(r, 1, accB0, accB1, accB2, accB3, accB4) \
+    }
     for (; tile < ntiles; tile += gridDim.x) {
         const int b = tile / tiles_per_img, t0 = (tile - b * tiles_per_img) * 10;
         const int nxt = tile + gridDim.x;
@@ -191,50 +237,13 @@ __global__ __launch_bounds__(256, (CIN < 8 ? 2 : 1)) void conv_first_fwd_pool_sb
         int bpos = 0;
         f32x16 accA0 = zero16(), accA1 = zero16(), accA2 = zero16(), accA3 = zero16(), accA4 = zero16();
         f32x16 accB0 = zero16(), accB1 = zero16(), accB2 = zero16(), accB3 = zero16(), accB4 = zero16();
-#pragma unroll
-        for (int s = 0; s < NS; ++s) {
-            const unsigned short* pa = pbase + (kg ? CPSB_AOFF(s, 1) : CPSB_AOFF(s, 0));
-            // elements 2 s, 2 s + 1 of the tap-8 pixel.  The offset is laundered through an empty asm: seen as consecutive, the four k-steps' dwords
-            // were merged into one ds_read_b128 per (row, plane) that stayed live for the whole tile — 60 registers, 84 spill instructions, 462 us
-            int p8o = 2 * s;
-            asm volatile("" : "+s"(p8o));
-            const unsigned short* p8 = pbase + (2 * 66 + 2) * CP + p8o;
-            const unsigned psel = s == 3 ? (kg ? 0x03020100u : 0x05040100u) : (kg ? 0x07060100u : 0x05040100u);   // tap 7 keeps its 1.0 (the bias)
-            const unsigned short* wp = wbase + 16 * s;
-            const bf16x8 bh0 = *reinterpret_cast<const bf16x8*>(wp), bh1 = *reinterpret_cast<const bf16x8*>(wp + 32 * KW);
-            bf16x8 bm0 = bh0, bm1 = bh1, bl0 = bh0, bl1 = bh1;       // (single-product mode: unused)
-            if (!ONE) {
-                bm0 = *reinterpret_cast<const bf16x8*>(wp + WPLANE); bm1 = *reinterpret_cast<const bf16x8*>(wp + WPLANE + 32 * KW);
-                bl0 = *reinterpret_cast<const bf16x8*>(wp + 2 * WPLANE); bl1 = *reinterpret_cast<const bf16x8*>(wp + 2 * WPLANE + 32 * KW);
-            }
-            CPSB_ROW(0, accA0, accB0)
-            CPSB_ROW(1, accA1, accB1)
-            CPSB_ROW(2, accA2, accB2)
-            CPSB_ROW(3, accA3, accB3)
-            CPSB_ROW(4, accA4, accB4)
-        }
-        if (live) {
-            CPSB_STATS(0, accA0) CPSB_STATS(0, accA1) CPSB_STATS(0, accA2) CPSB_STATS(0, accA3) CPSB_STATS(0, accA4)
-            CPSB_STATS(1, accB0) CPSB_STATS(1, accB1) CPSB_STATS(1, accB2) CPSB_STATS(1, accB3) CPSB_STATS(1, accB4)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) CPSB_DRAIN(r, 0, accA0, accA1, accA2, accA3, accA4)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) CPSB_DRAIN(r, 1, accB0, accB1, accB2, accB3, accB4)
-        }
+        CPSB_TILE_MFMA()
+        if (live) CPSB_TILE_DRAIN()
         // single patch buffer: everyone is done reading it, then the prefetched tile replaces it
         lds_barrier();
         CPSB_COMMIT()
         lds_barrier();
     }
-#undef CPSB_DRAIN
-#undef CPSB_STATS
-#undef CPSB_ROW
-#undef CPSB_FRAG
-#undef CPSB_AOFF
-#undef CPSB_TAP
-#undef CPSB_ISSUE
-#undef CPSB_COMMIT
-#undef CPSB_SLOT
     if (stat_partial) {
         float s1[2], s2[2];
 #pragma unroll
@@ -255,13 +264,225 @@ __global__ __launch_bounds__(256, (CIN < 8 ? 2 : 1)) void conv_first_fwd_pool_sb
     }
 }
 
+// ---- ping-pong form (CIN = 7; option "conv1_pingpong").  In the kernel above a wave runs a tile's 240 MFMAs and then its all-VALU epilogue, and the two
+// workgroups of a CU do so in phase: both waves of a SIMD want the matrix pipe, then both leave it empty.  Here ONE 512-thread workgroup holds both: wave
+// groups G0 = waves 0-3 and G1 = waves 4-7, each with the wave roles, the fragment addressing and a patch of one workgroup above, and G1 one phase behind:
+//
+//      barrier k:      0          1          2          3                 2 trips
+//      G0         | mfma t0  | drain t0 | mfma t1  | drain t1 | ... | drain |  --   |
+//      G1         |   --     | mfma t0  | drain t0 | mfma t1  | ... | mfma  | drain |
+//
+// so on every SIMD one wave is in its matrix segment while its partner (wave + 4) is in its vector segment.  "drain" is statistics + window extremes of
+// the tile in the accumulators (which stay in registers across the barrier) and the NEXT tile's patch: its global loads are issued at the head of the
+// phase (their 21 staging registers are then free during the matrix segment, which needs them for its read-ahead) and committed at its end; a patch is
+// written by its own group only, in the phase after that group's reads of it.
+// Group g of block b is virtual workgroup v of the kernel above's grid (conv1_pp_sched.h): the same tiles in the same order, partial row v with the same
+// fold: zext, amax and the statistics partials are the same bits.  Barrier discipline: every branch around work is wave-uniform and holds NO barrier;
+// all s_barrier of the loop are the four lds_barrier() below plus the two __syncthreads() of the prologue and the one of the statistics tail.
+// LDS: two patches, one copy of the weight planes, red [8][128] = 105.25 KB: one workgroup per CU, two waves per SIMD as above.
+template <int CIN>
+struct PoolSbPpGeom {
+    using G = PoolSbGeom<CIN>;
+    static constexpr size_t SMEM = (size_t)(6 * G::PLANE + 3 * G::WPLANE) * 2 + 1024 * sizeof(float);
+};
+
+template <int CIN, bool WRITE_AMAX, bool ONE>
+__global__ __launch_bounds__(512) void conv_first_fwd_pool_sbpp_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                                        const float* __restrict__ bias, const float* __restrict__ gamma,
+                                                                        float* __restrict__ zext, unsigned char* __restrict__ amax,
+                                                                        float* __restrict__ stat_partial, int B, int H) {
+    using G = PoolSbGeom<CIN>;
+    constexpr int CP = G::CP, NS = G::NS, KW = G::KW, PLANE = G::PLANE, WPLANE = G::WPLANE;
+    extern __shared__ __attribute__((aligned(16))) unsigned short cpsb_smem[];
+    const int wave8 = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int pg = wave8 >> 2;                                   // wave group (scalar)
+    const int tid = threadIdx.x & 255, lane = tid & 63;          // thread, wave and roles INSIDE the group: those of the 4-wave kernel
+    const int wave = wave8 & 3;
+    unsigned short* patch = cpsb_smem + pg * (3 * PLANE);        // [2] x [3][12][66][CP]
+    unsigned short* Wl = cpsb_smem + 6 * PLANE;                  // [3][64][KW]
+    float* red = reinterpret_cast<float*>(Wl + 3 * WPLANE) + pg * 512;   // [2] x [4][128]
+    const int kg = lane >> 5, li = lane & 31;
+    const int grp = wave >> 1, strip = wave & 1;
+    for (int idx = threadIdx.x; idx < (6 * PLANE + 3 * WPLANE) / 2; idx += 512) reinterpret_cast<unsigned*>(cpsb_smem)[idx] = 0u;   // halo columns stay zero
+    __syncthreads();
+    cpsb_stage_weights<CIN, ONE, 512>(Wl, w, bias, gamma, threadIdx.x);
+    const unsigned smask[2] = {gamma[li] < 0.f ? 0x80000000u : 0u, gamma[32 + li] < 0.f ? 0x80000000u : 0u};
+    const int tiles_per_img = (H + 9) / 10;
+    const int HP = H / 5;
+    const Conv1PpSched sc = conv1_pp_sched(B, H);
+    const int v = conv1_pp_virtual(blockIdx.x, pg);
+    float stg[3][CIN];
+    if (conv1_pp_active(sc, v, 0)) {
+        CPSB_ISSUE(conv1_pp_tile(sc, v, 0))
+        CPSB_COMMIT()
+    }
+    __syncthreads();
+    typedef float f32x2s __attribute__((ext_vector_type(2)));
+    f32x2s s1p[2] = {{0.f, 0.f}, {0.f, 0.f}}, s2p[2] = {{0.f, 0.f}, {0.f, 0.f}};
+    const unsigned short* pbase = patch + ((5 * grp) * 66 + 32 * strip + li) * CP;
+    const unsigned short* wbase = Wl + li * KW + 8 * kg;
+    const int lane_e = kg * 64 + li;
+    // the matrix segment, software-pipelined by one patch row: with its partner in the vector segment a wave has the matrix pipe to itself, and every
+    // LDS wait in front of an MFMA is idle pipe time (with CPSB_TILE_MFMA's stream this kernel was slower than the 4-wave one, whose two workgroups
+    // cover each other's waits).  Reads are issued where registers die: the high plane of row q + 1 at the head of row q, the mid plane of row q + 1
+    // behind row q's eighth MFMA (the last use of its high plane), the low plane of row q at its head (eight MFMAs cover it), the next k-step's high
+    // weight planes behind the last row's eighth MFMA (the last use of the low ones).  The tap-8 element is merged in (v_perm) only when a plane is
+    // used, and a sched_barrier keeps each plane's wait behind the MFMAs that cover its read.  The MFMA order per accumulator is CPSB_ROW's: the same sums.
+#define CPSB_RAW(s_, j_, pl_, R_, R8_)                                                                  \
+    {                                                                                                   \
+        const unsigned short* ap_ = pbase + (kg ? CPSB_AOFF(s_, 1) : CPSB_AOFF(s_, 0)) + (j_) * 66 * CP + (pl_) * PLANE; \
+        int p8o_ = 2 * (s_);                                                                            \
+        asm volatile("" : "+s"(p8o_));                                                                  \
+        const unsigned short* p8_ = pbase + (2 * 66 + 2 + (j_) * 66) * CP + (pl_) * PLANE + p8o_;       \
+        R_ = *reinterpret_cast<const u32x4*>(ap_); R8_ = *reinterpret_cast<const unsigned*>(p8_);       \
+    }
+#define CPSB_FIX(s_, R_, R8_)                                                                           \
+    ([&]() {                                                                                            \
+        u32x4 f_ = R_;                                                                                  \
+        f_.w = __builtin_amdgcn_perm(R8_, f_.w, (s_) == 3 ? (kg ? 0x03020100u : 0x05040100u) : (kg ? 0x07060100u : 0x05040100u)); \
+        return __builtin_bit_cast(bf16x8, f_);                                                          \
+    }())
+#define CPSB_STEP(s_, j_, has_next_, ns_, nj_, ACCA_, ACCB_, AFTER8_)                                   \
+    {                                                                                                   \
+        u32x4 cl = ch;                                                                                  \
+        unsigned c8l = 0u;                                                                              \
+        if (!ONE) CPSB_RAW(s_, j_, 2, cl, c8l)                                                          \
+        if (has_next_) CPSB_RAW(ns_, nj_, 0, nh, n8h)                                                   \
+        __builtin_amdgcn_sched_barrier(0);                                                              \
+        const bf16x8 ah = CPSB_FIX(s_, ch, c8h);                                                        \
+        bf16x8 am = ah;                                                                                 \
+        ACCA_ = mfma_bf16(ah, bh0, ACCA_); ACCB_ = mfma_bf16(ah, bh1, ACCB_);                           \
+        if (!ONE) {                                                                                     \
+        ACCA_ = mfma_bf16(ah, bm0, ACCA_); ACCB_ = mfma_bf16(ah, bm1, ACCB_);                           \
+        __builtin_amdgcn_sched_barrier(0);      /* a plane's wait stays behind the MFMAs that cover its read */ \
+        am = CPSB_FIX(s_, cm, c8m);                                                                     \
+        ACCA_ = mfma_bf16(am, bh0, ACCA_); ACCB_ = mfma_bf16(am, bh1, ACCB_); ACCA_ = mfma_bf16(ah, bl0, ACCA_); ACCB_ = mfma_bf16(ah, bl1, ACCB_);   \
+        __builtin_amdgcn_sched_barrier(0);                                                              \
+        if (has_next_) CPSB_RAW(ns_, nj_, 1, nm, n8m)      /* the high plane of this row is dead: room for the next row's mid plane */ \
+        }                                                                                               \
+        AFTER8_                                                                                         \
+        __builtin_amdgcn_sched_barrier(0);                                                              \
+        if (!ONE) {                                                                                     \
+        const bf16x8 al = CPSB_FIX(s_, cl, c8l);                                                        \
+        ACCA_ = mfma_bf16(al, bh0, ACCA_); ACCB_ = mfma_bf16(al, bh1, ACCB_); ACCA_ = mfma_bf16(am, bm0, ACCA_); ACCB_ = mfma_bf16(am, bm1, ACCB_);   \
+        }                                                                                               \
+        __builtin_amdgcn_sched_barrier(0);                                                              \
+        ch = nh; c8h = n8h; cm = nm; c8m = n8m;                                                         \
+    }
+    static_assert(G::PACK, "the ping-pong form is CIN = 7's");
+    if (conv1_pp_pre_barriers(pg)) lds_barrier();
+    for (int it = 0; it < sc.trips; ++it) {
+        const bool act = conv1_pp_active(sc, v, it);             // scalar: (block, group, iteration) alone
+        const int tile = conv1_pp_tile(sc, v, it);
+        const int b = tile / tiles_per_img, t0 = (tile - b * tiles_per_img) * 10;
+        const int tg = t0 + 5 * grp;
+        const bool live = tg < H;
+        const size_t er = ((size_t)(b * HP + tg / 5) * 16 + 8 * strip) * 64;
+        float best = 0.f;
+        int bpos = 0;
+        f32x16 accA0 = zero16(), accA1 = zero16(), accA2 = zero16(), accA3 = zero16(), accA4 = zero16();
+        f32x16 accB0 = zero16(), accB1 = zero16(), accB2 = zero16(), accB3 = zero16(), accB4 = zero16();
+        if (act) {
+            u32x4 ch, nh = {0u, 0u, 0u, 0u}, cm = nh, nm = nh;
+            unsigned c8h, n8h = 0u, c8m = 0u, n8m = 0u;
+            CPSB_RAW(0, 0, 0, ch, c8h)
+            if (!ONE) CPSB_RAW(0, 0, 1, cm, c8m)
+            bf16x8 nbh0 = *reinterpret_cast<const bf16x8*>(wbase), nbh1 = *reinterpret_cast<const bf16x8*>(wbase + 32 * KW);
+            _Pragma("unroll") for (int s = 0; s < NS; ++s) {
+                const unsigned short* wp = wbase + 16 * s;
+                const bf16x8 bh0 = nbh0, bh1 = nbh1;
+                bf16x8 bm0 = bh0, bm1 = bh1, bl0 = bh0, bl1 = bh1;
+                if (!ONE) {
+                    bm0 = *reinterpret_cast<const bf16x8*>(wp + WPLANE); bm1 = *reinterpret_cast<const bf16x8*>(wp + WPLANE + 32 * KW);
+                    bl0 = *reinterpret_cast<const bf16x8*>(wp + 2 * WPLANE); bl1 = *reinterpret_cast<const bf16x8*>(wp + 2 * WPLANE + 32 * KW);
+                }
+                CPSB_STEP(s, 0, true, s, 1, accA0, accB0, )
+                CPSB_STEP(s, 1, true, s, 2, accA1, accB1, )
+                CPSB_STEP(s, 2, true, s, 3, accA2, accB2, )
+                CPSB_STEP(s, 3, true, s, 4, accA3, accB3, )
+                // the low weight planes are dead behind the last row's eighth MFMA: room for the next k-step's high planes
+                CPSB_STEP(s, 4, s + 1 < NS, s + 1, 0, accA4, accB4,
+                          if (s + 1 < NS) { nbh0 = *reinterpret_cast<const bf16x8*>(wp + 16); nbh1 = *reinterpret_cast<const bf16x8*>(wp + 16 + 32 * KW); })
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        lds_barrier();                          // the partner group's matrix segment starts here
+        __builtin_amdgcn_sched_barrier(0);
+        if (act) {
+            const int nxt = conv1_pp_tile(sc, v, it + 1);
+            const bool more = nxt < sc.ntiles;
+            if (more) CPSB_ISSUE(nxt)
+            __builtin_amdgcn_sched_barrier(0);
+            if (live) CPSB_TILE_DRAIN()
+            if (more) CPSB_COMMIT()             // this group is done reading its patch since the barrier above
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        lds_barrier();
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    if (conv1_pp_post_barriers(pg)) lds_barrier();
+    if (stat_partial) {
+        float s1[2], s2[2];
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            s1[c] = __uint_as_float(__float_as_uint(s1p[c].x + s1p[c].y) ^ smask[c]);
+            s2[c] = s2p[c].x + s2p[c].y;
+            s1[c] += __shfl_xor(s1[c], 32);
+            s2[c] += __shfl_xor(s2[c], 32);
+        }
+        if (kg == 0) {
+            red[wave * 128 + li] = s1[0];
+            red[wave * 128 + 32 + li] = s1[1];
+            red[wave * 128 + 64 + li] = s2[0];
+            red[wave * 128 + 96 + li] = s2[1];
+        }
+        __syncthreads();
+        if (tid < 128 && v < sc.vgrid) stat_partial[(size_t)v * 128 + tid] = (red[tid] + red[128 + tid]) + (red[256 + tid] + red[384 + tid]);
+    }
+}
+#undef CPSB_STEP
+#undef CPSB_FIX
+#undef CPSB_RAW
+#undef CPSB_TILE_DRAIN
+#undef CPSB_TILE_MFMA
+#undef CPSB_DRAIN
+#undef CPSB_STATS
+#undef CPSB_ROW
+#undef CPSB_FRAG
+#undef CPSB_AOFF
+#undef CPSB_TAP
+#undef CPSB_ISSUE
+#undef CPSB_COMMIT
+#undef CPSB_SLOT
+
+static int launch_cpsb_pp(hipStream_t st, const KernelChoices& kc, const float* x, const float* w, const float* bias, const float* gamma, float* zext,
+                          unsigned char* amax, float* stat_partial, int* n_partial, int B, int H) {
+    static_assert(CPSB_MAX_PERSISTENT == C1PP_MAX_VIRTUAL, "the ping-pong kernel plays the 4-wave kernel's grid");
+    const Conv1PpSched sc = conv1_pp_sched(B, H);
+    const size_t smem = PoolSbPpGeom<7>::SMEM;
+#define CPSB_PP_GO(A_, ONE_)                                                                                         \
+    {                                                                                                                \
+        hipFuncSetAttribute(reinterpret_cast<const void*>(conv_first_fwd_pool_sbpp_kernel<7, A_, ONE_>),             \
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);                                  \
+        hipLaunchKernelGGL((conv_first_fwd_pool_sbpp_kernel<7, A_, ONE_>), dim3(sc.nblocks), dim3(512), smem, st, x, w, bias, \
+                           gamma, zext, amax, stat_partial, B, H);                                                   \
+    }
+    if (amax) { if (kc.mfma_one) CPSB_PP_GO(true, true) else CPSB_PP_GO(true, false) }
+    else { if (kc.mfma_one) CPSB_PP_GO(false, true) else CPSB_PP_GO(false, false) }
+#undef CPSB_PP_GO
+    if (n_partial) *n_partial = sc.vgrid;
+    return 0;
+}
+
 template <int CIN>
 static int launch_cpsb(hipStream_t st, const KernelChoices& kc, const float* x, const float* w, const float* bias, const float* gamma, float* zext,
                        unsigned char* amax, float* stat_partial, int* n_partial, int B, int H) {
     using G = PoolSbGeom<CIN>;
+    if (CIN == 7 && kc.conv1_pingpong)      // CIN = 10: two patches do not fit the LDS
+        return launch_cpsb_pp(st, kc, x, w, bias, gamma, zext, amax, stat_partial, n_partial, B, H);
     const int ntiles = B * ((H + 9) / 10);
     const int grid = ntiles < CPSB_MAX_PERSISTENT ? ntiles : CPSB_MAX_PERSISTENT;
-#define CPSB_GO(A_)                                                                                                  \
+#define CPSB_GO(A_)                                                                                                 \
     {                                                                                                                \
         if (kc.mfma_one) {                                                                                           \
         hipFuncSetAttribute(reinterpret_cast<const void*>(conv_first_fwd_pool_sb_kernel<CIN, A_, true>),             \

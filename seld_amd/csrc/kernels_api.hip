@@ -41,6 +41,7 @@ int seld_k_set_option(const char* key, int value) {
     if (!strcmp(key, "conv1_split_bf16")) { k_conv1_split_bf16 = value != 0; return SELD_OK; }
     if (!strcmp(key, "gemm_tn_split_bf16")) { k_gemm_tn_split_bf16 = value != 0; return SELD_OK; }
     if (!strcmp(key, "bf16_single")) { k_kc.mfma_one = value != 0; return SELD_OK; }
+    if (!strcmp(key, "conv1_pingpong")) { k_kc.conv1_pingpong = value != 0; return SELD_OK; }
     if (!strcmp(key, "gsb_dbg")) { k_kc.gsb_dbg = value; return SELD_OK; }
     if (!strcmp(key, "xc_w16")) { k_kc.xc_w16 = value != 0; return SELD_OK; }
     if (!strcmp(key, "xc_xcd_map")) { k_kc.xc_xcd_map = value != 0; return SELD_OK; }

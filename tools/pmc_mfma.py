@@ -11,7 +11,7 @@ from collections import defaultdict
 
 N_SIMD = 256 * 4
 GROUPS = {  # group -> (kernel-name substring, fp32-equivalent GFLOP per launch at B=32, T=3000 or None)
-    "conv1_fwd": "conv_first_fwd_pool_sb_kernel", "conv1_gram (side stream)": "conv_first_gram_kernel",
+    "conv1_fwd": "conv_first_fwd_pool_sb", "conv1_gram (side stream)": "conv_first_gram_kernel",
     "conv2_fwd_dgrad (W=16)": "conv64_fwd_sbd_kernel<4", "conv3_fwd_dgrad (W=4)": "conv64_fwd_sbd_kernel<2",
     "conv2_wgrad": "conv64_wgrad_sb_kernel<4", "conv3_wgrad": "conv64_wgrad_sb_kernel<2",
     "gemm_sb (4-wave: GRU in-projections, dX)": "gemm_sb_kernel", "gemm_sb16 (16-wave)": "gemm_sb16_kernel",

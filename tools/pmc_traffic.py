@@ -19,7 +19,7 @@ def source_hashes():
 
 
 GROUPS = {  # bench.py timer group -> kernel-name substring
-    "conv1_fwd": "conv_first_fwd_pool_sb_kernel", "conv1_fwd_f32": "conv_first_fwd_pool_kernel",
+    "conv1_fwd": "conv_first_fwd_pool_sbpp_kernel", "conv1_fwd_4wave": "conv_first_fwd_pool_sb_kernel", "conv1_fwd_f32": "conv_first_fwd_pool_kernel",
     "conv1_wgrad": "conv_first_msparse_kernel", "conv1_gram": "conv_first_gram_kernel",
     "conv1_wgrad_fused": "conv_first_wgrad_fused_kernel",
     "gru_fwd": "gru_fwd_kernel", "gru_bwd": "gru_bwd_kernel",
