@@ -18,11 +18,21 @@
 // CIN = 7 and by default (option "conv1_pingpong"), conv_first_fwd_pool_sbpp_kernel: one 8-wave workgroup per CU whose two wave groups alternate
 // matrix and vector segments across workgroup barriers, with the matrix segment software-pipelined over its LDS reads.  Same tiles per (virtual)
 // workgroup in the same order, same MFMA order per accumulator: the same bits.  The schedule arithmetic is conv1_pp_sched.h.
+// The vector segment runs beside the partner wave's MFMAs, where both waves' vector instructions share the 24 issue cycles an MFMA leaves free: it is
+// written to the COUNT (tools/isa_mix.py, profiles/conv1_issue_budget.json): no packed fp32 (this file is built with -fno-slp-vectorize), no fmaxf.
 #include "common.h"
 #include "sb_tile.h"
 #include "conv1_pp_sched.h"
 
 #define CPSB_MAX_PERSISTENT 512
+
+// v_max3_f32 by name.  fmaxf quiets every operand first (a v_max_f32 x, x per accumulator register: 160 a tile), which a maximum of MFMA results has
+// no use for; beside the partner wave's MFMAs every vector instruction of the epilogue is paid in issue slots
+__device__ __forceinline__ float cpsb_max3(float a, float b, float c) {
+    float d;
+    asm("v_max3_f32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
+    return d;
+}
 
 template <int CIN>
 struct PoolSbGeom {
@@ -139,8 +149,7 @@ __global__ __launch_bounds__(256, (CIN < 8 ? 2 : 1)) void conv_first_fwd_pool_sb
         CPSB_COMMIT()
     }
     __syncthreads();
-    typedef float f32x2s __attribute__((ext_vector_type(2)));
-    f32x2s s1p[2] = {{0.f, 0.f}, {0.f, 0.f}}, s2p[2] = {{0.f, 0.f}, {0.f, 0.f}};
+    float s1x[2] = {0.f, 0.f}, s1y[2] = {0.f, 0.f}, s2x[2] = {0.f, 0.f}, s2y[2] = {0.f, 0.f};
     // A fragment of k-step s: lane (li, kg) reads the 8 slots [c0, c0 + 8) of pixel (row + dy, bin + dx) with
     // k0 = 16 s + 8 kg, tap = min(k0 / CP, 8) (past tap 8 the weights are zero: any finite pixel will do), c0 = k0 % CP
 #define CPSB_TAP(s_, g_) ((16 * (s_) + 8 * (g_)) / CP > 8 ? 8 : (16 * (s_) + 8 * (g_)) / CP)
@@ -172,13 +181,15 @@ __global__ __launch_bounds__(256, (CIN < 8 ? 2 : 1)) void conv_first_fwd_pool_sb
 #define CPSB_DRAIN(r_, c_, Y0, Y1, Y2, Y3, Y4)                                                          \
     {                                                                                                   \
         const float w0 = Y0[r_], w1 = Y1[r_], w2 = Y2[r_], w3 = Y3[r_], w4 = Y4[r_];                    \
-        const float hi5 = fmaxf(fmaxf(fmaxf(w0, w1), fmaxf(w2, w3)), w4);                               \
+        const float hi5 = cpsb_max3(cpsb_max3(w0, w1, w2), w3, w4);                                     \
         const bool take_ = ((r_) & 3) == 0 || hi5 > best;     /* strict: the first extreme in scan order wins ties */ \
         if (WRITE_AMAX) {    /* training: remember WHERE the extreme is: position row * 4 + column of the window */ \
             int row_ = 4;                                                                               \
             row_ = (w3 == hi5) ? 3 : row_; row_ = (w2 == hi5) ? 2 : row_;                               \
             row_ = (w1 == hi5) ? 1 : row_; row_ = (w0 == hi5) ? 0 : row_;                               \
-            bpos = take_ ? row_ * 4 + ((r_) & 3) : bpos;                                                \
+            int pos_ = row_ * 4 + ((r_) & 3);                                                           \
+            asm("" : "+v"(pos_));    /* computed for every lane: sunk under take_ it became a branch per register */ \
+            bpos = take_ ? pos_ : bpos;                                                                 \
         }                                                                                               \
         best = take_ ? hi5 : best;                                                                      \
         if (((r_) & 3) == 3) {                                                                          \
@@ -186,12 +197,14 @@ __global__ __launch_bounds__(256, (CIN < 8 ? 2 : 1)) void conv_first_fwd_pool_sb
             if (WRITE_AMAX) (amax + (er + (size_t)((2 * ((r_) >> 2)) * 64 + 32 * (c_))))[lane_e] = (unsigned char)bpos; \
         }                                                                                               \
     }
-    // BN statistics of one accumulator tile: packed adds / FMAs over register pairs (any pairing sums to the same totals)
+    // BN statistics of one accumulator tile: even registers into the x accumulators, odd ones into the y accumulators (any pairing sums to the same
+    // totals).  Scalar v_add_f32 / v_fma_f32 on purpose: beside MFMAs a v_pk_add_f32 / v_pk_fma_f32 costs more issue than the two it replaces
 #define CPSB_STATS(c_, Y)                                                                               \
     _Pragma("unroll") for (int r = 0; r < 16; r += 2) {                                                 \
-        const f32x2s y2 = {Y[r], Y[r + 1]};                                                             \
-        s1p[c_] += y2;                                                                                  \
-        s2p[c_] = __builtin_elementwise_fma(y2, y2, s2p[c_]);                                           \
+        s1x[c_] += Y[r];                                                                                \
+        s2x[c_] = __builtin_fmaf(Y[r], Y[r], s2x[c_]);                                                  \
+        s1y[c_] += Y[r + 1];                                                                            \
+        s2y[c_] = __builtin_fmaf(Y[r + 1], Y[r + 1], s2y[c_]);                                          \
     }
     // the matrix segment of a tile: NS k-steps x 5 rows into the ten accumulator tiles accA0 .. accB4.
     // p8o: elements 2 s, 2 s + 1 of the tap-8 pixel.  The offset is laundered through an empty asm: seen as consecutive, the four k-steps' dwords
@@ -248,8 +261,8 @@ __global__ __launch_bounds__(256, (CIN < 8 ? 2 : 1)) void conv_first_fwd_pool_sb
         float s1[2], s2[2];
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
-            s1[c] = __uint_as_float(__float_as_uint(s1p[c].x + s1p[c].y) ^ smask[c]);     // negated channels: flip the sum back
-            s2[c] = s2p[c].x + s2p[c].y;
+            s1[c] = __uint_as_float(__float_as_uint(s1x[c] + s1y[c]) ^ smask[c]);     // negated channels: flip the sum back
+            s2[c] = s2x[c] + s2y[c];
             s1[c] += __shfl_xor(s1[c], 32);
             s2[c] += __shfl_xor(s2[c], 32);
         }
@@ -317,8 +330,7 @@ __global__ __launch_bounds__(512) void conv_first_fwd_pool_sbpp_kernel(const flo
         CPSB_COMMIT()
     }
     __syncthreads();
-    typedef float f32x2s __attribute__((ext_vector_type(2)));
-    f32x2s s1p[2] = {{0.f, 0.f}, {0.f, 0.f}}, s2p[2] = {{0.f, 0.f}, {0.f, 0.f}};
+    float s1x[2] = {0.f, 0.f}, s1y[2] = {0.f, 0.f}, s2x[2] = {0.f, 0.f}, s2y[2] = {0.f, 0.f};
     const unsigned short* pbase = patch + ((5 * grp) * 66 + 32 * strip + li) * CP;
     const unsigned short* wbase = Wl + li * KW + 8 * kg;
     const int lane_e = kg * 64 + li;
@@ -328,12 +340,10 @@ __global__ __launch_bounds__(512) void conv_first_fwd_pool_sbpp_kernel(const flo
     // behind row q's eighth MFMA (the last use of its high plane), the low plane of row q at its head (eight MFMAs cover it), the next k-step's high
     // weight planes behind the last row's eighth MFMA (the last use of the low ones).  The tap-8 element is merged in (v_perm) only when a plane is
     // used, and a sched_barrier keeps each plane's wait behind the MFMAs that cover its read.  The MFMA order per accumulator is CPSB_ROW's: the same sums.
-#define CPSB_RAW(s_, j_, pl_, R_, R8_)                                                                  \
+#define CPSB_RAW(s_, j_, pl_, R_, R8_, P8O_)                                                            \
     {                                                                                                   \
         const unsigned short* ap_ = pbase + (kg ? CPSB_AOFF(s_, 1) : CPSB_AOFF(s_, 0)) + (j_) * 66 * CP + (pl_) * PLANE; \
-        int p8o_ = 2 * (s_);                                                                            \
-        asm volatile("" : "+s"(p8o_));                                                                  \
-        const unsigned short* p8_ = pbase + (2 * 66 + 2 + (j_) * 66) * CP + (pl_) * PLANE + p8o_;       \
+        const unsigned short* p8_ = pbase + (2 * 66 + 2 + (j_) * 66) * CP + (pl_) * PLANE + (P8O_);     \
         R_ = *reinterpret_cast<const u32x4*>(ap_); R8_ = *reinterpret_cast<const unsigned*>(p8_);       \
     }
 #define CPSB_FIX(s_, R_, R8_)                                                                           \
@@ -346,8 +356,8 @@ __global__ __launch_bounds__(512) void conv_first_fwd_pool_sbpp_kernel(const flo
     {                                                                                                   \
         u32x4 cl = ch;                                                                                  \
         unsigned c8l = 0u;                                                                              \
-        if (!ONE) CPSB_RAW(s_, j_, 2, cl, c8l)                                                          \
-        if (has_next_) CPSB_RAW(ns_, nj_, 0, nh, n8h)                                                   \
+        if (!ONE) CPSB_RAW(s_, j_, 2, cl, c8l, p8c)                                                     \
+        if (has_next_) CPSB_RAW(ns_, nj_, 0, nh, n8h, (ns_) == (s_) ? p8c : p8n)                        \
         __builtin_amdgcn_sched_barrier(0);                                                              \
         const bf16x8 ah = CPSB_FIX(s_, ch, c8h);                                                        \
         bf16x8 am = ah;                                                                                 \
@@ -358,7 +368,7 @@ __global__ __launch_bounds__(512) void conv_first_fwd_pool_sbpp_kernel(const flo
         am = CPSB_FIX(s_, cm, c8m);                                                                     \
         ACCA_ = mfma_bf16(am, bh0, ACCA_); ACCB_ = mfma_bf16(am, bh1, ACCB_); ACCA_ = mfma_bf16(ah, bl0, ACCA_); ACCB_ = mfma_bf16(ah, bl1, ACCB_);   \
         __builtin_amdgcn_sched_barrier(0);                                                              \
-        if (has_next_) CPSB_RAW(ns_, nj_, 1, nm, n8m)      /* the high plane of this row is dead: room for the next row's mid plane */ \
+        if (has_next_) CPSB_RAW(ns_, nj_, 1, nm, n8m, (ns_) == (s_) ? p8c : p8n)      /* the high plane of this row is dead: room for the next row's mid plane */ \
         }                                                                                               \
         AFTER8_                                                                                         \
         __builtin_amdgcn_sched_barrier(0);                                                              \
@@ -380,16 +390,23 @@ __global__ __launch_bounds__(512) void conv_first_fwd_pool_sbpp_kernel(const flo
         const size_t er = ((size_t)(b * HP + tg / 5) * 16 + 8 * strip) * 64;
         float best = 0.f;
         int bpos = 0;
-        f32x16 accA0 = zero16(), accA1 = zero16(), accA2 = zero16(), accA3 = zero16(), accA4 = zero16();
-        f32x16 accB0 = zero16(), accB1 = zero16(), accB2 = zero16(), accB3 = zero16(), accB4 = zero16();
+        // set and read under act only: zeroed here, in front of the branch, they cost the matrix segment 160 v_mov per tile for the path that never reads them
+        f32x16 accA0, accA1, accA2, accA3, accA4, accB0, accB1, accB2, accB3, accB4;
         if (act) {
+            accA0 = accA1 = accA2 = accA3 = accA4 = accB0 = accB1 = accB2 = accB3 = accB4 = zero16();
             u32x4 ch, nh = {0u, 0u, 0u, 0u}, cm = nh, nm = nh;
             unsigned c8h, n8h = 0u, c8m = 0u, n8m = 0u;
-            CPSB_RAW(0, 0, 0, ch, c8h)
-            if (!ONE) CPSB_RAW(0, 0, 1, cm, c8m)
+            // offset of the tap-8 dword of k-step s (elements 2 s, 2 s + 1), laundered ONCE per k-step (see CPSB_TILE_MFMA): its fifteen reads share
+            // one address register; laundered per read, each one paid an s_mov, a hazard s_nop and a v_lshl_add in the matrix wave's own gaps
+            int p8c = 0;
+            asm volatile("" : "+s"(p8c));
+            CPSB_RAW(0, 0, 0, ch, c8h, p8c)
+            if (!ONE) CPSB_RAW(0, 0, 1, cm, c8m, p8c)
             bf16x8 nbh0 = *reinterpret_cast<const bf16x8*>(wbase), nbh1 = *reinterpret_cast<const bf16x8*>(wbase + 32 * KW);
             _Pragma("unroll") for (int s = 0; s < NS; ++s) {
                 const unsigned short* wp = wbase + 16 * s;
+                int p8n = 2 * (s + 1);
+                asm volatile("" : "+s"(p8n));
                 const bf16x8 bh0 = nbh0, bh1 = nbh1;
                 bf16x8 bm0 = bh0, bm1 = bh1, bl0 = bh0, bl1 = bh1;
                 if (!ONE) {
@@ -403,6 +420,7 @@ __global__ __launch_bounds__(512) void conv_first_fwd_pool_sbpp_kernel(const flo
                 // the low weight planes are dead behind the last row's eighth MFMA: room for the next k-step's high planes
                 CPSB_STEP(s, 4, s + 1 < NS, s + 1, 0, accA4, accB4,
                           if (s + 1 < NS) { nbh0 = *reinterpret_cast<const bf16x8*>(wp + 16); nbh1 = *reinterpret_cast<const bf16x8*>(wp + 16 + 32 * KW); })
+                p8c = p8n;
             }
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -425,8 +443,8 @@ __global__ __launch_bounds__(512) void conv_first_fwd_pool_sbpp_kernel(const flo
         float s1[2], s2[2];
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
-            s1[c] = __uint_as_float(__float_as_uint(s1p[c].x + s1p[c].y) ^ smask[c]);
-            s2[c] = s2p[c].x + s2p[c].y;
+            s1[c] = __uint_as_float(__float_as_uint(s1x[c] + s1y[c]) ^ smask[c]);
+            s2[c] = s2x[c] + s2y[c];
             s1[c] += __shfl_xor(s1[c], 32);
             s2[c] += __shfl_xor(s2[c], 32);
         }
