@@ -455,6 +455,31 @@ int seld_k_gemm_tn(const float* A, const float* Bm, float* C, float* colsum, int
  * round 5); fused = 0: the separate passes (dw3x3_bwd_data, dw3x3_bwd_w, xc_reduce). */
 int seld_k_xc_dw_bwd(const float* dy, const float* k, const float* xin, const float* add, const float* aff, const float* bn_mean,
                      const float* bn_invstd, float* dx, float* dk, float* sums, int B, int H, int fused);
+/* xception_block's other kernels, one family per call (xception.hip), with the launchers and combines of the model path.  All tensors NHWC fp32 with
+ * 64 channels; aff (may be NULL) = [scale 64 | shift 64] as above; options "xc_w16" / "xc_xcd_map" of seld_k_set_option apply to the depthwise
+ * launches.  NULL required pointers and sizes below 1: SELD_ERR_INVALID; what a launcher refuses: SELD_ERR_UNSUPPORTED; both before any launch.
+ *
+ * The depthwise 3x3 forward alone: y [B,H,W,64] = DepthwiseConv2D(3, 'same', use_bias=False)(relu(x) or relu(x scale + shift)), k [3][3][64].
+ * W = 16 runs the row-per-workgroup kernel unless "xc_w16" is 0; any other W the generic kernel. */
+int seld_k_xc_dw_fwd(const float* x, const float* k, const float* aff, float* y, int B, int H, int W);
+/* One unit's forward on [B,H,16,64]: dwo = the depthwise output, z = dwo wpw (wpw [64 in][64 out], Keras pointwise_kernel), and, with sums != NULL,
+ * sums [128] = [sum z | sum z^2] over the pixels (NULL: the launch without statistics, as in inference).  fused = 1: xc_unit_fwd_kernel + the
+ * combine of its per-workgroup partials; fused = 0: the depthwise kernel, the fp32 GEMM and xc_reduce, the "xc_fused_fwd" = 0 route. */
+int seld_k_xc_unit_fwd(const float* x, const float* kdw, const float* wpw, const float* aff, float* dwo, float* z, float* sums, int B, int H,
+                       int fused);
+/* The pointwise half of a unit's backward over npix pixels (any npix >= 1): with dz = scale (gy - c1 - (z - mean) invstd c2), c1c2 = [c1 64 | c2 64],
+ * f1 [npix,64] = dz wpw^T (the gradient w.r.t. dwo) and dw [64][64] = dwo^T dz.  mode 1: xc_pw_bwd_kernel + the one-stage slab combine; mode 2: the
+ * same kernel + the two-stage combine ("xc_nowait"); mode 0: xc_bn_bwd_dz, the TN product + its combine and the fp32 GEMM ("xc_fused_pw_bwd" = 0). */
+int seld_k_xc_pw_bwd(const float* z, const float* gy, const float* dwo, const float* wpw, const float* mean, const float* invstd,
+                     const float* scale, const float* c1c2, float* f1, float* dw, int64_t npix, int mode);
+/* sums [128] = [sum z | sum z^2] over npix pixels (xc_reduce_kernel + combine) */
+int seld_k_xc_bn_stats(const float* z, float* sums, int64_t npix);
+/* out = z scale + shift (+ res; res may be NULL) */
+int seld_k_xc_bn_apply(const float* z, const float* scale, const float* shift, const float* res, float* out, int64_t npix);
+/* Training-mode BatchNormalization's backward given the batch's mean / invstd and scale = gamma invstd: dbeta = sum dy, dgamma = sum dy xhat,
+ * c1c2 [128] = [dbeta / npix | dgamma / npix] (written), dz = scale (dy - c1 - xhat c2)  (xc_reduce_kernel, bn_bwd_finalize, xc_bn_bwd_dz) */
+int seld_k_xc_bn_bwd(const float* z, const float* dy, const float* mean, const float* invstd, const float* scale, float* dz, float* dgamma,
+                     float* dbeta, float* c1c2, int64_t npix);
 /* Bidirectional(GRU(128, reset_after=True), merge_mode='mul') recurrence (modules.py:311-316).
  * gx_* [B,S,384] = x*kernel + bias[0]; U_* [128,384]; brec_* = bias[1]; h_* [B,S,128]; out = h_f*h_b.
  * saved_* [B,S,128,4] (per unit: z, r, hh, h*U_h+b) may be NULL. */

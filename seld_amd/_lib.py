@@ -162,6 +162,12 @@ SIGNATURES = {
     "seld_k_gemm_pair_k": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I]),
     "seld_k_gemm_sb": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I]),
     "seld_k_xc_dw_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I]),
+    "seld_k_xc_dw_fwd": (_I, [_P, _P, _P, _P, _I, _I, _I]),
+    "seld_k_xc_unit_fwd": (_I, [_P] * 7 + [_I, _I, _I]),
+    "seld_k_xc_pw_bwd": (_I, [_P] * 10 + [_L, _I]),
+    "seld_k_xc_bn_stats": (_I, [_P, _P, _L]),
+    "seld_k_xc_bn_apply": (_I, [_P, _P, _P, _P, _P, _L]),
+    "seld_k_xc_bn_bwd": (_I, [_P] * 9 + [_L]),
     "seld_k_gemm_tn": (_I, [_P, _P, _P, _P, _I, _I, _I]),
     "seld_k_gru_fwd": (_I, [_P] * 11 + [_I] * 3),
     "seld_k_gru_bwd": (_I, [_P] * 11 + [_I] * 3),

@@ -313,6 +313,92 @@ int seld_k_xc_dw_bwd(const float* dy, const float* k, const float* xin, const fl
     return done();
 }
 
+// ---- xception_block's other kernels, one family per entry point (xception.hip): the launchers and combines of forward_xception / backward_xception
+int seld_k_xc_dw_fwd(const float* x, const float* k, const float* aff, float* y, int B, int H, int W) {
+    if (!x || !k || !y || B < 1 || H < 1 || W < 1) return SELD_ERR_INVALID;
+    if ((int64_t)B * H * W > INT32_MAX) return SELD_ERR_UNSUPPORTED;      // the launcher's row count is an int
+    if (launch_dw3x3_fwd(0, k_kc, x, k, y, B, H, W, aff)) return SELD_ERR_UNSUPPORTED;
+    return done();
+}
+
+int seld_k_xc_unit_fwd(const float* x, const float* kdw, const float* wpw, const float* aff, float* dwo, float* z, float* sums, int B, int H,
+                       int fused) {
+    if (!x || !kdw || !wpw || !dwo || !z || B < 1 || H < 1) return SELD_ERR_INVALID;
+    const int64_t npix = (int64_t)B * H * 16;
+    if (npix > INT32_MAX) return SELD_ERR_UNSUPPORTED;      // tile / row counts and the product's M are ints
+    Scratch s;
+    float* part = sums ? s.get((size_t)xc_partial_capacity() * 128) : nullptr;
+    if (sums && !part) return SELD_ERR_NOMEM;
+    int np = 0;
+    if (fused) {
+        if (launch_xc_unit_fwd(0, x, kdw, wpw, dwo, z, part, &np, B, H, 16, aff)) return SELD_ERR_UNSUPPORTED;
+    } else {
+        if (launch_dw3x3_fwd(0, k_kc, x, kdw, dwo, B, H, 16, aff)) return SELD_ERR_UNSUPPORTED;
+        if (launch_gemm(0, dwo, 64, wpw, 64, nullptr, z, 64, (int)npix, 64, 64, 0, 0, 0)) return SELD_ERR_UNSUPPORTED;
+        if (sums) launch_xc_bn_stats(0, z, part, &np, npix);
+    }
+    if (sums) launch_reduce_slabs(0, part, np, 128, sums, 128, 0);
+    return done();
+}
+
+int seld_k_xc_pw_bwd(const float* z, const float* gy, const float* dwo, const float* wpw, const float* mean, const float* invstd,
+                     const float* scale, const float* c1c2, float* f1, float* dw, int64_t npix, int mode) {
+    if (!z || !gy || !dwo || !wpw || !mean || !invstd || !scale || !c1c2 || !f1 || !dw || npix < 1 || mode < 0 || mode > 2) return SELD_ERR_INVALID;
+    if (mode == 0 && npix > INT32_MAX) return SELD_ERR_UNSUPPORTED;      // the two products' M is an int
+    Scratch s;
+    int ns = 0;
+    if (mode) {
+        float* slab = s.get((size_t)xc_pw_bwd_slabs() * 4096);
+        float* tmp = s.get((size_t)reduce_slabs_groups(xc_pw_bwd_slabs()) * 4096);
+        if (!slab || !tmp) return SELD_ERR_NOMEM;
+        if (launch_xc_pw_bwd(0, z, gy, dwo, wpw, mean, invstd, scale, c1c2, f1, slab, &ns, npix)) return SELD_ERR_UNSUPPORTED;
+        if (mode == 2) launch_reduce_slabs_2stage(0, slab, ns, 4096, dw, 4096, tmp);      // the xc_nowait path's combine
+        else launch_reduce_slabs(0, slab, ns, 4096, dw, 4096, 0);
+    } else {
+        const int splits = 512;      // backward_xception's: many short splits, the slab is only 64 x 64 (+ 64)
+        float* dz = s.get((size_t)npix * 64);
+        float* slab = s.get((size_t)splits * (4096 + 64));
+        if (!dz || !slab) return SELD_ERR_NOMEM;
+        launch_xc_bn_bwd_dz(0, z, gy, mean, invstd, scale, c1c2, dz, npix);
+        if (launch_gemm_tn(0, dwo, 64, dz, 64, slab, &ns, (int)npix, 64, 64, 0, 0, 0, splits)) return SELD_ERR_UNSUPPORTED;
+        launch_reduce_slabs2(0, slab, ns, 64 * 64 + 64, dw, 64 * 64, nullptr, 0);
+        if (launch_gemm(0, dz, 64, wpw, 64, nullptr, f1, 64, (int)npix, 64, 64, 1, 0, 0)) return SELD_ERR_UNSUPPORTED;
+    }
+    return done();
+}
+
+int seld_k_xc_bn_stats(const float* z, float* sums, int64_t npix) {
+    if (!z || !sums || npix < 1) return SELD_ERR_INVALID;
+    Scratch s;
+    float* part = s.get((size_t)xc_partial_capacity() * 128);
+    if (!part) return SELD_ERR_NOMEM;
+    int np = 0;
+    if (launch_xc_bn_stats(0, z, part, &np, npix)) return SELD_ERR_UNSUPPORTED;
+    launch_reduce_slabs(0, part, np, 128, sums, 128, 0);
+    return done();
+}
+
+int seld_k_xc_bn_apply(const float* z, const float* scale, const float* shift, const float* res, float* out, int64_t npix) {
+    if (!z || !scale || !shift || !out || npix < 1) return SELD_ERR_INVALID;
+    if (npix > ((int64_t)1 << 35)) return SELD_ERR_UNSUPPORTED;      // one workgroup per 16 pixels: the grid is 32-bit
+    if (launch_xc_bn_apply(0, z, scale, shift, res, out, npix)) return SELD_ERR_UNSUPPORTED;
+    return done();
+}
+
+int seld_k_xc_bn_bwd(const float* z, const float* dy, const float* mean, const float* invstd, const float* scale, float* dz, float* dgamma,
+                     float* dbeta, float* c1c2, int64_t npix) {
+    if (!z || !dy || !mean || !invstd || !scale || !dz || !dgamma || !dbeta || !c1c2 || npix < 1) return SELD_ERR_INVALID;
+    if (npix > ((int64_t)1 << 35)) return SELD_ERR_UNSUPPORTED;      // one workgroup per 16 pixels: the grid is 32-bit
+    Scratch s;
+    float* part = s.get((size_t)xc_partial_capacity() * 128);
+    if (!part) return SELD_ERR_NOMEM;
+    int np = 0;
+    if (launch_xc_bn_bwd_reduce(0, z, dy, mean, invstd, part, &np, npix)) return SELD_ERR_UNSUPPORTED;
+    launch_bn_bwd_finalize(0, part, np, (double)npix, dgamma, dbeta, c1c2, 64);
+    launch_xc_bn_bwd_dz(0, z, dy, mean, invstd, scale, c1c2, dz, npix);
+    return done();
+}
+
 int seld_k_gemm_tn(const float* A, const float* Bm, float* C, float* colsum, int M, int K1, int N) {
     if (!A || !Bm || !C) return SELD_ERR_INVALID;
     Scratch s;

@@ -8,6 +8,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import xception_oracle as XO
 from helpers import REL_TOL, check, dev, ptr, rel_err
 
 pytestmark = pytest.mark.gpu
@@ -170,8 +171,12 @@ def test_conv_first_fwd_pool(seld_lib, B, H, Cin):
     assert seld_lib.seld_k_conv_first_fwd_pool(ptr(xd), ptr(wd), ptr(bd), ptr(gd), None, ptr(ze2), None, None, B, H - 1, Cin) != 0
 
 
-@pytest.mark.parametrize("B,H,W,pt,pf", [(2, 50, 64, 5, 4), (2, 10, 16, 1, 4), (3, 10, 4, 1, 2)])
-def test_bn_relu_pool(seld_lib, B, H, W, pt, pf):
+@pytest.mark.parametrize("B,H,W,pt,pf,ident", [pytest.param(*c, i, id="-".join(map(str, c)) + ("-ident" if i else ""))
+                                               for c, i in [((2, 50, 64, 5, 4), 0), ((2, 10, 16, 1, 4), 0), ((3, 10, 4, 1, 2), 0), ((2, 10, 16, 1, 8), 0),
+                                                            ((1, 7, 16, 1, 8), 0), ((2, 10, 16, 1, 8), 1)]])
+def test_bn_relu_pool(seld_lib, B, H, W, pt, pf, ident):
+    """(1, 8) on W = 16: xception_block's exit pool; ident: with the identity coefficients xc_ident supplies there (scale 1, shift 0: ReLU ->
+    MaxPooling2D alone; the forward, which is what runs with them)"""
     rng = np.random.default_rng(4)
     z = rng.standard_normal((B, H, W, 64)).astype(np.float32)
     gamma = (rng.uniform(0.5, 1.5, 64) * np.where(rng.random(64) < 0.2, -1, 1)).astype(np.float32)
@@ -179,6 +184,13 @@ def test_bn_relu_pool(seld_lib, B, H, W, pt, pf):
     gamma[5], beta[5] = 0.0, 0.25    # degenerate channel: y constant > 0, argmax = first window element
     gamma[9], beta[9] = 0.0, -0.25   # degenerate channel killed by the ReLU
     zt = torch.as_tensor(z, dtype=torch.float64, ).requires_grad_(True)
+    if ident:
+        p = F.max_pool2d(torch.relu(zt).permute(0, 3, 1, 2), (pt, pf), (pt, pf)).permute(0, 2, 3, 1)
+        pd = torch.full(tuple(p.shape), float("nan"), device="cuda")
+        zd, one, zero = dev(z), dev(np.ones(64)), dev(np.zeros(64))
+        assert seld_lib.seld_k_bn_relu_pool_fwd(ptr(zd), ptr(one), ptr(zero), ptr(pd), B, H, W, 64, pt, pf) == 0
+        check(f"bn_relu_pool_fwd identity {B,H,W,pt,pf}", pd.cpu().numpy(), p.detach().numpy())
+        return
     g = torch.as_tensor(gamma, dtype=torch.float64).requires_grad_(True)
     bt = torch.as_tensor(beta, dtype=torch.float64).requires_grad_(True)
     mean = zt.mean(dim=(0, 1, 2))
@@ -726,13 +738,16 @@ def _rn_conv_fwd_bwd(seld_lib, B, H, W, Cin, Cout, ksize, stride_f):
 
 
 @pytest.mark.parametrize("fused", [1, 0])
-@pytest.mark.parametrize("B,H,aff,with_add,sums", [(2, 37, 1, 0, 1), (3, 8, 1, 0, 0), (1, 1, 0, 1, 0), (2, 50, 0, 0, 0), (2, 3, 0, 1, 0), (5, 13, 1, 0, 1)])
+@pytest.mark.parametrize("B,H,aff,with_add,sums", [(2, 37, 1, 0, 1), (3, 8, 1, 0, 0), (1, 1, 0, 1, 0), (2, 50, 0, 0, 0), (2, 3, 0, 1, 0), (5, 13, 1, 0, 1),
+                                                   (9, 59, 1, 0, 1), (9, 59, 0, 1, 0)])
 def test_xc_depthwise_backward(seld_lib, B, H, aff, with_add, sums, fused):
     """xception_block's depthwise 3x3 backward through seld_k_xc_dw_bwd, in ONE pass (fused = 1: input gradient + kernel-gradient slabs + the
     previous BatchNormalization's backward sums, dw3x3_w16_bwd_fused; round 5) and as the separate passes (fused = 0), against autograd in fp64:
     the unit is  a = relu(z scale + shift)  (or relu(x)),  y = DepthwiseConv2D(3, 'same', use_bias=False)(a),  L = sum(y dy):
     dx = dL/d(pre-ReLU input) (+ add), dk = dL/dk, sums = [sum dx | sum dx xhat].  Ragged sizes: one image row, rows that are not a multiple of the
-    four a workgroup takes, several images (the halo must not cross an image boundary)."""
+    four a workgroup takes, several images (the halo must not cross an image boundary); (9, 59): 531 rows = more than dw3x3_bwd_w's 512 workgroups
+    (its strided second pass) and 133 fused slabs (a third, partial group of 64 in the two-stage combine; a ragged last group of 16 in the partial
+    fold) — there every pre-activation is first moved at least 1e-4 away from zero, where fp32 takes no ReLU gate differently."""
     rng = np.random.default_rng(B * 100 + H)
     shp = (B, H, 16, 64)
     xin = rng.standard_normal(shp).astype(np.float32)
@@ -743,6 +758,9 @@ def test_xc_depthwise_backward(seld_lib, B, H, aff, with_add, sums, fused):
     sh = (rng.standard_normal(64) * 0.3).astype(np.float32)
     mean = (rng.standard_normal(64) * 0.2).astype(np.float32)
     invstd = (rng.random(64) + 0.5).astype(np.float32)
+    if (B, H) == XO.DW_BWD_BIG:
+        xin, _ = XO.apply_gate_margin(xin, np.concatenate([sc, sh]) if aff else None)
+        assert XO.gate_margin(xin, np.concatenate([sc, sh]) if aff else None) >= XO.GATE_MARGIN
     # fp64 reference by autograd
     z = torch.as_tensor(xin, dtype=torch.float64)
     pre = (z * torch.as_tensor(sc, dtype=torch.float64) + torch.as_tensor(sh, dtype=torch.float64)) if aff else z.clone()
