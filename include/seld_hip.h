@@ -490,6 +490,18 @@ int seld_k_gru_fwd(const float* gx_f, const float* gx_b, const float* U_f, const
 int seld_k_gru_bwd(const float* dout, const float* h_f, const float* h_b, const float* saved_f,
                    const float* saved_b, const float* U_f, const float* U_b, float* dgx_f, float* dgx_b,
                    float* dgh_f, float* dgh_b, int B, int S, int units);
+/* The same recurrence under Keras recurrent_dropout (training; modules.py:312-314), as the training context launches it: rm_* [B,128] hold
+ * 0 | 1/(1-rate) per (clip, unit), constant over the sequence; the previous state is multiplied by rm before the recurrent product and before
+ * the blend.  h_* is the unmasked output, hm_* [B,S,128] = h * rm the masked state sequence the backward pass reads as h_prev; saved_* as above,
+ * required.  Null stream, synchronous.  units != 128: SELD_ERR_UNSUPPORTED before any other check; a NULL pointer, B < 1 or S < 1:
+ * SELD_ERR_INVALID, nothing enqueued. */
+int seld_k_gru_drop_fwd(const float* gx_f, const float* gx_b, const float* U_f, const float* U_b, const float* brec_f, const float* brec_b,
+                        const float* rm_f, const float* rm_b, float* h_f, float* h_b, float* hm_f, float* hm_b, float* saved_f, float* saved_b,
+                        int B, int S, int units);
+/* BPTT of it ('mul' merge: dh = dout * h_other): the carry is the gradient w.r.t. the masked state times rm */
+int seld_k_gru_drop_bwd(const float* dout, const float* h_f, const float* h_b, const float* hm_f, const float* hm_b, const float* saved_f,
+                        const float* saved_b, const float* U_f, const float* U_b, const float* rm_f, const float* rm_b, float* dgx_f, float* dgx_b,
+                        float* dgh_f, float* dgh_b, int B, int S, int units);
 /* BinaryCrossentropy + MSE|MMSE on head outputs (train.py:26-29, losses.py:4-13): losses and the
  * gradients w.r.t. the PRE-activation head outputs (sigmoid / tanh folded in). */
 int seld_k_losses(const float* sed, const float* doa, const float* y_sed, const float* y_doa,

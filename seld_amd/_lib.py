@@ -171,6 +171,8 @@ SIGNATURES = {
     "seld_k_gemm_tn": (_I, [_P, _P, _P, _P, _I, _I, _I]),
     "seld_k_gru_fwd": (_I, [_P] * 11 + [_I] * 3),
     "seld_k_gru_bwd": (_I, [_P] * 11 + [_I] * 3),
+    "seld_k_gru_drop_fwd": (_I, [_P] * 14 + [_I] * 3),
+    "seld_k_gru_drop_bwd": (_I, [_P] * 15 + [_I] * 3),
     "seld_k_losses": (_I, [_P, _P, _P, _P, C.POINTER(LossCfg), _P, _P, _P, _P, _I, _I, _I]),
     "seld_k_adam": (_I, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _L]),
     "seld_k_losses_v2": (_I, [_P, _P, _P, _P, C.POINTER(V2Cfg), _P, _P, _P, _P, _I, _I, _I]),

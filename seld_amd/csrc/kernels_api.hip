@@ -432,6 +432,29 @@ int seld_k_gru_bwd(const float* dout, const float* h_f, const float* h_b, const 
     return done();
 }
 
+// the recurrent-dropout forms, as the training context launches them (forward.hip's forward_gru, backward.hip's backward_gru)
+int seld_k_gru_drop_fwd(const float* gx_f, const float* gx_b, const float* U_f, const float* U_b, const float* brec_f, const float* brec_b,
+                        const float* rm_f, const float* rm_b, float* h_f, float* h_b, float* hm_f, float* hm_b, float* saved_f, float* saved_b,
+                        int B, int S, int units) {
+    if (units != 128) return SELD_ERR_UNSUPPORTED;
+    if (!gx_f || !gx_b || !U_f || !U_b || !brec_f || !brec_b || !rm_f || !rm_b || !h_f || !h_b || !hm_f || !hm_b || !saved_f || !saved_b || B < 1 ||
+        S < 1)
+        return SELD_ERR_INVALID;
+    if (launch_gru_fwd(0, gx_f, gx_b, U_f, U_b, brec_f, brec_b, h_f, h_b, saved_f, saved_b, B, S, rm_f, rm_b, hm_f, hm_b)) return SELD_ERR_INVALID;
+    return done();
+}
+
+int seld_k_gru_drop_bwd(const float* dout, const float* h_f, const float* h_b, const float* hm_f, const float* hm_b, const float* saved_f,
+                        const float* saved_b, const float* U_f, const float* U_b, const float* rm_f, const float* rm_b, float* dgx_f, float* dgx_b,
+                        float* dgh_f, float* dgh_b, int B, int S, int units) {
+    if (units != 128) return SELD_ERR_UNSUPPORTED;
+    if (!dout || !h_f || !h_b || !hm_f || !hm_b || !saved_f || !saved_b || !U_f || !U_b || !rm_f || !rm_b || !dgx_f || !dgx_b || !dgh_f || !dgh_b ||
+        B < 1 || S < 1)
+        return SELD_ERR_INVALID;
+    if (launch_gru_bwd(0, dout, h_f, h_b, saved_f, saved_b, U_f, U_b, dgx_f, dgx_b, dgh_f, dgh_b, B, S, rm_f, rm_b, hm_f, hm_b)) return SELD_ERR_INVALID;
+    return done();
+}
+
 int seld_k_losses(const float* sed, const float* doa, const float* y_sed, const float* y_doa, const seld_loss_cfg* cfg,
                   float* sloss, float* dloss, float* dsed_pre, float* ddoa_pre, int B, int S, int nc) {
     if (!sed || !doa || !y_sed || !y_doa || !cfg || !sloss || !dloss) return SELD_ERR_INVALID;

@@ -41,14 +41,20 @@ def lstm_recurrence(gx, U, reverse: bool):
     return torch.stack(hs, 1), torch.stack(cs, 1)
 
 
-def gru_recurrence(gx, U, brec, reverse: bool, probe=None):
+def gru_recurrence(gx, U, brec, reverse: bool, probe=None, rec_mask=None, aux=None):
     """the step loop of oracle.seldnet_oracle.gru_direction from gx [B,S,3u] = x kernel + bias[0]; probe [B,S,3u] (zeros) is added to the recurrent-side
-    pre-activation h U + bias[1], so that its gradient is the kernels' dgh"""
+    pre-activation h U + bias[1], so that its gradient is the kernels' dgh.  rec_mask [B,u] (Keras recurrent_dropout; GRUCell.call, implementation
+    2, as gru_direction states it): the previous state is multiplied by the mask before the recurrent product AND before the blend; the emitted h[t]
+    is the unmasked state.  aux: a dict that receives what the kernels save for the backward pass, each [B,S,u]: z, r, hh and gh_h, the candidate
+    gate's recurrent pre-activation h_prev U_h + brec_h"""
     B, S, _ = gx.shape
     u = U.shape[0]
     h = gx.new_zeros(B, u)
     hs = [None] * S
+    kept = {k: [None] * S for k in ("z", "r", "hh", "gh_h")}
     for t in (range(S - 1, -1, -1) if reverse else range(S)):
+        if rec_mask is not None:
+            h = h * rec_mask
         gh = h @ U + brec
         if probe is not None:
             gh = gh + probe[:, t]
@@ -57,6 +63,10 @@ def gru_recurrence(gx, U, brec, reverse: bool, probe=None):
         hh = torch.tanh(gx[:, t, 2 * u:] + r * gh[:, 2 * u:])
         h = z * h + (1 - z) * hh
         hs[t] = h
+        for k, v in (("z", z), ("r", r), ("hh", hh), ("gh_h", gh[:, 2 * u:])):
+            kept[k][t] = v
+    if aux is not None:
+        aux.update({k: torch.stack(v, 1).detach() for k, v in kept.items()})
     return torch.stack(hs, 1)
 
 
@@ -84,6 +94,19 @@ UNI_CASE = (3, 17)
 SATURATED = (2, 10, 8.0)          # inputs x 8: |z| far in the gates' flat ends
 GRU_DH_CASES = [(2, 10), (1, 1)]
 GRU_MUL_CASE = (3, 60)
+# tests/test_gru_gpu.py: one below, at and one above one and two chunks of both GRU kernels; 53: a ragged tail behind 3 forward / 6 backward chunks
+GRU_EDGE_S = (2, 7, 8, 9, 15, 16, 17, 31, 32, 33, 53)
+GRU_EDGE_CASES = [(2, s) for s in GRU_EDGE_S] + [(3, 53)]
+GRU_BPTT_S = (8, 9, 17, 53)       # the backward kernels alone, on the oracle's own forward values
+# recurrent dropout.  Keras scales the masked state by 1 / (1 - rate) at every step: at rate 0.5 |h| grows without bound along the sequence (1.7e4 at
+# S = 17) and no fp32 evaluation stays near fp64, so the rate is 0.2 (tests/test_rnn_cpu.py holds |h| <= 4 and the fp32 margin for every case here)
+GRU_DROP_RATE = 0.2
+GRU_DROP_CASES = [(3, s) for s in (1, 9, 17, 33, 53)]
+GRU_DROP_AT_CHUNKS = [(2, s) for s in (8, 16, 32)]      # the same at the lengths that are whole chunks of both kernels
+GRU_DROP_BPTT_CASES = [(3, s) for s in GRU_BPTT_S]
+GRU_BATCH_CASE = (5, 17)          # every clip of a batch against that clip alone
+GRU_SMALLER_BATCH = (2, 17, 3)    # B, S, the batch the buffers are sized for
+GRU_SATURATED = (2, 17, 8.0)
 
 
 def recurrence_inputs(kind: str, B: int, S: int, scale: float = 1.0, seed: int = 0):
@@ -108,17 +131,85 @@ def lstm_reference(ins, dtype=torch.float64, dirs=(0, 1)):
     return out
 
 
-def gru_reference(ins, dtype=torch.float64, dirs=(0, 1), dh=None):
-    """-> {h, dgx, dgh: [per direction] numpy}; dh: the output gradients to use instead of ins['dh']"""
-    out = {"h": [], "dgx": [], "dgh": []}
+def gru_drop_masks(B: int, rate: float, seed: int = 0):
+    """-> float32 [2][B,128], 0 | 1 / (1 - rate): seeded numpy draws, one per direction (the mask values are an INPUT of the dropout kernels; the
+    library's own Philox draws are tests/test_model_gpu.py's subject)"""
+    rng = np.random.default_rng([B, U_, int(round(rate * 1000)), seed])
+    return f32(np.stack([(rng.random((B, U_)) >= rate) for _ in (0, 1)]) / (1.0 - rate))
+
+
+GRU_SAVED = ("z", "r", "hh", "gh_h")      # the planes of the kernels' saved gates [t][unit][4]
+
+
+def gru_reference(ins, dtype=torch.float64, dirs=(0, 1), dh=None, rec_mask=None, mul=False):
+    """-> {h, dgx, dgh, z, r, hh, gh_h: [per direction] numpy}; dh: the output gradients to use instead of ins['dh'].  rec_mask [2][B,128]: recurrent
+    dropout (see gru_recurrence), adds hm = h * rec_mask.  mul: the objective is (h_f h_b dout).sum() with dout = ins['dh'][0], the 'mul' merge of
+    seld_k_gru_bwd, and out = [h_f h_b] is returned too"""
+    out = {k: [] for k in ("h", "dgx", "dgh") + GRU_SAVED}
+    hs, leaves = [], []
     for d in dirs:
         gx = torch.tensor(ins["gx"][d], dtype=dtype, requires_grad=True)
         probe = torch.zeros_like(gx, requires_grad=True)
-        h = gru_recurrence(gx, torch.tensor(ins["U"][d], dtype=dtype), torch.tensor(ins["brec"][d], dtype=dtype), bool(d), probe)
-        go = torch.tensor((ins["dh"] if dh is None else dh)[d], dtype=dtype)
-        g, gp = torch.autograd.grad((h * go).sum(), (gx, probe))
-        out["h"].append(h.detach().numpy()); out["dgx"].append(g.numpy()); out["dgh"].append(gp.numpy())
+        aux = {}
+        m = None if rec_mask is None else torch.tensor(rec_mask[d], dtype=dtype)
+        h = gru_recurrence(gx, torch.tensor(ins["U"][d], dtype=dtype), torch.tensor(ins["brec"][d], dtype=dtype), bool(d), probe, m, aux)
+        hs.append(h); leaves += [gx, probe]
+        out["h"].append(h.detach().numpy())
+        for k in GRU_SAVED:
+            out[k].append(aux[k].numpy())
+        if m is not None:
+            out.setdefault("hm", []).append((h.detach() * m[:, None, :]).numpy())
+    if mul:
+        assert tuple(dirs) == (0, 1) and dh is None
+        y = hs[0] * hs[1]
+        out["out"] = [y.detach().numpy()]
+        grads = torch.autograd.grad((y * torch.tensor(ins["dh"][0], dtype=dtype)).sum(), leaves)
+    else:
+        grads = torch.autograd.grad(sum((h * torch.tensor((ins["dh"] if dh is None else dh)[d], dtype=dtype)).sum() for h, d in zip(hs, dirs)), leaves)
+    out["dgx"], out["dgh"] = [g.numpy() for g in grads[0::2]], [g.numpy() for g in grads[1::2]]
     return out
+
+
+def gru_saved(ref, i: int):
+    """the saved-gates tensor [B,S,128,4] of direction entry i of a gru_reference result, as the kernels lay it out"""
+    return np.stack([ref[k][i] for k in GRU_SAVED], -1)
+
+
+def gru_pieces(got, ref):
+    """everything in `got` beside its reference, per direction entry and PER GATE BLOCK, so that a small block cannot hide behind a large one: h, hm,
+    out whole; dgx, dgh by their z | r | h thirds; saved [B,S,128,4] by its four planes against ref's z, r, hh, gh_h.  -> [(name, got, ref)]"""
+    res = []
+    for k, arrs in got.items():
+        for i, a in enumerate(arrs):
+            a = np.asarray(a)
+            if k in ("h", "hm", "out"):
+                res.append((f"{k}[{i}]", a, ref[k][i]))
+            elif k in ("dgx", "dgh"):
+                for g, gate in enumerate("zrh"):
+                    res.append((f"{k}[{i}].{gate}", a[..., g * U_:(g + 1) * U_], ref[k][i][..., g * U_:(g + 1) * U_]))
+            elif k == "saved":
+                a = a.reshape(ref["z"][i].shape + (4,))
+                for g, plane in enumerate(GRU_SAVED):
+                    res.append((f"saved[{i}].{plane}", a[..., g], ref[plane][i]))
+            else:
+                raise KeyError(k)
+    for name, a, b in res:
+        assert a.shape == np.asarray(b).shape, f"{name}: {a.shape} against {np.asarray(b).shape}"
+    return res
+
+
+def gru_compare(tag, got, ref, tol):
+    """helpers.check (max|d| / max|ref| <= tol, finite) on every piece of gru_pieces(got, ref); every piece is measured and printed before the
+    failures are raised together.  -> {piece: error}"""
+    from helpers import check, rel_err
+    bad = []
+    for name, a, b in gru_pieces(got, ref):
+        try:
+            check(f"{tag} {name}", a, b, tol)
+        except AssertionError as e:
+            bad.append(str(e))
+    assert not bad, "; ".join(bad)
+    return {name: rel_err(a, b) for name, a, b in gru_pieces(got, ref)}
 
 
 def merge_inputs(rows: int, units: int, mode: str):

@@ -14,7 +14,8 @@ from conftest import ROOT
 from helpers import rel_err
 from oracle import seldnet_oracle as O
 
-NEW_SYMBOLS = ("seld_rnn_lstm_fwd", "seld_rnn_lstm_bwd", "seld_rnn_gru_fwd", "seld_rnn_gru_bwd", "seld_rnn_merge_fwd", "seld_rnn_merge_bwd")
+NEW_SYMBOLS = ("seld_rnn_lstm_fwd", "seld_rnn_lstm_bwd", "seld_rnn_gru_fwd", "seld_rnn_gru_bwd", "seld_rnn_merge_fwd", "seld_rnn_merge_bwd",
+               "seld_k_gru_drop_fwd", "seld_k_gru_drop_bwd")
 FP32_MARGIN = 5e-5
 
 
@@ -83,6 +84,97 @@ def test_gru_probe_gradient_is_the_recurrent_side_gradient():
             hp[:, :-1] = hh[:, 1:]
         assert rel_err(np.einsum("bsu,bsg->ug", hp, dgh), gU.numpy()) <= 1e-10
         assert rel_err(dgh.sum((0, 1)), gb.numpy()) <= 1e-10
+
+
+def test_masked_gru_recurrence_matches_the_oracle_gru_direction():
+    """recurrent dropout: R.gru_recurrence(rec_mask=...) against oracle.seldnet_oracle.gru_direction(rec_mask=...), the restatement of Keras
+    GRUCell.call that the model tests run on; and what it hands out as the saved gates rebuilds h from the MASKED previous state"""
+    torch.manual_seed(2)
+    B, S, D, u = 3, 9, 20, 128
+    x = torch.randn(B, S, D, dtype=torch.float64, requires_grad=True)
+    dy = torch.randn(B, S, u, dtype=torch.float64)
+    k, r, b = torch.randn(D, 3 * u, dtype=torch.float64) / D ** 0.5, torch.randn(u, 3 * u, dtype=torch.float64) / u ** 0.5, 0.1 * torch.randn(2, 3 * u, dtype=torch.float64)
+    m = torch.tensor(R.gru_drop_masks(B, 0.5)[0], dtype=torch.float64)
+    assert 0.2 < float((m == 0).double().mean()) < 0.8
+    for rev in (False, True):
+        want = O.gru_direction(x, k, r, b, rev, rec_mask=m)
+        aux = {}
+        mine = R.gru_recurrence(x @ k + b[0], r, b[1], rev, rec_mask=m, aux=aux)
+        (gw,), (gm,) = torch.autograd.grad((want * dy).sum(), x), torch.autograd.grad((mine * dy).sum(), x)
+        assert rel_err(mine.detach().numpy(), want.detach().numpy()) <= 1e-10
+        assert rel_err(gm.numpy(), gw.numpy()) <= 1e-10
+        assert rel_err(mine.detach().numpy(), O.gru_direction(x, k, r, b, rev).detach().numpy()) > 1e-2      # the mask matters
+        h = mine.detach()
+        hp = torch.zeros_like(h)      # the masked previous state
+        if rev:
+            hp[:, :-1] = h[:, 1:] * m[:, None, :]
+        else:
+            hp[:, 1:] = h[:, :-1] * m[:, None, :]
+        assert rel_err((aux["z"] * hp + (1 - aux["z"]) * aux["hh"]).numpy(), h.numpy()) <= 1e-12
+        assert rel_err(aux["gh_h"].numpy(), (hp @ r + b[1])[..., 2 * u:].numpy()) <= 1e-12
+        assert rel_err(aux["hh"].numpy(), torch.tanh((x @ k + b[0])[..., 2 * u:] + aux["r"] * aux["gh_h"]).detach().numpy()) <= 1e-12
+
+
+def _gru_steps_fp32(ins, d, mask=None, fault=None):
+    """a plain numpy fp32 step loop of one direction -> (h, hm, saved [B,S,128,4]), with one deliberate mistake of the kind a kernel could make:
+    'border': h_prev is taken from the wrong neighbour at ONE step, the first of the forward kernel's second chunk (t = 16 in the forward
+    direction, t = S - 17 in the reverse one); 'swap': z and r change places in the saved gates; 'blend': the blend uses the unmasked state"""
+    gx, U, brec = ins["gx"][d], ins["U"][d], ins["brec"][d]
+    B, S, _ = gx.shape
+    u = 128
+    sig = lambda a: (1 / (1 + np.exp(-a, dtype=np.float32))).astype(np.float32)
+    hs, sv = np.zeros((B, S, u), np.float32), np.zeros((B, S, u, 4), np.float32)
+    h = np.zeros((B, u), np.float32)
+    order = list(range(S - 1, -1, -1) if d else range(S))
+    for n, t in enumerate(order):
+        raw = h
+        if fault == "border" and n == 16:
+            raw = hs[:, order[n - 2]]
+        hp = raw if mask is None else raw * mask[d]
+        gh = hp @ U + brec
+        z, r = sig(gx[:, t, :u] + gh[:, :u]), sig(gx[:, t, u:2 * u] + gh[:, u:2 * u])
+        hh = np.tanh(gx[:, t, 2 * u:] + r * gh[:, 2 * u:])
+        h = z * (raw if fault == "blend" else hp) + (1 - z) * hh
+        hs[:, t] = h
+        sv[:, t] = np.stack([r, z, hh, gh[:, 2 * u:]] if fault == "swap" else [z, r, hh, gh[:, 2 * u:]], -1)
+    return hs, (hs if mask is None else hs * mask[d][:, None, :]), sv
+
+
+@pytest.mark.parametrize("fault", [None, "border", "swap", "blend"])
+def test_the_gru_comparison_can_fail(fault):
+    """R.gru_compare, the function tests/test_gru_gpu.py holds the kernels to, passes a correct fp32 evaluation and reports each wrong one above the
+    GPU tests' 1e-4"""
+    B, S = 3, 33
+    ins = R.recurrence_inputs("gru", B, S)
+    masks = R.gru_drop_masks(B, R.GRU_DROP_RATE) if fault == "blend" else None
+    ref = R.gru_reference(ins, rec_mask=masks)
+    if fault is None:
+        R.gru_compare("fp32 oracle", _as_kernel_outputs(R.gru_reference(ins, torch.float32)), ref, 1e-4)
+        masks = R.gru_drop_masks(B, R.GRU_DROP_RATE)
+        ref_m = R.gru_reference(ins, rec_mask=masks)
+        R.gru_compare("fp32 oracle, masked", _as_kernel_outputs(R.gru_reference(ins, torch.float32, rec_mask=masks)), ref_m, 1e-4)
+        for m, rf in ((None, ref), (masks, ref_m)):      # the step loop that carries the mistakes below is right without them
+            runs = [_gru_steps_fp32(ins, d, m) for d in (0, 1)]
+            got = {"h": [x[0] for x in runs], "saved": [x[2] for x in runs]}
+            if m is not None:
+                got["hm"] = [x[1] for x in runs]
+            R.gru_compare("fp32 step loop", got, rf, 1e-4)
+        return
+    for d in (0, 1):
+        h, hm, sv = _gru_steps_fp32(ins, d, masks, fault)
+        got = {"h": [h], "saved": [sv]}
+        one = {k: [v[d]] for k, v in ref.items()}
+        with pytest.raises(AssertionError, match="rel err"):
+            R.gru_compare(f"{fault}[{d}]", got, one, 1e-4)
+        errs = {n: rel_err(a, b) for n, a, b in R.gru_pieces(got, one)}
+        if fault == "swap":      # h is right; the two planes alone are wrong
+            assert errs["h[0]"] <= FP32_MARGIN and errs["saved[0].z"] > 1e-4 and errs["saved[0].r"] > 1e-4 and errs["saved[0].hh"] <= FP32_MARGIN
+        else:
+            assert errs["h[0]"] > 1e-4, errs
+        if fault == "border":      # one step alone is wrong, and what follows it
+            t = 16 if d == 0 else S - 17
+            before = slice(0, t) if d == 0 else slice(t + 1, S)
+            assert rel_err(h[:, before], ref["h"][d][:, before]) <= FP32_MARGIN and rel_err(h[:, t], ref["h"][d][:, t]) > 1e-4
 
 
 @pytest.mark.parametrize("mode", R.MERGES)
@@ -183,13 +275,96 @@ def test_fp32_margin_of_the_lstm_cases(B, S, scale):
             _margin(f"lstm {(B, S, scale)} {k}[{d}]", a[k][d], b[k][d])
 
 
-@pytest.mark.parametrize("B,S", R.GRU_DH_CASES + [R.GRU_MUL_CASE, R.UNI_CASE])
+def _as_kernel_outputs(ref):
+    """a gru_reference result in the shape the GPU tests hand to R.gru_compare: the four saved quantities as one [B,S,128,4] tensor per direction"""
+    got = {k: v for k, v in ref.items() if k not in R.GRU_SAVED}
+    got["saved"] = [R.gru_saved(ref, i) for i in range(len(ref["h"]))]
+    return got
+
+
+def _gru_margin(tag, ins, **kw):
+    """fp32 against fp64 through the GPU tests' own comparison (per direction, per gate block) at FP32_MARGIN; -> the fp64 result"""
+    a, b = R.gru_reference(ins, torch.float32, **kw), R.gru_reference(ins, **kw)
+    R.gru_compare(tag, _as_kernel_outputs(a), b, FP32_MARGIN)
+    return b
+
+
+GRU_PLAIN_CASES = sorted(set(R.GRU_DH_CASES + [R.GRU_MUL_CASE, R.UNI_CASE, R.GRU_BATCH_CASE, R.GRU_SMALLER_BATCH[:2]] + R.GRU_EDGE_CASES))
+
+
+@pytest.mark.parametrize("B,S", GRU_PLAIN_CASES)
 def test_fp32_margin_of_the_gru_cases(B, S):
+    """every (B, S) of tests/test_rnn_gpu.py and tests/test_gru_gpu.py without dropout, with the directions' output gradients as given and with the
+    'mul' merge's: h, out, the saved gates, dgx, dgh"""
     ins = R.recurrence_inputs("gru", B, S)
-    a, b = R.gru_reference(ins, torch.float32), R.gru_reference(ins)
+    a, b = R.gru_reference(ins, torch.float32), _gru_margin(f"gru dh {(B, S)}", ins)
     for k in ("h", "dgx", "dgh"):
         for d in (0, 1):
             _margin(f"gru {(B, S)} {k}[{d}]", a[k][d], b[k][d])
+    _gru_margin(f"gru mul {(B, S)}", ins, mul=True)
+
+
+def test_fp32_margin_of_the_saturated_gru_case():
+    B, S, scale = R.GRU_SATURATED
+    ins = R.recurrence_inputs("gru", B, S, scale)
+    assert np.abs(ins["gx"]).max() > 30
+    _gru_margin(f"gru dh x{scale}", ins)
+    _gru_margin(f"gru mul x{scale}", ins, mul=True)
+
+
+@pytest.mark.parametrize("B,S", sorted(set(R.GRU_DROP_CASES + R.GRU_DROP_AT_CHUNKS + R.GRU_DROP_BPTT_CASES + [R.GRU_BATCH_CASE])))
+def test_fp32_margin_of_the_gru_dropout_cases(B, S):
+    """Keras scales the masked state by 1 / (1 - rate) at every step, so |h| is not bounded by 1 under recurrent dropout: the rate and the lengths
+    of the cases are those at which the state stays small (|h| <= 4 in fp64) and fp32 stays within the margin"""
+    ins, masks = R.recurrence_inputs("gru", B, S), R.gru_drop_masks(B, R.GRU_DROP_RATE)
+    assert set(np.unique(masks)) == {0.0, np.float32(1 / (1 - R.GRU_DROP_RATE))} and (masks == 0).any(-1).all()      # every clip drops a unit
+    b = _gru_margin(f"gru dropout {(B, S)}", ins, rec_mask=masks, mul=True)
+    assert max(np.abs(h).max() for h in b["h"]) <= 4
+    for d in (0, 1):
+        assert np.array_equal(b["hm"][d], b["h"][d] * masks[d][:, None, :].astype(np.float64))
+
+
+def _bptt_fp32(ref, ins, d, dh, mask=None):
+    """the backward pass alone, as tests/test_gru_gpu.py's isolated test feeds the kernels: a plain numpy fp32 BPTT of direction d (the equations at
+    the head of gru.hip's backward kernel) on the fp64 oracle's h, hm and saved quantities rounded to fp32 -> dgx, dgh [B,S,384]"""
+    f = np.float32
+    z, r, hh, gh = (R.f32(ref[k][d]) for k in R.GRU_SAVED)
+    hprev_src = R.f32(ref["hm" if mask is not None else "h"][d])
+    U, dh = R.f32(ins["U"][d]), R.f32(dh)
+    B, S, u = z.shape
+    dgx, dgh = np.zeros((B, S, 3 * u), f), np.zeros((B, S, 3 * u), f)
+    carry = np.zeros((B, u), f)
+    for t in (range(S) if d else range(S - 1, -1, -1)):      # the forward's processing order, backwards
+        tp = t + 1 if d else t - 1
+        hp = hprev_src[:, tp] if 0 <= tp < S else np.zeros((B, u), f)
+        g = dh[:, t] + carry
+        a_h = g * (1 - z[:, t]) * (1 - hh[:, t] * hh[:, t])
+        a_z = g * (hp - hh[:, t]) * z[:, t] * (1 - z[:, t])
+        a_r = a_h * gh[:, t] * r[:, t] * (1 - r[:, t])
+        dgx[:, t] = np.concatenate([a_z, a_r, a_h], -1)
+        dgh[:, t] = np.concatenate([a_z, a_r, a_h * r[:, t]], -1)
+        carry = g * z[:, t] + dgh[:, t] @ U.T
+        if mask is not None:
+            carry = carry * mask[d]
+        assert carry.dtype == f
+    return dgx, dgh
+
+
+@pytest.mark.parametrize("S", R.GRU_BPTT_S)
+def test_fp32_margin_of_the_isolated_bptt_cases(S):
+    B = 2
+    ins = R.recurrence_inputs("gru", B, S)
+    ref = R.gru_reference(ins)
+    runs = [_bptt_fp32(ref, ins, d, ins["dh"][d]) for d in (0, 1)]
+    R.gru_compare(f"bptt dh {(B, S)}", {"dgx": [x[0] for x in runs], "dgh": [x[1] for x in runs]}, ref, FP32_MARGIN)
+    ref = R.gru_reference(ins, mul=True)
+    runs = [_bptt_fp32(ref, ins, d, ins["dh"][0] * R.f32(ref["h"][1 - d])) for d in (0, 1)]
+    R.gru_compare(f"bptt mul {(B, S)}", {"dgx": [x[0] for x in runs], "dgh": [x[1] for x in runs]}, ref, FP32_MARGIN)
+    B = R.GRU_DROP_BPTT_CASES[0][0]
+    ins, masks = R.recurrence_inputs("gru", B, S), R.gru_drop_masks(B, R.GRU_DROP_RATE)
+    ref = R.gru_reference(ins, rec_mask=masks, mul=True)
+    runs = [_bptt_fp32(ref, ins, d, ins["dh"][0] * R.f32(ref["h"][1 - d]), masks) for d in (0, 1)]
+    R.gru_compare(f"bptt drop {(B, S)}", {"dgx": [x[0] for x in runs], "dgh": [x[1] for x in runs]}, ref, FP32_MARGIN)
 
 
 @pytest.mark.parametrize("name", sorted(R.STAGE_CASES))
