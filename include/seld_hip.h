@@ -355,6 +355,20 @@ int64_t seld_dcase_update_scratch_bytes(int64_t N, int n_files, int block_size);
 int seld_dcase_update(const float* sed, const float* doa, const float* sed_thresh, const double* gt_xyz, const uint8_t* gt_slot,
                       const int32_t* gt_n, const int32_t* file_off, int n_files, int n_classes, int K, int block_size, double doa_threshold,
                       double* state, void* scratch, void* stream);
+/* the per-class threshold sweep: table [n_classes * n_cand + 1][11] doubles (device).  Row c * n_cand + k holds the eleven counters, in
+ * seld_dcase_update's order, for the threshold vector base_thresh [nc] (device) with entry c replaced by cand[k] (cand [n_cand], device);
+ * the last row is base_thresh itself.  The table is overwritten.  Every row has the bits seld_dcase_update leaves in a zeroed state
+ * for that vector: the distances and the arg-min slots do not depend on a threshold and are computed once per (segment, class), and
+ * total_DE is added in that call's order (classes, then slots, ascending within a segment; seld_dcase_update's reduction over the
+ * segments).  Candidates may repeat and come in any order; active iff sed > threshold in fp32.  No atomics.  `scratch` =
+ * seld_dcase_sweep_scratch_bytes(N, n_files, nc, n_cand, block_size) bytes (device, 8-byte aligned), linear in
+ * segments * nc * (n_cand + 1).  The refusals and the one copy of seld_dcase_update, and SELD_ERR_INVALID (-1 from the scratch
+ * function) for n_cand outside 1..SELD_DCASE_MAX_CAND or a NULL cand or table. */
+#define SELD_DCASE_MAX_CAND 16
+int64_t seld_dcase_sweep_scratch_bytes(int64_t N, int n_files, int n_classes, int n_cand, int block_size);
+int seld_dcase_sweep(const float* sed, const float* doa, const float* base_thresh, const float* cand, const double* gt_xyz,
+                     const uint8_t* gt_slot, const int32_t* gt_n, const int32_t* file_off, int n_files, int n_classes, int K, int n_cand,
+                     int block_size, double doa_threshold, double* table, void* scratch, void* stream);
 /* the tf.where + gather of utils.write_answer (utils.py:249-264) for every file at once: the active (frame-in-file, class) pairs in
  * row-major order, file after file, and class c's DOA vector beside each.  row_fc int32 [cap, 2], row_xyz fp32 [cap, 3] with
  * cap = N nc; row_off int32 [n_files + 1]: file f's rows are [row_off[f], row_off[f + 1]).  All three on the device.  `scratch` =

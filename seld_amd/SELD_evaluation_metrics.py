@@ -1,7 +1,8 @@
 """Host-side mirror of the reference's SELD_evaluation_metrics.py: the segment-based, location-aware DCASE score.  The eleven counters
 live on the device and seld_dcase_update (seld_amd/csrc/dcase.hip) accumulates all files of a call in one pass over the ensembled
 outputs, where the reference scores a file at a time from nested dicts read back from a csv file (SELD_evaluation_metrics.py:63-154).
-`compute_seld_scores` reads the eleven doubles."""
+`compute_seld_scores` reads the eleven doubles.  `sweep_seld_scores` (seld_dcase_sweep) returns the counters of every single-class
+threshold change in one call: what seld_amd/search_best.py descends on."""
 from __future__ import annotations
 
 import ctypes as C
@@ -38,10 +39,8 @@ class SELDMetrics_(object):
     def reset_states(self):
         self.state.zero_()
 
-    def update_seld_scores(self, pred, gt, sed_thresh=0.5):
-        """pred: (sed [T, nc], doa [T, 3nc]) device tensors of one file, or a list of such pairs; gt: what utils.pack_labels returned for
-        that file, a list of those, or utils.concat_labels of the list (packed and uploaded once, scored many times).  A class is active
-        where sed > sed_thresh (a scalar or a per-class sequence).  All files are scored in one seld_dcase_update call."""
+    def _inputs(self, pred, gt):
+        """the checks and device tensors update_seld_scores and sweep_seld_scores share -> (sed, doa, gt, n_files)"""
         if isinstance(pred, (list, tuple)) and len(pred) == 2 and isinstance(pred[0], torch.Tensor):
             pred = [pred]
         pred = list(pred)
@@ -62,16 +61,49 @@ class SELDMetrics_(object):
         dev = self._dev
         sed = torch.cat([torch.as_tensor(s, dtype=torch.float32, device=dev) for s, _ in pred]).contiguous()
         doa = torch.cat([torch.as_tensor(d, dtype=torch.float32, device=dev) for _, d in pred]).contiguous()
+        return sed, doa, gt, len(pred)
+
+    def _scratch_of(self, need):
+        if self._scratch is None or self._scratch.numel() * 8 < need:
+            self._scratch = torch.empty((need + 7) // 8, dtype=torch.int64, device=self._dev)
+        return self._scratch
+
+    def update_seld_scores(self, pred, gt, sed_thresh=0.5):
+        """pred: (sed [T, nc], doa [T, 3nc]) device tensors of one file, or a list of such pairs; gt: what utils.pack_labels returned for
+        that file, a list of those, or utils.concat_labels of the list (packed and uploaded once, scored many times).  A class is active
+        where sed > sed_thresh (a scalar or a per-class sequence).  All files are scored in one seld_dcase_update call."""
+        sed, doa, gt, n_files = self._inputs(pred, gt)
+        nc, dev = self._nb_classes, self._dev
         xyz, slot, n = gt.to_device(dev)
         thr = torch.as_tensor(utils.thresh_table(sed_thresh, nc)).to(dev)
-        n_files = len(pred)
-        need = int(self.lib.seld_dcase_update_scratch_bytes(gt.n_frames, n_files, utils.SEGMENT_FRAMES))
-        if self._scratch is None or self._scratch.numel() * 8 < need:
-            self._scratch = torch.empty((need + 7) // 8, dtype=torch.int64, device=dev)
+        scratch = self._scratch_of(int(self.lib.seld_dcase_update_scratch_bytes(gt.n_frames, n_files, utils.SEGMENT_FRAMES)))
         st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         _lib.check(self.lib.seld_dcase_update(sed.data_ptr(), doa.data_ptr(), thr.data_ptr(), xyz.data_ptr(), slot.data_ptr(), n.data_ptr(),
                                               gt.file_off.ctypes.data_as(C.POINTER(C.c_int32)), n_files, nc, gt.K, utils.SEGMENT_FRAMES,
-                                              self._spatial_T, self.state.data_ptr(), self._scratch.data_ptr(), st))
+                                              self._spatial_T, self.state.data_ptr(), scratch.data_ptr(), st))
+
+    def sweep_seld_scores(self, pred, gt, base_thresh, candidates):
+        """One seld_dcase_sweep call over `pred` and `gt` (as update_seld_scores takes them) -> (table float64 [nc, M, 11], base float64 [11]),
+        numpy: table[c, k] holds the counters update_seld_scores would leave in a fresh state for `base_thresh` (a scalar or a per-class
+        sequence) with class c's entry replaced by candidates[k], bit for bit; `base` those of base_thresh itself.  self.state is not touched."""
+        sed, doa, gt, n_files = self._inputs(pred, gt)
+        nc, dev = self._nb_classes, self._dev
+        cand = np.ascontiguousarray(np.asarray(candidates, np.float32).reshape(-1))
+        M = int(cand.size)
+        need = int(self.lib.seld_dcase_sweep_scratch_bytes(gt.n_frames, n_files, nc, M, utils.SEGMENT_FRAMES))
+        if need < 0:
+            raise ValueError(f"sweep_seld_scores: {M} candidates (1..16 are swept at once), or outputs past 32-bit indexing")
+        xyz, slot, n = gt.to_device(dev)
+        thr = torch.as_tensor(utils.thresh_table(base_thresh, nc)).to(dev)
+        cand_d = torch.as_tensor(cand).to(dev)
+        table = torch.empty((nc * M + 1, self.state.numel()), dtype=torch.float64, device=dev)
+        scratch = self._scratch_of(need)
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(self.lib.seld_dcase_sweep(sed.data_ptr(), doa.data_ptr(), thr.data_ptr(), cand_d.data_ptr(), xyz.data_ptr(), slot.data_ptr(),
+                                             n.data_ptr(), gt.file_off.ctypes.data_as(C.POINTER(C.c_int32)), n_files, nc, gt.K, M,
+                                             utils.SEGMENT_FRAMES, self._spatial_T, table.data_ptr(), scratch.data_ptr(), st))
+        out = table.cpu().numpy()
+        return out[:-1].reshape(nc, M, -1), out[-1].copy()
 
     def counters(self) -> dict:
         return dict(zip(STATE_NAMES, self.state.cpu().numpy().tolist()))

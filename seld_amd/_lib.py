@@ -141,6 +141,8 @@ SIGNATURES = {
     "seld_dcase_state_size": (_I, []),
     "seld_dcase_update_scratch_bytes": (_L, [_L, _I, _I]),
     "seld_dcase_update": (_I, [_P, _P, _P, _P, _P, _P, C.POINTER(C.c_int32), _I, _I, _I, _I, C.c_double, _P, _P, _P]),
+    "seld_dcase_sweep_scratch_bytes": (_L, [_L, _I, _I, _I, _I]),
+    "seld_dcase_sweep": (_I, [_P, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_int32), _I, _I, _I, _I, _I, C.c_double, _P, _P, _P]),
     "seld_answer_rows_scratch_bytes": (_L, [_L, _I, _I]),
     "seld_answer_rows": (_I, [_P, _P, _P, C.POINTER(C.c_int32), _I, _I, _P, _P, _P, _P, _P]),
     "seld_profile_enable": (_I, [_P, _I]),

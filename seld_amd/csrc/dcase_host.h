@@ -6,8 +6,19 @@
 
 #define SELD_DCASE_STATE 11
 #define SELD_DCASE_MAX_BLOCK 32
+#define SELD_DCASE_SWEEP_SLOTS 8          // SELD_DCASE_MAX_SLOTS: track averages kept per (segment, class, threshold)
 
 namespace dcase_host {
+
+// seld_dcase_sweep's own arguments: 1..max_cand candidates (SELD_DCASE_MAX_CAND), a candidate list and a table to write
+inline bool sweep_args_ok(int n_cand, int max_cand, const void* cand, const void* table) {
+    return n_cand >= 1 && n_cand <= max_cand && cand != nullptr && table != nullptr;
+}
+
+// bytes of the sweep's per-(segment, class, threshold) records for `segs` segments: one packed counter word and the track averages
+inline int64_t sweep_record_bytes(int64_t segs, int n_classes, int n_cand) {
+    return segs * n_classes * (int64_t)(n_cand + 1) * (1 + SELD_DCASE_SWEEP_SLOTS) * 8;
+}
 
 // file_off[0] == 0 and strictly ascending (every file has a frame); -> N = file_off[n_files], or -1
 inline int64_t total_frames(const int32_t* file_off, int n_files) {

@@ -2,7 +2,10 @@
 
   1. HIP events around SELDMetrics_.update_seld_scores + utils.answer_rows for --files files of 600 label frames and 12 classes
      (random activity and reference tracks, labels packed and uploaded beforehand);
-  2. the wall time of one trainv2 evaluate_fn on one [3000, 64, 7] clip with the small SS5 configuration of the tests.
+  2. the wall time of one trainv2 evaluate_fn on one [3000, 64, 7] clip with the small SS5 configuration of the tests;
+  3. HIP events around one SELDMetrics_.sweep_seld_scores (12 classes, search_best.BASE_THRESHOLD on a flat 0.5 table) on the files of 1.,
+     and around the loop it replaces: the same 97 threshold vectors through update_seld_scores, one call each from a reset state, the
+     states kept on the device and copied to the host once.  The two are timed alternately.
 
 python tools/bench_dcase.py [--files 100] [--reps 20]  -> one JSON line
 """
@@ -65,8 +68,46 @@ def main():
     fn(model, 1)
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
+    from seld_amd import search_best
+    cand = search_best.BASE_THRESHOLD
+    vectors = []
+    for c in range(nc):
+        for v in cand:
+            vectors.append(utils.thresh_table(0.5, nc))
+            vectors[-1][c] = v
+    vectors.append(utils.thresh_table(0.5, nc))
+
+    def sweep():
+        return m.sweep_seld_scores(outs, packed, 0.5, cand)
+
+    def loop():
+        states = []
+        for v in vectors:
+            m.reset_states()
+            m.update_seld_scores(outs, packed, v)
+            states.append(m.state.clone())
+        return torch.stack(states).cpu().numpy()
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        out = fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1), out
+    sw, lp = [], []
+    for i in range(a.reps + 3):
+        t_s, (table, base) = timed(sweep)
+        t_l, states = timed(loop)
+        sw.append(t_s)
+        lp.append(t_l)
+    same = bool(np.array_equal(np.concatenate([table.reshape(-1, 11), base[None]]).view(np.uint64), states.view(np.uint64)))
+    sw, lp = np.array(sw[3:]), np.array(lp[3:])
     print(json.dumps({"files": a.files, "frames": T, "classes": nc, "reps": a.reps, "score_and_rows_ms_median": float(np.median(ms)),
-                      "p10": float(np.percentile(ms, 10)), "p90": float(np.percentile(ms, 90)), "evaluate_fn_wall_s": wall}))
+                      "p10": float(np.percentile(ms, 10)), "p90": float(np.percentile(ms, 90)), "evaluate_fn_wall_s": wall,
+                      "candidates": len(cand), "sweep_ms_median": float(np.median(sw)), "sweep_p10": float(np.percentile(sw, 10)),
+                      "sweep_p90": float(np.percentile(sw, 90)), "loop97_ms_median": float(np.median(lp)),
+                      "loop97_p10": float(np.percentile(lp, 10)), "loop97_p90": float(np.percentile(lp, 90)), "sweep_equals_loop_bits": same}))
 
 
 if __name__ == "__main__":
