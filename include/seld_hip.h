@@ -326,6 +326,19 @@ int seld_aug_gather_sign(float* x, int B, int64_t outer, int R, int64_t inner, c
  *   SELD_ERR_UNSUPPORTED for F * C > 16384. */
 int seld_aug_v2(float* x, int B, int T, int F, int C, int period, const float* shift, int n_shift_ch, const int* t_off, const int* t_size,
                 int n_t, const int* f_off, const int* f_size, int n_f, void* stream);
+/* seld_aug_mcs: transforms.mcs_aug (transforms.py:202-291, with its tf_cond / is_invertible / stab helpers), the CGMM mask estimator, in
+ *   ONE launch over x [B,T,F,C] float32: per (b, f) column, in float64, the covariance initialisation, `iteration` EM rounds and
+ *   out[b,t,f,:] = x[b,t,f,:] * float32(lambda_noise[b,t,f]) of the last round (the product in fp32).  `out` may be x itself (in place); any
+ *   other overlap is the caller's error.  lambda (nullable) receives lambda_noise as [B,T,F] doubles; stab_adds (nullable) receives, as
+ *   int32 [B,F,2,iteration+1], the number of diagonal additions (0..6) of every stab call: class noisy then class noise, the
+ *   initialisation's call first.  Fixed summation order, no atomics: two calls give the same bits.  Asynchronous on `stream`, no allocation,
+ *   no host synchronisation.  Before anything is enqueued: SELD_ERR_INVALID for a NULL x or out, B, T or F < 1, iteration < 1 (the
+ *   reference's function has no result there), a theta that is negative or not finite; SELD_ERR_UNSUPPORTED for C outside 1..10 and for
+ *   T > seld_aug_mcs_max_frames(C).  Non-finite inputs are outside the contract: that column's output is unspecified.
+ * seld_aug_mcs_max_frames: the largest T the kernel holds on chip for this C (>= 3000 for every C <= 10); 0 for an unsupported C. */
+int seld_aug_mcs_max_frames(int C);
+int seld_aug_mcs(const float* x, float* out, double* lambda, int32_t* stab_adds, int B, int T, int F, int C, int iteration, double theta,
+                 void* stream);
 
 /* ---- SELD metrics on the device: SELDMetrics.update_states (metrics.py:60-154), which the reference runs in TF
  * eager mode on the host after every step (train.py:82-83).  `state` = seld_metrics_state_size(nc) doubles

@@ -13,7 +13,8 @@ flip ~ U{0,1}^3, swap ~ U{0,2}, acs index ~ U{0..7}) and only the small tables g
   random_ups_and_downs(x, rng)                             trainv2.py:120-124   one N(0, 0.2^2) shift per sample on the first 4 channels
   v2_sample_transforms(x, rng, time, freq, period)         trainv2.py:133-140   that shift, 10 time masks and 6 frequency masks in ONE
                                                                                pass (seld_aug_v2)
-mcs_aug (CGMM mask estimation in float64, transforms.py:237-292) is outside the accelerated path."""
+  mcs_aug(iteration, theta)(x, y)                           transforms.py:202-291   CGMM mask estimation in float64, one kernel for the whole
+                                                                               function (seld_aug_mcs); mcs_mask returns the mask itself"""
 from __future__ import annotations
 
 import collections
@@ -250,3 +251,49 @@ def acs_aug(x, y, rng=None, draws=None):
     nc = y.shape[-1] // 4
     _gather_sign(y, B, int(np.prod(y.shape[1:-1])), 4, nc, y_src, y_sgn)
     return x, y
+
+
+def _mcs_input(x):
+    """the shape the kernel holds on chip, judged by the library before the tensor itself is"""
+    if not isinstance(x, torch.Tensor) or x.dim() != 4:
+        raise ValueError("mcs_aug: x must be a [B,T,F,C] tensor")
+    max_frames = _lib.load().seld_aug_mcs_max_frames(int(x.shape[3]))
+    if max_frames == 0 or x.shape[1] > max_frames:
+        raise ValueError(f"mcs_aug: x {tuple(x.shape)}: 1..10 channels" + (f" and at most {max_frames} frames" if max_frames else ""))
+    return _dev_tensor(x, "x")
+
+
+def _mcs(x, out, lam, adds, iteration, theta):
+    B, T, F, Cc = x.shape
+    rc = _lib.load().seld_aug_mcs(_ptr(x), _ptr(out), _ptr(lam), _ptr(adds), B, T, F, Cc, int(iteration), float(theta), _stream())
+    if rc in (-1, -2):
+        raise ValueError(f"mcs_aug: {_lib.ERR_NAMES[rc]} for x {tuple(x.shape)}, iteration {iteration}, theta {theta}: needs iteration >= 1, a finite "
+                         f"theta >= 0, 1..10 channels and at most seld_aug_mcs_max_frames(C) frames")
+    if rc:
+        raise _lib.SeldError(rc, "seld_aug_mcs failed")
+
+
+def mcs_aug(iteration: int, theta=1e-6):
+    """transforms.mcs_aug (transforms.py:231-291): _mcs_aug(x, y) -> (x, y) multiplies x [B,T,F,C] (device), in place, by the noise mask of a
+    two-class complex-Gaussian mixture model fitted per (sample, frequency bin) in float64 over `iteration` EM rounds; y is returned untouched."""
+    if int(iteration) < 1:
+        raise ValueError("mcs_aug: iteration must be at least 1 (the reference's function has no result otherwise)")
+
+    def _mcs_aug(x, y):
+        _mcs(_mcs_input(x), x, None, None, iteration, theta)
+        return x, y
+    return _mcs_aug
+
+
+def mcs_mask(x, iteration, theta=1e-6):
+    """-> (lambda_noise [B,T,F] float64, stab_adds [B,F,2,iteration+1] int32: the diagonal additions of every stab call, class noisy then class
+    noise, the initialisation's call first).  x [B,T,F,C] (device) is left alone."""
+    if int(iteration) < 1:
+        raise ValueError("mcs_mask: iteration must be at least 1")
+    x = _mcs_input(x)
+    B, T, F, _ = x.shape
+    out = torch.empty_like(x)
+    lam = torch.empty((B, T, F), dtype=torch.float64, device=x.device)
+    adds = torch.empty((B, F, 2, int(iteration) + 1), dtype=torch.int32, device=x.device)
+    _mcs(x, out, lam, adds, iteration, theta)
+    return lam, adds
