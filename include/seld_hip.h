@@ -813,6 +813,52 @@ int seld_stem_conv_wgrad(const float* x, const float* dz, float* dkernel, float*
                          void* stream);
 int seld_pool2d_fwd(const float* x, float* y, unsigned char* idx, int B, int H, int W, int C, int ph, int pw, int same, void* stream);
 int seld_pool2d_bwd(const float* dy, const unsigned char* idx, float* dx, int B, int H, int W, int C, int ph, int pw, int same, void* stream);
+/* ---- the voice-activity model (vad.hip): models.spectro_temporal_attention_based_VAD (reference models.py:105-163), its loss
+ * (models_test.py:59-60) and the irregular frame window (train_vad_baseline.py:76-106), under the seld_m_* contract: fp32 device tensors,
+ * asynchronous on `stream`, no allocation, no atomics and fixed summation orders (two runs give the same bits).  SELD_ERR_INVALID, before
+ * anything is enqueued, for a NULL required pointer or a size < 1; SELD_ERR_UNSUPPORTED outside a kernel's stated range.
+ *   seld_vad_gate_pool_fwd   the spectral tail (models.py:120-122): y [rows, W / 2, C] (contiguous) = max(g[r, 2w, c], g[r, 2w + 1, c]),
+ *                            g = a * sigmoid(b) — MaxPooling2D([1, 2]), 'valid': an odd last column is left out.  a, b: [rows, W, C] views whose
+ *                            pixels are `ld` >= C floats apart (the two column halves of one [npix, 2 C] product: ld = 2 C).  idx (may be
+ *                            NULL: inference, y is bit-identical): one byte per output, 0 | 1 = the column of the pair that won; the first
+ *                            maximum stays (v > best, as seld_pool2d_fwd).  Any rows, W >= 2, C >= 1; four channels per thread where
+ *                            C % 4 == 0, ld % 4 == 0 and the pointers are aligned.  SELD_ERR_INVALID for W < 2 or ld < C.
+ *   seld_vad_gate_pool_bwd   da, db ([rows, W, C] views of pixel stride ld, as a and b), ALL W columns: with s = sigmoid(b) recomputed,
+ *                            da = dy s and db = dy a s (1 - s) at the recorded winner, exactly 0 at the loser and in the odd last column.
+ *   seld_vad_tattn_fwd       the temporal attention (models.py:145-153) from q [B, Nt] and k, v [B, T, Nt] BEFORE their sigmoid (the
+ *                            BatchNormalization outputs).  Column n = d H + h (the head is the fast index of Reshape((Nt / H, H))):
+ *                            s[b,t,h] = Nt^-1/2 sum_d sig(q)[b,dH+h] sig(k)[b,t,dH+h];  P = softmax over t of s;  y [B,T,Nt] = sig(v) P[b,t,h];
+ *                            score [B,T] = softmax over t of sum_h s.  P [B,T,H] is written for the backward (may be NULL: inference, y and
+ *                            score are bit-identical).  One workgroup per clip; every sum over d, t or h runs in an order the shape alone fixes.
+ *                            Range: Nt % H == 0, 1 <= H <= Nt <= 512, 1 <= T <= 64 (s lives in LDS: Nt + T H + T floats <= 133,376 B);
+ *                            SELD_ERR_UNSUPPORTED beyond, SELD_ERR_INVALID for Nt % H != 0 or H > Nt.
+ *   seld_vad_tattn_bwd       dq [B,Nt], dk, dv [B,T,Nt] with respect to the pre-sigmoid inputs from dy [B,T,Nt] and dscore [B,T]; P and score
+ *                            as the forward wrote them.  With c = Nt^-1/2: dP[t,h] = sum_d dy sig(v);  dS[t] = score[t] (dscore[t] -
+ *                            sum_t' score dscore);  ds[t,h] = P (dP - sum_t' P dP) + dS[t];  dsig(q)[d,h] = c sum_t ds sig(k);  dsig(k) = c ds
+ *                            sig(q);  dsig(v) = dy P;  each times sig (1 - sig).  The forward's range.
+ *   seld_vad_bce             tf.keras.backend.binary_crossentropy on probabilities, meaned: with pc = clip(p, 1e-7, 1 - 1e-7),
+ *                            loss (+)= weight / n sum -(y log(pc + 1e-7) + (1 - y) log(1 - pc + 1e-7));  dp (may be NULL) = weight / n times its
+ *                            derivative, 0 where the clip is active.  `accumulate` != 0 adds to *loss (one call per output of the model).
+ *                            Two-stage sum in a fixed order; scratch: seld_vad_bce_scratch(n) floats (-1 for n < 1).
+ *   seld_vad_windows         seq_to_windows: win [n_windows, Wn, D], win[n,i,:] = x[n + offs[i],:] for x [len, D], n_windows = len - offs[Wn-1].
+ *                            offs: HOST array of Wn offsets, non-decreasing, offs[0] = 0 (preprocess_window's result), copied into the
+ *                            launch.  SELD_ERR_INVALID for an unsorted table, offs[0] != 0 or len <= offs[Wn-1]; SELD_ERR_UNSUPPORTED for
+ *                            Wn > SELD_VAD_MAX_WINDOW.
+ *   seld_vad_unwindow        windows_to_seq: seq [n_windows + offs[Wn-1], D], seq[m,:] = sum_i win[m - offs[i], i, :] / (count[m] + 1e-8) over
+ *                            the i with 0 <= m - offs[i] < n_windows, added in the order of i. */
+#define SELD_VAD_MAX_NT 512
+#define SELD_VAD_MAX_T 64
+#define SELD_VAD_MAX_WINDOW 64
+int seld_vad_gate_pool_fwd(const float* a, const float* b, int ld, float* y, unsigned char* idx, int64_t rows, int W, int C, void* stream);
+int seld_vad_gate_pool_bwd(const float* a, const float* b, int ld, const unsigned char* idx, const float* dy, float* da, float* db, int64_t rows,
+                           int W, int C, void* stream);
+int seld_vad_tattn_fwd(const float* q, const float* k, const float* v, float* y, float* score, float* P, int B, int T, int Nt, int H, void* stream);
+int seld_vad_tattn_bwd(const float* q, const float* k, const float* v, const float* P, const float* score, const float* dy, const float* dscore,
+                       float* dq, float* dk, float* dv, int B, int T, int Nt, int H, void* stream);
+int64_t seld_vad_bce_scratch(int64_t n);
+int seld_vad_bce(const float* p, const float* y, float* loss, float* dp, float* scratch, int64_t n, float weight, int accumulate, void* stream);
+int seld_vad_windows(const float* x, float* win, const int32_t* offs, int Wn, int64_t len, int D, void* stream);
+int seld_vad_unwindow(const float* win, float* seq, const int32_t* offs, int Wn, int64_t n_windows, int D, void* stream);
 /* Measurement aid (bench.py, SURVEY.md §8(d) "state the step-latency floor"): the shader clock the card holds while `blocks`
  * workgroups of 512 threads run a VALU-only loop (the load shape of the GRU recurrence: 2B workgroups, no MFMA), from
  * s_memtime / s_memrealtime (100 MHz) inside the kernel.  No reference counterpart. */

@@ -246,6 +246,14 @@ SIGNATURES = {
     "seld_stem_conv_wgrad": (_I, [_P, _P, _P, _P, _P] + [_I] * 6 + [_P]),
     "seld_pool2d_fwd": (_I, [_P, _P, _P] + [_I] * 7 + [_P]),
     "seld_pool2d_bwd": (_I, [_P, _P, _P] + [_I] * 7 + [_P]),
+    "seld_vad_gate_pool_fwd": (_I, [_P, _P, _I, _P, _P, _L, _I, _I, _P]),
+    "seld_vad_gate_pool_bwd": (_I, [_P, _P, _I, _P, _P, _P, _P, _L, _I, _I, _P]),
+    "seld_vad_tattn_fwd": (_I, [_P] * 6 + [_I] * 4 + [_P]),
+    "seld_vad_tattn_bwd": (_I, [_P] * 10 + [_I] * 4 + [_P]),
+    "seld_vad_bce_scratch": (_L, [_L]),
+    "seld_vad_bce": (_I, [_P, _P, _P, _P, _P, _L, _F, _I, _P]),
+    "seld_vad_windows": (_I, [_P, _P, C.POINTER(C.c_int32), _I, _L, _I, _P]),
+    "seld_vad_unwindow": (_I, [_P, _P, C.POINTER(C.c_int32), _I, _L, _I, _P]),
     "seld_k_rn_conv": (_I, [_P, _P, _P] + [_I] * 7),
     "seld_k_rn_conv_stats": (_I, [_P, _P, _P] + [_I] * 7 + [_P]),
     "seld_k_rn_conv_bwd": (_I, [_P, _P, _P, _P, _P] + [_I] * 7),

@@ -302,6 +302,15 @@ def conv_temporal(input_shape, model_config, device=None):
     return ConvTemporalNet(input_shape, model_config, device)
 
 
+def spectro_temporal_attention_based_VAD(input_shape, model_config, device=None, dropout: bool = False):
+    """reference models.spectro_temporal_attention_based_VAD (models.py:105-163): gated spectral convolutions, a pipe net, the temporal attention
+    and a post net -> [out, pipe, score] — a vad.SpectroTemporalVAD for input_shape (B, T, F, C), composed from module operators and the
+    seld_vad_* kernels (float32).  dropout=True accepts the library's counter-based Dropout draws in place of TensorFlow's; without it
+    dropout_rate must be present and 0.  Configuration errors are ValueErrors raised without a device."""
+    from .vad import SpectroTemporalVAD
+    return SpectroTemporalVAD(input_shape, model_config, device, dropout)
+
+
 def seldnet_v1(input_shape, model_config, device=None, dtype: str = "float32") -> SeldNet:
     """reference models.seldnet_v1 (models.py:36-52; model_config/seldnet_v1.json): seldnet whose DOA output is coupled to the SED
     output, doa_out = tanh(doa * Concatenate([sed] * 3)) (seld_arch.output_coupling)."""
