@@ -537,6 +537,36 @@ int seld_k_losses(const float* sed, const float* doa, const float* y_sed, const 
 /* Keras Adam update (train.py:311,34); step is 1-based */
 int seld_k_adam(float* theta, const float* g, float* m, float* v, int64_t n, float lr, float beta1,
                 float beta2, float eps, int64_t step);
+/* The rest of loss_adam.hip as the fused models' training step launches it, one launcher per entry point (tests/test_step_tail_gpu.py).  Null
+ * stream, synchronous.  SELD_ERR_INVALID before any HIP call for: a NULL required pointer, a size below 1, a float4 operand that is not 16-byte
+ * aligned, and what each comment below names.
+ * seld_k_losses_strided: seld_m_losses with the launcher's remaining arguments.  ld_sed / ld_doa: row strides in floats of dsed_pre / ddoa_pre
+ *   (<= 0: dense, nc / 3 nc; a positive stride below the row length is refused) — the fused heads write both into one [rows][n_sed + n_doa]
+ *   buffer.  defer_finalize != 0: sloss (and dloss in MMSE mode) are NOT written; seld_k_losses_finalize writes them from the per-workgroup
+ *   partials the first call left in `scratch`, which must be untouched in between.  scratch: seld_m_losses_scratch(B * S) floats, 8-byte
+ *   aligned; the MMSE denominator sits behind loss_scratch_floats(rows) = 2 rows + 64 of them.  doa_loss outside SELD_DOA_*: refused. */
+int seld_k_losses_strided(const float* sed, const float* doa, const float* y_sed, const float* y_doa, const seld_loss_cfg* cfg, float* sloss,
+                          float* dloss, float* dsed_pre, int ld_sed, float* ddoa_pre, int ld_doa, float* scratch, int B, int S, int nc,
+                          int defer_finalize);
+int seld_k_losses_finalize(const seld_loss_cfg* cfg, float* sloss, float* dloss, float* scratch, int B, int S, int nc);
+/* utils.adaptive_clip_grad on ONE variable of Keras shape `shape` (HOST array, rank 1..4) at theta + off / g + off: g is clipped in place per
+ * unit, theta is only read.  rank outside 1..4, off < 0, a dimension below 1 or more than INT32_MAX elements: refused. */
+int seld_k_agc(const float* theta, float* g, int64_t off, int rank, const int64_t* shape_host);
+/* dy *= act'(.) from the stored output y = act(.): act 1 sigmoid, 2 tanh, 3 relu (other values refused); n % 4 == 0 */
+int seld_k_act_bwd(const float* y, float* dy, int64_t n, int act);
+/* models.seldnet_v1's output coupling: out (and out2 unless NULL) [rows, 3 nc] = tanh(doa1 * [sed | sed | sed]); its backward in place on the
+ * losses' gradients (ddoa_pre holds d / d(doa1 sed) on entry; dsed_pre is added to).  ld_sed < nc or ld_doa < 3 nc: refused. */
+int seld_k_v1_couple_fwd(const float* sed, const float* doa1, float* out, float* out2, int rows, int nc);
+int seld_k_v1_couple_bwd(const float* sed, const float* doa1, float* dsed_pre, int ld_sed, float* ddoa_pre, int ld_doa, int rows, int nc);
+/* simple_dense_block with kernel_size > 1: xe [B, S, ks * C] lays the ks frames a 'same' Conv1D tap reads side by side (zero outside the clip);
+ * time_fold is its transpose, dx [B, S, C] (+)= the taps in order.  C % 4 == 0. */
+int seld_k_time_expand(const float* x, float* xe, int B, int S, int C, int ks);
+int seld_k_time_fold(const float* dxe, float* dx, int B, int S, int C, int ks, int accumulate);
+/* out[r][f] (+)= in[r][f] * mask[r / S][f]: a per-clip mask over the feature axis (the GRU layers' input dropout).  F % 4 == 0. */
+int seld_k_mask_rows(const float* in, const float* mask, float* out, int64_t rows, int S, int F, int accumulate);
+/* The fused path's dropout (four elements per thread; seld_dropout is the module operator's kernel): out = in * [u >= rate] / (1 - rate) with
+ * the uniforms of oracle/seldnet_oracle.py::philox_uniform(n, seed, layer, step).  in == out allowed.  n % 4 == 0, rate in [0, 1). */
+int seld_k_dropout4(const float* in, float* out, int64_t n, float rate, uint64_t seed, unsigned layer, unsigned step);
 /* The v2 loss stage alone (trainv2.py:38-44), like seld_k_losses: sed / y_sed [B,S,nc], doa / y_doa [B,S,3nc]; sloss, dloss 1 float each;
  * dsed_pre / ddoa_pre (may be NULL): the objective's gradients w.r.t. the heads' pre-activations.  Refusals as seld_train_fwd_bwd_v2. */
 int seld_k_losses_v2(const float* sed, const float* doa, const float* y_sed, const float* y_doa, const seld_v2_cfg* cfg, float* sloss,

@@ -179,6 +179,16 @@ SIGNATURES = {
     "seld_k_gru_drop_bwd": (_I, [_P] * 15 + [_I] * 3),
     "seld_k_losses": (_I, [_P, _P, _P, _P, C.POINTER(LossCfg), _P, _P, _P, _P, _I, _I, _I]),
     "seld_k_adam": (_I, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _L]),
+    "seld_k_losses_strided": (_I, [_P, _P, _P, _P, C.POINTER(LossCfg), _P, _P, _P, _I, _P, _I, _P, _I, _I, _I, _I]),
+    "seld_k_losses_finalize": (_I, [C.POINTER(LossCfg), _P, _P, _P, _I, _I, _I]),
+    "seld_k_agc": (_I, [_P, _P, _L, _I, C.POINTER(_L)]),
+    "seld_k_act_bwd": (_I, [_P, _P, _L, _I]),
+    "seld_k_v1_couple_fwd": (_I, [_P, _P, _P, _P, _I, _I]),
+    "seld_k_v1_couple_bwd": (_I, [_P, _P, _P, _I, _P, _I, _I, _I]),
+    "seld_k_time_expand": (_I, [_P, _P, _I, _I, _I, _I]),
+    "seld_k_time_fold": (_I, [_P, _P, _I, _I, _I, _I, _I]),
+    "seld_k_mask_rows": (_I, [_P, _P, _P, _L, _I, _I, _I]),
+    "seld_k_dropout4": (_I, [_P, _P, _L, _F, _U64, _U, _U]),
     "seld_k_losses_v2": (_I, [_P, _P, _P, _P, C.POINTER(V2Cfg), _P, _P, _P, _P, _I, _I, _I]),
     "seld_k_reg_agc_adabelief": (_I, [_P, _P, _P, _P, _L, _I, C.POINTER(_L), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                  _F, _F, _F, _F, _F, _F, _L]),

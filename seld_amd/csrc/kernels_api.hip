@@ -481,6 +481,89 @@ int seld_k_adam(float* theta, const float* g, float* m, float* v, int64_t n, flo
     return done();
 }
 
+// ---- loss_adam.hip's other kernels and launcher arguments, one launcher per entry point: what api.hip's run_losses / seld_adam_step, forward.hip's
+// forward_heads / forward_gru and backward.hip's backward_heads / backward_gru pass.  Every refusal comes before the first HIP call.
+static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+static bool loss_args_ok(const seld_loss_cfg* cfg, const float* scratch, int B, int S, int nc) {
+    return cfg && scratch && ((uintptr_t)scratch & 7) == 0 && B >= 1 && S >= 1 && nc >= 1 && (int64_t)B * S <= INT32_MAX / 4 &&
+           cfg->doa_loss >= SELD_DOA_MSE && cfg->doa_loss <= SELD_DOA_MSLE;
+}
+
+int seld_k_losses_strided(const float* sed, const float* doa, const float* y_sed, const float* y_doa, const seld_loss_cfg* cfg, float* sloss,
+                          float* dloss, float* dsed_pre, int ld_sed, float* ddoa_pre, int ld_doa, float* scratch, int B, int S, int nc,
+                          int defer_finalize) {
+    if (!sed || !doa || !y_sed || !y_doa || !sloss || !dloss || !loss_args_ok(cfg, scratch, B, S, nc)) return SELD_ERR_INVALID;
+    if ((ld_sed > 0 && ld_sed < nc) || (ld_doa > 0 && ld_doa < 3 * nc)) return SELD_ERR_INVALID;      // <= 0: dense rows, as the launcher reads it
+    const int rows = B * S;
+    float* den = scratch + loss_scratch_floats(rows);
+    if (cfg->doa_loss == SELD_DOA_MMSE) {
+        if (cfg->mmse_den > 0.f) launch_fill(0, den, 1, cfg->mmse_den);
+        else launch_mmse_den(0, y_doa, den, scratch, rows, nc);
+    }
+    launch_losses(0, sed, doa, y_sed, y_doa, cfg->doa_loss, cfg->w_sed, cfg->w_doa, cfg->sed_grad_scale, den, sloss, dloss, dsed_pre, ddoa_pre, scratch,
+                  B, S, nc, ld_sed, ld_doa, defer_finalize ? 1 : 0);
+    return done();
+}
+
+int seld_k_losses_finalize(const seld_loss_cfg* cfg, float* sloss, float* dloss, float* scratch, int B, int S, int nc) {
+    if (!sloss || !dloss || !loss_args_ok(cfg, scratch, B, S, nc)) return SELD_ERR_INVALID;
+    launch_losses_finalize(0, cfg->doa_loss, scratch + loss_scratch_floats(B * S), sloss, dloss, scratch, B, S, nc);
+    return done();
+}
+
+int seld_k_agc(const float* theta, float* g, int64_t off, int rank, const int64_t* shape) {
+    if (!theta || !g || !shape || off < 0 || rank < 1 || rank > 4) return SELD_ERR_INVALID;
+    int64_t n = 1;
+    for (int i = 0; i < rank; ++i) {
+        if (shape[i] < 1 || shape[i] > INT32_MAX || n * shape[i] > INT32_MAX) return SELD_ERR_INVALID;      // the launcher's rows and cols are ints
+        n *= shape[i];
+    }
+    launch_agc(0, theta, g, off, rank, shape, nullptr);
+    return done();
+}
+
+int seld_k_act_bwd(const float* y, float* dy, int64_t n, int act) {
+    if (!y || !dy || n < 1 || (n & 3) || act < 1 || act > 3 || !al16(y) || !al16(dy)) return SELD_ERR_INVALID;
+    if (launch_act_bwd(0, y, dy, n, act)) return SELD_ERR_INVALID;
+    return done();
+}
+
+int seld_k_v1_couple_fwd(const float* sed, const float* doa1, float* out, float* out2, int rows, int nc) {
+    if (!sed || !doa1 || !out || rows < 1 || nc < 1) return SELD_ERR_INVALID;
+    launch_v1_couple_fwd(0, sed, doa1, out, out2, rows, nc);
+    return done();
+}
+
+int seld_k_v1_couple_bwd(const float* sed, const float* doa1, float* dsed_pre, int ld_sed, float* ddoa_pre, int ld_doa, int rows, int nc) {
+    if (!sed || !doa1 || !dsed_pre || !ddoa_pre || rows < 1 || nc < 1 || ld_sed < nc || ld_doa < 3 * nc) return SELD_ERR_INVALID;
+    launch_v1_couple_bwd(0, sed, doa1, dsed_pre, ld_sed, ddoa_pre, ld_doa, rows, nc);
+    return done();
+}
+
+int seld_k_time_expand(const float* x, float* xe, int B, int S, int C, int ks) {
+    if (!x || !xe || B < 1 || S < 1 || C < 1 || ks < 1 || (C & 3) || !al16(x) || !al16(xe)) return SELD_ERR_INVALID;
+    if (launch_time_expand(0, x, xe, B, S, C, ks)) return SELD_ERR_INVALID;
+    return done();
+}
+
+int seld_k_time_fold(const float* dxe, float* dx, int B, int S, int C, int ks, int accumulate) {
+    if (!dxe || !dx || B < 1 || S < 1 || C < 1 || ks < 1 || (C & 3) || !al16(dxe) || !al16(dx)) return SELD_ERR_INVALID;
+    if (launch_time_fold(0, dxe, dx, B, S, C, ks, accumulate)) return SELD_ERR_INVALID;
+    return done();
+}
+
+int seld_k_mask_rows(const float* in, const float* mask, float* out, int64_t rows, int S, int F, int accumulate) {
+    if (!in || !mask || !out || rows < 1 || S < 1 || F < 1 || (F & 3) || !al16(in) || !al16(mask) || !al16(out)) return SELD_ERR_INVALID;
+    if (launch_mask_rows(0, in, mask, out, rows, S, F, accumulate)) return SELD_ERR_INVALID;
+    return done();
+}
+
+int seld_k_dropout4(const float* in, float* out, int64_t n, float rate, uint64_t seed, unsigned layer, unsigned step) {
+    if (!in || !out || n < 1 || (n & 3) || !(rate >= 0.f && rate < 1.f) || !al16(in) || !al16(out)) return SELD_ERR_INVALID;
+    if (launch_dropout(0, in, out, n, rate, seed, layer, step)) return SELD_ERR_INVALID;
+    return done();
+}
+
 // VALU-only load on `blocks` CUs (the recurrence's shape); lane 0 of every block reports shader cycles and 100 MHz ticks
 __global__ __launch_bounds__(512) void valu_clock_kernel(unsigned long long* out, int iters, float seed) {
     float a = seed + threadIdx.x * 1e-9f, b = seed * 0.5f;
