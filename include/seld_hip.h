@@ -473,6 +473,54 @@ int seld_k_gemm_sb(const float* A0, const float* A1, const float* B0, const floa
  * (the matching bias gradient, produced by the same launch) */
 int seld_k_gemm_tn(const float* A, const float* Bm, float* C, float* colsum, int M, int K1, int N);
 
+/* The same launchers with every argument the train step passes (tests/test_gemm_family_gpu.py).  Refusals: SELD_ERR_INVALID, nothing written.
+ *   seld_k_gemm_ex   the fp32 MFMA GEMM with leading dimensions.  mode 0: C = act(A op(B) + bias) (+C); stat_part (may be NULL): the BatchNorm
+ *                    partials [(column / 64) * row blocks + row / 64][sum 64 | sum of squares 64] of the product's epilogue (no bias / act /
+ *                    accumulate); addg is always refused here.  mode 1: also C1 = act(A op(B1) + bias1).  mode 2: C = act(A op(B) + A1 op(B1)
+ *                    + bias) (+C), K % 32 == 0.  mode 3: mode 0, C1 = a copy of C (same ldc).  mode 4: N = n0 + n1 columns of one product,
+ *                    nsplit = n0: C [M][n0] = act0(..), C1 [M][n1] = act1(..), act = act0 | act1 << 4, M0 / M1 (may be NULL) copies; ldb = N.
+ *                    act: 0 none, 1 sigmoid, 2 tanh, 3 relu.
+ *   seld_k_gemm_sb_ex  the split-bf16 GEMM (K % 32 == 0, N % 128 == 0, lda % 4 == 0): B0 / B1 are split inside, transb 0 [K][N], 1 [N][K], 2 a 3x3
+ *                    kernel [9][N][ldb] as the matrix of its input-gradient convolution.  backward (needs transb != 0): the four-product form
+ *                    under option "bwd_four_products".  mode / act as above (modes 0..2); accum: C += .  stat_part: partials per 128-row block;
+ *                    addg + gate4: C[e] += addg[e] where bit (e & 3) of gate4[e >> 2] is set, e = row * ldc + column (ldc % 4 == 0).
+ *                    conv_C > 0: A0 is an NHWC image [M = B H W][conv_C] and K = 9 conv_C (3x3 'same').
+ *   seld_k_gemm_tn_ex  C [K1][N] = A[M][K1]^T B[M][N] on the fp32 kernel: S > 0 and shift = +-1 take A's rows shifted inside each S-row sequence
+ *                    (zero outside it); colsum with want_bias; max_splits 0 = the default; chunk_rows 32 or 64; *nslab = the splits taken.
+ *   seld_k_gemm_tn_sb_ex  1..4 jobs (K1 = 128, N % 128 == 0) of the split-bf16 kernel in one launch: A, lda, shift, Bm, C, colsum are arrays
+ *                    of njobs entries (colsum NULL unless want_bias).   seld_k_gemm_tn_sb_tiles: its tile mode, K1 % 128 == 0, slab_cap floats of
+ *                    slab space; conv_C > 0: A is an NHWC image and K1 = 9 conv_C (the kernel gradient of a 3x3 'same' convolution).
+ *   seld_k_reduce_slabs_ex  which 0: out_w[n_w] (+)= sum_z slab[z * stride + i]; 1: [out_w | out_b] from slabs of n_w + n_b; 2: two stages through
+ *                    tmp [seld_k_reduce_slabs_groups(nslab)][n_w].   seld_k_reduce_slabs2_batch: which 1 for njobs consecutive groups of nslab slabs.
+ *   seld_k_heads_weff / seld_k_heads_grad  the folded head weights [W1 W2 ; b1 W2 + b2] of both heads ([K + 1][n[0] + n[1]], n[0] + n[1] <= 64) and the
+ *                    four gradients of each head from F [K][n[0] + n[1]] and cs; every pointer argument but weff, F, cs is an array of two.
+ *   seld_k_weight_prep  the merged pre-pass launch and the three stand-alone ones from the same inputs, into separate targets.
+ *   seld_k_mul       out = a * b elementwise, n % 4 == 0. */
+int seld_k_gemm_ex(const float* A, int lda, const float* Bm, int ldb, const float* bias, float* C, int ldc, int M, int N, int K, int transb, int act,
+                   int accumulate, int mode, const float* A1, const float* B1, const float* bias1, float* C1, float* M0, float* M1, int nsplit,
+                   float* stat_part, const float* addg);
+int seld_k_gemm_sb_ex(const float* A0, const float* A1, int lda, const float* B0, const float* B1, int ldb, int transb, const float* bias0,
+                      const float* bias1, float* C0, float* C1, int ldc, int M, int N, int K, int act, int mode, int accum, int backward,
+                      float* stat_part, const float* addg, const unsigned char* gate4, int conv_C, int conv_H, int conv_W);
+int seld_k_gemm_tn_ex(const float* A, int lda, const float* Bm, int ldb, float* C, float* colsum, int M, int K1, int N, int S, int shift,
+                      int want_bias, int max_splits, int chunk_rows, int* nslab);
+int seld_k_gemm_tn_sb_ex(int njobs, const float* const* A, const int* lda, const int* shift, const float* const* Bm, int ldb, float* const* C,
+                         float* const* colsum, int M, int N, int S, int want_bias, int* nslab);
+int seld_k_gemm_tn_sb_tiles(const float* A, int lda, const float* Bm, int ldb, float* C, int M, int K1, int N, int64_t slab_cap, int conv_C, int conv_H,
+                            int conv_W, int* nslab);
+int seld_k_reduce_slabs_groups(int nslab);
+int seld_k_reduce_slabs_ex(int which, const float* slab, int nslab, int64_t stride, float* out_w, int64_t n_w, float* out_b, int64_t n_b, int accumulate,
+                           float* tmp);
+int seld_k_reduce_slabs2_batch(const float* slab, int nslab, int64_t stride, int njobs, float* const* out_w, float* const* out_b, int64_t n_w, int64_t n_b);
+int seld_k_heads_weff(const float* const* w1, const float* const* b1, const float* const* w2, const float* const* b2, const int* n, int K, int Hd, float* weff);
+int seld_k_heads_grad(const float* const* w1, const float* const* b1, const float* const* w2, float* const* dw1, float* const* db1, float* const* dw2,
+                      float* const* db2, const int* n, int K, int Hd, const float* F, const float* cs);
+int seld_k_weight_prep(int na, const float* const* a_src, const int* a_ldb, const int* a_transb, const int* a_K, const int* a_N,
+                       unsigned short* const* a_fused, unsigned short* const* a_alone, int nb, const float* const* b_w, const int* b_flip,
+                       unsigned short* const* b_fused, unsigned short* const* b_alone, const float* const* w1, const float* const* b1,
+                       const float* const* w2, const float* const* b2, const int* n, int K, int Hd, float* weff_fused, float* weff_alone);
+int seld_k_mul(const float* a, const float* b, float* out, int64_t n);
+
 /* xception_block's depthwise 3x3 backward on [B,H,16,64] NHWC (xception.hip; spec/XCEPTION_BLOCK.md: the unit is ReLU -> depthwise 3x3 ->
  * pointwise -> BatchNormalization).  dy: the gradient w.r.t. the depthwise OUTPUT; xin: the unit's input (aff == NULL) or, with aff = [scale 64 |
  * shift 64], the PREVIOUS unit's pre-BN tensor z (the activation is then relu(z scale + shift)); add (may be NULL): a residual gradient added to dx;

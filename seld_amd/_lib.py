@@ -173,6 +173,18 @@ SIGNATURES = {
     "seld_k_xc_bn_apply": (_I, [_P, _P, _P, _P, _P, _L]),
     "seld_k_xc_bn_bwd": (_I, [_P] * 9 + [_L]),
     "seld_k_gemm_tn": (_I, [_P, _P, _P, _P, _I, _I, _I]),
+    "seld_k_gemm_ex": (_I, [_P, _I, _P, _I, _P, _P, _I] + [_I] * 7 + [_P] * 6 + [_I, _P, _P]),
+    "seld_k_gemm_sb_ex": (_I, [_P, _P, _I, _P, _P, _I, _I, _P, _P, _P, _P] + [_I] * 8 + [_P, _P, _P, _I, _I, _I]),
+    "seld_k_gemm_tn_ex": (_I, [_P, _I, _P, _I, _P, _P] + [_I] * 8 + [C.POINTER(C.c_int)]),
+    "seld_k_gemm_tn_sb_ex": (_I, [_I, _P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, C.POINTER(C.c_int)]),
+    "seld_k_gemm_tn_sb_tiles": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _L, _I, _I, _I, C.POINTER(C.c_int)]),
+    "seld_k_reduce_slabs_groups": (_I, [_I]),
+    "seld_k_reduce_slabs_ex": (_I, [_I, _P, _I, _L, _P, _L, _P, _L, _I, _P]),
+    "seld_k_reduce_slabs2_batch": (_I, [_P, _I, _L, _I, _P, _P, _L, _L]),
+    "seld_k_heads_weff": (_I, [_P, _P, _P, _P, _P, _I, _I, _P]),
+    "seld_k_heads_grad": (_I, [_P] * 8 + [_I, _I, _P, _P]),
+    "seld_k_weight_prep": (_I, [_I] + [_P] * 7 + [_I] + [_P] * 9 + [_I, _I, _P, _P]),
+    "seld_k_mul": (_I, [_P, _P, _P, _L]),
     "seld_k_gru_fwd": (_I, [_P] * 11 + [_I] * 3),
     "seld_k_gru_bwd": (_I, [_P] * 11 + [_I] * 3),
     "seld_k_gru_drop_fwd": (_I, [_P] * 14 + [_I] * 3),

@@ -724,6 +724,175 @@ int seld_k_rn_bn_bwd(const float* z, const float* dy, const float* mask, const f
     return done();
 }
 
+// ---- the GEMM family's launchers with every argument the model passes (gemm.hip, gemm_sb.hip, gemm_tn_sb.hip, prep.hip): leading dimensions,
+// modes, epilogues, split limits, jobs.  Pass-throughs: what a launcher refuses comes back as SELD_ERR_INVALID, before anything is written to an output.
+int seld_k_gemm_ex(const float* A, int lda, const float* Bm, int ldb, const float* bias, float* C, int ldc, int M, int N, int K, int transb, int act,
+                   int accumulate, int mode, const float* A1, const float* B1, const float* bias1, float* C1, float* M0, float* M1, int nsplit,
+                   float* stat_part, const float* addg) {
+    if (!A || !Bm || !C || mode < 0 || mode > 4) return SELD_ERR_INVALID;
+    if ((mode == 1 && (!B1 || !C1)) || (mode == 2 && (!A1 || !B1)) || (mode == 3 && !C1)) return SELD_ERR_INVALID;
+    if (mode == 4 && (!C1 || transb || nsplit < 1 || nsplit >= N || accumulate)) return SELD_ERR_INVALID;
+    if (mode && (stat_part || addg)) return SELD_ERR_INVALID;
+    GemmEpi epi;
+    epi.stat_part = stat_part; epi.addg = addg;
+    int rc;
+    if (mode == 0) rc = launch_gemm(0, A, lda, Bm, ldb, bias, C, ldc, M, N, K, transb, act, accumulate, epi);
+    else if (mode == 1) rc = launch_gemm_dual_n(0, A, lda, Bm, B1, ldb, bias, bias1, C, C1, ldc, M, N, K, transb, act);
+    else if (mode == 2) rc = launch_gemm_dual_k(0, A, A1, lda, Bm, B1, ldb, bias, C, ldc, M, N, K, transb, act, accumulate);
+    else if (mode == 3) rc = launch_gemm_mirror(0, A, lda, Bm, ldb, bias, C, C1, ldc, M, N, K, transb, act);
+    else rc = launch_gemm_heads(0, A, lda, Bm, bias, C, C1, M0, M1, M, nsplit, N - nsplit, K, act & 15, act >> 4);
+    if (rc) return SELD_ERR_INVALID;
+    return done();
+}
+
+// B0 / B1 are split here as the model's callers do: transb 0 = [K][N] (a forward product), 1 = [N][K] and 2 = a 3x3 kernel [9][N][ldb] read as the
+// matrix of its input-gradient convolution; a transposed job's mid plane is rounded, which is what the four-product form (`backward`) reads
+int seld_k_gemm_sb_ex(const float* A0, const float* A1, int lda, const float* B0, const float* B1, int ldb, int transb, const float* bias0,
+                      const float* bias1, float* C0, float* C1, int ldc, int M, int N, int K, int act, int mode, int accum, int backward,
+                      float* stat_part, const float* addg, const unsigned char* gate4, int conv_C, int conv_H, int conv_W) {
+    if (!A0 || !B0 || !C0 || mode < 0 || mode > 2 || (mode && !B1) || (mode == 1 && !C1) || (mode == 2 && !A1) || transb < 0 || transb > 2) return SELD_ERR_INVALID;
+    if (M <= 0 || N <= 0 || K <= 0 || (K % 32) || (backward && !transb)) return SELD_ERR_INVALID;
+    Scratch s;
+    const size_t ne = gemm_sb_split_elems(K, N);
+    unsigned short* sp = reinterpret_cast<unsigned short*>(s.get(ne));   // 2 operands x ne bf16 = ne floats
+    if (!sp) return SELD_ERR_NOMEM;
+    const float* src[2] = {B0, B1};
+    unsigned short* dst[2] = {sp, sp + ne};
+    const int ldbs[2] = {ldb, ldb}, tb[2] = {transb, transb}, Ks[2] = {K, K}, Ns[2] = {N, N};
+    if (launch_gemm_split_b(0, k_kc, mode ? 2 : 1, src, dst, ldbs, tb, Ks, Ns)) return SELD_ERR_INVALID;
+    GemmEpi epi;
+    epi.stat_part = stat_part; epi.addg = addg; epi.gate4 = gate4;
+    if (launch_gemm_sb(0, k_kc, backward != 0, epi, A0, A1, lda, dst[0], mode ? dst[1] : nullptr, bias0, bias1, C0, C1, ldc, M, N, K, act, mode, accum,
+                       conv_C, conv_H, conv_W))
+        return SELD_ERR_INVALID;
+    return done();
+}
+
+int seld_k_gemm_tn_ex(const float* A, int lda, const float* Bm, int ldb, float* C, float* colsum, int M, int K1, int N, int S, int shift,
+                      int want_bias, int max_splits, int chunk_rows, int* nslab) {
+    if (!A || !Bm || !C || !nslab || (want_bias != 0) != (colsum != nullptr) || M <= 0 || K1 <= 0 || N <= 0 || max_splits < 0) return SELD_ERR_INVALID;
+    Scratch s;
+    const int64_t per = (int64_t)K1 * N + N;
+    float* slab = s.get((size_t)(max_splits ? max_splits : gemm_tn_max_splits()) * per);
+    if (!slab) return SELD_ERR_NOMEM;
+    int ns = 0;
+    if (launch_gemm_tn(0, A, lda, Bm, ldb, slab, &ns, M, K1, N, S, shift, want_bias, max_splits, chunk_rows)) return SELD_ERR_INVALID;
+    if (colsum) launch_reduce_slabs2(0, slab, ns, per, C, (int64_t)K1 * N, colsum, N);
+    else launch_reduce_slabs(0, slab, ns, per, C, (int64_t)K1 * N, 0);
+    *nslab = ns;
+    return done();
+}
+
+// 1 .. TN_MAX_JOBS products of one shape in one launch (K1 = 128), combined by the batch reduction; colsum (an array of njobs pointers) with want_bias
+int seld_k_gemm_tn_sb_ex(int njobs, const float* const* A, const int* lda, const int* shift, const float* const* Bm, int ldb, float* const* C,
+                         float* const* colsum, int M, int N, int S, int want_bias, int* nslab) {
+    if (njobs < 1 || njobs > TN_MAX_JOBS || !A || !lda || !shift || !Bm || !C || !nslab || (want_bias != 0) != (colsum != nullptr) || M <= 0 || N <= 0)
+        return SELD_ERR_INVALID;
+    TnJobs jobs = {};
+    for (int j = 0; j < njobs; ++j) {
+        if (!A[j] || !Bm[j] || !C[j] || (want_bias && !colsum[j])) return SELD_ERR_INVALID;
+        jobs.A[j] = A[j]; jobs.B[j] = Bm[j]; jobs.lda[j] = lda[j]; jobs.shift[j] = shift[j]; jobs.out_w[j] = C[j]; jobs.out_b[j] = want_bias ? colsum[j] : nullptr;
+    }
+    Scratch s;
+    const int64_t per = (int64_t)128 * N + N;
+    // the launcher takes at most one split per 160 rows (rounding the rows of a split up to whole chunks only lowers the count)
+    float* slab = s.get((size_t)njobs * std::min(gemm_tn_max_splits(), (M + 159) / 160) * per);
+    if (!slab) return SELD_ERR_NOMEM;
+    int ns = 0;
+    if (launch_gemm_tn_sb_batch(0, k_kc, jobs, njobs, ldb, slab, &ns, M, N, S, want_bias)) return SELD_ERR_INVALID;
+    launch_reduce_slabs2_batch(0, slab, ns, per, jobs, njobs, (int64_t)128 * N, want_bias ? N : 0);
+    *nslab = ns;
+    return done();
+}
+
+// tile mode (K1 % 128 == 0, optionally the implicit im2col of a 3x3 kernel gradient): slab_cap floats of slab space limit the splits
+int seld_k_gemm_tn_sb_tiles(const float* A, int lda, const float* Bm, int ldb, float* C, int M, int K1, int N, int64_t slab_cap, int conv_C, int conv_H,
+                            int conv_W, int* nslab) {
+    if (!A || !Bm || !C || !nslab || slab_cap < 1 || slab_cap > ((int64_t)1 << 28)) return SELD_ERR_INVALID;
+    Scratch s;
+    float* slab = s.get((size_t)slab_cap);
+    if (!slab) return SELD_ERR_NOMEM;
+    int ns = 0;
+    if (launch_gemm_tn_sb_tiles(0, k_kc, A, lda, Bm, ldb, slab, slab_cap, &ns, M, K1, N, conv_C, conv_H, conv_W)) return SELD_ERR_INVALID;
+    launch_reduce_slabs2(0, slab, ns, (int64_t)K1 * N, C, (int64_t)K1 * N, nullptr, 0);
+    *nslab = ns;
+    return done();
+}
+
+int seld_k_reduce_slabs_groups(int nslab) { return reduce_slabs_groups(nslab); }
+
+// which 0: out_w[n_w] (+)= sum of slabs; 1: [out_w n_w | out_b n_b] = sum of slabs; 2: two stages through tmp [seld_k_reduce_slabs_groups(nslab)][n_w]
+int seld_k_reduce_slabs_ex(int which, const float* slab, int nslab, int64_t stride, float* out_w, int64_t n_w, float* out_b, int64_t n_b, int accumulate,
+                           float* tmp) {
+    if (!slab || !out_w || nslab < 1 || n_w < 1 || n_b < 0 || stride < n_w + n_b || which < 0 || which > 2) return SELD_ERR_INVALID;
+    if ((which == 1) != (n_b > 0) || (n_b > 0 && !out_b) || (which != 0 && accumulate) || (which == 2 && !tmp)) return SELD_ERR_INVALID;
+    if (which == 0) launch_reduce_slabs(0, slab, nslab, stride, out_w, n_w, accumulate);
+    else if (which == 1) launch_reduce_slabs2(0, slab, nslab, stride, out_w, n_w, out_b, n_b);
+    else launch_reduce_slabs_2stage(0, slab, nslab, stride, out_w, n_w, tmp);
+    return done();
+}
+
+// job j's slabs follow job j - 1's (nslab slabs each), as launch_gemm_tn_sb_batch leaves them
+int seld_k_reduce_slabs2_batch(const float* slab, int nslab, int64_t stride, int njobs, float* const* out_w, float* const* out_b, int64_t n_w, int64_t n_b) {
+    if (!slab || !out_w || nslab < 1 || njobs < 1 || njobs > TN_MAX_JOBS || n_w < 1 || n_b < 0 || stride < n_w + n_b || (n_b > 0 && !out_b)) return SELD_ERR_INVALID;
+    TnJobs jobs = {};
+    for (int j = 0; j < njobs; ++j) {
+        if (!out_w[j] || (n_b > 0 && !out_b[j])) return SELD_ERR_INVALID;
+        jobs.out_w[j] = out_w[j]; jobs.out_b[j] = n_b > 0 ? out_b[j] : nullptr;
+    }
+    launch_reduce_slabs2_batch(0, slab, nslab, stride, jobs, njobs, n_w, n_b);
+    return done();
+}
+
+// w1, b1, w2, b2, n: arrays of two (the SED head, the DOA head); weff [K + 1][n[0] + n[1]]
+int seld_k_heads_weff(const float* const* w1, const float* const* b1, const float* const* w2, const float* const* b2, const int* n, int K, int Hd, float* weff) {
+    if (!w1 || !b1 || !w2 || !b2 || !n || !weff || K < 1 || Hd < 1 || n[0] < 1 || n[1] < 1) return SELD_ERR_INVALID;
+    if (launch_heads_weff(0, w1, b1, w2, b2, n, K, Hd, weff)) return SELD_ERR_INVALID;
+    return done();
+}
+
+int seld_k_heads_grad(const float* const* w1, const float* const* b1, const float* const* w2, float* const* dw1, float* const* db1, float* const* dw2,
+                      float* const* db2, const int* n, int K, int Hd, const float* F, const float* cs) {
+    if (!w1 || !b1 || !w2 || !dw1 || !db1 || !dw2 || !db2 || !n || !F || !cs || K < 1 || Hd < 1 || n[0] < 1 || n[1] < 1 || n[0] + n[1] > 64) return SELD_ERR_INVALID;
+    if (launch_heads_grad(0, w1, b1, w2, dw1, db1, dw2, db2, n, K, Hd, F, cs)) return SELD_ERR_INVALID;
+    return done();
+}
+
+// the merged pre-pass launch (prep.hip) into the *_fused targets and the three stand-alone launches into the *_alone ones, from the same inputs:
+// na GEMM weight splits (dst: 3 K N bf16 each), nb 64 -> 64 conv weight splits (dst: 9 * 3 * 4096 bf16 each), the folded head weights (weff_fused
+// NULL: off).  Nothing to do (0, 0, off) launches nothing.
+int seld_k_weight_prep(int na, const float* const* a_src, const int* a_ldb, const int* a_transb, const int* a_K, const int* a_N,
+                       unsigned short* const* a_fused, unsigned short* const* a_alone, int nb, const float* const* b_w, const int* b_flip,
+                       unsigned short* const* b_fused, unsigned short* const* b_alone, const float* const* w1, const float* const* b1,
+                       const float* const* w2, const float* const* b2, const int* n, int K, int Hd, float* weff_fused, float* weff_alone) {
+    if (na < 0 || nb < 0 || (na && (!a_src || !a_ldb || !a_transb || !a_K || !a_N || !a_fused || !a_alone)) || (nb && (!b_w || !b_flip || !b_fused || !b_alone)))
+        return SELD_ERR_INVALID;
+    if (weff_fused && (!weff_alone || !w1 || !b1 || !w2 || !b2 || !n)) return SELD_ERR_INVALID;
+    GemmSplitJobs a = {};
+    SplitWeightJobs b = {};
+    HeadsLin h = {};
+    a.njobs = na;
+    for (int i = 0; i < na && i < GSB_MAX_JOBS; ++i) {
+        a.src[i] = a_src[i]; a.dst[i] = a_fused[i]; a.ldb[i] = a_ldb[i]; a.transb[i] = a_transb[i]; a.K[i] = a_K[i]; a.N[i] = a_N[i];
+    }
+    for (int i = 0; i < nb && i < 8; ++i) { b.w[i] = b_w[i]; b.dst[i] = b_fused[i]; b.flip[i] = b_flip[i]; }
+    if (weff_fused) {
+        for (int i = 0; i < 2; ++i) { h.w1[i] = w1[i]; h.b1[i] = b1[i]; h.w2[i] = w2[i]; h.b2[i] = b2[i]; h.n[i] = n[i]; }
+        h.K = K; h.Hd = Hd;
+    }
+    if (launch_weight_prep(0, k_kc, a, na, b, nb, h, weff_fused)) return SELD_ERR_INVALID;
+    if (na && launch_gemm_split_b(0, k_kc, na, a_src, a_alone, a_ldb, a_transb, a_K, a_N)) return SELD_ERR_INVALID;
+    if (nb && launch_split_weights_batch(0, k_kc, nb, b_w, b_alone, b_flip)) return SELD_ERR_INVALID;
+    if (weff_fused && launch_heads_weff(0, w1, b1, w2, b2, n, K, Hd, weff_alone)) return SELD_ERR_INVALID;
+    return done();
+}
+
+int seld_k_mul(const float* a, const float* b, float* out, int64_t n) {
+    if (!a || !b || !out || n < 1 || !al16(a) || !al16(b) || !al16(out)) return SELD_ERR_INVALID;
+    if (launch_mul(0, a, b, out, n)) return SELD_ERR_INVALID;
+    return done();
+}
+
 int seld_device_clocks(int device, int* compute_units, int* clock_khz, int* mem_clock_khz, int* mem_bus_bits) {
     hipDeviceProp_t p;
     if (hipGetDeviceProperties(&p, device) != hipSuccess) return SELD_ERR_HIP;

@@ -302,7 +302,7 @@ def test_gemm_split_bf16(seld_lib, M, N, K, transb, mode):
         check("gemm_sb second product", C1.cpu().numpy(), A0.astype(np.float64) @ op(B1) + b1)
 
 
-@pytest.mark.parametrize("M,N,mode", [(19200, 384, 1), (1203, 256, 0), (33, 384, 1), (4000, 128, 1)])
+@pytest.mark.parametrize("M,N,mode", [(19200, 384, 1), (1203, 256, 0), (33, 384, 1), (4000, 128, 1), (1, 256, 0), (31, 384, 1)])
 def test_gemm_k128_b_stationary_form_is_bit_identical(seld_lib, M, N, mode):
     """The opt-in K = 128 form with B stationary in LDS (gemm_sbp_kernel: persistent workgroups, no barrier after the prologue; option gsb_dbg
     bit 6, round 5) takes the products and k-steps in the tiled kernel's order: the same bits, ragged row counts included."""
