@@ -937,6 +937,50 @@ int64_t seld_vad_bce_scratch(int64_t n);
 int seld_vad_bce(const float* p, const float* y, float* loss, float* dp, float* scratch, int64_t n, float weight, int accumulate, void* stream);
 int seld_vad_windows(const float* x, float* win, const int32_t* offs, int Wn, int64_t len, int D, void* stream);
 int seld_vad_unwindow(const float* win, float* seq, const int32_t* offs, int Wn, int64_t n_windows, int D, void* stream);
+/* The data path of the voice-activity task (csrc/vad_feat.hip): the front end, frame labels and window batches of
+ * vad_dataloader.py and the counters behind the Keras metrics of train_vad_baseline.py.  The seld_m_* contract: fp32 device tensors,
+ * asynchronous on `stream`, no allocation after create, no host synchronisation; SELD_ERR_INVALID for NULL or out-of-range scalars before
+ * anything is enqueued, SELD_ERR_UNSUPPORTED for sizes with no kernel.  Every device read is bounded by the totals passed as host scalars:
+ * a wrong table gives wrong values, never an out-of-range access.  A corpus is PACKED: the utterances lie end to end, file i owns samples
+ * sample_starts[i] .. sample_starts[i+1] and rows frame_starts[i] .. frame_starts[i+1] (device int64 [n_files + 1] each).
+ *   seld_vad_feat_create     the handle of load_wav_and_extract_feat (vad_dataloader.py:77-98) with get_mel_scale's matrix (109-115): mono,
+ *                            hop n_fft / 2; it holds the periodic Hann window, the twiddles and the sparse filter table (each filter a
+ *                            contiguous bin range of seld_vad_mel_matrix_host(n_mels, n_fft / 2 + 1, sample_rate, 0, sample_rate / 2)).
+ *                            n_fft in {512, 1024, 2048} and 1 <= n_mels <= SELD_VAD_MAX_MELS, SELD_ERR_UNSUPPORTED beyond.
+ *                            The tables live on `device`; the caller's current device is the same after the call as before it.  Every
+ *                            tensor and the stream given to seld_vad_feat_extract must belong to the handle's device: this is not checked.
+ *   seld_vad_feat_frames     host only: frames of tf.signal.stft(frame_length = n_fft, frame_step = n_fft / 2) without padding or centring:
+ *                            0 if n_samples < n_fft, else 1 + (n_samples - n_fft) / (n_fft / 2).
+ *   seld_vad_mel_matrix_host host only, no device: w [n_bins, n_mels] = tf.signal.linear_to_mel_weight_matrix, built in double and rounded
+ *                            once: mel(f) = 1127 ln(1 + f / 700); n_mels + 2 edges equally spaced in mel from lower_hz to upper_hz; bin k at
+ *                            k (sample_rate / 2) / (n_bins - 1); weight max(0, min(rising, falling slope)), both slopes in mel; row 0 zero.
+ *   seld_vad_feat_extract    out [total_frames, n_mels] (the reference's [frames, n_mels, 1]) from wav [total_samples] (lines 86-97): per
+ *                            frame periodic Hann, real FFT (fp32, one frame per transform: a frame's values depend on its samples alone),
+ *                            |X| = sqrt(re^2 + im^2), the mel projection in ascending bin order (an empty filter: exactly 0).  logmel:
+ *                            log(min(max(s, 1e-8), M)), M the FILE's maximum of s; normalize: (v - min) / (max - min) over the file.  The
+ *                            arithmetic is literal: a silent or constant file comes out all NaN, as the reference's does.
+ *   seld_vad_frame_labels    load_label (lines 101-106): y [total_frames], y[t] = rintf(sum of labels[s .. s + n_fft) / n_fft) (tf.round: half
+ *                            to even) with s the frame's first sample; the sum runs in an order n_fft alone fixes.
+ *   seld_vad_gather          apply_window (lines 126-136) for a batch: x_out [B, Wn, D], x_out[b,i,:] = feat[pos[b] + offs[i], :], y_out [B, Wn]
+ *                            likewise from y; feat [total_frames, D], pos device int64 [B] (absolute rows), offs the HOST table of
+ *                            seld_vad_windows (same refusals), copied into the launch; rows are clamped into [0, total_frames).
+ *   seld_vad_score_update    the counters of Keras AUC / Precision / Recall / binary_accuracy (train_vad_baseline.py:49, 216-224): counts
+ *                            (device int64 [NT + 1][2], ADDED to) [k][y != 0] += 1 with k the number of thresholds (ascending fp32 device
+ *                            table, NT <= 1024) that pred > thr holds for in fp32; a NaN lands in bucket 0.  Integer atomics: exact in any
+ *                            order.  The rates, their suffix sums and the trapezoid are the caller's float64 arithmetic. */
+#define SELD_VAD_MAX_MELS 256
+typedef struct seld_vadfeat seld_vadfeat;
+int seld_vad_feat_create(int sample_rate, int n_fft, int n_mels, int device, seld_vadfeat** out);
+void seld_vad_feat_destroy(seld_vadfeat* f);
+int64_t seld_vad_feat_frames(int n_fft, int64_t n_samples);
+int seld_vad_mel_matrix_host(int n_mels, int n_bins, int sample_rate, double lower_hz, double upper_hz, float* w);
+int seld_vad_feat_extract(seld_vadfeat* f, const float* wav, const int64_t* sample_starts, const int64_t* frame_starts, int n_files,
+                          int64_t total_samples, int64_t total_frames, int logmel, int normalize, float* out, void* stream);
+int seld_vad_frame_labels(const float* labels, const int64_t* sample_starts, const int64_t* frame_starts, int n_files, int64_t total_samples,
+                          int64_t total_frames, int n_fft, float* y, void* stream);
+int seld_vad_gather(const float* feat, const float* y, const int64_t* pos, const int32_t* offs, int Wn, int B, int D, int64_t total_frames,
+                    float* x_out, float* y_out, void* stream);
+int seld_vad_score_update(const float* pred, const float* y, int64_t n, const float* thresholds, int NT, int64_t* counts, void* stream);
 /* Measurement aid (bench.py, SURVEY.md §8(d) "state the step-latency floor"): the shader clock the card holds while `blocks`
  * workgroups of 512 threads run a VALU-only loop (the load shape of the GRU recurrence: 2B workgroups, no MFMA), from
  * s_memtime / s_memrealtime (100 MHz) inside the kernel.  No reference counterpart. */

@@ -276,6 +276,14 @@ SIGNATURES = {
     "seld_vad_bce": (_I, [_P, _P, _P, _P, _P, _L, _F, _I, _P]),
     "seld_vad_windows": (_I, [_P, _P, C.POINTER(C.c_int32), _I, _L, _I, _P]),
     "seld_vad_unwindow": (_I, [_P, _P, C.POINTER(C.c_int32), _I, _L, _I, _P]),
+    "seld_vad_feat_create": (_I, [_I, _I, _I, _I, C.POINTER(_P)]),
+    "seld_vad_feat_destroy": (None, [_P]),
+    "seld_vad_feat_frames": (_L, [_I, _L]),
+    "seld_vad_mel_matrix_host": (_I, [_I, _I, _I, C.c_double, C.c_double, _P]),
+    "seld_vad_feat_extract": (_I, [_P, _P, _P, _P, _I, _L, _L, _I, _I, _P, _P]),
+    "seld_vad_frame_labels": (_I, [_P, _P, _P, _I, _L, _L, _I, _P, _P]),
+    "seld_vad_gather": (_I, [_P, _P, _P, C.POINTER(C.c_int32), _I, _I, _I, _L, _P, _P, _P]),
+    "seld_vad_score_update": (_I, [_P, _P, _L, _P, _I, _P, _P]),
     "seld_k_rn_conv": (_I, [_P, _P, _P] + [_I] * 7),
     "seld_k_rn_conv_stats": (_I, [_P, _P, _P] + [_I] * 7 + [_P]),
     "seld_k_rn_conv_bwd": (_I, [_P, _P, _P, _P, _P] + [_I] * 7),

@@ -14,6 +14,7 @@
 //   fixed LDS tree; stage two: one workgroup adds the partials the same way.
 // seld_vad_windows / _unwindow — the irregular frame window of train_vad_baseline.py:76-106; the offset table rides in the launch.
 #include "common.h"
+#include "vad_win.h"
 
 namespace {
 
@@ -283,11 +284,6 @@ __global__ __launch_bounds__(256) void bce_final_kernel(const float* __restrict_
 }
 
 // ------------------------------------------------------------------------------------------------ frame windows
-struct WinTable {
-    int n, width;      // entries, offs[n - 1]
-    int offs[SELD_VAD_MAX_WINDOW];
-};
-
 __global__ __launch_bounds__(256) void vad_windows_kernel(const float* __restrict__ x, float* __restrict__ win, int64_t total, int D, WinTable tb) {
     const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;      // over [n_windows][Wn][D]
     if (e >= total) return;
@@ -311,19 +307,6 @@ __global__ __launch_bounds__(256) void vad_unwindow_kernel(const float* __restri
         cnt += 1.f;
     }
     seq[e] = acc / (cnt + 1e-8f);
-}
-
-int win_table(const int32_t* offs, int Wn, WinTable& tb) {
-    if (!offs || Wn < 1) return SELD_ERR_INVALID;
-    if (Wn > SELD_VAD_MAX_WINDOW) return SELD_ERR_UNSUPPORTED;
-    if (offs[0] != 0) return SELD_ERR_INVALID;
-    for (int i = 0; i < Wn; ++i) {
-        if (i && offs[i] < offs[i - 1]) return SELD_ERR_INVALID;
-        tb.offs[i] = offs[i];
-    }
-    for (int i = Wn; i < SELD_VAD_MAX_WINDOW; ++i) tb.offs[i] = 0;
-    tb.n = Wn, tb.width = offs[Wn - 1];
-    return SELD_OK;
 }
 
 }  // namespace
