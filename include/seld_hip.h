@@ -937,6 +937,25 @@ int64_t seld_vad_bce_scratch(int64_t n);
 int seld_vad_bce(const float* p, const float* y, float* loss, float* dp, float* scratch, int64_t n, float weight, int accumulate, void* stream);
 int seld_vad_windows(const float* x, float* win, const int32_t* offs, int Wn, int64_t len, int D, void* stream);
 int seld_vad_unwindow(const float* win, float* seq, const int32_t* offs, int Wn, int64_t n_windows, int D, void* stream);
+/* ---- the head of models.vad_architecture (vadarch.hip; reference models.py:98-102): Dense(U, sigmoid) on x [rows, D] (contiguous) with the
+ * Keras kernel w [D, U] and bias b [U], U from 1 to SELD_VADARCH_MAX_U, and its backward from seld_vad_bce's loss — exact fp32 FMA chains
+ * (no MFMA: a row-dot), x read once.  The seld_m_* contract: fp32 device tensors, asynchronous on `stream`, no allocation, no atomics, fixed
+ * summation orders (two runs give the same bits).  SELD_ERR_INVALID, before anything is enqueued, for a NULL required pointer or a size < 1;
+ * SELD_ERR_UNSUPPORTED for U > SELD_VADARCH_MAX_U or more rows than one launch covers.
+ *   seld_vadarch_head_fwd          p [rows, U] = sigmoid(b[u] + sum_d x[r,d] w[d,u]).  The order of the sum over d depends on D alone (not on
+ *                                  rows, the grid or the alignment); float4 loads of x where D % 4 == 0 and x is 16-byte aligned.
+ *   seld_vadarch_head_bwd_scratch  floats of `scratch` for (rows, D, U); -1 outside the range.  It never falls as rows grows: scratch sized for
+ *                                  the largest batch serves every smaller one.
+ *   seld_vadarch_head_bwd          with n = rows U and pc = clip(p, 1e-7, 1 - 1e-7): *loss = weight / n sum -(y log(pc + 1e-7) + (1 - y)
+ *                                  log(1 - pc + 1e-7)) (overwritten); dp its derivative, 0 where the clip is active; dz = dp p (1 - p);
+ *                                  dx [rows, D] = dz w^T (may be NULL: the head sits on the data; written once, never read),
+ *                                  dw [D, U] = x^T dz, db [U] = the column sums of dz.  y [rows, U].  The loss, dw and db are two-stage
+ *                                  sums: per chunk of rows (rows alone fixes the chunks), then over the chunks, both in ascending order. */
+#define SELD_VADARCH_MAX_U 8
+int seld_vadarch_head_fwd(const float* x, const float* w, const float* b, float* p, int64_t rows, int D, int U, void* stream);
+int64_t seld_vadarch_head_bwd_scratch(int64_t rows, int D, int U);
+int seld_vadarch_head_bwd(const float* x, const float* w, const float* p, const float* y, float* loss, float* dx, float* dw, float* db,
+                          float* scratch, int64_t rows, int D, int U, float weight, void* stream);
 /* The data path of the voice-activity task (csrc/vad_feat.hip): the front end, frame labels and window batches of
  * vad_dataloader.py and the counters behind the Keras metrics of train_vad_baseline.py.  The seld_m_* contract: fp32 device tensors,
  * asynchronous on `stream`, no allocation after create, no host synchronisation; SELD_ERR_INVALID for NULL or out-of-range scalars before

@@ -274,6 +274,9 @@ SIGNATURES = {
     "seld_vad_tattn_bwd": (_I, [_P] * 10 + [_I] * 4 + [_P]),
     "seld_vad_bce_scratch": (_L, [_L]),
     "seld_vad_bce": (_I, [_P, _P, _P, _P, _P, _L, _F, _I, _P]),
+    "seld_vadarch_head_fwd": (_I, [_P, _P, _P, _P, _L, _I, _I, _P]),
+    "seld_vadarch_head_bwd_scratch": (_L, [_L, _I, _I]),
+    "seld_vadarch_head_bwd": (_I, [_P] * 9 + [_L, _I, _I, _F, _P]),
     "seld_vad_windows": (_I, [_P, _P, C.POINTER(C.c_int32), _I, _L, _I, _P]),
     "seld_vad_unwindow": (_I, [_P, _P, C.POINTER(C.c_int32), _I, _L, _I, _P]),
     "seld_vad_feat_create": (_I, [_I, _I, _I, _I, C.POINTER(_P)]),

@@ -311,6 +311,16 @@ def spectro_temporal_attention_based_VAD(input_shape, model_config, device=None,
     return SpectroTemporalVAD(input_shape, model_config, device, dropout)
 
 
+def vad_architecture(input_shape, model_config, device=None, fused_head=None):
+    """reference models.vad_architecture (models.py:81-102): the optional flatten, the BLOCK* chain in string order, force_1d_inputs and
+    Dense(last_unit, sigmoid) — a modules.VadArchNet for input_shape (B, Wn, F, C), the batch in front as spectro_temporal_attention_based_VAD
+    takes it (float32).  The chain's kinds are mother_block / mother_stage and every 3-D kind of models.conv_temporal; simple_dense_block's
+    Dropout draws from the library's counter-based generator.  fused_head: the head's kernels (csrc/vadarch.hip) or the composed operators;
+    None = the model's default.  Configuration errors are ValueErrors raised without a device; device='meta' gives the plan alone."""
+    from .modules import VadArchNet
+    return VadArchNet(input_shape, model_config, device, fused_head)
+
+
 def seldnet_v1(input_shape, model_config, device=None, dtype: str = "float32") -> SeldNet:
     """reference models.seldnet_v1 (models.py:36-52; model_config/seldnet_v1.json): seldnet whose DOA output is coupled to the SED
     output, doa_out = tanh(doa * Concatenate([sed] * 3)) (seld_arch.output_coupling)."""

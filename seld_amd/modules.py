@@ -26,6 +26,10 @@ else).  There is no CPU or PyTorch fallback.
                                                   MaxPool2D (seld_pool2d_*), the BLOCK* chain (mother blocks, then every 3-D kind, DenseBlock =
                                                   simple_dense_block as a body block) and a block or stage as each head (_StageHead)
 
+  models.vad_architecture (models.py:81-102)                          VadArchNet: the optional flatten, the same BLOCK* chain (DenseBlock with its Dropout layers wired, Dense
+                                                  variables on the 2-D tensor) and Dense(last_unit, sigmoid) + binary cross-entropy as one fused head
+                                                  (seld_vadarch_head_* of vadarch.hip) or composed from Linear, seld_m_act and seld_vad_bce
+
 The shared pieces, each in one place:
   Linear               GEMM + bias with its backward: Dense, Conv1D and Conv2D (im2col in front of it where the window is wider than one
                        sample), the heads' layers (Head) and the squeeze-and-excitation pair (_SqueezeExcite)
@@ -156,6 +160,7 @@ class _Rt:
         self.tr: List[Tuple[str, Tuple[int, ...]]] = []
         self.nt: List[Tuple[str, Tuple[int, ...]]] = []
         self._views: Dict[str, torch.Tensor] = {}
+        self.linears: List[Tuple[int, int, int]] = []      # (rows, K, N) of every Linear built on this runtime: the plan's dense products
         self.params = self.grads = self.state = None
         self._slab = None
         self._bn_scratch = None
@@ -294,6 +299,7 @@ class Linear:
         rt.var(f"{name}.kernel", kshape or (self.K, self.N))
         rt.var(f"{name}.bias", (self.N,))
         self.z = rt.empty(rows, self.N)
+        rt.linears.append((int(rows), self.K, self.N))
 
     def forward(self, x, rows):
         rt = self.rt
@@ -1685,45 +1691,65 @@ def _build_second(kind: str, rt, cfg: dict, S: int, D: int, B: int, prefix=None,
     return st
 
 
-def check_dense_config(cfg: dict) -> None:
-    """reference modules.simple_dense_block (modules.py:350-376) as a body block"""
+def check_dense_config(cfg: dict, dropout: bool = False) -> float:
+    """reference modules.simple_dense_block (modules.py:350-376) as a body block -> its dropout_rate as the fp32 the kernels compare with.
+    dropout: the owner wires the block's Dropout layers (seld_dropout behind each activation: models.vad_architecture) and the rate may be
+    any in [0, 1); without it the rate must be 0, as before"""
     if "units" not in cfg or not isinstance(cfg["units"], (list, tuple)):
         raise ValueError("simple_dense_block: `units` is a list, one entry per layer")
     if any(int(u) < 1 for u in cfg["units"]) or int(cfg.get("kernel_size", 1)) < 1:
         raise ValueError("simple_dense_block: units and kernel_size >= 1")
     _check_activation(cfg, None, "dense_activation")
+    if dropout:
+        rate = float(np.float32(cfg.get("dropout_rate", 0) or 0))
+        if not 0.0 <= rate < 1.0:
+            raise ValueError(f"simple_dense_block: dropout_rate {cfg.get('dropout_rate')!r}: 0 <= dropout_rate < 1")
+        return rate
     if float(cfg.get("dropout_rate", 0) or 0) != 0.0:
         raise ValueError("simple_dense_block: dropout_rate must be 0 — its Dropout layers are wired on the fused path only (models.SeldNet), as for "
                          "the composed heads; the composed path's Dropout covers the attention kinds")
+    return 0.0
 
 
 class DenseBlock:
     """reference modules.simple_dense_block (modules.py:350-376) as a body block on [B*S, D]: one Conv1D(units, kernel_size, 'same') +
     dense_activation per entry of `units` (variables `{prefix}.dense{j}`), out_dim = the last width; `units` = []: the identity (which is
-    also what identity_block is, modules.py:639-642)."""
+    also what identity_block is, modules.py:639-642).  dropout (models.vad_architecture): a dropout_rate above 0 puts seld_dropout behind
+    each layer's activation (modules.py:372-373), site j = the layer, on the block's own streams DROP_STREAM0 + 32 * first_block + j (_Drop);
+    training only.  flat: the input is the reference's 2-D tensor (S = 1), where the block builds Dense — kernel (D, u), kernel_size unused."""
 
-    def __init__(self, rt: _Rt, cfg: dict, S: int, D: int, prefix: str, B: int):
-        check_dense_config(cfg)
+    def __init__(self, rt: _Rt, cfg: dict, S: int, D: int, prefix: str, B: int, dropout: bool = False, first_block: int = 0, flat: bool = False):
+        rate = check_dense_config(cfg, dropout)
         self.rt, self.S, self.D = rt, int(S), int(D)
         self.act = ACT[cfg.get("dense_activation", None)]
+        self.drop = _Drop(rt, rate)
+        self.drop.base = DROP_STREAM0 + 32 * int(first_block)
         k, R = int(cfg.get("kernel_size", 1)), B * self.S
-        self.layers = []      # (layer, its activation y, the gradient of its pre-activation, the gradient of its input)
+        if flat and self.S != 1:
+            raise ValueError("simple_dense_block: a 2-D input has no time axis (S = 1)")
+        self.layers = []      # (layer, its activation y, the gradient of its pre-activation, the gradient of its input, of y behind the Dropout)
         for j, u in enumerate(int(u) for u in cfg["units"]):
-            self.layers.append((Conv1D(rt, f"{prefix}.dense{j}", B, self.S, D, u, k), rt.empty(R, u), rt.empty(R, u), rt.empty(R, D)))
+            lin = Dense(rt, f"{prefix}.dense{j}", R, D, u) if flat else Conv1D(rt, f"{prefix}.dense{j}", B, self.S, D, u, k)
+            self.layers.append((lin, rt.empty(R, u), rt.empty(R, u), rt.empty(R, D), rt.empty(R, u) if rate > 0.0 else None))
             D = u
         self.out_dim, self.out_shape = int(D), (self.S, int(D))
 
     def forward(self, x, B, training):
         R = B * self.S
         x = x.reshape(R, self.D)
-        for lin, y, _, _ in self.layers:
+        self.drop.begin(training)
+        for j, (lin, y, _, _, _) in enumerate(self.layers):
             self.rt.act(lin.forward(x, R), y[:R], self.act)
+            if self.drop.on:
+                self.drop.apply(j, y[:R], y[:R])
             x = y[:R]
         return x
 
     def backward(self, dy, B):
         R = B * self.S
-        for lin, _, dpre, dx in reversed(self.layers):
+        for j, (lin, _, dpre, dx, dd) in reversed(list(enumerate(self.layers))):
+            if self.drop.on:
+                dy = self.drop.apply(j, dy, dd[:R])
             self.rt.act_bwd(lin.z[:R], dy, dpre[:R], self.act)
             lin.backward(dpre[:R], dx[:R], R)
             dy = dx[:R]
@@ -2192,6 +2218,8 @@ class ConvTemporalNet(ComposedSeldNet):
     ComposedSeldNet's.  Every stage of the chain draws its Dropout masks from streams of its own (Stage: first_block).  device='meta': the
     plan alone — variables and shapes without a device (nothing can be run)."""
 
+    DENSE_KW: dict = {}      # what _build_3d passes to a DenseBlock beyond its place in the chain (VadArchNet: dropout, flat)
+
     def __init__(self, input_shape, model_config: dict, device=None):
         cfg = copy.deepcopy(model_config)
         meta = device == "meta"
@@ -2268,7 +2296,7 @@ class ConvTemporalNet(ComposedSeldNet):
     def _build_3d(self, kind: str, args: dict, S: int, D: int, B: int, prefix: str):
         kind, args = canonical_kind(kind, args)
         if kind == "simple_dense_block":
-            blk = DenseBlock(self.rt, args, S, D, prefix, B)
+            blk = DenseBlock(self.rt, args, S, D, prefix, B, first_block=self.n_built, **self.DENSE_KW)
             self.n_built += 1
             return blk
         pre = SECOND_KINDS[kind][2]
@@ -2325,6 +2353,225 @@ class ConvTemporalNet(ComposedSeldNet):
         self.stem_bn.backward(self.stem_dact[:B], self.stem_dz[:B], B)
         self.stem_conv.backward(self.stem_dz[:B], B)
         self._mark("first_bwd")
+
+
+DENSE_KINDS = ("simple_dense_block", "simple_dense_stage", "identity_block")      # the 3-D kinds that also take the reference's 2-D tensor
+
+
+class VadArchNet(ComposedSeldNet):
+    """models.vad_architecture(input_shape = (B, Wn, F, C), model_config) (reference models.py:81-102) composed from module operators:
+
+      flatten (default True)   the window becomes [B, Wn F C]: the reference's 2-D tensor, on which simple_dense_block builds Dense (variables
+                               (D, u)) and nothing with a time axis or a Conv2D can follow — only DENSE_KINDS; a 4-D kind is a ValueError
+      blocks  the BLOCK* keys in string order (chain_blocks): mother_block / mother_stage while the tensor is 4-D; the first 3-D kind
+              (CHAIN_3D, built by ConvTemporalNet._build_3d) flattens it to [B, Wn, F C]; a 4-D kind behind a 3-D one is a ValueError.
+              simple_dense_block's Dropout layers are wired here (DenseBlock dropout=True)
+      head    layers.force_1d_inputs, Dense(last_unit, sigmoid) (variables out.kernel (D, last_unit), out.bias), the trailing axis squeezed
+              where last_unit = 1: the prediction is [B, last_unit] (flatten) or [B, Wn', last_unit]
+      loss    binary cross-entropy against a label of the prediction's shape (nas_vad.py:172-173)
+
+    fused_head: True — the head runs on seld_vadarch_head_fwd / _bwd (csrc/vadarch.hip; last_unit <= 8), which give the loss, dx, dw and db
+    from one read of x; False — Linear + seld_m_act + seld_vad_bce + seld_m_act_bwd; None — FUSED_HEAD where last_unit <= 8 (tools/
+    bench_vadarch.py measures one against the other: DESIGN.md section 3x).  Weights I/O, summary, the Dropout counters and batches of
+    1 .. B are ComposedSeldNet's; device='meta': the plan alone."""
+    FUSED_HEAD = True
+    MAX_FUSED_UNITS = 8      # SELD_VADARCH_MAX_U
+    _build_3d = ConvTemporalNet._build_3d
+
+    def __init__(self, input_shape, model_config: dict, device=None, fused_head=None):
+        cfg = copy.deepcopy(model_config)
+        meta = device == "meta"
+        if not meta and not torch.cuda.is_available():
+            VadArchNet(input_shape, cfg, "meta", fused_head)      # the configuration errors first, without a device
+            raise RuntimeError("seld_amd needs a HIP device: there is no CPU fallback")
+        self._dev = torch.device("meta") if meta else torch.device("cuda", torch.cuda.current_device() if device is None else int(device))
+        if len(input_shape) != 4 or min(int(v) for v in input_shape) < 1:
+            raise ValueError(f"vad_architecture: input_shape {tuple(input_shape)!r}: [B, Wn, F, C], all >= 1")
+        B, Wn, Fq, Ch = (int(v) for v in input_shape)
+        self.input_shape = (B, Wn, Fq, Ch)
+        self.flatten, self.last_unit = bool(cfg.get("flatten", True)), int(cfg.get("last_unit", 1))
+        if self.last_unit < 1:
+            raise ValueError(f"vad_architecture: last_unit {cfg.get('last_unit')!r} must be >= 1")
+        if fused_head and self.last_unit > self.MAX_FUSED_UNITS:
+            raise ValueError(f"vad_architecture: the fused head takes last_unit <= {self.MAX_FUSED_UNITS}, not {self.last_unit}")
+        self.fused = (self.FUSED_HEAD and self.last_unit <= self.MAX_FUSED_UNITS) if fused_head is None else bool(fused_head)
+        rt = self.rt = _Rt(self._dev)
+        rt.dropout = True
+        self.lib = rt.lib
+        self.DENSE_KW = {"dropout": True, "flat": self.flatten}
+        self.blocks, self.body, self.stream_bases, self.n_built = [], [], {}, 0
+        shape = (Wn, Fq, Ch)
+        S, D = (1, Wn * Fq * Ch) if self.flatten else (Wn, None)
+        for i, key in enumerate(chain_blocks(cfg)):
+            kind, args = cfg[key], cfg.get(f"{key}_ARGS")
+            if args is None:
+                raise ValueError(f"vad_architecture: {key} has no {key}_ARGS")
+            if kind in CHAIN_4D:
+                if self.flatten:
+                    raise ValueError(f"vad_architecture: {key} = {kind!r} takes a 4-D tensor, but flatten has made the input 2-D")
+                if D is not None:
+                    raise ValueError(f"vad_architecture: {key} = {kind!r} takes a 4-D tensor, but a block in front of it has made it 3-D")
+                cfgs, c = [], copy.deepcopy(args)
+                for _ in range(int(args["depth"]) if kind == "mother_stage" else 1):
+                    cfgs.append(copy.deepcopy(c))
+                    c["strides"] = (1, 1)       # modules.py:41
+                for d, c in enumerate(cfgs):
+                    blk = MotherBlock(rt, c, shape, f"b{i}.mb{d}", B)
+                    self.blocks.append(blk)
+                    shape = blk.out_shape
+                    self.n_built += 1
+            elif kind in CHAIN_3D:
+                if self.flatten and kind not in DENSE_KINDS:
+                    raise ValueError(f"vad_architecture: {key} = {kind!r} needs a time axis, but flatten has made the input 2-D: one of {DENSE_KINDS}")
+                if D is None:
+                    S, D = shape[0], shape[1] * shape[2]      # layers.force_1d_inputs (layers.py:41-47): feature = f * C + c
+                blk = self._build_3d(kind, args, S, D, B, f"b{i}")
+                self.body.append(blk)
+                D = blk.out_dim
+            else:
+                raise ValueError(f"vad_architecture: {key} = {kind!r}: one of {CHAIN_4D + CHAIN_3D}")
+        self.shape4 = shape
+        if D is None:
+            S, D = shape[0], shape[1] * shape[2]
+        self.S, self.D = int(S), int(D)
+        R, U = B * self.S, self.last_unit
+        self.on_data = not self.blocks and not any(getattr(b, "layers", True) for b in self.body)      # nothing trainable in front of the head
+        if self.fused:      # the kernels read the variables themselves: no Linear, no pre-activation buffer
+            rt.var("out.kernel", (self.D, U))
+            rt.var("out.bias", (U,))
+            rt.linears.append((R, self.D, U))
+            self.out = None
+        else:
+            self.out = Linear(rt, "out", R, self.D, U)
+        rt.finalize()
+        self.variables, self.state_variables = rt.variables, rt.state_variables
+        self.n_params, self.n_state = rt.n_params, rt.n_state
+        self.dfeat = None if self.on_data else rt.empty(R, self.D)
+        self.d_p, self.dz = (None, None) if self.fused else (rt.empty(R, U), rt.empty(R, U))
+        self.loss_scratch = rt.empty(int(rt.lib.seld_vad_bce_scratch(R * U)))
+        self.head_scratch = rt.empty(int(rt.lib.seld_vadarch_head_bwd_scratch(R, self.D, U))) if self.fused else None
+        self.adam_step = 0
+        self._marks = None
+        if not meta:
+            self._init_weights()
+
+    def output_shape(self, B=None):
+        """the prediction's (and the label's) shape for a batch of B windows"""
+        B = self.input_shape[0] if B is None else int(B)
+        lead = (B,) if self.flatten else (B, self.S)
+        return lead if self.last_unit == 1 else lead + (self.last_unit,)
+
+    def summary(self) -> str:
+        lines = [f"VadArchNet input {self.input_shape} -> {list(self.output_shape())} ({'fused' if self.fused else 'composed'} head)"]
+        lines += [f"  {n:32s} {str(sh):20s} {int(np.prod(sh)):8d}" for n, _, sh in self.variables]
+        lines.append(f"Trainable params: {self.n_params}; non-trainable: {self.n_state}")
+        text = "\n".join(lines)
+        print(text)
+        return text
+
+    def complexity(self) -> dict:
+        """{'flops', 'params'}: params = n_params; flops = the multiply-adds per window of the plan's dense products, the sum over every
+        Linear layer (Dense, Conv1D, Conv2D and projection, the head) of (rows / B) K N.  Our own count, read off the plan: it is NOT claimed
+        to equal the reference's model_complexity.vad_architecture_complexity (closed forms per stage, which also count normalisations and
+        activations)."""
+        B = self.input_shape[0]
+        return {"flops": int(sum((rows // B) * K * N for rows, K, N in self.rt.linears)), "params": int(self.n_params)}
+
+    # ---------------------------------------------------------------- forward / backward
+    def _forward(self, x, training: bool):
+        rt = self.rt
+        B = x.shape[0]
+        R = B * self.S
+        if training:
+            rt.next_draws()
+        h = x
+        for blk in self.blocks:
+            h = blk.forward(h, B, training)
+        h = h.reshape(R, -1)
+        for blk in self.body:
+            h = blk.forward(h, B, training)
+        return self._head_forward(h, R).view(self.output_shape(B))
+
+    def _head_forward(self, h, R):
+        """h [R, D] -> the probabilities [R, last_unit]; h is kept for the backward"""
+        rt, U = self.rt, self.last_unit
+        self.feat = h
+        p = rt.empty(R, U)
+        if self.fused:
+            rt.ck(rt.lib.seld_vadarch_head_fwd(rt.p(h), rt.p(rt.w("out.kernel")), rt.p(rt.w("out.bias")), rt.p(p), R, self.D, U, rt.st()))
+        else:
+            rt.act(self.out.forward(h, R), p, ACT["sigmoid"])
+        return p
+
+    def __call__(self, x, training: bool = False):
+        return self._forward(self._prep(x), bool(training))
+
+    def _label(self, y, B):
+        y = torch.as_tensor(y, dtype=torch.float32, device=self._dev).contiguous()
+        if tuple(y.shape) != self.output_shape(B):
+            raise ValueError(f"label shape {tuple(y.shape)}: the prediction's is {self.output_shape(B)}")
+        return y
+
+    def _loss(self, p, y, want_grads: bool):
+        """mean binary cross-entropy -> a device scalar; want_grads: the head's variables' gradients and dfeat are written"""
+        rt = self.rt
+        R, U = p.numel() // self.last_unit, self.last_unit
+        loss = torch.empty((), dtype=torch.float32, device=self._dev)
+        if self.fused and want_grads:
+            rt.ck(rt.lib.seld_vadarch_head_bwd(rt.p(self.feat), rt.p(rt.w("out.kernel")), rt.p(p), rt.p(y), rt.p(loss), rt.p(self.dfeat),
+                                               rt.p(rt.g("out.kernel")), rt.p(rt.g("out.bias")), rt.p(self.head_scratch), R, self.D, U, 1.0, rt.st()))
+            return loss
+        rt.ck(rt.lib.seld_vad_bce(rt.p(p), rt.p(y), rt.p(loss), rt.p(self.d_p) if want_grads else None, rt.p(self.loss_scratch), R * U, 1.0, 0,
+                                  rt.st()))
+        if want_grads:
+            rt.act_bwd(self.out.z[:R], self.d_p[:R], self.dz[:R], ACT["sigmoid"])
+            self.out.backward(self.dz, self.dfeat, R)
+        return loss
+
+    def _backward(self, B):
+        """from dfeat, the gradient of the head's input, to every other variable's gradient"""
+        if self.on_data:
+            return
+        R = B * self.S
+        dy = self.dfeat[:R]
+        for blk in reversed(self.body):
+            dy = blk.backward(dy, B)
+        if self.blocks:
+            dy = dy[:R].reshape(B, *self.shape4)
+            for blk in reversed(self.blocks):
+                dy = blk.backward(dy, None, B)
+
+    # ---------------------------------------------------------------- steps
+    def train_step(self, x, y, optimizer):
+        """one step of model.fit on (x, y of the prediction's shape) -> (prediction, loss).  optimizer: train.Adam (seld_m_adam) or
+        trainv2.AdaBelief (seld_v2_opt without regulariser and clipping), as SpectroTemporalVAD takes them; no host synchronisation"""
+        from .trainv2 import AdaBelief
+        rt = self.rt
+        x = self._prep(x)
+        B = x.shape[0]
+        y = self._label(y, B)
+        belief = isinstance(optimizer, AdaBelief)
+        if belief:
+            self._v2_get_plan()      # its one-time allocation and copies come before the step's first launch
+        p = self._forward(x, True)
+        loss = self._loss(p, y, True)
+        self._backward(B)
+        if belief:
+            self._v2_opt(optimizer, 0.0, 0.0)
+        else:
+            self.adam_step += 1
+            rt.ck(rt.lib.seld_m_adam(rt.p(rt.params), rt.p(rt.grads), rt.p(rt.adam_m), rt.p(rt.adam_v), self.n_params, optimizer.learning_rate,
+                                     optimizer.beta_1, optimizer.beta_2, optimizer.epsilon, self.adam_step, rt.st()))
+        return p, loss
+
+    def test_step(self, x, y):
+        x = self._prep(x)
+        y = self._label(y, x.shape[0])
+        p = self._forward(x, False)
+        return p, self._loss(p, y, False)
+
+    def train_step_v2(self, *a, **k):
+        raise ValueError("the trainv2 recipe (SELD losses) is not this model's: train_step(x, y, optimizer)")
 
 
 def mother_block(model_config: dict):

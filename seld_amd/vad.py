@@ -392,12 +392,20 @@ def windows_to_seq(windows: torch.Tensor, window) -> torch.Tensor:
     return seq
 
 
-def predict_sequence(model: SpectroTemporalVAD, x, window, batch_size=None) -> torch.Tensor:
-    """train_vad_baseline.py:206-214: x [len, F, C] -> windows -> the model's `out` in batches -> windows_to_seq: [len, 1]"""
+def model_out(model, x) -> torch.Tensor:
+    """the prediction the recipes score: SpectroTemporalVAD's `out` (the first of its three outputs) or the one tensor a models.vad_architecture
+    returns"""
+    r = model(x)
+    return r[0] if isinstance(r, (list, tuple)) else r
+
+
+def predict_sequence(model, x, window, batch_size=None) -> torch.Tensor:
+    """train_vad_baseline.py:206-214: x [len, F, C] -> windows -> the model's prediction (model_out) in batches -> windows_to_seq: [len, 1]
+    (SpectroTemporalVAD) or [len] (a models.vad_architecture whose prediction is [B, Wn])"""
     x = torch.as_tensor(x, dtype=torch.float32).to(model._dev)
     wins = seq_to_windows(x, window)
     bs = model.input_shape[0] if batch_size is None else int(batch_size)
     if not 1 <= bs <= model.input_shape[0]:
         raise ValueError(f"batch_size {batch_size!r}: 1 .. {model.input_shape[0]}, the batch the model was built for")
-    outs = [model(wins[i:i + bs])[0] for i in range(0, wins.shape[0], bs)]
+    outs = [model_out(model, wins[i:i + bs]) for i in range(0, wins.shape[0], bs)]
     return windows_to_seq(torch.cat(outs, dim=0), window)
