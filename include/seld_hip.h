@@ -730,6 +730,31 @@ int seld_rnn_gru_fwd(const float* gx_f, const float* gx_b, const float* U_f, con
 int seld_rnn_gru_bwd(const float* dh_f, const float* dh_b, const float* h_f, const float* h_b, const float* saved_f, const float* saved_b,
                      const float* U_f, const float* U_b, float* dgx_f, float* dgx_b, float* dgh_f, float* dgh_b, int B, int S, int units,
                      void* stream);
+/* The same recurrences under Keras dropout / recurrent_dropout (modules.py:312-315, 338-340 pass dropout_rate as both), training only; the
+ * contract of the four entries above, with every buffer the backward reads REQUIRED (the masks, c_*, hm_*, saved_*).  rm_* [B,128]: the state
+ * mask of each direction, 0 | 1/(1-rate) per (clip, unit), constant over the sequence.  The input mask is not these entries' business: the
+ * caller projects x * im (seld_rnn_mask_rows) into gx_*.
+ * LSTM (LSTMCell.call, implementation 2): z = gx[t] + (h_prev rm) U; c' = f c + i g, c is never masked; h' = o tanh(c'), emitted unmasked.
+ * The kernels scale their register copy of U by rm (lstm.hip), so h_*, c_*, saved_* are laid out as by seld_rnn_lstm_fwd and a mask of ones
+ * gives its bits.  BPTT: the carry into the previous step is rm (dgx[t] U^T); dU = (h_prev rm)^T dgx (seld_rnn_mask_rows on h_*, then
+ * seld_m_gemm_tn with seq = S, shift = -1 | +1). */
+int seld_rnn_lstm_drop_fwd(const float* gx_f, const float* gx_b, const float* U_f, const float* U_b, const float* rm_f, const float* rm_b,
+                           float* h_f, float* h_b, float* c_f, float* c_b, float* saved_f, float* saved_b, int B, int S, int units, void* stream);
+int seld_rnn_lstm_drop_bwd(const float* dh_f, const float* dh_b, const float* c_f, const float* c_b, const float* saved_f, const float* saved_b,
+                           const float* U_f, const float* U_b, const float* rm_f, const float* rm_b, float* dgx_f, float* dgx_b, int B, int S,
+                           int units, void* stream);
+/* GRU (GRUCell.call, implementation 2, reset_after=True; seld_k_gru_drop_fwd / _bwd per direction and on `stream`): h_prev rm goes into the
+ * recurrent product AND the blend; h_* is the unmasked output, hm_* [B,S,128] = h rm the masked state sequence, which the backward reads in
+ * h_*'s place (and the caller as the shifted operand of dU); dh_* are the two directions' output gradients, used as given. */
+int seld_rnn_gru_drop_fwd(const float* gx_f, const float* gx_b, const float* U_f, const float* U_b, const float* brec_f, const float* brec_b,
+                          const float* rm_f, const float* rm_b, float* h_f, float* h_b, float* hm_f, float* hm_b, float* saved_f, float* saved_b,
+                          int B, int S, int units, void* stream);
+int seld_rnn_gru_drop_bwd(const float* dh_f, const float* dh_b, const float* hm_f, const float* hm_b, const float* saved_f, const float* saved_b,
+                          const float* U_f, const float* U_b, const float* rm_f, const float* rm_b, float* dgx_f, float* dgx_b, float* dgh_f,
+                          float* dgh_b, int B, int S, int units, void* stream);
+/* seld_k_mask_rows on `stream`, asynchronous, with the same refusals: out[r][f] (+)= in[r][f] * mask[r / S][f]; F % 4 == 0, 16-byte aligned.
+ * Named with the recurrence entries it serves: the seld_m_* set is the one tests/test_module_ops_gpu.py calls one by one (above). */
+int seld_rnn_mask_rows(const float* in, const float* mask, float* out, int64_t rows, int S, int F, int accumulate, void* stream);
 /* Bidirectional(merge_mode) (modules.py:341-342) on h_f, h_b [rows, units]: out / dout [rows, units], or [rows, 2 units] for SELD_MERGE_CONCAT (the
  * forward direction first).  Any units >= 1 (float4 where units % 4 == 0 and the pointers are 16-byte aligned); only SELD_MERGE_MUL reads h_* in the
  * backward (they may be NULL otherwise); SELD_ERR_INVALID for an unknown mode. */

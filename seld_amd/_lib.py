@@ -234,6 +234,11 @@ SIGNATURES = {
     "seld_rnn_lstm_bwd": (_I, [_P] * 10 + [_I] * 3 + [_P]),
     "seld_rnn_gru_fwd": (_I, [_P] * 10 + [_I] * 3 + [_P]),
     "seld_rnn_gru_bwd": (_I, [_P] * 12 + [_I] * 3 + [_P]),
+    "seld_rnn_lstm_drop_fwd": (_I, [_P] * 12 + [_I] * 3 + [_P]),
+    "seld_rnn_lstm_drop_bwd": (_I, [_P] * 12 + [_I] * 3 + [_P]),
+    "seld_rnn_gru_drop_fwd": (_I, [_P] * 14 + [_I] * 3 + [_P]),
+    "seld_rnn_gru_drop_bwd": (_I, [_P] * 14 + [_I] * 3 + [_P]),
+    "seld_rnn_mask_rows": (_I, [_P, _P, _P, _L, _I, _I, _I, _P]),
     "seld_rnn_merge_fwd": (_I, [_P, _P, _P, _L, _I, _I, _P]),
     "seld_rnn_merge_bwd": (_I, [_P, _P, _P, _P, _P, _L, _I, _I, _P]),
     "seld_m_losses_scratch": (_L, [_I]),

@@ -347,14 +347,19 @@ int launch_gru_bwd(hipStream_t st, const float* dout, const float* h_f, const fl
                    float* dgh_f, float* dgh_b, int B, int S, const float* rm_f = nullptr, const float* rm_b = nullptr, const float* hm_f = nullptr,
                    const float* hm_b = nullptr);
 // the same kernels for reference modules.RNN_block (seld_rnn_gru_*): one direction alone; output gradients per direction, used as given
-int launch_gru_fwd_uni(hipStream_t st, const float* gx, const float* U, const float* brec, float* h, float* sv, int B, int S);
+// rm (with hm; the two-direction forward is launch_gru_fwd's): the recurrent-dropout forms (seld_rnn_gru_drop_*); h_* is then not read by the backward
+int launch_gru_fwd_uni(hipStream_t st, const float* gx, const float* U, const float* brec, float* h, float* sv, int B, int S,
+                       const float* rm = nullptr, float* hm = nullptr);
 int launch_gru_bwd_dh(hipStream_t st, const float* dh_f, const float* dh_b, const float* h_f, const float* h_b, const float* sv_f, const float* sv_b,
-                      const float* U_f, const float* U_b, float* dgx_f, float* dgx_b, float* dgh_f, float* dgh_b, int B, int S);
-// lstm.hip: LSTM(128) recurrence, one (gx_b / dh_b == nullptr) or two directions; c_f == nullptr: nothing is saved for the backward pass
+                      const float* U_f, const float* U_b, float* dgx_f, float* dgx_b, float* dgh_f, float* dgh_b, int B, int S,
+                      const float* rm_f = nullptr, const float* rm_b = nullptr, const float* hm_f = nullptr, const float* hm_b = nullptr);
+// lstm.hip: LSTM(128) recurrence, one (gx_b / dh_b == nullptr) or two directions; c_f == nullptr: nothing is saved for the backward pass;
+// rm_f (rm_b with the second direction) [B][128]: the recurrent-dropout forms (seld_rnn_lstm_drop_*), which always save
 int launch_lstm_fwd(hipStream_t st, const float* gx_f, const float* gx_b, const float* U_f, const float* U_b, float* h_f, float* h_b,
-                    float* c_f, float* c_b, float* sv_f, float* sv_b, int B, int S);
+                    float* c_f, float* c_b, float* sv_f, float* sv_b, int B, int S, const float* rm_f = nullptr, const float* rm_b = nullptr);
 int launch_lstm_bwd(hipStream_t st, const float* dh_f, const float* dh_b, const float* c_f, const float* c_b, const float* sv_f,
-                    const float* sv_b, const float* U_f, const float* U_b, float* dgx_f, float* dgx_b, int B, int S);
+                    const float* sv_b, const float* U_f, const float* U_b, float* dgx_f, float* dgx_b, int B, int S,
+                    const float* rm_f = nullptr, const float* rm_b = nullptr);
 int launch_mul(hipStream_t st, const float* a, const float* b, float* out, int64_t n);
 
 struct seld_loss_cfg;

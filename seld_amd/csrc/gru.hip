@@ -210,8 +210,15 @@ int launch_gru_fwd(hipStream_t st, const float* gx_f, const float* gx_b, const f
     return 0;
 }
 
-// seld_rnn_gru_fwd with one direction: grid B
-int launch_gru_fwd_uni(hipStream_t st, const float* gx, const float* U, const float* brec, float* h, float* sv, int B, int S) {
+// seld_rnn_gru_fwd with one direction: grid B.  rm: seld_rnn_gru_drop_fwd's (sv and hm are then required)
+int launch_gru_fwd_uni(hipStream_t st, const float* gx, const float* U, const float* brec, float* h, float* sv, int B, int S, const float* rm,
+                       float* hm) {
+    if (rm) {
+        if (!hm || !sv) return -1;
+        hipLaunchKernelGGL((gru_fwd_kernel<true, false, true, true>), dim3(B), dim3(512), 0, st, gx, nullptr, U, nullptr, brec, nullptr, h, nullptr, sv, nullptr,
+                           S, rm, nullptr, hm, nullptr);
+        return 0;
+    }
     if (sv) hipLaunchKernelGGL((gru_fwd_kernel<true, true, false, true>), dim3(B), dim3(512), 0, st, gx, nullptr, U, nullptr, brec, nullptr, h, nullptr, sv, nullptr, S);
     else hipLaunchKernelGGL((gru_fwd_kernel<false, true, false, true>), dim3(B), dim3(512), 0, st, gx, nullptr, U, nullptr, brec, nullptr, h, nullptr, sv, nullptr, S);
     return 0;
@@ -444,8 +451,17 @@ int launch_gru_bwd(hipStream_t st, const float* dout, const float* h_f, const fl
 
 // seld_rnn_gru_bwd: the two directions' output gradients as given (dh_b == nullptr: one direction, grid B)
 int launch_gru_bwd_dh(hipStream_t st, const float* dh_f, const float* dh_b, const float* h_f, const float* h_b, const float* sv_f, const float* sv_b,
-                      const float* U_f, const float* U_b, float* dgx_f, float* dgx_b, float* dgh_f, float* dgh_b, int B, int S) {
+                      const float* U_f, const float* U_b, float* dgx_f, float* dgx_b, float* dgh_f, float* dgh_b, int B, int S, const float* rm_f,
+                      const float* rm_b, const float* hm_f, const float* hm_b) {
     const size_t smem = (size_t)(2 * GRUB_CH * GRUB_ROW + 2 * GRUB_GL) * sizeof(float);
+    if (rm_f) {      // recurrent dropout (seld_rnn_gru_drop_bwd): h_prev is hm, h_* is not read
+        if (!hm_f || (dh_b && (!rm_b || !hm_b))) return -1;
+        auto kd = dh_b ? gru_bwd_kernel<false, true, 1> : gru_bwd_kernel<false, true, 2>;
+        hipFuncSetAttribute(reinterpret_cast<const void*>(kd), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+        hipLaunchKernelGGL(kd, dim3((dh_b ? 2 : 1) * B), dim3(512), smem, st, dh_f, h_f, h_b, sv_f, sv_b, U_f, U_b, dgx_f, dgx_b, dgh_f, dgh_b, S,
+                           rm_f, rm_b, hm_f, hm_b, dh_b);
+        return 0;
+    }
     auto kern = dh_b ? gru_bwd_kernel<true, false, 1> : gru_bwd_kernel<true, false, 2>;
     hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
     hipLaunchKernelGGL(kern, dim3((dh_b ? 2 : 1) * B), dim3(512), smem, st, dh_f, h_f, h_b, sv_f, sv_b, U_f, U_b, dgx_f, dgx_b, dgh_f, dgh_b, S,

@@ -14,6 +14,14 @@
 // of the quad carries the unit's cell state c in a register for the whole sequence.
 // BPTT: gru_bwd_kernel's register blocking of the transposed mat-vec (512 -> 128: 4 outputs x 32 columns per lane, 8 ds_read_b128 per step),
 // and its 16 lanes per 4 units map onto (unit, gate i | f | g | o) exactly: no idle role.
+//
+// DROP (Keras LSTM recurrent_dropout, reference modules.py:338-340; training only): the previous state is multiplied by a per-(clip, unit) mask
+// rm = 0 | 1 / (1 - rate), constant over the sequence, ahead of the recurrent product — LSTMCell.call, implementation 2: z = gx[t] + (h rm) U.
+// c is never masked and the emitted h is the unmasked one.  A workgroup serves ONE clip for the whole sequence, so the mask is folded into the
+// register copy of U while it is loaded and the step loop is the undropped kernel's, instruction for instruction:
+//   forward: (h rm) U = h (diag(rm) U): row k of U is scaled by rm[b][k];
+//   BPTT:    the carry rm (dz U^T) = dz (diag(rm) U)^T: row j of U^T's operand, i.e. the lane's output j, is scaled by rm[b][j].
+// A mask of ones multiplies by 1.0f: the bits of the undropped kernels.
 #include "common.h"
 
 namespace {
@@ -31,12 +39,13 @@ __device__ __forceinline__ float tanh_(float x) { return fmaf(-2.f, __builtin_am
 #define LSTM_HL 144    // padded h vector: index k lives at k + 4 * (k >> 5) (the 4 quarters start in different bank groups)
 
 // SAVE: c [S][128] and the activations [S][unit][i f g o] are stored for the backward pass; the arithmetic of h does not depend on it
-template <bool SAVE>
+template <bool SAVE, bool DROP = false>
 __global__ __launch_bounds__(512) void lstm_fwd_kernel(const float* __restrict__ gx_f, const float* __restrict__ gx_b,
                                                        const float* __restrict__ U_f, const float* __restrict__ U_b,
                                                        float* __restrict__ h_f, float* __restrict__ h_b, float* __restrict__ c_f,
                                                        float* __restrict__ c_b, float* __restrict__ sv_f, float* __restrict__ sv_b, int S,
-                                                       int ndir) {
+                                                       int ndir, const float* __restrict__ rm_f = nullptr,
+                                                       const float* __restrict__ rm_b = nullptr) {
     const int b = ndir == 2 ? blockIdx.x >> 1 : blockIdx.x, dir = ndir == 2 ? blockIdx.x & 1 : 0;
     const float* gx = (dir ? gx_b : gx_f) + (size_t)b * S * LSTM_G;
     const float* U = dir ? U_b : U_f;
@@ -59,6 +68,11 @@ __global__ __launch_bounds__(512) void lstm_fwd_kernel(const float* __restrict__
             const int col = (a ^ q) * LSTM_U + j;
             u[a][p].x = U[(size_t)(32 * q + 2 * p) * LSTM_G + col];
             u[a][p].y = U[(size_t)(32 * q + 2 * p + 1) * LSTM_G + col];
+            if constexpr (DROP) {      // diag(rm) U: rows 32q + 2p, + 1
+                const float* rm = (dir ? rm_b : rm_f) + (size_t)b * LSTM_U;
+                u[a][p].x *= rm[32 * q + 2 * p];
+                u[a][p].y *= rm[32 * q + 2 * p + 1];
+            }
         }
     // lane q finishes gate q: sigmoid(x) = rcp(1 + exp2(-log2e x)); lane 2: tanh(x) = 2 rcp(1 + exp2(-2 log2e x)) - 1
     const float nsc = q == 2 ? -2.f * L2E : -L2E, am = q == 2 ? 2.f : 1.f, aa = q == 2 ? -1.f : 0.f;
@@ -161,11 +175,13 @@ __global__ __launch_bounds__(512) void lstm_fwd_kernel(const float* __restrict__
 // [32cp, 32cp+32), U^T's four rows in the order a ^ (cp & 3) (as gru_bwd_kernel), and the gate gradient of (unit j0 + (cp & 3), gate cp >> 2).
 // Everything of a step except dh and dc is prepared by pre() for the NEXT step while this step's mat-vec runs: behind the carry sit one add, two
 // fma and one multiply.
+template <bool DROP = false>
 __global__ __launch_bounds__(512) void lstm_bwd_kernel(const float* __restrict__ dh_f, const float* __restrict__ dh_b,
                                                        const float* __restrict__ c_f, const float* __restrict__ c_b,
                                                        const float* __restrict__ sv_f, const float* __restrict__ sv_b,
                                                        const float* __restrict__ U_f, const float* __restrict__ U_b,
-                                                       float* __restrict__ dgx_f, float* __restrict__ dgx_b, int S, int ndir) {
+                                                       float* __restrict__ dgx_f, float* __restrict__ dgx_b, int S, int ndir,
+                                                       const float* __restrict__ rm_f = nullptr, const float* __restrict__ rm_b = nullptr) {
     const int b = ndir == 2 ? blockIdx.x >> 1 : blockIdx.x, dir = ndir == 2 ? blockIdx.x & 1 : 0;
     const float* dO = (dir ? dh_b : dh_f) + (size_t)b * S * LSTM_U;
     const float* Cs = (dir ? c_b : c_f) + (size_t)b * S * LSTM_U;
@@ -187,6 +203,11 @@ __global__ __launch_bounds__(512) void lstm_bwd_kernel(const float* __restrict__
             const int ar = a ^ (cp & 3);
             ut[a][p].x = U[(size_t)(j0 + ar) * LSTM_G + 32 * cp + 2 * p];
             ut[a][p].y = U[(size_t)(j0 + ar) * LSTM_G + 32 * cp + 2 * p + 1];
+            if constexpr (DROP) {      // diag(rm) U: row j0 + ar, the output accumulator a sums
+                const float m = (dir ? rm_b : rm_f)[(size_t)b * LSTM_U + j0 + ar];
+                ut[a][p].x *= m;
+                ut[a][p].y *= m;
+            }
         }
     // BPTT step s is time t = S-1-s (dir 0) or s (dir 1); c_prev(t) = c[t-1] (dir 0) / c[t+1] (dir 1), zero outside the sequence
     const int cshift = dir ? 1 : -1;
@@ -321,22 +342,26 @@ __global__ __launch_bounds__(512) void lstm_bwd_kernel(const float* __restrict__
 
 }  // namespace
 
-// gx_b == nullptr: one direction (grid B).  SAVE form iff c_f is given.
+// gx_b == nullptr: one direction (grid B).  SAVE form iff c_f is given.  rm_f: the DROP form (training: c and sv are given)
 int launch_lstm_fwd(hipStream_t st, const float* gx_f, const float* gx_b, const float* U_f, const float* U_b, float* h_f, float* h_b,
-                    float* c_f, float* c_b, float* sv_f, float* sv_b, int B, int S) {
+                    float* c_f, float* c_b, float* sv_f, float* sv_b, int B, int S, const float* rm_f, const float* rm_b) {
     const int ndir = gx_b ? 2 : 1;
+    if (rm_f && (!c_f || !sv_f || (ndir == 2 && !rm_b))) return -1;
     const size_t smem = (size_t)(2 * LSTMF_CH * LSTM_G + 2 * LSTM_HL) * sizeof(float);
-    auto kern = c_f ? lstm_fwd_kernel<true> : lstm_fwd_kernel<false>;
+    auto kern = rm_f ? lstm_fwd_kernel<true, true> : c_f ? lstm_fwd_kernel<true> : lstm_fwd_kernel<false>;
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return -1;
-    hipLaunchKernelGGL(kern, dim3(ndir * B), dim3(512), smem, st, gx_f, gx_b, U_f, U_b, h_f, h_b, c_f, c_b, sv_f, sv_b, S, ndir);
+    hipLaunchKernelGGL(kern, dim3(ndir * B), dim3(512), smem, st, gx_f, gx_b, U_f, U_b, h_f, h_b, c_f, c_b, sv_f, sv_b, S, ndir, rm_f, rm_b);
     return 0;
 }
 
 int launch_lstm_bwd(hipStream_t st, const float* dh_f, const float* dh_b, const float* c_f, const float* c_b, const float* sv_f,
-                    const float* sv_b, const float* U_f, const float* U_b, float* dgx_f, float* dgx_b, int B, int S) {
+                    const float* sv_b, const float* U_f, const float* U_b, float* dgx_f, float* dgx_b, int B, int S, const float* rm_f,
+                    const float* rm_b) {
     const int ndir = dh_b ? 2 : 1;
+    if (rm_f && ndir == 2 && !rm_b) return -1;
     const size_t smem = (size_t)(2 * LSTMB_CH * LSTMB_ROW + 2 * LSTMB_GL) * sizeof(float);
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(lstm_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return -1;
-    hipLaunchKernelGGL(lstm_bwd_kernel, dim3(ndir * B), dim3(512), smem, st, dh_f, dh_b, c_f, c_b, sv_f, sv_b, U_f, U_b, dgx_f, dgx_b, S, ndir);
+    auto kern = rm_f ? lstm_bwd_kernel<true> : lstm_bwd_kernel<false>;
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return -1;
+    hipLaunchKernelGGL(kern, dim3(ndir * B), dim3(512), smem, st, dh_f, dh_b, c_f, c_b, sv_f, sv_b, U_f, U_b, dgx_f, dgx_b, S, ndir, rm_f, rm_b);
     return 0;
 }

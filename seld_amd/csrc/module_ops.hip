@@ -577,6 +577,58 @@ int seld_rnn_gru_bwd(const float* dh_f, const float* dh_b, const float* h_f, con
     launch_gru_bwd_dh((hipStream_t)stream, dh_f, dh_b, h_f, h_b, saved_f, saved_b, U_f, U_b, dgx_f, dgx_b, dgh_f, dgh_b, B, S);
     return ok();
 }
+/* ---- the same recurrences under Keras dropout / recurrent_dropout (reference modules.py:312-315, 338-340; training: everything the backward
+ * reads is required).  The state masks rm_* [B,128] ride in the kernels (gru.hip / lstm.hip: DROP); the input masks are seld_rnn_mask_rows in
+ * front of the projections ------------------------------------------------------------------------------------------------------------- */
+int seld_rnn_lstm_drop_fwd(const float* gx_f, const float* gx_b, const float* U_f, const float* U_b, const float* rm_f, const float* rm_b,
+                           float* h_f, float* h_b, float* c_f, float* c_b, float* saved_f, float* saved_b, int B, int S, int units, void* stream) {
+    if (units != 128) return SELD_ERR_UNSUPPORTED;
+    if (!gx_f || !U_f || !rm_f || !h_f || !c_f || !saved_f || B < 1 || S < 1) return SELD_ERR_INVALID;
+    if (gx_b ? (!U_b || !rm_b || !h_b || !c_b || !saved_b) : (U_b || rm_b || h_b || c_b || saved_b)) return SELD_ERR_INVALID;
+    if (S > RNN_MAX_S || B > 0x3fffffff) return SELD_ERR_UNSUPPORTED;
+    if (launch_lstm_fwd((hipStream_t)stream, gx_f, gx_b, U_f, U_b, h_f, h_b, c_f, c_b, saved_f, saved_b, B, S, rm_f, rm_b)) return SELD_ERR_HIP;
+    return ok();
+}
+int seld_rnn_lstm_drop_bwd(const float* dh_f, const float* dh_b, const float* c_f, const float* c_b, const float* saved_f, const float* saved_b,
+                           const float* U_f, const float* U_b, const float* rm_f, const float* rm_b, float* dgx_f, float* dgx_b, int B, int S,
+                           int units, void* stream) {
+    if (units != 128) return SELD_ERR_UNSUPPORTED;
+    if (!dh_f || !c_f || !saved_f || !U_f || !rm_f || !dgx_f || B < 1 || S < 1) return SELD_ERR_INVALID;
+    if (dh_b ? (!c_b || !saved_b || !U_b || !rm_b || !dgx_b) : (c_b || saved_b || U_b || rm_b || dgx_b)) return SELD_ERR_INVALID;
+    if (S > RNN_MAX_S || B > 0x3fffffff) return SELD_ERR_UNSUPPORTED;
+    if (launch_lstm_bwd((hipStream_t)stream, dh_f, dh_b, c_f, c_b, saved_f, saved_b, U_f, U_b, dgx_f, dgx_b, B, S, rm_f, rm_b)) return SELD_ERR_HIP;
+    return ok();
+}
+int seld_rnn_gru_drop_fwd(const float* gx_f, const float* gx_b, const float* U_f, const float* U_b, const float* brec_f, const float* brec_b,
+                          const float* rm_f, const float* rm_b, float* h_f, float* h_b, float* hm_f, float* hm_b, float* saved_f, float* saved_b,
+                          int B, int S, int units, void* stream) {
+    if (units != 128) return SELD_ERR_UNSUPPORTED;
+    if (!gx_f || !U_f || !brec_f || !rm_f || !h_f || !hm_f || !saved_f || B < 1 || S < 1) return SELD_ERR_INVALID;
+    if (gx_b ? (!U_b || !brec_b || !rm_b || !h_b || !hm_b || !saved_b) : (U_b || brec_b || rm_b || h_b || hm_b || saved_b)) return SELD_ERR_INVALID;
+    if (S > RNN_MAX_S || B > 0x3fffffff) return SELD_ERR_UNSUPPORTED;
+    if (gx_b ? launch_gru_fwd((hipStream_t)stream, gx_f, gx_b, U_f, U_b, brec_f, brec_b, h_f, h_b, saved_f, saved_b, B, S, rm_f, rm_b, hm_f, hm_b)
+             : launch_gru_fwd_uni((hipStream_t)stream, gx_f, U_f, brec_f, h_f, saved_f, B, S, rm_f, hm_f))
+        return SELD_ERR_HIP;
+    return ok();
+}
+int seld_rnn_gru_drop_bwd(const float* dh_f, const float* dh_b, const float* hm_f, const float* hm_b, const float* saved_f, const float* saved_b,
+                          const float* U_f, const float* U_b, const float* rm_f, const float* rm_b, float* dgx_f, float* dgx_b, float* dgh_f,
+                          float* dgh_b, int B, int S, int units, void* stream) {
+    if (units != 128) return SELD_ERR_UNSUPPORTED;
+    if (!dh_f || !hm_f || !saved_f || !U_f || !rm_f || !dgx_f || !dgh_f || B < 1 || S < 1) return SELD_ERR_INVALID;
+    if (dh_b ? (!hm_b || !saved_b || !U_b || !rm_b || !dgx_b || !dgh_b) : (hm_b || saved_b || U_b || rm_b || dgx_b || dgh_b)) return SELD_ERR_INVALID;
+    if (S > RNN_MAX_S || B > 0x3fffffff) return SELD_ERR_UNSUPPORTED;
+    if (launch_gru_bwd_dh((hipStream_t)stream, dh_f, dh_b, nullptr, nullptr, saved_f, saved_b, U_f, U_b, dgx_f, dgx_b, dgh_f, dgh_b, B, S, rm_f, rm_b,
+                          hm_f, hm_b))
+        return SELD_ERR_HIP;
+    return ok();
+}
+/* seld_k_mask_rows's kernel on the caller's stream, with the same refusals */
+int seld_rnn_mask_rows(const float* in, const float* mask, float* out, int64_t rows, int S, int F, int accumulate, void* stream) {
+    if (!in || !mask || !out || rows < 1 || S < 1 || F < 1 || (F & 3) || !al16(in) || !al16(mask) || !al16(out)) return SELD_ERR_INVALID;
+    if (launch_mask_rows((hipStream_t)stream, in, mask, out, rows, S, F, accumulate)) return SELD_ERR_INVALID;
+    return ok();
+}
 int seld_rnn_merge_fwd(const float* h_f, const float* h_b, float* out, int64_t rows, int units, int mode, void* stream) {
     if (!h_f || !h_b || !out || rows < 1 || units < 1 || mode < SELD_MERGE_MUL || mode > SELD_MERGE_SUM) return SELD_ERR_INVALID;
     int64_t n = rows * units;

@@ -20,7 +20,8 @@ else).  There is no CPU or PyTorch fallback.
                                                   depthwise Conv1D module, LayerNormalization in front or behind
 
   RNN_block / RNN_stage (modules.py:64-83, 322-347)                  GRU or LSTM (units 128: the recurrence kernels of gru.hip / lstm.hip), one direction or
-                                                  Bidirectional with merge_mode mul | concat | ave | sum (seld_rnn_*)
+                                                  Bidirectional with merge_mode mul | concat | ave | sum (seld_rnn_*); dropout_rate = Keras dropout and
+                                                  recurrent_dropout: per-clip input and state masks in training (seld_rnn_mask_rows, seld_rnn_*_drop_*)
 
   models.conv_temporal (models.py:54-78)                              ConvTemporalNet: StemConv2D (seld_stem_conv_* of stem.hip) + BatchNormalization + relu +
                                                   MaxPool2D (seld_pool2d_*), the BLOCK* chain (mother blocks, then every 3-D kind, DenseBlock =
@@ -37,8 +38,9 @@ The shared pieces, each in one place:
   _ConvTail            depthwise Conv1D -> BatchNormalization -> swish -> pointwise Conv1D: the conformer's and the attention block's
   _Attention           the attention layers' buffers; _HeadMajorAttention: the reference's own two layers' packing and projections
   _Recurrent           the recurrent blocks' variables, input projections and weight gradients (RNNBlock, BidirectionalGRUBlock)
-  _Drop                one block's Dropout layers (transformer, conformer and absolute-position attention blocks; training only): the draw
-                       streams and the calls of seld_dropout; the attention probabilities are dropped inside seld_attn_drop_fwd / _bwd
+  _Drop                one block's Dropout layers (transformer, conformer and absolute-position attention blocks, and the recurrent blocks'
+                       cell masks; training only): the draw streams and the calls of seld_dropout; the attention probabilities are dropped inside
+                       seld_attn_drop_fwd / _bwd
   Stage, SECOND_KINDS  every SECOND kind is a Stage of blocks of one class; the table names the class, its config check and its prefix, and
                        the eight factories and ComposedSeldNet build from it (_second_factory, _build_second)
 
@@ -262,7 +264,8 @@ class _Drop:
         5                                   second FFN, behind the activation second FF, behind the activation
         6                                   second FFN, behind its output    second FF, behind its output
 
-    (a site keeps its number where a configuration leaves its module out).  Element e of a [rows, C] tensor draws word e & 3 of counter
+    (a site keeps its number where a configuration leaves its module out); the recurrent blocks (_Recurrent) draw their cells' masks on sites
+    0 / 1 = the forward direction's input / state mask, 2 / 3 = the backward direction's.  Element e of a [rows, C] tensor draws word e & 3 of counter
     (e >> 2, layer, step, e >> 34): seld_dropout; the attention probabilities draw inside the kernels: seld_attn_drop_fwd / _bwd.  Nothing is
     stored: the backward calls the same operators with the runtime's dropout_cur.  The rate is above 0 only where the owner of the runtime accepted
     these draws in place of TensorFlow's (_Rt.dropout: a ComposedSeldNet, or a factory called with dropout=True)."""
@@ -1283,8 +1286,19 @@ class AttentionBlock:
 RNN_MERGE = ("mul", "concat", "ave", "sum")      # what tf.keras.layers.Bidirectional merges into ONE tensor
 
 
-def check_rnn_config(cfg: dict, stage: bool = False) -> None:
-    """reference modules.RNN_block / RNN_stage (modules.py:64-83, 322-347): the mandatory keys; what has no kernel here is refused, not ignored"""
+def _recurrent_rate(cfg: dict, who: str) -> float:
+    """dropout_rate of a recurrent kind whose owner accepted the library's draws, as the fp32 seld_dropout compares with (absent or None: the
+    reference's 0, modules.py:306, 329); 0 <= rate < 1"""
+    r = float(np.float32(cfg.get("dropout_rate", 0.0) or 0.0))
+    if not 0.0 <= r < 1.0:      # NaN fails both comparisons
+        raise ValueError(f"{who}: dropout_rate {cfg.get('dropout_rate')!r}: 0 <= dropout_rate < 1")
+    return r
+
+
+def check_rnn_config(cfg: dict, stage: bool = False, dropout: bool = False) -> None:
+    """reference modules.RNN_block / RNN_stage (modules.py:64-83, 322-347): the mandatory keys; what has no kernel here is refused, not ignored.
+    dropout: the owner accepted the library's draws for the cells' input and state masks (_Recurrent), and dropout_rate may be any rate in
+    [0, 1); without it the rate must be 0"""
     who = f"RNN_{'stage' if stage else 'block'}"
     for key in ("units",) + (("depth",) if stage else ()):
         if key not in cfg:
@@ -1293,7 +1307,9 @@ def check_rnn_config(cfg: dict, stage: bool = False) -> None:
         raise ValueError(f"{who}: units {cfg['units']!r}: the recurrence kernels are built for 128 units")
     if stage and int(cfg["depth"]) < 1:
         raise ValueError(f"{who}: depth >= 1")
-    if float(cfg.get("dropout_rate", 0.0) or 0.0) != 0.0:
+    if dropout:
+        _recurrent_rate(cfg, who)
+    elif float(cfg.get("dropout_rate", 0.0) or 0.0) != 0.0:
         raise ValueError(f"{who}: dropout / recurrent_dropout inside the recurrence kernels (per-clip input and state masks) are not implemented on "
                          "the composed path, whose Dropout (seld_dropout, seld_attn_drop_*) covers the attention kinds only: dropout_rate must be 0")
     if bool(cfg.get("bidirectional", True)) and cfg.get("merge_mode", "mul") not in RNN_MERGE:
@@ -1305,9 +1321,16 @@ class _Recurrent:
     """What the recurrent blocks share on [B*S, D] with 128 units and gate width G (GRU, reset_after=True: 384, LSTM: 512), per direction
     `name` of `names`: the variables kernel (D, G), recurrent_kernel (128, G), bias (GRU (2, 384): input row | recurrent row; LSTM (512,)),
     the input projections gx, the states h and sv, the pre-activation gradients dgx (GRU: and dgh, behind the reset gate), the input's
-    gradient din — and the GEMMs in front of and behind the recurrence kernels."""
+    gradient din — and the GEMMs in front of and behind the recurrence kernels.
 
-    def __init__(self, rt: _Rt, names, S: int, D: int, G: int, B: int):
+    Keras dropout / recurrent_dropout (`rate` > 0, training; reference modules.py:312-315, 338-340 pass dropout_rate as both): every cell —
+    each direction — owns an input mask im [B, D] and a state mask rm [B, 128] of 0 | 1 / (1 - rate), drawn once per training forward and
+    constant over the sequence: seld_dropout on ones, sites (_Drop) 0 / 1 = the forward direction's input / state mask, 2 / 3 = the backward
+    direction's.  The directions then project their own xm = x * im (seld_rnn_mask_rows), the recurrences run as seld_rnn_*_drop_*, the merge
+    as seld_rnn_merge_*; backward: the weight gradients read xm and the masked state sequence hm = h * rm, din = sum over the directions of
+    (dgx kernel^T) * im.  The blocks' `lstm`, `bi`, `mode`, `c`, `dh` and `out` say which recurrence and merge."""
+
+    def __init__(self, rt: _Rt, names, S: int, D: int, G: int, B: int, rate: float = 0.0):
         self.rt, self.names, self.S, self.D, self.G, self.B = rt, names, int(S), int(D), G, B
         for n in names:
             rt.var(f"{n}.kernel", (self.D, G)); rt.var(f"{n}.recurrent_kernel", (128, G)); rt.var(f"{n}.bias", (512,) if G == 512 else (2, 384))
@@ -1317,6 +1340,19 @@ class _Recurrent:
         self.dgx = [e(R, G) for _ in range(nd)]
         self.dgh = [e(R, G) for _ in range(nd)] if G == 384 else self.dgx      # LSTM: no reset gate, one pre-activation gradient
         self.din = e(R, self.D)
+        self.drop = _Drop(rt, rate)
+        if rate > 0.0:
+            if self.D % 4:
+                raise ValueError(f"recurrent dropout on an input width of {self.D}: the mask kernel (seld_rnn_mask_rows) moves float4, D % 4 == 0")
+            self.ones = torch.ones(B * max(self.D, 128), dtype=torch.float32, device=rt.dev)
+            self.im, self.rm = [e(B, self.D) for _ in range(nd)], [e(B, 128) for _ in range(nd)]
+            self.xm, self.hm = [e(R, self.D) for _ in range(nd)], [e(R, 128) for _ in range(nd)]
+            self.dxm = e(R, self.D)
+
+    def _pair(self, ts, none=False):
+        """the (forward, backward) pointer pair of a per-direction buffer list; one direction: (pointer, NULL)"""
+        p = self.rt.p
+        return (None, None) if none else (p(ts[0]), p(ts[1]) if len(self.names) == 2 else None)
 
     def _project(self, x, R):
         """gx = x kernel + the input bias, per direction"""
@@ -1337,20 +1373,74 @@ class _Recurrent:
             rt.gemm(self.dgx[d], rt.w(f"{n}.kernel"), None, self.din, R, self.D, self.G, transb=1, accumulate=d)
         return self.din[:R]
 
+    def _mask_rows(self, src, mask, dst, R, F, accumulate=0):
+        rt = self.rt
+        rt.ck(rt.lib.seld_rnn_mask_rows(rt.p(src), rt.p(mask), rt.p(dst), R, self.S, F, int(accumulate), rt.st()))
+
+    def _dropped_forward(self, x, B):
+        """the training forward at rate > 0 -> [B*S, out_dim]"""
+        rt, lib, R = self.rt, self.rt.lib, B * self.S
+        for d, n in enumerate(self.names):
+            self.drop.apply(2 * d, self.ones[:B * self.D], self.im[d][:B])
+            self.drop.apply(2 * d + 1, self.ones[:B * 128], self.rm[d][:B])
+            self._mask_rows(x, self.im[d], self.xm[d], R, self.D)
+            rt.gemm(self.xm[d], rt.w(f"{n}.kernel"), rt.w(f"{n}.bias")[:self.G], self.gx[d], R, self.G, self.D)
+        U = self._pair([rt.w(f"{n}.recurrent_kernel") for n in self.names])
+        if self.lstm:
+            rt.ck(lib.seld_rnn_lstm_drop_fwd(*self._pair(self.gx), *U, *self._pair(self.rm), *self._pair(self.h), *self._pair(self.c),
+                                             *self._pair(self.sv), B, self.S, 128, rt.st()))
+        else:
+            brec = self._pair([rt.w(f"{n}.bias")[384:] for n in self.names])
+            rt.ck(lib.seld_rnn_gru_drop_fwd(*self._pair(self.gx), *U, *brec, *self._pair(self.rm), *self._pair(self.h), *self._pair(self.hm),
+                                            *self._pair(self.sv), B, self.S, 128, rt.st()))
+        if not self.bi:
+            return self.h[0][:R]
+        rt.ck(lib.seld_rnn_merge_fwd(rt.p(self.h[0]), rt.p(self.h[1]), rt.p(self.out), R, 128, self.mode, rt.st()))
+        return self.out[:R]
+
+    def _dropped_backward(self, dy, B):
+        """its backward: dy [B*S, out_dim] -> the input's gradient [B*S, D]"""
+        rt, lib, R = self.rt, self.rt.lib, B * self.S
+        if self.bi:
+            rt.ck(lib.seld_rnn_merge_bwd(rt.p(dy), rt.p(self.h[0]), rt.p(self.h[1]), rt.p(self.dh[0]), rt.p(self.dh[1]), R, 128, self.mode, rt.st()))
+            dh = self._pair(self.dh)
+        else:
+            self._dy = dy.contiguous()      # kept: the kernel reads it after this call returns
+            dh = (rt.p(self._dy), None)
+        U = self._pair([rt.w(f"{n}.recurrent_kernel") for n in self.names])
+        if self.lstm:
+            rt.ck(lib.seld_rnn_lstm_drop_bwd(*dh, *self._pair(self.c), *self._pair(self.sv), *U, *self._pair(self.rm), *self._pair(self.dgx), B,
+                                             self.S, 128, rt.st()))
+        else:
+            rt.ck(lib.seld_rnn_gru_drop_bwd(*dh, *self._pair(self.hm), *self._pair(self.sv), *U, *self._pair(self.rm), *self._pair(self.dgx),
+                                            *self._pair(self.dgh), B, self.S, 128, rt.st()))
+        for d, n in enumerate(self.names):
+            gb = rt.g(f"{n}.bias")
+            if self.lstm:      # the GRU kernel stored its masked state sequence
+                self._mask_rows(self.h[d], self.rm[d], self.hm[d], R, 128)
+            rt.gemm_tn(self.xm[d], self.dgx[d], rt.g(f"{n}.kernel"), gb[:self.G], R, self.D, self.G)
+            rt.gemm_tn(self.hm[d], self.dgh[d], rt.g(f"{n}.recurrent_kernel"), gb[384:] if self.G == 384 else None, R, 128, self.G, seq=self.S,
+                       shift=-1 if d == 0 else 1)
+            rt.gemm(self.dgx[d], rt.w(f"{n}.kernel"), None, self.dxm, R, self.D, self.G, transb=1)
+            self._mask_rows(self.dxm, self.im[d], self.din, R, self.D, accumulate=d)
+        return self.din[:R]
+
 
 class RNNBlock(_Recurrent):
     """reference modules.RNN_block (modules.py:322-347) on [B*S, D]: rnn_type 'GRU' -> GRU(128, reset_after=True), ANYTHING else -> LSTM(128)
     (modules.py:334-337), return_sequences=True; bidirectional -> Bidirectional(merge_mode), whose variables are the forward layer's, then the
     backward layer's (`{prefix}.fwd.*`, `{prefix}.bwd.*`; one direction: `{prefix}.*`).  With bidirectional=False merge_mode is ignored.
-    GRU: kernel (D, 384), recurrent_kernel (128, 384), bias (2, 384);  LSTM: kernel (D, 512), recurrent_kernel (128, 512), bias (512,)."""
+    GRU: kernel (D, 384), recurrent_kernel (128, 384), bias (2, 384);  LSTM: kernel (D, 512), recurrent_kernel (128, 512), bias (512,).
+    dropout_rate > 0 (a runtime whose owner accepted the library's draws): the cells' dropout and recurrent_dropout, in training (_Recurrent)."""
 
     def __init__(self, rt: _Rt, cfg: dict, S: int, D: int, prefix: str, B: int):
-        check_rnn_config(cfg)
+        check_rnn_config(cfg, dropout=rt.dropout)
         self.prefix = prefix
         self.lstm = cfg.get("rnn_type", "GRU") != "GRU"
         self.bi = bool(cfg.get("bidirectional", True))
         self.mode = _lib.SELD_MERGE[cfg.get("merge_mode", "mul")] if self.bi else None
-        super().__init__(rt, [f"{prefix}.fwd", f"{prefix}.bwd"] if self.bi else [prefix], S, D, 512 if self.lstm else 384, B)
+        super().__init__(rt, [f"{prefix}.fwd", f"{prefix}.bwd"] if self.bi else [prefix], S, D, 512 if self.lstm else 384, B,
+                         _recurrent_rate(cfg, "RNN_block") if rt.dropout else 0.0)
         self.out_dim = 256 if self.bi and cfg.get("merge_mode", "mul") == "concat" else 128
         R, nd = B * self.S, len(self.names)
         e = rt.empty
@@ -1359,23 +1449,21 @@ class RNNBlock(_Recurrent):
         self.out = e(R, self.out_dim) if self.bi else None
         self.out_shape = (self.S, self.out_dim)
 
-    def _two(self, ts, none=False):
-        """the (forward, backward) pointer pair of a per-direction buffer list; one direction: (pointer, NULL)"""
-        p = self.rt.p
-        return (None, None) if none else (p(ts[0]), p(ts[1]) if self.bi else None)
-
     def forward(self, x, B, training):
         """x [B*S, D] (or any contiguous view of it) -> [B*S, out_dim]"""
         rt, lib = self.rt, self.rt.lib
         R = B * self.S
+        self.drop.begin(training)
+        if self.drop.on:
+            return self._dropped_forward(x.reshape(R, self.D), B)
         self._project(x.reshape(R, self.D), R)
-        U = self._two([rt.w(f"{n}.recurrent_kernel") for n in self.names])
+        U = self._pair([rt.w(f"{n}.recurrent_kernel") for n in self.names])
         if self.lstm:
-            rt.ck(lib.seld_rnn_lstm_fwd(*self._two(self.gx), *U, *self._two(self.h), *self._two(self.c, not training), *self._two(self.sv, not training),
+            rt.ck(lib.seld_rnn_lstm_fwd(*self._pair(self.gx), *U, *self._pair(self.h), *self._pair(self.c, not training), *self._pair(self.sv, not training),
                                         B, self.S, 128, rt.st()))
         else:
-            brec = self._two([rt.w(f"{n}.bias")[384:] for n in self.names])
-            rt.ck(lib.seld_rnn_gru_fwd(*self._two(self.gx), *U, *brec, *self._two(self.h), *self._two(self.sv, not training), B, self.S, 128, rt.st()))
+            brec = self._pair([rt.w(f"{n}.bias")[384:] for n in self.names])
+            rt.ck(lib.seld_rnn_gru_fwd(*self._pair(self.gx), *U, *brec, *self._pair(self.h), *self._pair(self.sv, not training), B, self.S, 128, rt.st()))
         if not self.bi:
             return self.h[0][:R]
         rt.ck(lib.seld_rnn_merge_fwd(rt.p(self.h[0]), rt.p(self.h[1]), rt.p(self.out), R, 128, self.mode, rt.st()))
@@ -1386,24 +1474,28 @@ class RNNBlock(_Recurrent):
         rt, lib = self.rt, self.rt.lib
         R = B * self.S
         dy = dy.reshape(R, self.out_dim)
+        if self.drop.on:
+            return self._dropped_backward(dy, B)
         if self.bi:
             rt.ck(lib.seld_rnn_merge_bwd(rt.p(dy), rt.p(self.h[0]), rt.p(self.h[1]), rt.p(self.dh[0]), rt.p(self.dh[1]), R, 128, self.mode, rt.st()))
-            dh = self._two(self.dh)
+            dh = self._pair(self.dh)
         else:
             self._dy = dy.contiguous()      # kept: the kernel reads it after this call returns
             dh = (rt.p(self._dy), None)
-        U = self._two([rt.w(f"{n}.recurrent_kernel") for n in self.names])
+        U = self._pair([rt.w(f"{n}.recurrent_kernel") for n in self.names])
         if self.lstm:
-            rt.ck(lib.seld_rnn_lstm_bwd(*dh, *self._two(self.c), *self._two(self.sv), *U, *self._two(self.dgx), B, self.S, 128, rt.st()))
+            rt.ck(lib.seld_rnn_lstm_bwd(*dh, *self._pair(self.c), *self._pair(self.sv), *U, *self._pair(self.dgx), B, self.S, 128, rt.st()))
         else:
-            rt.ck(lib.seld_rnn_gru_bwd(*dh, *self._two(self.h), *self._two(self.sv), *U, *self._two(self.dgx), *self._two(self.dgh), B, self.S, 128,
+            rt.ck(lib.seld_rnn_gru_bwd(*dh, *self._pair(self.h), *self._pair(self.sv), *U, *self._pair(self.dgx), *self._pair(self.dgh), B, self.S, 128,
                                        rt.st()))
         return self._weight_grads(R)
 
 
-def check_gru_config(cfg: dict, stage: bool = False) -> None:
-    """reference modules.bidirectional_GRU_block (modules.py:302-319): one layer per entry of `units`"""
-    if float(cfg.get("dropout_rate", 0.0)) != 0.0:
+def check_gru_config(cfg: dict, stage: bool = False, dropout: bool = False) -> None:
+    """reference modules.bidirectional_GRU_block (modules.py:302-319): one layer per entry of `units`.  dropout: as check_rnn_config's"""
+    if dropout:
+        _recurrent_rate(cfg, "bidirectional_GRU_block")
+    elif float(cfg.get("dropout_rate", 0.0)) != 0.0:
         raise ValueError("bidirectional_GRU_block: GRU dropout / recurrent_dropout masks exist on the fused path only (models.SeldNet), not among "
                          "the composed path's Dropout operators: dropout_rate must be 0")
     if any(int(u) != 128 for u in cfg["units"]):
@@ -1412,17 +1504,24 @@ def check_gru_config(cfg: dict, stage: bool = False) -> None:
 
 class BidirectionalGRUBlock(_Recurrent):
     """One layer of reference modules.bidirectional_GRU_block (modules.py:302-319) on [B*S, D]: Bidirectional(GRU(128, return_sequences=True),
-    merge_mode='mul'), the recurrences and the merge in the fused operators seld_m_gru_fwd / _bwd."""
+    merge_mode='mul'), the recurrences and the merge in the fused operators seld_m_gru_fwd / _bwd.  dropout_rate > 0 (a runtime whose owner
+    accepted the library's draws), in training: the cells' masks, the recurrences per direction and the 'mul' merge as its own operator
+    (_Recurrent)."""
+    lstm, bi, mode = False, True, _lib.SELD_MERGE["mul"]
 
     def __init__(self, rt: _Rt, cfg: dict, S: int, D: int, prefix: str, B: int):
-        check_gru_config(cfg)
-        super().__init__(rt, [f"{prefix}.fwd", f"{prefix}.bwd"], S, D, 384, B)
+        check_gru_config(cfg, dropout=rt.dropout)
+        super().__init__(rt, [f"{prefix}.fwd", f"{prefix}.bwd"], S, D, 384, B, _recurrent_rate(cfg, "bidirectional_GRU_block") if rt.dropout else 0.0)
         self.out = rt.empty(B * self.S, 128)
+        self.dh = [rt.empty(B * self.S, 128) for _ in (0, 1)] if self.drop.rate > 0.0 else None
         self.out_dim, self.out_shape = 128, (self.S, 128)
 
     def forward(self, x, B, training):
         rt, p = self.rt, self.rt.p
         R = B * self.S
+        self.drop.begin(training)
+        if self.drop.on:
+            return self._dropped_forward(x.reshape(R, self.D), B)
         self._project(x.reshape(R, self.D), R)
         U = [p(rt.w(f"{n}.recurrent_kernel")) for n in self.names]
         brec = [p(rt.w(f"{n}.bias")[384:]) for n in self.names]
@@ -1433,6 +1532,8 @@ class BidirectionalGRUBlock(_Recurrent):
     def backward(self, dy, B):
         rt, p = self.rt, self.rt.p
         R = B * self.S
+        if self.drop.on:
+            return self._dropped_backward(dy.reshape(R, 128), B)
         U = [p(rt.w(f"{n}.recurrent_kernel")) for n in self.names]
         rt.ck(rt.lib.seld_m_gru_bwd(p(dy), p(self.h[0]), p(self.h[1]), p(self.sv[0]), p(self.sv[1]), *U, p(self.dgx[0]), p(self.dgx[1]),
                                     p(self.dgh[0]), p(self.dgh[1]), B, self.S, 128, rt.st()))
@@ -1666,7 +1767,7 @@ SECOND_KINDS = {
 assert tuple(SECOND_KINDS) == COMPOSED_SECOND + CONFORMER_SECOND + ATTENTION_SECOND + RNN_SECOND
 
 
-DROPOUT_KINDS = COMPOSED_SECOND[1:] + CONFORMER_SECOND + ATTENTION_SECOND      # the SECOND kinds whose Dropouts can draw (_Drop)
+DROPOUT_KINDS = COMPOSED_SECOND + CONFORMER_SECOND + ATTENTION_SECOND + RNN_SECOND      # the SECOND kinds whose Dropouts can draw (_Drop): all
 
 
 def _check_second(kind: str, cfg: dict, D=None, dropout: bool = False) -> None:
