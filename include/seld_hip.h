@@ -339,6 +339,34 @@ int seld_aug_v2(float* x, int B, int T, int F, int C, int period, const float* s
 int seld_aug_mcs_max_frames(int C);
 int seld_aug_mcs(const float* x, float* out, double* lambda, int32_t* stab_adds, int B, int T, int F, int C, int iteration, double theta,
                  void* stream);
+/* Time-domain mixing: data_loader.TDM_aug (data_loader.py:188-234), which train.get_tdm_dataset (train.py:210-261) runs on the host over the
+ *   whole training split every --tdm_epoch epochs (train.py:279-288, 341-356).  The host makes the reference's draws and passes them as a plan,
+ *   int32 [B][K][4] = (cls, st, offset, td_offset) on the device (16-byte aligned): insertion k of a clip adds `st` label frames of bank class
+ *   `cls`, from frame td_offset of that class's track, at label frame `offset` of the clip.  nc = W / 4; a label row is [activity | x | y | z].
+ *   Both calls are asynchronous on `stream`: no allocation, no copy, no host synchronisation, no atomics, fixed order (the same bits every call).
+ * seld_aug_tdm_labels: the labels, y [B][T][W] in place.  bank_y holds the classes' label tracks packed row-wise: class k is rows
+ *   bank_row0[k] .. bank_row0[k] + bank_rows[k] of [W] floats (int64 [n_cls] each, device).  One workgroup per clip runs its K insertions in
+ *   order: v[f] = (sum_{c<nc} y[off+f][c] < max_per_frame ? 1 : 0) * (1 - y[off+f][cls]) for f < st (sum over c ascending in fp32; fractional
+ *   activities give a fractional v, as in the reference), then y[off+f][:] += bank_y[cls][td+f][:] * v[f] (multiply, then add).  valid, float
+ *   [B][K][ld_valid], is WRITTEN: v[f] for f < st, 0 behind.  A plan row that reaches outside the clip, the class's track or ld_valid
+ *   (cls outside [0, n_cls), st outside [1, min(T, ld_valid)], offset < 0, offset + st > T, td_offset < 0, td_offset + st > bank_rows[cls])
+ *   is skipped and its valid row is 0: nothing outside a buffer is read.  The reference's early return when sum(v) == 0 adds zeros here.
+ * seld_aug_tdm_mix: the waveforms, x_in -> x_out [B][C][N], N >= T * spf (spf = samples per label frame, 2400 in the reference); x_out == x_in
+ *   is allowed (in place), any other overlap is the caller's error.  bank_x packing: class k's waveform is ONE block [C][n_k] of floats that
+ *   starts at bank_x + bank_s0[k] (channel c at + c * n_k), the blocks one behind the other; bank_s0 is int64 [n_cls + 1] on the device, its
+ *   last entry the end of the last block, so that n_k = (bank_s0[k+1] - bank_s0[k]) / C is known to the kernel, which skips a plan row with
+ *   (td_offset + st) * spf > n_k.  `valid` is what seld_aug_tdm_labels wrote for this plan.  One workgroup per (clip, label frame) holds
+ *   the frame's C x spf samples in registers and applies the insertions that cover it in plan order, x = x + t * v[f - offset] (multiply, then
+ *   add: the bits of the reference's x[i] += pad(...) one insertion after the other); a frame no insertion covers is not touched in place and
+ *   copied out of place, as are the samples at and behind T * spf.  float4 accesses when spf % 4 == 0, N % 4 == 0 and x_in, x_out and bank_x
+ *   are 16-byte aligned (a class with bank_s0[k] % 4 != 0 or n_k % 4 != 0 is then read with scalar loads), else a scalar form.
+ * Before anything is enqueued, both: SELD_ERR_INVALID for a NULL pointer, B, T, W, C, spf or n_cls < 1, W % 4 != 0, K < 0, ld_valid < 1,
+ *   N < T * spf, a plan that is not 16-byte aligned, more bank classes than label classes (n_cls > W / 4); SELD_ERR_UNSUPPORTED for K > 32 and for more than 2^24 - 1 workgroups (B, or B * T).
+ *   K == 0: SELD_OK, nothing enqueued (plan and valid may be NULL) — except the mix out of place, which still copies x_in to x_out. */
+int seld_aug_tdm_labels(float* y, int B, int T, int W, const float* bank_y, const int64_t* bank_row0, const int64_t* bank_rows, int n_cls,
+                        const int32_t* plan, int K, int max_per_frame, float* valid, int ld_valid, void* stream);
+int seld_aug_tdm_mix(const float* x_in, float* x_out, int B, int C, int64_t N, int T, int spf, const float* bank_x, const int64_t* bank_s0,
+                     int n_cls, const int32_t* plan, int K, const float* valid, int ld_valid, void* stream);
 
 /* ---- SELD metrics on the device: SELDMetrics.update_states (metrics.py:60-154), which the reference runs in TF
  * eager mode on the host after every step (train.py:82-83).  `state` = seld_metrics_state_size(nc) doubles

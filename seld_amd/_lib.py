@@ -137,6 +137,8 @@ SIGNATURES = {
     "seld_aug_v2": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _I, _P, _P, _I, _P]),
     "seld_aug_mcs_max_frames": (_I, [_I]),
     "seld_aug_mcs": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, C.c_double, _P]),
+    "seld_aug_tdm_labels": (_I, [_P, _I, _I, _I, _P, _P, _P, _I, _P, _I, _I, _P, _I, _P]),
+    "seld_aug_tdm_mix": (_I, [_P, _P, _I, _I, _L, _I, _I, _P, _P, _I, _P, _I, _P, _I, _P]),
     "seld_metrics_state_size": (_I, [_I]),
     "seld_metrics_scratch_floats": (_L, [_I, _I, _I, _I]),
     "seld_metrics_update": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P]),

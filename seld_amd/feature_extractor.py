@@ -161,6 +161,34 @@ def apply_normalizer_array(feature, mean, std, eps: float = 1e-8, n_frames: int 
     return out
 
 
+def polar_to_cartesian(coordinates) -> np.ndarray:
+    """reference feature_extractor.polar_to_cartesian (feature_extractor.py:256-271): [..., (azimuth, elevation[, r])] degrees -> [..., (x, y, z)]."""
+    c = np.asarray(coordinates)
+    azi, ele = c[..., 0] * np.pi / 180, c[..., 1] * np.pi / 180
+    r = c[..., 2] if c.shape[-1] == 3 else 1
+    return np.stack([r * np.cos(azi) * np.cos(ele), r * np.sin(azi) * np.cos(ele), r * np.sin(ele)], axis=-1)
+
+
+def extract_labels(path: str, n_classes: int = 14, max_frames=None) -> np.ndarray:
+    """reference feature_extractor.extract_labels (feature_extractor.py:91-114), host side: a metadata csv of rows
+    `frame, class, track, azimuth, elevation` (integers) -> float32 [frames, 4 * n_classes] = [activity | x | y | z], frames = the last labelled
+    frame + 1, or max_frames when that is larger."""
+    rows = []
+    with open(path, 'r') as o:
+        for line in o.readlines():
+            frame, cls, _, azi, ele = list(map(int, line.split(',')))
+            rows.append([frame, cls, azi, ele])
+    rows = np.stack(rows, axis=0)
+    cart = polar_to_cartesian(rows[..., 2:])
+    output_len = int(rows[..., 0].max()) + 1
+    if max_frames is not None:
+        output_len = max(max_frames, output_len)
+    outputs = np.zeros((output_len, 4, n_classes), dtype='float32')
+    for (frame, cls), xyz in zip(rows[:, :2], cart):
+        outputs[int(frame), :, int(cls)] = [1., *xyz]
+    return outputs.reshape([-1, 4 * n_classes])
+
+
 def extract_features_device(wav, sample_rate, mode="foa", n_mels=64, **kwargs) -> torch.Tensor:
     return FeatureExtractor(sample_rate, mode, n_mels, **kwargs)(wav)
 

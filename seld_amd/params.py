@@ -38,6 +38,10 @@ def build_parser() -> argparse.ArgumentParser:
     args.add_argument('--use_tfm', action='store_true')
     args.add_argument('--loop_time', type=int, default=5, help='times of train dataset iter for an epoch')
     args.add_argument('--tdm_epoch', type=int, default=2, help="epochs of applying tdm augmentation. If 0, don't use it.")
+    # the reference hard-codes these three (train.py:212-214, 222: /media/data1/datasets/DCASE2020/{foa_dev, metadata_dev} and ./foa_dev_tdm)
+    args.add_argument('--tdm_wav_path', type=str, default='', help='directory of the *.wav clips time-domain mixing starts from')
+    args.add_argument('--tdm_label_path', type=str, default='', help='directory of their metadata *.csv files')
+    args.add_argument('--tdm_bank_path', type=str, default='', help='directory that holds foa_dev_tdm/tdm_{noise,label}_{k}.npy')
     # metric
     args.add_argument('--lad_doa_thresh', type=int, default=20)
     args.add_argument('--sed_loss', type=str, default='BCE', choices=['BCE', 'FOCAL'])
@@ -64,6 +68,8 @@ def get_param(known=None, model_config_dir: str = './model_config'):
         # a .call method but no __call__ (losses.py:38-48), and trainstep calls sed_loss(y, p) (train.py:26) -> TypeError
         raise ValueError('--sed_loss FOCAL has no MI355X kernel (built: BCE); the reference raises on it too (Focal_Loss is not callable)')
     if config.use_tdm:
-        raise ValueError('--use_tdm: time-domain mixing works on raw wavs outside the accelerated path (SURVEY.md §2); '
-                         '--use_tfm and --use_acs run on the device')
+        missing = [f'--{k}' for k in ('tdm_wav_path', 'tdm_label_path', 'tdm_bank_path') if not getattr(config, k)]
+        if missing:
+            raise ValueError('--use_tdm: time-domain mixing reads raw wavs, their metadata and the noise bank, and the reference hard-codes where '
+                             f'(train.py:212-223); here the paths are flags, and {", ".join(missing)} {"is" if len(missing) == 1 else "are"} missing')
     return config, model_config
