@@ -438,6 +438,14 @@ int seld_k_set_option(const char* key, int value);
  * stats (may be NULL): [2*64] = per-channel sum(z), sum(z^2) over B*H*W (BatchNormalization batch statistics). */
 int seld_k_conv3x3_fwd(const float* x, const float* w, const float* bias, float* z, float* stats,
                        int B, int H, int W, int Cin, int Cout);
+/* The same 64 -> 64 convolution with the previous block's BatchNormalization + ReLU applied while x is loaded (split-bf16 region kernel, W = 16 or 4):
+ * x is the previous block's window-extreme tensor, a = max(0, fma(x, pre_scale[c], pre_shift[c])) the arithmetic of seld_k_bn_relu_ext,
+ * z = conv(a) + bias and stats as in seld_k_conv3x3_fwd(a), bit for bit.  pre_out (may be NULL: inference) [B,H,W,64] receives a and must not be x.
+ * ext_out (may be NULL; W = 16, needs ext_gamma [64]) [B,H,4,64]: per (1,4) window and channel the maximum of z where ext_gamma >= 0, the minimum
+ * where ext_gamma < 0.  pre_scale == NULL: the plain convolution.  SELD_ERR_UNSUPPORTED wherever the launcher refuses (another width with pre_scale
+ * or ext_out, ext_out without pre_scale or ext_gamma, pre_out == x, option "bf16_single" with pre_scale). */
+int seld_k_conv3x3_fwd_pre(const float* x, const float* pre_scale, const float* pre_shift, const float* w, const float* bias, float* z, float* stats,
+                           float* pre_out, const float* ext_gamma, float* ext_out, int B, int H, int W);
 /* First conv block forward with the (5,4) MaxPooling2D reduction folded into the convolution (layers.py:27-37,
  * seldnet.json FIRST_ARGS pool_size[0]): x [B,H,64,Cin] (Cin 7 or 10, H % 5 == 0) -> z [B,H,64,64] (may be NULL:
  * not stored), zext [B,H/5,16,64] = per pooling window max(z) where gamma >= 0 / min(z) where gamma < 0, amax

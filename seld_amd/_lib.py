@@ -154,6 +154,7 @@ SIGNATURES = {
     "seld_profile_get": (_I, [_P, _I, C.c_char_p, _I, C.POINTER(_L), C.POINTER(C.c_double)]),
     "seld_profile_reset": (_I, [_P]),
     "seld_k_conv3x3_fwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I]),
+    "seld_k_conv3x3_fwd_pre": (_I, [_P] * 10 + [_I] * 3),
     "seld_k_conv_first_fwd_pool": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I]),
     "seld_k_conv1_gram": (_I, [_P, _P, _I, _I, _I]),
     "seld_k_conv1_train_gram": (_I, [_P] * 11 + [_I] * 3),

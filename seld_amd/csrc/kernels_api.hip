@@ -47,6 +47,7 @@ int seld_k_set_option(const char* key, int value) {
     if (!strcmp(key, "xc_xcd_map")) { k_kc.xc_xcd_map = value != 0; return SELD_OK; }
     if (!strcmp(key, "bwd_four_products")) { k_kc.bwd_four = value != 0; return SELD_OK; }
     if (!strcmp(key, "rn_split_bf16")) { k_rn_split_bf16 = value != 0; return SELD_OK; }
+    if (!strcmp(key, "dgrad_r8")) { k_kc.dgrad_r8 = value != 0; return SELD_OK; }
     return SELD_ERR_INVALID;
 }
 
@@ -67,6 +68,22 @@ int seld_k_conv3x3_fwd(const float* x, const float* w, const float* bias, float*
     else if (W == 64) rc = launch_conv_first_fwd(0, x, w, bias, z, part, &np, B, H, Cin);
     else return SELD_ERR_UNSUPPORTED;
     if (rc) return SELD_ERR_UNSUPPORTED;
+    if (stats) launch_reduce_slabs(0, part, np, 128, stats, 128, 0);
+    return done();
+}
+
+int seld_k_conv3x3_fwd_pre(const float* x, const float* pre_scale, const float* pre_shift, const float* w, const float* bias, float* z, float* stats,
+                           float* pre_out, const float* ext_gamma, float* ext_out, int B, int H, int W) {
+    if (!x || !w || !z || B <= 0 || H <= 0) return SELD_ERR_UNSUPPORTED;
+    Scratch s;
+    float* part = stats ? s.get((size_t)conv_stat_partial_capacity() * 128) : nullptr;
+    if (stats && !part) return SELD_ERR_NOMEM;
+    unsigned short* wsp = reinterpret_cast<unsigned short*>(s.get(9 * 3 * 4096 / 2 + 16));
+    if (!wsp) return SELD_ERR_NOMEM;
+    int np = 0;
+    const float* ws[1] = {w}; unsigned short* ds[1] = {wsp}; const int fl[1] = {0};
+    launch_split_weights_batch(0, k_kc, 1, ws, ds, fl);
+    if (launch_conv64_fwd_sb(0, k_kc, x, wsp, bias, z, part, &np, B, H, W, pre_scale, pre_shift, pre_out, ext_gamma, ext_out)) return SELD_ERR_UNSUPPORTED;
     if (stats) launch_reduce_slabs(0, part, np, 128, stats, 128, 0);
     return done();
 }

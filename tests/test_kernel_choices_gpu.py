@@ -97,6 +97,7 @@ def test_the_retired_conv64_dbuf_key_is_refused(seld_lib, seldnet_config):
     assert seld_lib.seld_k_set_option(b"conv64_dbuf", 1) != 0
     assert seld_lib.seld_k_set_option(b"conv64_dbuf", 0) != 0
     assert seld_lib.seld_k_set_option(b"bwd_four_products", 1) == 0
+    assert seld_lib.seld_k_set_option(b"dgrad_r8", 1) == 0              # the entry points' own copy of the key (its default)
 
 
 def test_kernel_entry_point_options_do_not_reach_a_context(seld_lib, seldnet_config, batch):
