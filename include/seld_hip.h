@@ -766,6 +766,20 @@ int seld_rnn_gru_fwd(const float* gx_f, const float* gx_b, const float* U_f, con
 int seld_rnn_gru_bwd(const float* dh_f, const float* dh_b, const float* h_f, const float* h_b, const float* saved_f, const float* saved_b,
                      const float* U_f, const float* U_b, float* dgx_f, float* dgx_b, float* dgh_f, float* dgh_b, int B, int S, int units,
                      void* stream);
+/* The same GRU recurrence and BPTT at ANY width units = u, 1 <= u <= 256 (gru_w.hip; the architecture search of nas_seldnet draws
+ * bidirectional_GRU_stage widths from 4 to 256).  The contract of seld_rnn_gru_fwd / _bwd with 128 read as u: gx_* [B,S,3u] (z | r | h), U_* [u,3u],
+ * brec_* [3u], h_* [B,S,u], saved_* [B,S,u,4] = z, r, hh, gh_h (NULL at inference; h has the same bits either way), dh_* [B,S,u] used as given,
+ * dgx_* / dgh_* [B,S,3u]; all *_b NULL = one direction.  No alignment beyond 4 bytes is assumed.  Refusals, in this order and before anything is
+ * enqueued: SELD_ERR_UNSUPPORTED for units outside 1..256; SELD_ERR_INVALID for a NULL required pointer, B or S < 1, a half-given direction;
+ * SELD_ERR_UNSUPPORTED for B or S above 2^30 or B * S above 2^40.  Exact fp32, fixed summation order, a clip's bits do not depend on the batch.
+ * seld_rnn_gruw_plan (no device needed): out = {kernel form (0: U in LDS, 1: U re-read through L2 every step), clips per workgroup, forward
+ * staging depth in steps, backward staging depth} for that width; returns the number of forms, SELD_ERR_UNSUPPORTED outside 1..256. */
+int seld_rnn_gruw_fwd(const float* gx_f, const float* gx_b, const float* U_f, const float* U_b, const float* brec_f, const float* brec_b, float* h_f,
+                      float* h_b, float* saved_f, float* saved_b, int B, int S, int units, void* stream);
+int seld_rnn_gruw_bwd(const float* dh_f, const float* dh_b, const float* h_f, const float* h_b, const float* saved_f, const float* saved_b,
+                      const float* U_f, const float* U_b, float* dgx_f, float* dgx_b, float* dgh_f, float* dgh_b, int B, int S, int units,
+                      void* stream);
+int seld_rnn_gruw_plan(int units, int32_t out[4]);
 /* The same recurrences under Keras dropout / recurrent_dropout (modules.py:312-315, 338-340 pass dropout_rate as both), training only; the
  * contract of the four entries above, with every buffer the backward reads REQUIRED (the masks, c_*, hm_*, saved_*).  rm_* [B,128]: the state
  * mask of each direction, 0 | 1/(1-rate) per (clip, unit), constant over the sequence.  The input mask is not these entries' business: the

@@ -237,6 +237,9 @@ SIGNATURES = {
     "seld_rnn_lstm_bwd": (_I, [_P] * 10 + [_I] * 3 + [_P]),
     "seld_rnn_gru_fwd": (_I, [_P] * 10 + [_I] * 3 + [_P]),
     "seld_rnn_gru_bwd": (_I, [_P] * 12 + [_I] * 3 + [_P]),
+    "seld_rnn_gruw_fwd": (_I, [_P] * 10 + [_I] * 3 + [_P]),
+    "seld_rnn_gruw_bwd": (_I, [_P] * 12 + [_I] * 3 + [_P]),
+    "seld_rnn_gruw_plan": (_I, [_I, C.POINTER(C.c_int32)]),
     "seld_rnn_lstm_drop_fwd": (_I, [_P] * 12 + [_I] * 3 + [_P]),
     "seld_rnn_lstm_drop_bwd": (_I, [_P] * 12 + [_I] * 3 + [_P]),
     "seld_rnn_gru_drop_fwd": (_I, [_P] * 14 + [_I] * 3 + [_P]),

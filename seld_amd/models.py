@@ -293,13 +293,14 @@ def seldnet(input_shape, model_config, device=None, dtype: str = "float32"):
     return SeldNet(input_shape, model_config, device, dtype)
 
 
-def conv_temporal(input_shape, model_config, device=None):
+def conv_temporal(input_shape, model_config, device=None, search: bool = False):
     """reference models.conv_temporal (models.py:54-78; model_config/SS5.json): conv2d_bn(filters, first_kernel_size) + MaxPooling2D(
     first_pool_size, 'same'), the BLOCK* chain in string order, and a SED and a DOA head that are blocks themselves — a
     modules.ConvTemporalNet, composed from module operators like every composed model (float32; train.trainstep / teststep take it; agc and
-    the trainv2 recipe stay refused for composed models).  Configuration errors are ValueErrors raised without a device."""
+    the trainv2 recipe stay refused for composed models).  Configuration errors are ValueErrors raised without a device.  search=True: GRU
+    kinds of any width in 1..256 and simple_dense_block's Dropout, as the architecture search draws them (ConvTemporalNet)."""
     from .modules import ConvTemporalNet
-    return ConvTemporalNet(input_shape, model_config, device)
+    return ConvTemporalNet(input_shape, model_config, device, search)
 
 
 def spectro_temporal_attention_based_VAD(input_shape, model_config, device=None, dropout: bool = False):

@@ -163,6 +163,7 @@ class _Rt:
         self.nt: List[Tuple[str, Tuple[int, ...]]] = []
         self._views: Dict[str, torch.Tensor] = {}
         self.linears: List[Tuple[int, int, int]] = []      # (rows, K, N) of every Linear built on this runtime: the plan's dense products
+        self.recurrent: List[Tuple[int, int, int, int]] = []      # (rows, D, units, G) of every recurrent layer's direction (_Recurrent)
         self.params = self.grads = self.state = None
         self._slab = None
         self._bn_scratch = None
@@ -172,6 +173,7 @@ class _Rt:
         self.dropout_step = 0
         self.dropout_cur = 0
         self.dropout = False      # the blocks built on this runtime may draw (the owner accepted the library's draws: _dropout_rate)
+        self.any_units = False    # the GRU blocks built on this runtime may have any width in 1..256 (seld_rnn_gruw_*: ConvTemporalNet search=True)
 
     def next_draws(self):
         """a model's training forward begins: new masks (Keras), backward or not"""
@@ -669,7 +671,7 @@ class Stage:
         self.rt, self.S, self.D = rt, int(S), int(D)
         self.model = False      # True: this stage IS the model (a factory built it on a runtime of its own), so its training forwards count the draws
         for i in range(int(depth)):
-            self.blocks.append(block(rt, cfg, S, D, f"{prefix}{i}", B))
+            self.blocks.append(block(rt, cfg, S, D, f"{prefix}{i}", B, **({"layer": i} if getattr(block, "PER_LAYER_UNITS", False) else {})))
             D = self.blocks[-1].out_dim
             if getattr(self.blocks[-1], "drop", None) is not None:
                 self.blocks[-1].drop.base = DROP_STREAM0 + 32 * (int(first_block) + i)
@@ -1295,15 +1297,30 @@ def _recurrent_rate(cfg: dict, who: str) -> float:
     return r
 
 
-def check_rnn_config(cfg: dict, stage: bool = False, dropout: bool = False) -> None:
+GRU_MIN_UNITS, GRU_MAX_UNITS = 1, 256      # seld_rnn_gruw_*
+
+
+def _is_gru_width(u) -> bool:
+    return isinstance(u, (int, np.integer)) and not isinstance(u, bool) and GRU_MIN_UNITS <= int(u) <= GRU_MAX_UNITS
+
+
+def check_rnn_config(cfg: dict, stage: bool = False, dropout: bool = False, any_units: bool = False) -> None:
     """reference modules.RNN_block / RNN_stage (modules.py:64-83, 322-347): the mandatory keys; what has no kernel here is refused, not ignored.
     dropout: the owner accepted the library's draws for the cells' input and state masks (_Recurrent), and dropout_rate may be any rate in
-    [0, 1); without it the rate must be 0"""
+    [0, 1); without it the rate must be 0.  any_units: a GRU may have any integer width in 1..256 (seld_rnn_gruw_*; the LSTM kernels and
+    the DROP forms stay 128-unit kernels)"""
     who = f"RNN_{'stage' if stage else 'block'}"
     for key in ("units",) + (("depth",) if stage else ()):
         if key not in cfg:
             raise ValueError(f"{who}: missing {key!r}")
-    if isinstance(cfg["units"], (list, tuple)) or int(cfg["units"]) != 128:
+    wide = any_units and cfg.get("rnn_type", "GRU") == "GRU"
+    if wide:
+        if not _is_gru_width(cfg["units"]):
+            raise ValueError(f"{who}: units {cfg['units']!r}: a GRU width is an integer in {GRU_MIN_UNITS}..{GRU_MAX_UNITS}")
+        if int(cfg["units"]) != 128 and float(cfg.get("dropout_rate", 0.0) or 0.0) != 0.0:
+            raise ValueError(f"{who}: dropout_rate {cfg.get('dropout_rate')!r} at {cfg['units']} units: the recurrences under dropout / "
+                             "recurrent_dropout (the DROP forms) are 128-unit kernels; at another width dropout_rate must be 0")
+    elif isinstance(cfg["units"], (list, tuple)) or int(cfg["units"]) != 128:
         raise ValueError(f"{who}: units {cfg['units']!r}: the recurrence kernels are built for 128 units")
     if stage and int(cfg["depth"]) < 1:
         raise ValueError(f"{who}: depth >= 1")
@@ -1318,8 +1335,9 @@ def check_rnn_config(cfg: dict, stage: bool = False, dropout: bool = False) -> N
 
 
 class _Recurrent:
-    """What the recurrent blocks share on [B*S, D] with 128 units and gate width G (GRU, reset_after=True: 384, LSTM: 512), per direction
-    `name` of `names`: the variables kernel (D, G), recurrent_kernel (128, G), bias (GRU (2, 384): input row | recurrent row; LSTM (512,)),
+    """What the recurrent blocks share on [B*S, D] with u units (128; a GRU on a runtime with any_units: 1..256) and gate width G (GRU,
+    reset_after=True: 3u, LSTM: 4u), per direction
+    `name` of `names`: the variables kernel (D, G), recurrent_kernel (u, G), bias (GRU (2, 3u): input row | recurrent row; LSTM (4u,)),
     the input projections gx, the states h and sv, the pre-activation gradients dgx (GRU: and dgh, behind the reset gate), the input's
     gradient din — and the GEMMs in front of and behind the recurrence kernels.
 
@@ -1330,15 +1348,20 @@ class _Recurrent:
     as seld_rnn_merge_*; backward: the weight gradients read xm and the masked state sequence hm = h * rm, din = sum over the directions of
     (dgx kernel^T) * im.  The blocks' `lstm`, `bi`, `mode`, `c`, `dh` and `out` say which recurrence and merge."""
 
-    def __init__(self, rt: _Rt, names, S: int, D: int, G: int, B: int, rate: float = 0.0):
-        self.rt, self.names, self.S, self.D, self.G, self.B = rt, names, int(S), int(D), G, B
+    def __init__(self, rt: _Rt, names, S: int, D: int, G: int, B: int, rate: float = 0.0, units: int = 128):
+        """units: the width u (a GRU on a runtime with any_units: 1..256, G = 3u; otherwise 128).  At u != 128 the GRU recurrences run on
+        seld_rnn_gruw_fwd / _bwd (gru_w.hip) with the merge as its own operator; at 128 on the calls the blocks always made"""
+        self.rt, self.names, self.S, self.D, self.G, self.B, self.u = rt, names, int(S), int(D), G, B, int(units)
+        u = self.u
+        assert G == (4 * u if self.lstm else 3 * u) and (u == 128 or (not self.lstm and rate == 0.0))
         for n in names:
-            rt.var(f"{n}.kernel", (self.D, G)); rt.var(f"{n}.recurrent_kernel", (128, G)); rt.var(f"{n}.bias", (512,) if G == 512 else (2, 384))
+            rt.var(f"{n}.kernel", (self.D, G)); rt.var(f"{n}.recurrent_kernel", (u, G)); rt.var(f"{n}.bias", (G,) if self.lstm else (2, G))
+            rt.recurrent.append((B * self.S, self.D, u, G))
         R, nd = B * self.S, len(names)
         e = rt.empty
-        self.gx, self.h, self.sv = [e(R, G) for _ in range(nd)], [e(R, 128) for _ in range(nd)], [e(R, 512) for _ in range(nd)]
+        self.gx, self.h, self.sv = [e(R, G) for _ in range(nd)], [e(R, u) for _ in range(nd)], [e(R, 4 * u) for _ in range(nd)]
         self.dgx = [e(R, G) for _ in range(nd)]
-        self.dgh = [e(R, G) for _ in range(nd)] if G == 384 else self.dgx      # LSTM: no reset gate, one pre-activation gradient
+        self.dgh = [e(R, G) for _ in range(nd)] if not self.lstm else self.dgx      # LSTM: no reset gate, one pre-activation gradient
         self.din = e(R, self.D)
         self.drop = _Drop(rt, rate)
         if rate > 0.0:
@@ -1368,10 +1391,36 @@ class _Recurrent:
             gb = rt.g(f"{n}.bias")
             rt.gemm_tn(self.x, self.dgx[d], rt.g(f"{n}.kernel"), gb[:self.G], R, self.D, self.G)
             # recurrent kernel: h_prev^T dgh — the forward direction saw h[t-1], the backward direction h[t+1]
-            rt.gemm_tn(self.h[d], self.dgh[d], rt.g(f"{n}.recurrent_kernel"), gb[384:] if self.G == 384 else None, R, 128, self.G, seq=self.S,
+            rt.gemm_tn(self.h[d], self.dgh[d], rt.g(f"{n}.recurrent_kernel"), gb[self.G:] if not self.lstm else None, R, self.u, self.G, seq=self.S,
                        shift=-1 if d == 0 else 1)
             rt.gemm(self.dgx[d], rt.w(f"{n}.kernel"), None, self.din, R, self.D, self.G, transb=1, accumulate=d)
         return self.din[:R]
+
+    def _wide_forward(self, x, B, training):
+        """the GRU forward at a width other than 128 -> [B*S, out_dim]"""
+        rt, lib, R = self.rt, self.rt.lib, B * self.S
+        self._project(x, R)
+        U = self._pair([rt.w(f"{n}.recurrent_kernel") for n in self.names])
+        brec = self._pair([rt.w(f"{n}.bias")[self.G:] for n in self.names])
+        rt.ck(lib.seld_rnn_gruw_fwd(*self._pair(self.gx), *U, *brec, *self._pair(self.h), *self._pair(self.sv, not training), B, self.S, self.u, rt.st()))
+        if not self.bi:
+            return self.h[0][:R]
+        rt.ck(lib.seld_rnn_merge_fwd(rt.p(self.h[0]), rt.p(self.h[1]), rt.p(self.out), R, self.u, self.mode, rt.st()))
+        return self.out[:R]
+
+    def _wide_backward(self, dy, B):
+        """its backward: dy [B*S, out_dim] -> the input's gradient [B*S, D]"""
+        rt, lib, R = self.rt, self.rt.lib, B * self.S
+        if self.bi:
+            rt.ck(lib.seld_rnn_merge_bwd(rt.p(dy), rt.p(self.h[0]), rt.p(self.h[1]), rt.p(self.dh[0]), rt.p(self.dh[1]), R, self.u, self.mode, rt.st()))
+            dh = self._pair(self.dh)
+        else:
+            self._dy = dy.contiguous()      # kept: the kernel reads it after this call returns
+            dh = (rt.p(self._dy), None)
+        U = self._pair([rt.w(f"{n}.recurrent_kernel") for n in self.names])
+        rt.ck(lib.seld_rnn_gruw_bwd(*dh, *self._pair(self.h), *self._pair(self.sv), *U, *self._pair(self.dgx), *self._pair(self.dgh), B, self.S, self.u,
+                                    rt.st()))
+        return self._weight_grads(R)
 
     def _mask_rows(self, src, mask, dst, R, F, accumulate=0):
         rt = self.rt
@@ -1434,18 +1483,19 @@ class RNNBlock(_Recurrent):
     dropout_rate > 0 (a runtime whose owner accepted the library's draws): the cells' dropout and recurrent_dropout, in training (_Recurrent)."""
 
     def __init__(self, rt: _Rt, cfg: dict, S: int, D: int, prefix: str, B: int):
-        check_rnn_config(cfg, dropout=rt.dropout)
+        check_rnn_config(cfg, dropout=rt.dropout, any_units=rt.any_units)
         self.prefix = prefix
         self.lstm = cfg.get("rnn_type", "GRU") != "GRU"
         self.bi = bool(cfg.get("bidirectional", True))
         self.mode = _lib.SELD_MERGE[cfg.get("merge_mode", "mul")] if self.bi else None
-        super().__init__(rt, [f"{prefix}.fwd", f"{prefix}.bwd"] if self.bi else [prefix], S, D, 512 if self.lstm else 384, B,
-                         _recurrent_rate(cfg, "RNN_block") if rt.dropout else 0.0)
-        self.out_dim = 256 if self.bi and cfg.get("merge_mode", "mul") == "concat" else 128
+        u = int(cfg["units"])
+        super().__init__(rt, [f"{prefix}.fwd", f"{prefix}.bwd"] if self.bi else [prefix], S, D, 4 * u if self.lstm else 3 * u, B,
+                         _recurrent_rate(cfg, "RNN_block") if rt.dropout else 0.0, u)
+        self.out_dim = 2 * u if self.bi and cfg.get("merge_mode", "mul") == "concat" else u
         R, nd = B * self.S, len(self.names)
         e = rt.empty
-        self.c = [e(R, 128) for _ in range(nd)] if self.lstm else None
-        self.dh = [e(R, 128) for _ in range(nd)] if self.bi else None
+        self.c = [e(R, u) for _ in range(nd)] if self.lstm else None
+        self.dh = [e(R, u) for _ in range(nd)] if self.bi else None
         self.out = e(R, self.out_dim) if self.bi else None
         self.out_shape = (self.S, self.out_dim)
 
@@ -1456,6 +1506,8 @@ class RNNBlock(_Recurrent):
         self.drop.begin(training)
         if self.drop.on:
             return self._dropped_forward(x.reshape(R, self.D), B)
+        if self.u != 128:
+            return self._wide_forward(x.reshape(R, self.D), B, training)
         self._project(x.reshape(R, self.D), R)
         U = self._pair([rt.w(f"{n}.recurrent_kernel") for n in self.names])
         if self.lstm:
@@ -1476,6 +1528,8 @@ class RNNBlock(_Recurrent):
         dy = dy.reshape(R, self.out_dim)
         if self.drop.on:
             return self._dropped_backward(dy, B)
+        if self.u != 128:
+            return self._wide_backward(dy, B)
         if self.bi:
             rt.ck(lib.seld_rnn_merge_bwd(rt.p(dy), rt.p(self.h[0]), rt.p(self.h[1]), rt.p(self.dh[0]), rt.p(self.dh[1]), R, 128, self.mode, rt.st()))
             dh = self._pair(self.dh)
@@ -1491,14 +1545,21 @@ class RNNBlock(_Recurrent):
         return self._weight_grads(R)
 
 
-def check_gru_config(cfg: dict, stage: bool = False, dropout: bool = False) -> None:
-    """reference modules.bidirectional_GRU_block (modules.py:302-319): one layer per entry of `units`.  dropout: as check_rnn_config's"""
+def check_gru_config(cfg: dict, stage: bool = False, dropout: bool = False, any_units: bool = False) -> None:
+    """reference modules.bidirectional_GRU_block (modules.py:302-319): one layer per entry of `units`.  dropout, any_units: as
+    check_rnn_config's"""
     if dropout:
         _recurrent_rate(cfg, "bidirectional_GRU_block")
     elif float(cfg.get("dropout_rate", 0.0)) != 0.0:
         raise ValueError("bidirectional_GRU_block: GRU dropout / recurrent_dropout masks exist on the fused path only (models.SeldNet), not among "
                          "the composed path's Dropout operators: dropout_rate must be 0")
-    if any(int(u) != 128 for u in cfg["units"]):
+    if any_units:
+        if not isinstance(cfg["units"], (list, tuple)) or not all(_is_gru_width(u) for u in cfg["units"]):
+            raise ValueError(f"bidirectional_GRU_block: units {cfg['units']!r}: a list of integers in {GRU_MIN_UNITS}..{GRU_MAX_UNITS}, one per layer")
+        if any(int(u) != 128 for u in cfg["units"]) and float(cfg.get("dropout_rate", 0.0) or 0.0) != 0.0:
+            raise ValueError(f"bidirectional_GRU_block: dropout_rate {cfg.get('dropout_rate')!r} at units {list(cfg['units'])!r}: the recurrences "
+                             "under dropout / recurrent_dropout (the DROP forms) are 128-unit kernels; at another width dropout_rate must be 0")
+    elif any(int(u) != 128 for u in cfg["units"]):
         raise ValueError("the recurrence kernels are built for 128 units")
 
 
@@ -1508,13 +1569,16 @@ class BidirectionalGRUBlock(_Recurrent):
     accepted the library's draws), in training: the cells' masks, the recurrences per direction and the 'mul' merge as its own operator
     (_Recurrent)."""
     lstm, bi, mode = False, True, _lib.SELD_MERGE["mul"]
+    PER_LAYER_UNITS = True      # Stage passes `layer`, the block's index in the stage: its width is cfg['units'][layer]
 
-    def __init__(self, rt: _Rt, cfg: dict, S: int, D: int, prefix: str, B: int):
-        check_gru_config(cfg, dropout=rt.dropout)
-        super().__init__(rt, [f"{prefix}.fwd", f"{prefix}.bwd"], S, D, 384, B, _recurrent_rate(cfg, "bidirectional_GRU_block") if rt.dropout else 0.0)
-        self.out = rt.empty(B * self.S, 128)
-        self.dh = [rt.empty(B * self.S, 128) for _ in (0, 1)] if self.drop.rate > 0.0 else None
-        self.out_dim, self.out_shape = 128, (self.S, 128)
+    def __init__(self, rt: _Rt, cfg: dict, S: int, D: int, prefix: str, B: int, layer: int = 0):
+        check_gru_config(cfg, dropout=rt.dropout, any_units=rt.any_units)
+        u = int(cfg["units"][layer])
+        super().__init__(rt, [f"{prefix}.fwd", f"{prefix}.bwd"], S, D, 3 * u, B,
+                         _recurrent_rate(cfg, "bidirectional_GRU_block") if rt.dropout else 0.0, u)
+        self.out = rt.empty(B * self.S, u)
+        self.dh = [rt.empty(B * self.S, u) for _ in (0, 1)] if self.drop.rate > 0.0 or u != 128 else None
+        self.out_dim, self.out_shape = u, (self.S, u)
 
     def forward(self, x, B, training):
         rt, p = self.rt, self.rt.p
@@ -1522,6 +1586,8 @@ class BidirectionalGRUBlock(_Recurrent):
         self.drop.begin(training)
         if self.drop.on:
             return self._dropped_forward(x.reshape(R, self.D), B)
+        if self.u != 128:
+            return self._wide_forward(x.reshape(R, self.D), B, training)
         self._project(x.reshape(R, self.D), R)
         U = [p(rt.w(f"{n}.recurrent_kernel")) for n in self.names]
         brec = [p(rt.w(f"{n}.bias")[384:]) for n in self.names]
@@ -1534,6 +1600,8 @@ class BidirectionalGRUBlock(_Recurrent):
         R = B * self.S
         if self.drop.on:
             return self._dropped_backward(dy.reshape(R, 128), B)
+        if self.u != 128:
+            return self._wide_backward(dy.reshape(R, self.u), B)
         U = [p(rt.w(f"{n}.recurrent_kernel")) for n in self.names]
         rt.ck(rt.lib.seld_m_gru_bwd(p(dy), p(self.h[0]), p(self.h[1]), p(self.sv[0]), p(self.sv[1]), *U, p(self.dgx[0]), p(self.dgx[1]),
                                     p(self.dgh[0]), p(self.dgh[1]), B, self.S, 128, rt.st()))
@@ -1770,9 +1838,11 @@ assert tuple(SECOND_KINDS) == COMPOSED_SECOND + CONFORMER_SECOND + ATTENTION_SEC
 DROPOUT_KINDS = COMPOSED_SECOND + CONFORMER_SECOND + ATTENTION_SECOND + RNN_SECOND      # the SECOND kinds whose Dropouts can draw (_Drop): all
 
 
-def _check_second(kind: str, cfg: dict, D=None, dropout: bool = False) -> None:
+def _check_second(kind: str, cfg: dict, D=None, dropout: bool = False, any_units: bool = False) -> None:
     _, check, _, stage, with_d = SECOND_KINDS[kind]
     kw = {"dropout": True} if dropout and kind in DROPOUT_KINDS else {}
+    if any_units and check in (check_gru_config, check_rnn_config):
+        kw["any_units"] = True
     check(cfg, stage, D, **kw) if with_d else check(cfg, stage, **kw)
 
 
@@ -1782,7 +1852,7 @@ def _build_second(kind: str, rt, cfg: dict, S: int, D: int, B: int, prefix=None,
     accepts the library's draws (_dropout_rate); a given rt carries its owner's choice"""
     block, _, pre, stage, _ = SECOND_KINDS[kind]
     dropout = bool(dropout) if rt is None else rt.dropout
-    _check_second(kind, cfg, D, dropout)
+    _check_second(kind, cfg, D, dropout, rt is not None and rt.any_units)
     own = rt is None
     rt = rt or _Rt(torch.device("cuda", torch.cuda.current_device()))
     rt.dropout = dropout
@@ -1973,8 +2043,8 @@ class ComposedSeldNet:
             if n.endswith("recurrent_kernel") and sh[1] == 512:      # LSTM: Keras' Orthogonal over the whole [128, 512]
                 q, r = np.linalg.qr(rng.standard_normal((512, 128)))
                 w[off:off + k] = (q * np.sign(np.diag(r))).T.reshape(-1)
-            elif n.endswith("recurrent_kernel"):
-                w[off:off + k] = np.concatenate([np.linalg.qr(rng.standard_normal((128, 128)))[0] for _ in range(3)], axis=1).reshape(-1)
+            elif n.endswith("recurrent_kernel"):      # GRU [u, 3u]: an orthogonal [u, u] per gate
+                w[off:off + k] = np.concatenate([np.linalg.qr(rng.standard_normal((sh[0], sh[0])))[0] for _ in range(3)], axis=1).reshape(-1)
             elif n.startswith("rnn") and n.endswith("bias") and sh == (512,):
                 w[off + 128:off + 256] = 1.0                          # LSTM unit_forget_bias: the forget slice of i | f | c | o
             elif n.endswith(("kernel", "pos_bias_u", "pos_bias_v")):      # the two biases take the kernel initializer (layers.py:343-356)
@@ -2317,15 +2387,19 @@ class ConvTemporalNet(ComposedSeldNet):
     Variables in the reference's creation order: stem.conv, stem.bn, b{i}.*, sed.*, sed_out, doa.*, doa_out; the BatchNormalization
     statistics in `state_variables` in the same order.  Weights I/O, the losses, train_step / test_step, profile and batches of 1 .. B are
     ComposedSeldNet's.  Every stage of the chain draws its Dropout masks from streams of its own (Stage: first_block).  device='meta': the
-    plan alone — variables and shapes without a device (nothing can be run)."""
+    plan alone — variables and shapes without a device (nothing can be run).
 
-    DENSE_KW: dict = {}      # what _build_3d passes to a DenseBlock beyond its place in the chain (VadArchNet: dropout, flat)
+    search=True (the architecture search, nas_seldnet): what its search spaces draw and the default refuses is built — a GRU kind of any
+    width in 1..256 (_Rt.any_units: seld_rnn_gruw_* at widths other than 128) and simple_dense_block's Dropout layers on the library's
+    draws (DenseBlock dropout=True, as in VadArchNet).  What the default builds, it builds with the same calls: the same bits."""
 
-    def __init__(self, input_shape, model_config: dict, device=None):
+    DENSE_KW: dict = {}      # what _build_3d passes to a DenseBlock beyond its place in the chain (search / VadArchNet: dropout; VadArchNet: flat)
+
+    def __init__(self, input_shape, model_config: dict, device=None, search: bool = False):
         cfg = copy.deepcopy(model_config)
         meta = device == "meta"
         if not meta and not torch.cuda.is_available():
-            ConvTemporalNet(input_shape, cfg, "meta")      # the configuration errors first, as the factories raise them without a device
+            ConvTemporalNet(input_shape, cfg, "meta", search)      # the configuration errors first, as the factories raise them without a device
             raise RuntimeError("seld_amd needs a HIP device: there is no CPU fallback")
         self._dev = torch.device("meta") if meta else torch.device("cuda", torch.cuda.current_device() if device is None else int(device))
         B, T, Fq, Ch = (int(v) for v in input_shape)
@@ -2333,6 +2407,10 @@ class ConvTemporalNet(ComposedSeldNet):
         self.n_classes = int(cfg.get("n_classes", 14))
         rt = self.rt = _Rt(self._dev)
         rt.dropout = True
+        self.search = bool(search)
+        if self.search:
+            rt.any_units = True
+            self.DENSE_KW = {"dropout": True}
         self.lib = rt.lib
         # ---- stem (layers.conv2d_bn + MaxPooling2D, models.py:62-64)
         self.stem_conv = StemConv2D(rt, "stem.conv", (T, Fq, Ch), int(cfg.get("filters", 32)), int(cfg.get("first_kernel_size", 7)), B)
@@ -2408,6 +2486,17 @@ class ConvTemporalNet(ComposedSeldNet):
 
     def summary(self) -> str:
         return super().summary().replace("ComposedSeldNet", "ConvTemporalNet", 1)
+
+    def complexity(self) -> dict:
+        """{'flops', 'params'}: params = n_params; flops = the multiply-adds per clip of the plan's products — as VadArchNet.complexity(), the
+        sum over every Linear layer (Dense, Conv1D, Conv2D, the stem, the heads) of (rows / B) K N, plus what the recurrent layers multiply
+        outside a Linear, per direction and layer: the input projection S D G and the recurrent product S u G (GRU: G = 3u, LSTM: 4u).  Our
+        own count, read off the plan: it is NOT claimed to equal the reference's model_complexity.conv_temporal_complexity (closed forms per
+        stage, which also count normalisations and activations)."""
+        B = self.input_shape[0]
+        flops = sum((rows // B) * K * N for rows, K, N in self.rt.linears)
+        flops += sum((rows // B) * (D + u) * G for rows, D, u, G in self.rt.recurrent)
+        return {"flops": int(flops), "params": int(self.n_params)}
 
     def _forward(self, x, training: bool):
         rt = self.rt
