@@ -176,12 +176,12 @@ static int backward_gru(seld_ctx* c, const float* dfeat, const float** din) {
         {
             PROF(c, "gru_bwd");
             if (gru_drop) {
-                if (launch_gru_bwd(st, dout, G.h[0], G.h[1], G.sv[0], G.sv[1], c->params + G.u_off[0], c->params + G.u_off[1], c->dgx[i][0],
-                                   c->dgx[i][1], c->dgh[i][0], c->dgh[i][1], B, S, G.rmask[0], G.rmask[1], G.hm[0], G.hm[1]))
+                if (launch_gru_bwd(st, GRU_BWD_MUL, dout, nullptr, G.h[0], G.h[1], G.sv[0], G.sv[1], c->params + G.u_off[0], c->params + G.u_off[1],
+                                   c->dgx[i][0], c->dgx[i][1], c->dgh[i][0], c->dgh[i][1], B, S, G.rmask[0], G.rmask[1], G.hm[0], G.hm[1]))
                     return fail(c, SELD_ERR_UNSUPPORTED, "gru_bwd (dropout)");
             } else
-            launch_gru_bwd(st, dout, G.h[0], G.h[1], G.sv[0], G.sv[1], c->params + G.u_off[0], c->params + G.u_off[1], c->dgx[i][0],
-                           c->dgx[i][1], c->dgh[i][0], c->dgh[i][1], B, S);
+            launch_gru_bwd(st, GRU_BWD_MUL, dout, nullptr, G.h[0], G.h[1], G.sv[0], G.sv[1], c->params + G.u_off[0], c->params + G.u_off[1],
+                           c->dgx[i][0], c->dgx[i][1], c->dgh[i][0], c->dgh[i][1], B, S);
         }
         // the input gradient the next BPTT (or the conv backward) waits for: main stream, enqueued AFTER the side stream is released for this layer's weight
         // gradients (ahead of the release: same box 2.651 / 2.650 ms per step against 2.639 / 2.635 — what the product gains the weight gradients lose under the next BPTT)

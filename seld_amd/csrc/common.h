@@ -339,20 +339,18 @@ int gemm_tn_max_splits();
 // floats of the kernel-gradient slab buffer a model context holds (the GRU's largest product, gemm_tn_max_splits() slabs of it)
 inline int64_t tn_slab_capacity() { return (int64_t)gemm_tn_max_splits() * (384 * 384 + 384); }
 
+// gru.hip: GRU(128) recurrence, one launcher per kernel template.  gx_b == nullptr: one direction (reference modules.RNN_block,
+// bidirectional=False); sv_f == nullptr: nothing is saved for the backward pass; rm_* [B][128] with hm_*: the recurrent-dropout forms
+// (seld_k_gru_drop_*, seld_rnn_gru_drop_*), which always save
 int launch_gru_fwd(hipStream_t st, const float* gx_f, const float* gx_b, const float* U_f, const float* U_b,
                    const float* brec_f, const float* brec_b, float* h_f, float* h_b, float* sv_f, float* sv_b,
                    int B, int S, const float* rm_f = nullptr, const float* rm_b = nullptr, float* hm_f = nullptr, float* hm_b = nullptr);
-int launch_gru_bwd(hipStream_t st, const float* dout, const float* h_f, const float* h_b, const float* sv_f,
-                   const float* sv_b, const float* U_f, const float* U_b, float* dgx_f, float* dgx_b,
-                   float* dgh_f, float* dgh_b, int B, int S, const float* rm_f = nullptr, const float* rm_b = nullptr, const float* hm_f = nullptr,
-                   const float* hm_b = nullptr);
-// the same kernels for reference modules.RNN_block (seld_rnn_gru_*): one direction alone; output gradients per direction, used as given
-// rm (with hm; the two-direction forward is launch_gru_fwd's): the recurrent-dropout forms (seld_rnn_gru_drop_*); h_* is then not read by the backward
-int launch_gru_fwd_uni(hipStream_t st, const float* gx, const float* U, const float* brec, float* h, float* sv, int B, int S,
-                       const float* rm = nullptr, float* hm = nullptr);
-int launch_gru_bwd_dh(hipStream_t st, const float* dh_f, const float* dh_b, const float* h_f, const float* h_b, const float* sv_f, const float* sv_b,
-                      const float* U_f, const float* U_b, float* dgx_f, float* dgx_b, float* dgh_f, float* dgh_b, int B, int S,
-                      const float* rm_f = nullptr, const float* rm_b = nullptr, const float* hm_f = nullptr, const float* hm_b = nullptr);
+// what `dout` is to the BPTT: the gradient of the 'mul' merge's output, which the kernel multiplies by the other direction's h (the fused
+// block) | the forward direction's output gradient beside the backward direction's dh_b, both used as given | one direction's, alone
+enum { GRU_BWD_MUL = 0, GRU_BWD_GIVEN2 = 1, GRU_BWD_GIVEN1 = 2 };
+int launch_gru_bwd(hipStream_t st, int mode, const float* dout, const float* dh_b, const float* h_f, const float* h_b, const float* sv_f,
+                   const float* sv_b, const float* U_f, const float* U_b, float* dgx_f, float* dgx_b, float* dgh_f, float* dgh_b, int B, int S,
+                   const float* rm_f = nullptr, const float* rm_b = nullptr, const float* hm_f = nullptr, const float* hm_b = nullptr);
 // lstm.hip: LSTM(128) recurrence, one (gx_b / dh_b == nullptr) or two directions; c_f == nullptr: nothing is saved for the backward pass;
 // rm_f (rm_b with the second direction) [B][128]: the recurrent-dropout forms (seld_rnn_lstm_drop_*), which always save
 int launch_lstm_fwd(hipStream_t st, const float* gx_f, const float* gx_b, const float* U_f, const float* U_b, float* h_f, float* h_b,

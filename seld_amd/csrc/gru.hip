@@ -196,31 +196,19 @@ __global__ __launch_bounds__(512) void gru_fwd_kernel(const float* __restrict__ 
     }
 }
 
+// The one forward launcher.  gx_b == nullptr: one direction (the UNI instantiation, grid B; no *_b argument is read).  sv_f == nullptr: inference,
+// nothing is saved.  rm_f: recurrent dropout (training: the gates are saved) — masks rm [B][128] and masked state sequences hm [B][S][128] per
+// direction; sv and hm are then required
 int launch_gru_fwd(hipStream_t st, const float* gx_f, const float* gx_b, const float* U_f, const float* U_b,
                    const float* brec_f, const float* brec_b, float* h_f, float* h_b, float* sv_f, float* sv_b,
                    int B, int S, const float* rm_f, const float* rm_b, float* hm_f, float* hm_b) {
-    if (rm_f) {      // recurrent dropout (training: the gates are saved): masks rm [B][128] per direction, masked state sequences hm [B][S][128]
-        if (!rm_b || !hm_f || !hm_b || !sv_f) return -1;
-        hipLaunchKernelGGL((gru_fwd_kernel<true, false, true>), dim3(2 * B), dim3(512), 0, st, gx_f, gx_b, U_f, U_b, brec_f, brec_b, h_f, h_b, sv_f, sv_b, S,
-                           rm_f, rm_b, hm_f, hm_b);
-        return 0;
-    }
-    if (sv_f) hipLaunchKernelGGL((gru_fwd_kernel<true, true>), dim3(2 * B), dim3(512), 0, st, gx_f, gx_b, U_f, U_b, brec_f, brec_b, h_f, h_b, sv_f, sv_b, S);
-    else hipLaunchKernelGGL((gru_fwd_kernel<false, true>), dim3(2 * B), dim3(512), 0, st, gx_f, gx_b, U_f, U_b, brec_f, brec_b, h_f, h_b, sv_f, sv_b, S);
-    return 0;
-}
-
-// seld_rnn_gru_fwd with one direction: grid B.  rm: seld_rnn_gru_drop_fwd's (sv and hm are then required)
-int launch_gru_fwd_uni(hipStream_t st, const float* gx, const float* U, const float* brec, float* h, float* sv, int B, int S, const float* rm,
-                       float* hm) {
-    if (rm) {
-        if (!hm || !sv) return -1;
-        hipLaunchKernelGGL((gru_fwd_kernel<true, false, true, true>), dim3(B), dim3(512), 0, st, gx, nullptr, U, nullptr, brec, nullptr, h, nullptr, sv, nullptr,
-                           S, rm, nullptr, hm, nullptr);
-        return 0;
-    }
-    if (sv) hipLaunchKernelGGL((gru_fwd_kernel<true, true, false, true>), dim3(B), dim3(512), 0, st, gx, nullptr, U, nullptr, brec, nullptr, h, nullptr, sv, nullptr, S);
-    else hipLaunchKernelGGL((gru_fwd_kernel<false, true, false, true>), dim3(B), dim3(512), 0, st, gx, nullptr, U, nullptr, brec, nullptr, h, nullptr, sv, nullptr, S);
+    const bool bi = gx_b != nullptr;
+    if (rm_f && (!hm_f || !sv_f || (bi && (!rm_b || !hm_b)))) return -1;
+    auto kern = rm_f   ? (bi ? gru_fwd_kernel<true, false, true> : gru_fwd_kernel<true, false, true, true>)
+                : sv_f ? (bi ? gru_fwd_kernel<true, true> : gru_fwd_kernel<true, true, false, true>)
+                       : (bi ? gru_fwd_kernel<false, true> : gru_fwd_kernel<false, true, false, true>);
+    hipLaunchKernelGGL(kern, dim3((bi ? 2 : 1) * B), dim3(512), 0, st, gx_f, gx_b, U_f, U_b, brec_f, brec_b, h_f, h_b, sv_f, sv_b, S, rm_f, rm_b, hm_f,
+                       hm_b);
     return 0;
 }
 
@@ -431,40 +419,22 @@ __global__ __launch_bounds__(512) void gru_bwd_kernel(const float* __restrict__ 
     }
 }
 
-int launch_gru_bwd(hipStream_t st, const float* dout, const float* h_f, const float* h_b, const float* sv_f,
-                   const float* sv_b, const float* U_f, const float* U_b, float* dgx_f, float* dgx_b,
-                   float* dgh_f, float* dgh_b, int B, int S, const float* rm_f, const float* rm_b, const float* hm_f, const float* hm_b) {
+// The one BPTT launcher.  mode = the kernel's MODE (GRU_BWD_*): MUL — dout is the gradient of the 'mul' merge's output, dh_b unused; GIVEN2 — dout and
+// dh_b are the two directions' output gradients; GIVEN1 — dout is the one direction's (grid B; no *_b argument is read).  rm_f: recurrent dropout —
+// h_prev is hm, and h_* is read as the merge partner alone (MUL)
+int launch_gru_bwd(hipStream_t st, int mode, const float* dout, const float* dh_b, const float* h_f, const float* h_b, const float* sv_f,
+                   const float* sv_b, const float* U_f, const float* U_b, float* dgx_f, float* dgx_b, float* dgh_f, float* dgh_b, int B, int S,
+                   const float* rm_f, const float* rm_b, const float* hm_f, const float* hm_b) {
+    const bool bi = mode != GRU_BWD_GIVEN1;
+    if (mode < GRU_BWD_MUL || mode > GRU_BWD_GIVEN1 || (mode == GRU_BWD_GIVEN2) != (dh_b != nullptr)) return -1;
+    if (rm_f && (!hm_f || (bi && (!rm_b || !hm_b)))) return -1;
+    using Kern = decltype(&gru_bwd_kernel<true, false, 0>);
+    static const Kern kerns[2][3] = {{gru_bwd_kernel<true, false, 0>, gru_bwd_kernel<true, false, 1>, gru_bwd_kernel<true, false, 2>},
+                                     {gru_bwd_kernel<false, true, 0>, gru_bwd_kernel<false, true, 1>, gru_bwd_kernel<false, true, 2>}};
+    const Kern kern = kerns[rm_f != nullptr][mode];
     const size_t smem = (size_t)(2 * GRUB_CH * GRUB_ROW + 2 * GRUB_GL) * sizeof(float);
-    if (rm_f) {      // recurrent dropout: see gru_fwd_kernel
-        if (!rm_b || !hm_f || !hm_b) return -1;
-        auto kd = gru_bwd_kernel<false, true>;
-        hipFuncSetAttribute(reinterpret_cast<const void*>(kd), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        hipLaunchKernelGGL(kd, dim3(2 * B), dim3(512), smem, st, dout, h_f, h_b, sv_f, sv_b, U_f, U_b, dgx_f, dgx_b, dgh_f, dgh_b, S, rm_f, rm_b, hm_f, hm_b, nullptr);
-        return 0;
-    }
-    auto kern = gru_bwd_kernel<true>;
     hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    hipLaunchKernelGGL(kern, dim3(2 * B), dim3(512), smem, st, dout, h_f, h_b, sv_f, sv_b, U_f, U_b, dgx_f, dgx_b,
-                       dgh_f, dgh_b, S, nullptr, nullptr, nullptr, nullptr, nullptr);
-    return 0;
-}
-
-// seld_rnn_gru_bwd: the two directions' output gradients as given (dh_b == nullptr: one direction, grid B)
-int launch_gru_bwd_dh(hipStream_t st, const float* dh_f, const float* dh_b, const float* h_f, const float* h_b, const float* sv_f, const float* sv_b,
-                      const float* U_f, const float* U_b, float* dgx_f, float* dgx_b, float* dgh_f, float* dgh_b, int B, int S, const float* rm_f,
-                      const float* rm_b, const float* hm_f, const float* hm_b) {
-    const size_t smem = (size_t)(2 * GRUB_CH * GRUB_ROW + 2 * GRUB_GL) * sizeof(float);
-    if (rm_f) {      // recurrent dropout (seld_rnn_gru_drop_bwd): h_prev is hm, h_* is not read
-        if (!hm_f || (dh_b && (!rm_b || !hm_b))) return -1;
-        auto kd = dh_b ? gru_bwd_kernel<false, true, 1> : gru_bwd_kernel<false, true, 2>;
-        hipFuncSetAttribute(reinterpret_cast<const void*>(kd), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        hipLaunchKernelGGL(kd, dim3((dh_b ? 2 : 1) * B), dim3(512), smem, st, dh_f, h_f, h_b, sv_f, sv_b, U_f, U_b, dgx_f, dgx_b, dgh_f, dgh_b, S,
-                           rm_f, rm_b, hm_f, hm_b, dh_b);
-        return 0;
-    }
-    auto kern = dh_b ? gru_bwd_kernel<true, false, 1> : gru_bwd_kernel<true, false, 2>;
-    hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    hipLaunchKernelGGL(kern, dim3((dh_b ? 2 : 1) * B), dim3(512), smem, st, dh_f, h_f, h_b, sv_f, sv_b, U_f, U_b, dgx_f, dgx_b, dgh_f, dgh_b, S,
-                       nullptr, nullptr, nullptr, nullptr, dh_b);
+    hipLaunchKernelGGL(kern, dim3((bi ? 2 : 1) * B), dim3(512), smem, st, dout, h_f, h_b, sv_f, sv_b, U_f, U_b, dgx_f, dgx_b, dgh_f, dgh_b, S, rm_f, rm_b,
+                       hm_f, hm_b, dh_b);
     return 0;
 }

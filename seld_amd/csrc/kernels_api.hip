@@ -445,7 +445,7 @@ int seld_k_gru_bwd(const float* dout, const float* h_f, const float* h_b, const 
                    int units) {
     if (units != 128) return SELD_ERR_UNSUPPORTED;
     if (!dout || !h_f || !h_b || !saved_f || !saved_b || !U_f || !U_b || !dgx_f || !dgx_b || !dgh_f || !dgh_b) return SELD_ERR_INVALID;
-    launch_gru_bwd(0, dout, h_f, h_b, saved_f, saved_b, U_f, U_b, dgx_f, dgx_b, dgh_f, dgh_b, B, S);
+    launch_gru_bwd(0, GRU_BWD_MUL, dout, nullptr, h_f, h_b, saved_f, saved_b, U_f, U_b, dgx_f, dgx_b, dgh_f, dgh_b, B, S);
     return done();
 }
 
@@ -468,7 +468,8 @@ int seld_k_gru_drop_bwd(const float* dout, const float* h_f, const float* h_b, c
     if (!dout || !h_f || !h_b || !hm_f || !hm_b || !saved_f || !saved_b || !U_f || !U_b || !rm_f || !rm_b || !dgx_f || !dgx_b || !dgh_f || !dgh_b ||
         B < 1 || S < 1)
         return SELD_ERR_INVALID;
-    if (launch_gru_bwd(0, dout, h_f, h_b, saved_f, saved_b, U_f, U_b, dgx_f, dgx_b, dgh_f, dgh_b, B, S, rm_f, rm_b, hm_f, hm_b)) return SELD_ERR_INVALID;
+    if (launch_gru_bwd(0, GRU_BWD_MUL, dout, nullptr, h_f, h_b, saved_f, saved_b, U_f, U_b, dgx_f, dgx_b, dgh_f, dgh_b, B, S, rm_f, rm_b, hm_f, hm_b))
+        return SELD_ERR_INVALID;
     return done();
 }
 

@@ -533,95 +533,99 @@ int seld_m_gru_bwd(const float* dout, const float* h_f, const float* h_b, const 
                    const float* U_b, float* dgx_f, float* dgx_b, float* dgh_f, float* dgh_b, int B, int S, int units, void* stream) {
     if (units != 128) return SELD_ERR_UNSUPPORTED;
     if (!dout || !h_f || !h_b || !saved_f || !saved_b || !U_f || !U_b || !dgx_f || !dgx_b || !dgh_f || !dgh_b || B < 1 || S < 1) return SELD_ERR_INVALID;
-    launch_gru_bwd((hipStream_t)stream, dout, h_f, h_b, saved_f, saved_b, U_f, U_b, dgx_f, dgx_b, dgh_f, dgh_b, B, S);
+    launch_gru_bwd((hipStream_t)stream, GRU_BWD_MUL, dout, nullptr, h_f, h_b, saved_f, saved_b, U_f, U_b, dgx_f, dgx_b, dgh_f, dgh_b, B, S);
     return ok();
 }
 /* ---- reference modules.RNN_block / RNN_stage (modules.py:64-83, 322-347): the LSTM recurrence (lstm.hip), the GRU recurrence per direction
  * with the output gradients as given (gru.hip's kernels), Bidirectional's merge ----------------------------------------------------------- */
 #define RNN_MAX_S (1 << 20)      /* the kernels form in-sequence byte offsets in 32 bits: S * 2048 B < 2^31 */
-int seld_rnn_lstm_fwd(const float* gx_f, const float* gx_b, const float* U_f, const float* U_b, float* h_f, float* h_b, float* c_f, float* c_b,
-                      float* saved_f, float* saved_b, int B, int S, int units, void* stream) {
+/* One function per recurrence holds its only validation; the plain and the _drop entries below are wrappers over it.  drop: Keras dropout /
+ * recurrent_dropout (reference modules.py:312-315, 338-340; training) — the state masks rm_* [B,128] ride in the kernels (gru.hip / lstm.hip:
+ * DROP; the input masks are seld_rnn_mask_rows in front of the projections), and everything the backward reads is required.  Without it a
+ * forward may leave `saved` (the LSTM: and `c`) NULL, for every direction alike.  Refusals, in this order: the width -> UNSUPPORTED; a missing
+ * pointer, B or S < 1 -> INVALID; half a second direction -> INVALID; S or B beyond the kernels' 32-bit offsets -> UNSUPPORTED */
+static int rnn_lstm_fwd(bool drop, const float* gx_f, const float* gx_b, const float* U_f, const float* U_b, const float* rm_f, const float* rm_b,
+                        float* h_f, float* h_b, float* c_f, float* c_b, float* saved_f, float* saved_b, int B, int S, int units, void* stream) {
     if (units != 128) return SELD_ERR_UNSUPPORTED;
-    if (!gx_f || !U_f || !h_f || B < 1 || S < 1 || (!c_f) != (!saved_f)) return SELD_ERR_INVALID;
-    if (gx_b ? (!U_b || !h_b || (!c_b) != (!c_f) || (!saved_b) != (!saved_f)) : (U_b || h_b || c_b || saved_b)) return SELD_ERR_INVALID;
-    if (S > RNN_MAX_S || B > 0x3fffffff) return SELD_ERR_UNSUPPORTED;
-    if (launch_lstm_fwd((hipStream_t)stream, gx_f, gx_b, U_f, U_b, h_f, h_b, c_f, c_b, saved_f, saved_b, B, S)) return SELD_ERR_HIP;
-    return ok();
-}
-int seld_rnn_lstm_bwd(const float* dh_f, const float* dh_b, const float* c_f, const float* c_b, const float* saved_f, const float* saved_b,
-                      const float* U_f, const float* U_b, float* dgx_f, float* dgx_b, int B, int S, int units, void* stream) {
-    if (units != 128) return SELD_ERR_UNSUPPORTED;
-    if (!dh_f || !c_f || !saved_f || !U_f || !dgx_f || B < 1 || S < 1) return SELD_ERR_INVALID;
-    if (dh_b ? (!c_b || !saved_b || !U_b || !dgx_b) : (c_b || saved_b || U_b || dgx_b)) return SELD_ERR_INVALID;      // a half-given backward side
-    if (S > RNN_MAX_S || B > 0x3fffffff) return SELD_ERR_UNSUPPORTED;
-    if (launch_lstm_bwd((hipStream_t)stream, dh_f, dh_b, c_f, c_b, saved_f, saved_b, U_f, U_b, dgx_f, dgx_b, B, S)) return SELD_ERR_HIP;
-    return ok();
-}
-int seld_rnn_gru_fwd(const float* gx_f, const float* gx_b, const float* U_f, const float* U_b, const float* brec_f, const float* brec_b, float* h_f,
-                     float* h_b, float* saved_f, float* saved_b, int B, int S, int units, void* stream) {
-    if (units != 128) return SELD_ERR_UNSUPPORTED;
-    if (!gx_f || !U_f || !brec_f || !h_f || B < 1 || S < 1) return SELD_ERR_INVALID;
-    if (gx_b ? (!U_b || !brec_b || !h_b || (!saved_b) != (!saved_f)) : (U_b || brec_b || h_b || saved_b)) return SELD_ERR_INVALID;
-    if (S > RNN_MAX_S || B > 0x3fffffff) return SELD_ERR_UNSUPPORTED;
-    if (gx_b) launch_gru_fwd((hipStream_t)stream, gx_f, gx_b, U_f, U_b, brec_f, brec_b, h_f, h_b, saved_f, saved_b, B, S);
-    else launch_gru_fwd_uni((hipStream_t)stream, gx_f, U_f, brec_f, h_f, saved_f, B, S);
-    return ok();
-}
-int seld_rnn_gru_bwd(const float* dh_f, const float* dh_b, const float* h_f, const float* h_b, const float* saved_f, const float* saved_b,
-                     const float* U_f, const float* U_b, float* dgx_f, float* dgx_b, float* dgh_f, float* dgh_b, int B, int S, int units,
-                     void* stream) {
-    if (units != 128) return SELD_ERR_UNSUPPORTED;
-    if (!dh_f || !h_f || !saved_f || !U_f || !dgx_f || !dgh_f || B < 1 || S < 1) return SELD_ERR_INVALID;
-    if (dh_b ? (!h_b || !saved_b || !U_b || !dgx_b || !dgh_b) : (h_b || saved_b || U_b || dgx_b || dgh_b)) return SELD_ERR_INVALID;
-    if (S > RNN_MAX_S || B > 0x3fffffff) return SELD_ERR_UNSUPPORTED;
-    launch_gru_bwd_dh((hipStream_t)stream, dh_f, dh_b, h_f, h_b, saved_f, saved_b, U_f, U_b, dgx_f, dgx_b, dgh_f, dgh_b, B, S);
-    return ok();
-}
-/* ---- the same recurrences under Keras dropout / recurrent_dropout (reference modules.py:312-315, 338-340; training: everything the backward
- * reads is required).  The state masks rm_* [B,128] ride in the kernels (gru.hip / lstm.hip: DROP); the input masks are seld_rnn_mask_rows in
- * front of the projections ------------------------------------------------------------------------------------------------------------- */
-int seld_rnn_lstm_drop_fwd(const float* gx_f, const float* gx_b, const float* U_f, const float* U_b, const float* rm_f, const float* rm_b,
-                           float* h_f, float* h_b, float* c_f, float* c_b, float* saved_f, float* saved_b, int B, int S, int units, void* stream) {
-    if (units != 128) return SELD_ERR_UNSUPPORTED;
-    if (!gx_f || !U_f || !rm_f || !h_f || !c_f || !saved_f || B < 1 || S < 1) return SELD_ERR_INVALID;
-    if (gx_b ? (!U_b || !rm_b || !h_b || !c_b || !saved_b) : (U_b || rm_b || h_b || c_b || saved_b)) return SELD_ERR_INVALID;
+    if (!gx_f || !U_f || !h_f || B < 1 || S < 1 || (drop ? (!rm_f || !c_f || !saved_f) : (!c_f) != (!saved_f))) return SELD_ERR_INVALID;
+    if (gx_b ? (!U_b || !h_b || (drop && !rm_b) || (!c_b) != (!c_f) || (!saved_b) != (!saved_f)) : (U_b || rm_b || h_b || c_b || saved_b))
+        return SELD_ERR_INVALID;
     if (S > RNN_MAX_S || B > 0x3fffffff) return SELD_ERR_UNSUPPORTED;
     if (launch_lstm_fwd((hipStream_t)stream, gx_f, gx_b, U_f, U_b, h_f, h_b, c_f, c_b, saved_f, saved_b, B, S, rm_f, rm_b)) return SELD_ERR_HIP;
     return ok();
 }
-int seld_rnn_lstm_drop_bwd(const float* dh_f, const float* dh_b, const float* c_f, const float* c_b, const float* saved_f, const float* saved_b,
-                           const float* U_f, const float* U_b, const float* rm_f, const float* rm_b, float* dgx_f, float* dgx_b, int B, int S,
-                           int units, void* stream) {
+static int rnn_lstm_bwd(bool drop, const float* dh_f, const float* dh_b, const float* c_f, const float* c_b, const float* saved_f,
+                        const float* saved_b, const float* U_f, const float* U_b, const float* rm_f, const float* rm_b, float* dgx_f, float* dgx_b,
+                        int B, int S, int units, void* stream) {
     if (units != 128) return SELD_ERR_UNSUPPORTED;
-    if (!dh_f || !c_f || !saved_f || !U_f || !rm_f || !dgx_f || B < 1 || S < 1) return SELD_ERR_INVALID;
-    if (dh_b ? (!c_b || !saved_b || !U_b || !rm_b || !dgx_b) : (c_b || saved_b || U_b || rm_b || dgx_b)) return SELD_ERR_INVALID;
+    if (!dh_f || !c_f || !saved_f || !U_f || (drop && !rm_f) || !dgx_f || B < 1 || S < 1) return SELD_ERR_INVALID;
+    if (dh_b ? (!c_b || !saved_b || !U_b || (drop && !rm_b) || !dgx_b) : (c_b || saved_b || U_b || rm_b || dgx_b)) return SELD_ERR_INVALID;
     if (S > RNN_MAX_S || B > 0x3fffffff) return SELD_ERR_UNSUPPORTED;
     if (launch_lstm_bwd((hipStream_t)stream, dh_f, dh_b, c_f, c_b, saved_f, saved_b, U_f, U_b, dgx_f, dgx_b, B, S, rm_f, rm_b)) return SELD_ERR_HIP;
     return ok();
 }
+/* hm_*: the masked state sequences the DROP forward stores for its backward */
+static int rnn_gru_fwd(bool drop, const float* gx_f, const float* gx_b, const float* U_f, const float* U_b, const float* brec_f, const float* brec_b,
+                       const float* rm_f, const float* rm_b, float* h_f, float* h_b, float* hm_f, float* hm_b, float* saved_f, float* saved_b, int B,
+                       int S, int units, void* stream) {
+    if (units != 128) return SELD_ERR_UNSUPPORTED;
+    if (!gx_f || !U_f || !brec_f || !h_f || (drop && (!rm_f || !hm_f || !saved_f)) || B < 1 || S < 1) return SELD_ERR_INVALID;
+    if (gx_b ? (!U_b || !brec_b || !h_b || (drop && (!rm_b || !hm_b)) || (!saved_b) != (!saved_f)) : (U_b || brec_b || rm_b || h_b || hm_b || saved_b))
+        return SELD_ERR_INVALID;
+    if (S > RNN_MAX_S || B > 0x3fffffff) return SELD_ERR_UNSUPPORTED;
+    if (launch_gru_fwd((hipStream_t)stream, gx_f, gx_b, U_f, U_b, brec_f, brec_b, h_f, h_b, saved_f, saved_b, B, S, rm_f, rm_b, hm_f, hm_b))
+        return SELD_ERR_HIP;
+    return ok();
+}
+/* hp_*: the state sequence the BPTT reads as h_prev — the forward's h, under dropout its hm (h itself is then not read) */
+static int rnn_gru_bwd(bool drop, const float* dh_f, const float* dh_b, const float* hp_f, const float* hp_b, const float* saved_f,
+                       const float* saved_b, const float* U_f, const float* U_b, const float* rm_f, const float* rm_b, float* dgx_f, float* dgx_b,
+                       float* dgh_f, float* dgh_b, int B, int S, int units, void* stream) {
+    if (units != 128) return SELD_ERR_UNSUPPORTED;
+    if (!dh_f || !hp_f || !saved_f || !U_f || (drop && !rm_f) || !dgx_f || !dgh_f || B < 1 || S < 1) return SELD_ERR_INVALID;
+    if (dh_b ? (!hp_b || !saved_b || !U_b || (drop && !rm_b) || !dgx_b || !dgh_b) : (hp_b || saved_b || U_b || rm_b || dgx_b || dgh_b))
+        return SELD_ERR_INVALID;
+    if (S > RNN_MAX_S || B > 0x3fffffff) return SELD_ERR_UNSUPPORTED;
+    if (launch_gru_bwd((hipStream_t)stream, dh_b ? GRU_BWD_GIVEN2 : GRU_BWD_GIVEN1, dh_f, dh_b, drop ? nullptr : hp_f, drop ? nullptr : hp_b, saved_f,
+                       saved_b, U_f, U_b, dgx_f, dgx_b, dgh_f, dgh_b, B, S, rm_f, rm_b, drop ? hp_f : nullptr, drop ? hp_b : nullptr))
+        return SELD_ERR_HIP;
+    return ok();
+}
+int seld_rnn_lstm_fwd(const float* gx_f, const float* gx_b, const float* U_f, const float* U_b, float* h_f, float* h_b, float* c_f, float* c_b,
+                      float* saved_f, float* saved_b, int B, int S, int units, void* stream) {
+    return rnn_lstm_fwd(false, gx_f, gx_b, U_f, U_b, nullptr, nullptr, h_f, h_b, c_f, c_b, saved_f, saved_b, B, S, units, stream);
+}
+int seld_rnn_lstm_drop_fwd(const float* gx_f, const float* gx_b, const float* U_f, const float* U_b, const float* rm_f, const float* rm_b,
+                           float* h_f, float* h_b, float* c_f, float* c_b, float* saved_f, float* saved_b, int B, int S, int units, void* stream) {
+    return rnn_lstm_fwd(true, gx_f, gx_b, U_f, U_b, rm_f, rm_b, h_f, h_b, c_f, c_b, saved_f, saved_b, B, S, units, stream);
+}
+int seld_rnn_lstm_bwd(const float* dh_f, const float* dh_b, const float* c_f, const float* c_b, const float* saved_f, const float* saved_b,
+                      const float* U_f, const float* U_b, float* dgx_f, float* dgx_b, int B, int S, int units, void* stream) {
+    return rnn_lstm_bwd(false, dh_f, dh_b, c_f, c_b, saved_f, saved_b, U_f, U_b, nullptr, nullptr, dgx_f, dgx_b, B, S, units, stream);
+}
+int seld_rnn_lstm_drop_bwd(const float* dh_f, const float* dh_b, const float* c_f, const float* c_b, const float* saved_f, const float* saved_b,
+                           const float* U_f, const float* U_b, const float* rm_f, const float* rm_b, float* dgx_f, float* dgx_b, int B, int S,
+                           int units, void* stream) {
+    return rnn_lstm_bwd(true, dh_f, dh_b, c_f, c_b, saved_f, saved_b, U_f, U_b, rm_f, rm_b, dgx_f, dgx_b, B, S, units, stream);
+}
+int seld_rnn_gru_fwd(const float* gx_f, const float* gx_b, const float* U_f, const float* U_b, const float* brec_f, const float* brec_b, float* h_f,
+                     float* h_b, float* saved_f, float* saved_b, int B, int S, int units, void* stream) {
+    return rnn_gru_fwd(false, gx_f, gx_b, U_f, U_b, brec_f, brec_b, nullptr, nullptr, h_f, h_b, nullptr, nullptr, saved_f, saved_b, B, S, units, stream);
+}
 int seld_rnn_gru_drop_fwd(const float* gx_f, const float* gx_b, const float* U_f, const float* U_b, const float* brec_f, const float* brec_b,
                           const float* rm_f, const float* rm_b, float* h_f, float* h_b, float* hm_f, float* hm_b, float* saved_f, float* saved_b,
                           int B, int S, int units, void* stream) {
-    if (units != 128) return SELD_ERR_UNSUPPORTED;
-    if (!gx_f || !U_f || !brec_f || !rm_f || !h_f || !hm_f || !saved_f || B < 1 || S < 1) return SELD_ERR_INVALID;
-    if (gx_b ? (!U_b || !brec_b || !rm_b || !h_b || !hm_b || !saved_b) : (U_b || brec_b || rm_b || h_b || hm_b || saved_b)) return SELD_ERR_INVALID;
-    if (S > RNN_MAX_S || B > 0x3fffffff) return SELD_ERR_UNSUPPORTED;
-    if (gx_b ? launch_gru_fwd((hipStream_t)stream, gx_f, gx_b, U_f, U_b, brec_f, brec_b, h_f, h_b, saved_f, saved_b, B, S, rm_f, rm_b, hm_f, hm_b)
-             : launch_gru_fwd_uni((hipStream_t)stream, gx_f, U_f, brec_f, h_f, saved_f, B, S, rm_f, hm_f))
-        return SELD_ERR_HIP;
-    return ok();
+    return rnn_gru_fwd(true, gx_f, gx_b, U_f, U_b, brec_f, brec_b, rm_f, rm_b, h_f, h_b, hm_f, hm_b, saved_f, saved_b, B, S, units, stream);
+}
+int seld_rnn_gru_bwd(const float* dh_f, const float* dh_b, const float* h_f, const float* h_b, const float* saved_f, const float* saved_b,
+                     const float* U_f, const float* U_b, float* dgx_f, float* dgx_b, float* dgh_f, float* dgh_b, int B, int S, int units,
+                     void* stream) {
+    return rnn_gru_bwd(false, dh_f, dh_b, h_f, h_b, saved_f, saved_b, U_f, U_b, nullptr, nullptr, dgx_f, dgx_b, dgh_f, dgh_b, B, S, units, stream);
 }
 int seld_rnn_gru_drop_bwd(const float* dh_f, const float* dh_b, const float* hm_f, const float* hm_b, const float* saved_f, const float* saved_b,
                           const float* U_f, const float* U_b, const float* rm_f, const float* rm_b, float* dgx_f, float* dgx_b, float* dgh_f,
                           float* dgh_b, int B, int S, int units, void* stream) {
-    if (units != 128) return SELD_ERR_UNSUPPORTED;
-    if (!dh_f || !hm_f || !saved_f || !U_f || !rm_f || !dgx_f || !dgh_f || B < 1 || S < 1) return SELD_ERR_INVALID;
-    if (dh_b ? (!hm_b || !saved_b || !U_b || !rm_b || !dgx_b || !dgh_b) : (hm_b || saved_b || U_b || rm_b || dgx_b || dgh_b)) return SELD_ERR_INVALID;
-    if (S > RNN_MAX_S || B > 0x3fffffff) return SELD_ERR_UNSUPPORTED;
-    if (launch_gru_bwd_dh((hipStream_t)stream, dh_f, dh_b, nullptr, nullptr, saved_f, saved_b, U_f, U_b, dgx_f, dgx_b, dgh_f, dgh_b, B, S, rm_f, rm_b,
-                          hm_f, hm_b))
-        return SELD_ERR_HIP;
-    return ok();
+    return rnn_gru_bwd(true, dh_f, dh_b, hm_f, hm_b, saved_f, saved_b, U_f, U_b, rm_f, rm_b, dgx_f, dgx_b, dgh_f, dgh_b, B, S, units, stream);
 }
 /* seld_k_mask_rows's kernel on the caller's stream, with the same refusals */
 int seld_rnn_mask_rows(const float* in, const float* mask, float* out, int64_t rows, int S, int F, int accumulate, void* stream) {

@@ -1304,6 +1304,27 @@ def _is_gru_width(u) -> bool:
     return isinstance(u, (int, np.integer)) and not isinstance(u, bool) and GRU_MIN_UNITS <= int(u) <= GRU_MAX_UNITS
 
 
+def _check_widths_and_rate(cfg: dict, who: str, widths, any_units: bool, dropout: bool, texts) -> None:
+    """The rules check_rnn_config and check_gru_config share, on the layers' `widths` (None: `units` has the wrong form): every width is 128 —
+    with any_units an integer in 1..256; the recurrences under dropout (the DROP forms) exist at 128 only; dropout_rate is a rate where the
+    owner accepted the library's draws (`dropout`) and 0 elsewhere.  texts: the caller's own words — its refusal of a width with any_units
+    and without, how the DROP refusal names the widths, its refusal of a rate without `dropout`"""
+    bad_any_width, bad_width, at, no_draws = texts
+    rate = float(cfg.get("dropout_rate", 0.0) or 0.0)
+    if any_units:
+        if widths is None or not all(_is_gru_width(u) for u in widths):
+            raise ValueError(bad_any_width)
+        if rate != 0.0 and any(int(u) != 128 for u in widths):
+            raise ValueError(f"{who}: dropout_rate {cfg.get('dropout_rate')!r} at {at}: the recurrences under dropout / recurrent_dropout (the "
+                             "DROP forms) are 128-unit kernels; at another width dropout_rate must be 0")
+    elif widths is None or any(int(u) != 128 for u in widths):
+        raise ValueError(bad_width)
+    if dropout:
+        _recurrent_rate(cfg, who)
+    elif rate != 0.0:
+        raise ValueError(no_draws)
+
+
 def check_rnn_config(cfg: dict, stage: bool = False, dropout: bool = False, any_units: bool = False) -> None:
     """reference modules.RNN_block / RNN_stage (modules.py:64-83, 322-347): the mandatory keys; what has no kernel here is refused, not ignored.
     dropout: the owner accepted the library's draws for the cells' input and state masks (_Recurrent), and dropout_rate may be any rate in
@@ -1313,44 +1334,48 @@ def check_rnn_config(cfg: dict, stage: bool = False, dropout: bool = False, any_
     for key in ("units",) + (("depth",) if stage else ()):
         if key not in cfg:
             raise ValueError(f"{who}: missing {key!r}")
-    wide = any_units and cfg.get("rnn_type", "GRU") == "GRU"
-    if wide:
-        if not _is_gru_width(cfg["units"]):
-            raise ValueError(f"{who}: units {cfg['units']!r}: a GRU width is an integer in {GRU_MIN_UNITS}..{GRU_MAX_UNITS}")
-        if int(cfg["units"]) != 128 and float(cfg.get("dropout_rate", 0.0) or 0.0) != 0.0:
-            raise ValueError(f"{who}: dropout_rate {cfg.get('dropout_rate')!r} at {cfg['units']} units: the recurrences under dropout / "
-                             "recurrent_dropout (the DROP forms) are 128-unit kernels; at another width dropout_rate must be 0")
-    elif isinstance(cfg["units"], (list, tuple)) or int(cfg["units"]) != 128:
-        raise ValueError(f"{who}: units {cfg['units']!r}: the recurrence kernels are built for 128 units")
+    u = cfg["units"]
+    _check_widths_and_rate(cfg, who, None if isinstance(u, (list, tuple)) else [u], any_units and cfg.get("rnn_type", "GRU") == "GRU", dropout, (
+        f"{who}: units {u!r}: a GRU width is an integer in {GRU_MIN_UNITS}..{GRU_MAX_UNITS}",
+        f"{who}: units {u!r}: the recurrence kernels are built for 128 units", f"{u} units",
+        f"{who}: dropout / recurrent_dropout inside the recurrence kernels (per-clip input and state masks) are not implemented on "
+        "the composed path, whose Dropout (seld_dropout, seld_attn_drop_*) covers the attention kinds only: dropout_rate must be 0"))
     if stage and int(cfg["depth"]) < 1:
         raise ValueError(f"{who}: depth >= 1")
-    if dropout:
-        _recurrent_rate(cfg, who)
-    elif float(cfg.get("dropout_rate", 0.0) or 0.0) != 0.0:
-        raise ValueError(f"{who}: dropout / recurrent_dropout inside the recurrence kernels (per-clip input and state masks) are not implemented on "
-                         "the composed path, whose Dropout (seld_dropout, seld_attn_drop_*) covers the attention kinds only: dropout_rate must be 0")
     if bool(cfg.get("bidirectional", True)) and cfg.get("merge_mode", "mul") not in RNN_MERGE:
         # None makes Bidirectional return a LIST (the reference's graph breaks on it); 'avg' (the reference's comment) is rejected by Keras itself
         raise ValueError(f"{who}: merge_mode {cfg.get('merge_mode')!r}: one of {RNN_MERGE}")
 
 
 class _Recurrent:
-    """What the recurrent blocks share on [B*S, D] with u units (128; a GRU on a runtime with any_units: 1..256) and gate width G (GRU,
-    reset_after=True: 3u, LSTM: 4u), per direction
-    `name` of `names`: the variables kernel (D, G), recurrent_kernel (u, G), bias (GRU (2, 3u): input row | recurrent row; LSTM (4u,)),
-    the input projections gx, the states h and sv, the pre-activation gradients dgx (GRU: and dgh, behind the reset gate), the input's
-    gradient din — and the GEMMs in front of and behind the recurrence kernels.
+    """The recurrent blocks' one forward and one backward on [B*S, D] with u units (128; a GRU on a runtime with any_units: 1..256) and gate
+    width G (GRU, reset_after=True: 3u, LSTM: 4u).  Per direction `name` of `names`: the variables kernel (D, G), recurrent_kernel (u, G),
+    bias (GRU (2, 3u): input row | recurrent row; LSTM (4u,)), the input projections gx, the states h and sv, the pre-activation gradients
+    dgx (GRU: and dgh, behind the reset gate); the input's gradient din.  A subclass says WHICH block this is — `lstm`, `bi`, `mode`,
+    `fusable`, the buffers `c`, `dh`, `out` — and the path is
 
-    Keras dropout / recurrent_dropout (`rate` > 0, training; reference modules.py:312-315, 338-340 pass dropout_rate as both): every cell —
-    each direction — owns an input mask im [B, D] and a state mask rm [B, 128] of 0 | 1 / (1 - rate), drawn once per training forward and
-    constant over the sequence: seld_dropout on ones, sites (_Drop) 0 / 1 = the forward direction's input / state mask, 2 / 3 = the backward
-    direction's.  The directions then project their own xm = x * im (seld_rnn_mask_rows), the recurrences run as seld_rnn_*_drop_*, the merge
-    as seld_rnn_merge_*; backward: the weight gradients read xm and the masked state sequence hm = h * rm, din = sum over the directions of
-    (dgx kernel^T) * im.  The blocks' `lstm`, `bi`, `mode`, `c`, `dh` and `out` say which recurrence and merge."""
+        forward    projection: gx = x kernel + input bias, per direction   ->  recurrence (_recurrence)  ->  merge (seld_rnn_merge_fwd; bi)
+        backward   merge (seld_rnn_merge_bwd; one direction: dy as given)  ->  recurrence  ->  weight gradients and din (_weight_grads)
+
+    with the recurrence one of (every pair of entries takes ..., B, S, u, stream):
+
+        cell  dropout on  u      fused   entries                    saved for the backward (sv; LSTM: and c)
+        GRU   no          128    yes     seld_m_gru_fwd / _bwd      in training; recurrence and the 'mul' merge are one operator
+        GRU   no          128    no      seld_rnn_gru_fwd / _bwd    in training
+        GRU   no          other  -       seld_rnn_gruw_fwd / _bwd   in training
+        GRU   yes         128    -       seld_rnn_gru_drop_*        always; the forward stores the masked states hm as well
+        LSTM  no          128    -       seld_rnn_lstm_fwd / _bwd   in training
+        LSTM  yes         128    -       seld_rnn_lstm_drop_*       always
+
+    Dropout on = Keras dropout / recurrent_dropout (`rate` > 0 and training; reference modules.py:312-315, 338-340 pass dropout_rate as
+    both): every cell — each direction — owns an input mask im [B, D] and a state mask rm [B, u] of 0 | 1 / (1 - rate), drawn once per training
+    forward and constant over the sequence: seld_dropout on ones, sites (_Drop) 0 / 1 = the forward direction's input / state mask, 2 / 3 =
+    the backward direction's.  A direction then projects its own xm = x * im (seld_rnn_mask_rows) and rm rides in the recurrence; backward,
+    the weight gradients read xm and the masked state sequence hm = h * rm, and din = the sum over the directions of (dgx kernel^T) * im."""
+    fusable = False      # at 128 units without dropout, the recurrences and the 'mul' merge are the fused seld_m_gru_fwd / _bwd
 
     def __init__(self, rt: _Rt, names, S: int, D: int, G: int, B: int, rate: float = 0.0, units: int = 128):
-        """units: the width u (a GRU on a runtime with any_units: 1..256, G = 3u; otherwise 128).  At u != 128 the GRU recurrences run on
-        seld_rnn_gruw_fwd / _bwd (gru_w.hip) with the merge as its own operator; at 128 on the calls the blocks always made"""
+        """units: the width u (a GRU on a runtime with any_units: 1..256, G = 3u; otherwise 128; under dropout 128)"""
         self.rt, self.names, self.S, self.D, self.G, self.B, self.u = rt, names, int(S), int(D), G, B, int(units)
         u = self.u
         assert G == (4 * u if self.lstm else 3 * u) and (u == 128 or (not self.lstm and rate == 0.0))
@@ -1367,9 +1392,9 @@ class _Recurrent:
         if rate > 0.0:
             if self.D % 4:
                 raise ValueError(f"recurrent dropout on an input width of {self.D}: the mask kernel (seld_rnn_mask_rows) moves float4, D % 4 == 0")
-            self.ones = torch.ones(B * max(self.D, 128), dtype=torch.float32, device=rt.dev)
-            self.im, self.rm = [e(B, self.D) for _ in range(nd)], [e(B, 128) for _ in range(nd)]
-            self.xm, self.hm = [e(R, self.D) for _ in range(nd)], [e(R, 128) for _ in range(nd)]
+            self.ones = torch.ones(B * max(self.D, u), dtype=torch.float32, device=rt.dev)
+            self.im, self.rm = [e(B, self.D) for _ in range(nd)], [e(B, u) for _ in range(nd)]
+            self.xm, self.hm = [e(R, self.D) for _ in range(nd)], [e(R, u) for _ in range(nd)]
             self.dxm = e(R, self.D)
 
     def _pair(self, ts, none=False):
@@ -1377,101 +1402,83 @@ class _Recurrent:
         p = self.rt.p
         return (None, None) if none else (p(ts[0]), p(ts[1]) if len(self.names) == 2 else None)
 
-    def _project(self, x, R):
-        """gx = x kernel + the input bias, per direction"""
-        rt = self.rt
-        self.x = x
-        for d, n in enumerate(self.names):
-            rt.gemm(x, rt.w(f"{n}.kernel"), rt.w(f"{n}.bias")[:self.G], self.gx[d], R, self.G, self.D)
-
-    def _weight_grads(self, R):
-        """dgx, dgh -> every variable's gradient and the input's [R, D]"""
-        rt = self.rt
-        for d, n in enumerate(self.names):
-            gb = rt.g(f"{n}.bias")
-            rt.gemm_tn(self.x, self.dgx[d], rt.g(f"{n}.kernel"), gb[:self.G], R, self.D, self.G)
-            # recurrent kernel: h_prev^T dgh — the forward direction saw h[t-1], the backward direction h[t+1]
-            rt.gemm_tn(self.h[d], self.dgh[d], rt.g(f"{n}.recurrent_kernel"), gb[self.G:] if not self.lstm else None, R, self.u, self.G, seq=self.S,
-                       shift=-1 if d == 0 else 1)
-            rt.gemm(self.dgx[d], rt.w(f"{n}.kernel"), None, self.din, R, self.D, self.G, transb=1, accumulate=d)
-        return self.din[:R]
-
-    def _wide_forward(self, x, B, training):
-        """the GRU forward at a width other than 128 -> [B*S, out_dim]"""
-        rt, lib, R = self.rt, self.rt.lib, B * self.S
-        self._project(x, R)
-        U = self._pair([rt.w(f"{n}.recurrent_kernel") for n in self.names])
-        brec = self._pair([rt.w(f"{n}.bias")[self.G:] for n in self.names])
-        rt.ck(lib.seld_rnn_gruw_fwd(*self._pair(self.gx), *U, *brec, *self._pair(self.h), *self._pair(self.sv, not training), B, self.S, self.u, rt.st()))
-        if not self.bi:
-            return self.h[0][:R]
-        rt.ck(lib.seld_rnn_merge_fwd(rt.p(self.h[0]), rt.p(self.h[1]), rt.p(self.out), R, self.u, self.mode, rt.st()))
-        return self.out[:R]
-
-    def _wide_backward(self, dy, B):
-        """its backward: dy [B*S, out_dim] -> the input's gradient [B*S, D]"""
-        rt, lib, R = self.rt, self.rt.lib, B * self.S
-        if self.bi:
-            rt.ck(lib.seld_rnn_merge_bwd(rt.p(dy), rt.p(self.h[0]), rt.p(self.h[1]), rt.p(self.dh[0]), rt.p(self.dh[1]), R, self.u, self.mode, rt.st()))
-            dh = self._pair(self.dh)
-        else:
-            self._dy = dy.contiguous()      # kept: the kernel reads it after this call returns
-            dh = (rt.p(self._dy), None)
-        U = self._pair([rt.w(f"{n}.recurrent_kernel") for n in self.names])
-        rt.ck(lib.seld_rnn_gruw_bwd(*dh, *self._pair(self.h), *self._pair(self.sv), *U, *self._pair(self.dgx), *self._pair(self.dgh), B, self.S, self.u,
-                                    rt.st()))
-        return self._weight_grads(R)
-
     def _mask_rows(self, src, mask, dst, R, F, accumulate=0):
         rt = self.rt
         rt.ck(rt.lib.seld_rnn_mask_rows(rt.p(src), rt.p(mask), rt.p(dst), R, self.S, F, int(accumulate), rt.st()))
 
-    def _dropped_forward(self, x, B):
-        """the training forward at rate > 0 -> [B*S, out_dim]"""
-        rt, lib, R = self.rt, self.rt.lib, B * self.S
-        for d, n in enumerate(self.names):
-            self.drop.apply(2 * d, self.ones[:B * self.D], self.im[d][:B])
-            self.drop.apply(2 * d + 1, self.ones[:B * 128], self.rm[d][:B])
-            self._mask_rows(x, self.im[d], self.xm[d], R, self.D)
-            rt.gemm(self.xm[d], rt.w(f"{n}.kernel"), rt.w(f"{n}.bias")[:self.G], self.gx[d], R, self.G, self.D)
-        U = self._pair([rt.w(f"{n}.recurrent_kernel") for n in self.names])
+    def _fused(self):
+        return self.fusable and self.u == 128 and not self.drop.on
+
+    def _recurrence(self, training=True):
+        """The recurrence of the current forward (the class's table) -> (stem, forward pointers, backward pointers): the calls are
+        `stem`_fwd(*forward pointers, B, S, u, stream) and `stem`_bwd(*output gradients, *backward pointers, B, S, u, stream)"""
+        rt, P, drop = self.rt, self._pair, self.drop.on
+        gx, h, U = P(self.gx), P(self.h), P([rt.w(f"{n}.recurrent_kernel") for n in self.names])
+        sv = P(self.sv, none=not (training or drop))      # inference saves nothing; the DROP forms always save
+        rm = P(self.rm) if drop else ()
         if self.lstm:
-            rt.ck(lib.seld_rnn_lstm_drop_fwd(*self._pair(self.gx), *U, *self._pair(self.rm), *self._pair(self.h), *self._pair(self.c),
-                                             *self._pair(self.sv), B, self.S, 128, rt.st()))
-        else:
-            brec = self._pair([rt.w(f"{n}.bias")[384:] for n in self.names])
-            rt.ck(lib.seld_rnn_gru_drop_fwd(*self._pair(self.gx), *U, *brec, *self._pair(self.rm), *self._pair(self.h), *self._pair(self.hm),
-                                            *self._pair(self.sv), B, self.S, 128, rt.st()))
+            return ("seld_rnn_lstm_drop" if drop else "seld_rnn_lstm", gx + U + rm + h + P(self.c, none=not (training or drop)) + sv,
+                    P(self.c) + sv + U + rm + P(self.dgx))
+        brec = P([rt.w(f"{n}.bias")[self.G:] for n in self.names])
+        dg = P(self.dgx) + P(self.dgh)
+        if drop:
+            return "seld_rnn_gru_drop", gx + U + brec + rm + h + P(self.hm) + sv, P(self.hm) + sv + U + rm + dg
+        if self._fused():
+            return "seld_m_gru", gx + U + brec + h + sv + (rt.p(self.out),), h + sv + U + dg
+        return "seld_rnn_gru" if self.u == 128 else "seld_rnn_gruw", gx + U + brec + h + sv, h + sv + U + dg
+
+    def forward(self, x, B, training):
+        """x [B*S, D] (or any contiguous view of it) -> [B*S, out_dim]"""
+        rt, R = self.rt, B * self.S
+        self.drop.begin(training)
+        self.x = x = x.reshape(R, self.D)
+        for d, n in enumerate(self.names):      # gx = x kernel + the input bias, per direction; under dropout from the direction's own xm = x * im
+            if self.drop.on:
+                self.drop.apply(2 * d, self.ones[:B * self.D], self.im[d][:B])
+                self.drop.apply(2 * d + 1, self.ones[:B * self.u], self.rm[d][:B])
+                self._mask_rows(x, self.im[d], self.xm[d], R, self.D)
+            rt.gemm(self.xm[d] if self.drop.on else x, rt.w(f"{n}.kernel"), rt.w(f"{n}.bias")[:self.G], self.gx[d], R, self.G, self.D)
+        stem, pointers, _ = self._recurrence(training)
+        rt.ck(getattr(rt.lib, stem + "_fwd")(*pointers, B, self.S, self.u, rt.st()))
         if not self.bi:
             return self.h[0][:R]
-        rt.ck(lib.seld_rnn_merge_fwd(rt.p(self.h[0]), rt.p(self.h[1]), rt.p(self.out), R, 128, self.mode, rt.st()))
+        if not self._fused():
+            rt.ck(rt.lib.seld_rnn_merge_fwd(rt.p(self.h[0]), rt.p(self.h[1]), rt.p(self.out), R, self.u, self.mode, rt.st()))
         return self.out[:R]
 
-    def _dropped_backward(self, dy, B):
-        """its backward: dy [B*S, out_dim] -> the input's gradient [B*S, D]"""
-        rt, lib, R = self.rt, self.rt.lib, B * self.S
-        if self.bi:
-            rt.ck(lib.seld_rnn_merge_bwd(rt.p(dy), rt.p(self.h[0]), rt.p(self.h[1]), rt.p(self.dh[0]), rt.p(self.dh[1]), R, 128, self.mode, rt.st()))
+    def backward(self, dy, B):
+        """dy [B*S, out_dim]: the output's gradient (after a training forward) -> the input's gradient [B*S, D] (a buffer of this block)"""
+        rt, R = self.rt, B * self.S
+        dy = dy.reshape(R, self.out_dim)
+        if self._fused():      # the kernel forms the 'mul' merge's gradient itself
+            dh = (rt.p(dy),)
+        elif self.bi:
+            rt.ck(rt.lib.seld_rnn_merge_bwd(rt.p(dy), rt.p(self.h[0]), rt.p(self.h[1]), rt.p(self.dh[0]), rt.p(self.dh[1]), R, self.u, self.mode,
+                                            rt.st()))
             dh = self._pair(self.dh)
         else:
             self._dy = dy.contiguous()      # kept: the kernel reads it after this call returns
             dh = (rt.p(self._dy), None)
-        U = self._pair([rt.w(f"{n}.recurrent_kernel") for n in self.names])
-        if self.lstm:
-            rt.ck(lib.seld_rnn_lstm_drop_bwd(*dh, *self._pair(self.c), *self._pair(self.sv), *U, *self._pair(self.rm), *self._pair(self.dgx), B,
-                                             self.S, 128, rt.st()))
-        else:
-            rt.ck(lib.seld_rnn_gru_drop_bwd(*dh, *self._pair(self.hm), *self._pair(self.sv), *U, *self._pair(self.rm), *self._pair(self.dgx),
-                                            *self._pair(self.dgh), B, self.S, 128, rt.st()))
+        stem, _, pointers = self._recurrence()
+        rt.ck(getattr(rt.lib, stem + "_bwd")(*dh, *pointers, B, self.S, self.u, rt.st()))
+        return self._weight_grads(R)
+
+    def _weight_grads(self, R):
+        """dgx, dgh -> every variable's gradient and the input's [R, D]; under dropout from the masked xm and hm, and through the input mask"""
+        rt, drop = self.rt, self.drop.on
         for d, n in enumerate(self.names):
             gb = rt.g(f"{n}.bias")
-            if self.lstm:      # the GRU kernel stored its masked state sequence
-                self._mask_rows(self.h[d], self.rm[d], self.hm[d], R, 128)
-            rt.gemm_tn(self.xm[d], self.dgx[d], rt.g(f"{n}.kernel"), gb[:self.G], R, self.D, self.G)
-            rt.gemm_tn(self.hm[d], self.dgh[d], rt.g(f"{n}.recurrent_kernel"), gb[384:] if self.G == 384 else None, R, 128, self.G, seq=self.S,
-                       shift=-1 if d == 0 else 1)
-            rt.gemm(self.dgx[d], rt.w(f"{n}.kernel"), None, self.dxm, R, self.D, self.G, transb=1)
-            self._mask_rows(self.dxm, self.im[d], self.din, R, self.D, accumulate=d)
+            if drop and self.lstm:      # the GRU kernel stored its masked state sequence
+                self._mask_rows(self.h[d], self.rm[d], self.hm[d], R, self.u)
+            rt.gemm_tn(self.xm[d] if drop else self.x, self.dgx[d], rt.g(f"{n}.kernel"), gb[:self.G], R, self.D, self.G)
+            # recurrent kernel: h_prev^T dgh — the forward direction saw h[t-1], the backward direction h[t+1]
+            rt.gemm_tn(self.hm[d] if drop else self.h[d], self.dgh[d], rt.g(f"{n}.recurrent_kernel"), None if self.lstm else gb[self.G:], R, self.u,
+                       self.G, seq=self.S, shift=-1 if d == 0 else 1)
+            if drop:
+                rt.gemm(self.dgx[d], rt.w(f"{n}.kernel"), None, self.dxm, R, self.D, self.G, transb=1)
+                self._mask_rows(self.dxm, self.im[d], self.din, R, self.D, accumulate=d)
+            else:
+                rt.gemm(self.dgx[d], rt.w(f"{n}.kernel"), None, self.din, R, self.D, self.G, transb=1, accumulate=d)
         return self.din[:R]
 
 
@@ -1480,7 +1487,9 @@ class RNNBlock(_Recurrent):
     (modules.py:334-337), return_sequences=True; bidirectional -> Bidirectional(merge_mode), whose variables are the forward layer's, then the
     backward layer's (`{prefix}.fwd.*`, `{prefix}.bwd.*`; one direction: `{prefix}.*`).  With bidirectional=False merge_mode is ignored.
     GRU: kernel (D, 384), recurrent_kernel (128, 384), bias (2, 384);  LSTM: kernel (D, 512), recurrent_kernel (128, 512), bias (512,).
-    dropout_rate > 0 (a runtime whose owner accepted the library's draws): the cells' dropout and recurrent_dropout, in training (_Recurrent)."""
+    The configuration picks the row of _Recurrent's table (`lstm`, the width, dropout_rate > 0 on a runtime whose owner accepted the library's
+    draws) and the merge (`bi`, `mode`); this class owns what only some of those need: the LSTM's cell states c, the directions' output
+    gradients dh and the merged output."""
 
     def __init__(self, rt: _Rt, cfg: dict, S: int, D: int, prefix: str, B: int):
         check_rnn_config(cfg, dropout=rt.dropout, any_units=rt.any_units)
@@ -1499,76 +1508,25 @@ class RNNBlock(_Recurrent):
         self.out = e(R, self.out_dim) if self.bi else None
         self.out_shape = (self.S, self.out_dim)
 
-    def forward(self, x, B, training):
-        """x [B*S, D] (or any contiguous view of it) -> [B*S, out_dim]"""
-        rt, lib = self.rt, self.rt.lib
-        R = B * self.S
-        self.drop.begin(training)
-        if self.drop.on:
-            return self._dropped_forward(x.reshape(R, self.D), B)
-        if self.u != 128:
-            return self._wide_forward(x.reshape(R, self.D), B, training)
-        self._project(x.reshape(R, self.D), R)
-        U = self._pair([rt.w(f"{n}.recurrent_kernel") for n in self.names])
-        if self.lstm:
-            rt.ck(lib.seld_rnn_lstm_fwd(*self._pair(self.gx), *U, *self._pair(self.h), *self._pair(self.c, not training), *self._pair(self.sv, not training),
-                                        B, self.S, 128, rt.st()))
-        else:
-            brec = self._pair([rt.w(f"{n}.bias")[384:] for n in self.names])
-            rt.ck(lib.seld_rnn_gru_fwd(*self._pair(self.gx), *U, *brec, *self._pair(self.h), *self._pair(self.sv, not training), B, self.S, 128, rt.st()))
-        if not self.bi:
-            return self.h[0][:R]
-        rt.ck(lib.seld_rnn_merge_fwd(rt.p(self.h[0]), rt.p(self.h[1]), rt.p(self.out), R, 128, self.mode, rt.st()))
-        return self.out[:R]
-
-    def backward(self, dy, B):
-        """dy [B*S, out_dim]: the output's gradient (after a training forward) -> the input's gradient [B*S, D] (a buffer of this block)"""
-        rt, lib = self.rt, self.rt.lib
-        R = B * self.S
-        dy = dy.reshape(R, self.out_dim)
-        if self.drop.on:
-            return self._dropped_backward(dy, B)
-        if self.u != 128:
-            return self._wide_backward(dy, B)
-        if self.bi:
-            rt.ck(lib.seld_rnn_merge_bwd(rt.p(dy), rt.p(self.h[0]), rt.p(self.h[1]), rt.p(self.dh[0]), rt.p(self.dh[1]), R, 128, self.mode, rt.st()))
-            dh = self._pair(self.dh)
-        else:
-            self._dy = dy.contiguous()      # kept: the kernel reads it after this call returns
-            dh = (rt.p(self._dy), None)
-        U = self._pair([rt.w(f"{n}.recurrent_kernel") for n in self.names])
-        if self.lstm:
-            rt.ck(lib.seld_rnn_lstm_bwd(*dh, *self._pair(self.c), *self._pair(self.sv), *U, *self._pair(self.dgx), B, self.S, 128, rt.st()))
-        else:
-            rt.ck(lib.seld_rnn_gru_bwd(*dh, *self._pair(self.h), *self._pair(self.sv), *U, *self._pair(self.dgx), *self._pair(self.dgh), B, self.S, 128,
-                                       rt.st()))
-        return self._weight_grads(R)
-
 
 def check_gru_config(cfg: dict, stage: bool = False, dropout: bool = False, any_units: bool = False) -> None:
     """reference modules.bidirectional_GRU_block (modules.py:302-319): one layer per entry of `units`.  dropout, any_units: as
     check_rnn_config's"""
-    if dropout:
-        _recurrent_rate(cfg, "bidirectional_GRU_block")
-    elif float(cfg.get("dropout_rate", 0.0)) != 0.0:
-        raise ValueError("bidirectional_GRU_block: GRU dropout / recurrent_dropout masks exist on the fused path only (models.SeldNet), not among "
-                         "the composed path's Dropout operators: dropout_rate must be 0")
-    if any_units:
-        if not isinstance(cfg["units"], (list, tuple)) or not all(_is_gru_width(u) for u in cfg["units"]):
-            raise ValueError(f"bidirectional_GRU_block: units {cfg['units']!r}: a list of integers in {GRU_MIN_UNITS}..{GRU_MAX_UNITS}, one per layer")
-        if any(int(u) != 128 for u in cfg["units"]) and float(cfg.get("dropout_rate", 0.0) or 0.0) != 0.0:
-            raise ValueError(f"bidirectional_GRU_block: dropout_rate {cfg.get('dropout_rate')!r} at units {list(cfg['units'])!r}: the recurrences "
-                             "under dropout / recurrent_dropout (the DROP forms) are 128-unit kernels; at another width dropout_rate must be 0")
-    elif any(int(u) != 128 for u in cfg["units"]):
-        raise ValueError("the recurrence kernels are built for 128 units")
+    u = cfg["units"]
+    listed = isinstance(u, (list, tuple))
+    _check_widths_and_rate(cfg, "bidirectional_GRU_block", u if listed or not any_units else None, any_units, dropout, (
+        f"bidirectional_GRU_block: units {u!r}: a list of integers in {GRU_MIN_UNITS}..{GRU_MAX_UNITS}, one per layer",
+        "the recurrence kernels are built for 128 units", f"units {list(u)!r}" if listed else "",
+        "bidirectional_GRU_block: GRU dropout / recurrent_dropout masks exist on the fused path only (models.SeldNet), not among "
+        "the composed path's Dropout operators: dropout_rate must be 0"))
 
 
 class BidirectionalGRUBlock(_Recurrent):
-    """One layer of reference modules.bidirectional_GRU_block (modules.py:302-319) on [B*S, D]: Bidirectional(GRU(128, return_sequences=True),
-    merge_mode='mul'), the recurrences and the merge in the fused operators seld_m_gru_fwd / _bwd.  dropout_rate > 0 (a runtime whose owner
-    accepted the library's draws), in training: the cells' masks, the recurrences per direction and the 'mul' merge as its own operator
-    (_Recurrent)."""
-    lstm, bi, mode = False, True, _lib.SELD_MERGE["mul"]
+    """One layer of reference modules.bidirectional_GRU_block (modules.py:302-319) on [B*S, D]: Bidirectional(GRU(units[layer],
+    return_sequences=True), merge_mode='mul') on _Recurrent's path.  What differs from an RNN_block with the same cell: at 128 units, when no
+    dropout is drawn, the recurrences and the 'mul' merge are ONE operator (seld_m_gru_fwd / _bwd: `fusable`), so the per-direction output
+    gradients dh exist only for the other forms (dropout_rate > 0, or another width)."""
+    lstm, bi, mode, fusable = False, True, _lib.SELD_MERGE["mul"], True
     PER_LAYER_UNITS = True      # Stage passes `layer`, the block's index in the stage: its width is cfg['units'][layer]
 
     def __init__(self, rt: _Rt, cfg: dict, S: int, D: int, prefix: str, B: int, layer: int = 0):
@@ -1579,33 +1537,6 @@ class BidirectionalGRUBlock(_Recurrent):
         self.out = rt.empty(B * self.S, u)
         self.dh = [rt.empty(B * self.S, u) for _ in (0, 1)] if self.drop.rate > 0.0 or u != 128 else None
         self.out_dim, self.out_shape = u, (self.S, u)
-
-    def forward(self, x, B, training):
-        rt, p = self.rt, self.rt.p
-        R = B * self.S
-        self.drop.begin(training)
-        if self.drop.on:
-            return self._dropped_forward(x.reshape(R, self.D), B)
-        if self.u != 128:
-            return self._wide_forward(x.reshape(R, self.D), B, training)
-        self._project(x.reshape(R, self.D), R)
-        U = [p(rt.w(f"{n}.recurrent_kernel")) for n in self.names]
-        brec = [p(rt.w(f"{n}.bias")[384:]) for n in self.names]
-        rt.ck(rt.lib.seld_m_gru_fwd(p(self.gx[0]), p(self.gx[1]), *U, *brec, p(self.h[0]), p(self.h[1]), p(self.sv[0]) if training else None,
-                                    p(self.sv[1]) if training else None, p(self.out), B, self.S, 128, rt.st()))
-        return self.out[:R]
-
-    def backward(self, dy, B):
-        rt, p = self.rt, self.rt.p
-        R = B * self.S
-        if self.drop.on:
-            return self._dropped_backward(dy.reshape(R, 128), B)
-        if self.u != 128:
-            return self._wide_backward(dy.reshape(R, self.u), B)
-        U = [p(rt.w(f"{n}.recurrent_kernel")) for n in self.names]
-        rt.ck(rt.lib.seld_m_gru_bwd(p(dy), p(self.h[0]), p(self.h[1]), p(self.sv[0]), p(self.sv[1]), *U, p(self.dgx[0]), p(self.dgx[1]),
-                                    p(self.dgh[0]), p(self.dgh[1]), B, self.S, 128, rt.st()))
-        return self._weight_grads(R)
 
 
 class _SqueezeExcite:

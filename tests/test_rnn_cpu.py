@@ -260,6 +260,66 @@ def test_header_binding_and_library_agree_on_the_new_symbols(seld_lib):
         assert re.search(r"#define SELD_MERGE_%s %d\b" % (mode.upper(), v), hdr)
 
 
+# ---------------------------------------------------------------- refusal order of the eight 128-unit recurrences, without a device
+# REFUSED calls only: each returns before any HIP call, so nothing is dereferenced and no device is needed.  The rules, in order:
+#   1. units != 128 -> UNSUPPORTED;  2. a required pointer NULL, B or S < 1 -> INVALID;  3. half a second direction -> INVALID;
+#   4. S > 2^20 or B > 0x3fffffff -> UNSUPPORTED.
+# The plain forwards may leave `saved` (the LSTM: and `c`) NULL, but for every direction alike; the DROP forms require them.
+INVALID, UNSUPPORTED = -1, -2
+_pairs = lambda *stems: [f"{s}_{d}" for s in stems for d in "fb"]
+RNN_ENTRIES = {      # entry -> (argument names in call order, the *_f arguments that may be NULL)
+    "seld_rnn_lstm_fwd": (_pairs("gx", "U", "h", "c", "saved"), {"c_f", "saved_f"}),
+    "seld_rnn_lstm_bwd": (_pairs("dh", "c", "saved", "U", "dgx"), set()),
+    "seld_rnn_gru_fwd": (_pairs("gx", "U", "brec", "h", "saved"), {"saved_f"}),
+    "seld_rnn_gru_bwd": (_pairs("dh", "h", "saved", "U", "dgx", "dgh"), set()),
+    "seld_rnn_lstm_drop_fwd": (_pairs("gx", "U", "rm", "h", "c", "saved"), set()),
+    "seld_rnn_lstm_drop_bwd": (_pairs("dh", "c", "saved", "U", "rm", "dgx"), set()),
+    "seld_rnn_gru_drop_fwd": (_pairs("gx", "U", "brec", "rm", "h", "hm", "saved"), set()),
+    "seld_rnn_gru_drop_bwd": (_pairs("dh", "hm", "saved", "U", "rm", "dgx", "dgh"), set()),
+}
+
+
+@pytest.mark.parametrize("op", sorted(RNN_ENTRIES))
+def test_refusal_order_of_the_128_unit_entries(seld_lib, op):
+    import ctypes as C
+    names, optional = RNN_ENTRIES[op]
+    p = C.c_void_p(1 << 20)      # never dereferenced: every call below is refused first
+
+    def call(B=1, S=1, units=128, **over):
+        return getattr(seld_lib, op)(*[over.get(n, p) for n in names], B, S, units, None)
+
+    one = {n: None for n in names if n.endswith("_b")}      # one direction
+    req = [n for n in names if n.endswith("_f") and n not in optional]
+    for u in (0, 127, 129):      # the width first, whatever else is wrong
+        assert call(units=u) == UNSUPPORTED
+        assert call(units=u, **{req[0]: None}) == UNSUPPORTED
+        assert call(units=u, B=0) == UNSUPPORTED
+    for n in req:      # each required pointer, with two directions and with one
+        assert call(**{n: None}) == INVALID, n
+        assert call(**one, **{n: None}) == INVALID, n
+        assert call(S=(1 << 20) + 1, **{n: None}) == INVALID, n      # the pointer before the length
+    for bad in ({"B": 0}, {"B": -1}, {"S": 0}, {"S": -1}):
+        assert call(**bad) == INVALID, bad
+        assert call(**one, **bad) == INVALID, bad
+    for n in one:      # half a second direction: one *_b argument missing, and one *_b argument alone
+        assert call(**{n: None}) == INVALID, n
+        if n != names[1]:      # names[1] (gx_b / dh_b) decides how many directions there are
+            assert call(**{m: None for m in one if m != n}) == INVALID, n
+        assert call(S=(1 << 20) + 1, **{n: None}) == INVALID, n
+    for n in sorted(optional):      # a plain forward: saved (and c) for one direction only, or saved without c
+        assert call(**{n: None}) == INVALID, n
+        assert call(**{n[:-1] + "b": None}) == INVALID, n
+        if len(optional) == 2:
+            assert call(**one, **{n: None}) == INVALID, n
+    if "drop" in op:      # the DROP forms always save
+        assert call(saved_f=None) == INVALID and call(saved_f=None, saved_b=None) == INVALID
+        assert call(**one, saved_f=None) == INVALID
+    for kw in ({}, one):
+        assert call(S=(1 << 20) + 1, **kw) == UNSUPPORTED
+        assert call(B=(1 << 30), **kw) == UNSUPPORTED
+        assert call(B=(1 << 30), S=(1 << 20) + 1, **kw) == UNSUPPORTED
+
+
 # ---------------------------------------------------------------- fp32 against fp64 on the GPU cases
 def _margin(name, a32, a64):
     e = rel_err(a32, a64)
