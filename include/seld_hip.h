@@ -875,7 +875,29 @@ int seld_attn_drop_fwd(const float* Q, const float* K, const float* V, int ldq, 
 int seld_attn_drop_bwd(const float* Q, const float* K, const float* V, int ldq, int ldk, int ldv, const float* O, const float* dO, const float* lse,
                        float* dQ, float* dK, float* dV, int lddq, int lddk, int lddv, float* scratch, int B, int S, int H, int d, float scale,
                        float rate, uint64_t seed, unsigned layer, unsigned step, void* stream);
-/*   seld_ln_fwd     tf.keras.layers.LayerNormalization over the last axis of [rows, C] (modules.py:395, 403: biased variance, eps inside the
+/*   seld_attnw_*    the five entries above for ANY head width d in 1 .. 64 (the reference's search spaces carry key_dim 2, 3, 4, 6, 12: nas_seldnet.py
+ *                   59-76), with the same arguments.  Layout as seld_attn_*: head h = columns h*d .. h*d+d-1, row strides >= H*d, O / dO [B*S, H*d]
+ *                   contiguous; single dwords move, so nothing beyond 4-byte alignment is assumed of a pointer, a stride or H*d.  A d that is no
+ *                   multiple of 8 runs the same three kernels at the padded width dp = 8 ceil(d / 8) with the columns dd >= d read as zeros and never
+ *                   written: a zero column adds exact zeros to every product chain, so the values are those of seld_attn_* at dp on zero-padded
+ *                   operands with the same `scale` (bit for bit; a zero's sign aside).  A multiple of 8 launches exactly what seld_attn_* launches.
+ *                   The dropout mask is a function of (seed, step, layer, b, h, n, m) and does not see d.  As seld_attn_*: no atomics, no [B,H,S,S]
+ *                   tensor, two runs are bit-identical, O is bit-identical with and without lse, rate 0 launches what seld_attnw_fwd / _bwd launch.
+ *                   scratch: seld_attnw_bwd_scratch(B, S, H, d) floats (B*H*S).
+ *   SELD_ERR_UNSUPPORTED (the scratch size -1) for d outside 1 .. 64 before any other check; then the checks of seld_attn_* / seld_attn_drop_* in
+ *   their order, B * H * S beyond 2^32 at rate > 0 included.  seld_attn_* themselves keep refusing a d that is no multiple of 8. */
+int seld_attnw_fwd(const float* Q, const float* K, const float* V, int ldq, int ldk, int ldv, float* O, float* lse, int B, int S, int H, int d,
+                   float scale, void* stream);
+int64_t seld_attnw_bwd_scratch(int B, int S, int H, int d);
+int seld_attnw_bwd(const float* Q, const float* K, const float* V, int ldq, int ldk, int ldv, const float* O, const float* dO, const float* lse,
+                   float* dQ, float* dK, float* dV, int lddq, int lddk, int lddv, float* scratch, int B, int S, int H, int d, float scale,
+                   void* stream);
+int seld_attnw_drop_fwd(const float* Q, const float* K, const float* V, int ldq, int ldk, int ldv, float* O, float* lse, int B, int S, int H, int d,
+                        float scale, float rate, uint64_t seed, unsigned layer, unsigned step, void* stream);
+int seld_attnw_drop_bwd(const float* Q, const float* K, const float* V, int ldq, int ldk, int ldv, const float* O, const float* dO, const float* lse,
+                        float* dQ, float* dK, float* dV, int lddq, int lddk, int lddv, float* scratch, int B, int S, int H, int d, float scale,
+                        float rate, uint64_t seed, unsigned layer, unsigned step, void* stream);
+/*   seld_ln_fwd    tf.keras.layers.LayerNormalization over the last axis of [rows, C] (modules.py:395, 403: biased variance, eps inside the
  *                   square root): y = xhat gamma + beta, xhat = (z - mean z) / sqrt(var z + eps), z = x + r — the residual r may be NULL, so
  *                   LayerNormalization()(x + attn) is one pass.  xhat [rows, C] and rstd [rows] are saved for the backward (both may be NULL
  *                   at inference).  Any C >= 1.

@@ -261,6 +261,11 @@ SIGNATURES = {
     "seld_attn_bwd": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _I, _I, _I, _I, _F, _P]),
     "seld_attn_drop_fwd": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _I, _I, _I, _I, _F, _F, _U64, _U, _U, _P]),
     "seld_attn_drop_bwd": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _I, _I, _I, _I, _F, _F, _U64, _U, _U, _P]),
+    "seld_attnw_fwd": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _I, _I, _I, _I, _F, _P]),
+    "seld_attnw_bwd_scratch": (_L, [_I, _I, _I, _I]),
+    "seld_attnw_bwd": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _I, _I, _I, _I, _F, _P]),
+    "seld_attnw_drop_fwd": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _I, _I, _I, _I, _F, _F, _U64, _U, _U, _P]),
+    "seld_attnw_drop_bwd": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _I, _I, _I, _I, _F, _F, _U64, _U, _U, _P]),
     "seld_ln_fwd": (_I, [_P, _P, _P, _P, _F, _P, _P, _P, _L, _I, _P]),
     "seld_ln_scratch": (_L, [_L, _I]),
     "seld_ln_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _P]),

@@ -25,6 +25,10 @@
 // of one group and the SAME 16 queries: each lane draws the words of four of them (register 4 g + (lane & 3), g = 0 .. 3) and the quad exchanges
 // the keep bits by DPP — four Philox calls per 32 x 32 block and lane there too, in place of one per element.
 // (b H + h) S + n must fit 32 bits: B H S <= 2^32, checked by the entry points.
+//
+// Any head width (seld_attnw_*: the same five entries for d in 1 .. 64).  A d that is no multiple of 8 runs the same kernels at D = 8 ceil(d / 8)
+// with RAG on: the columns dd >= d are loaded as zeros and never stored (attn_tile.h), so the values are those of seld_attn_* at D on zero-padded
+// operands, and the mask, which never saw D, is the same.  A multiple of 8 launches what seld_attn_* launches.
 #include "attn_tile.h"
 
 namespace {
@@ -62,11 +66,14 @@ __device__ __forceinline__ void attn_mask16(const AttnDrop& dr, int key0, int hi
     }
 }
 
-template <int D, bool DROP>
+// Each kernel is <D, DROP, RAG>.  RAG off: the head is D columns wide (the run-time d is not read).  RAG on (seld_attnw_*): the head is d < D columns
+// wide in memory, D = 8 ceil(d / 8), and the steps that touch global memory take d (attn_tile.h).  w = the head's width in memory.
+template <int D, bool DROP, bool RAG>
 __global__ __launch_bounds__(128) void attn_fwd_kernel(const float* __restrict__ Q, const float* __restrict__ K, const float* __restrict__ V, int ldq,
                                                        int ldk, int ldv, float* __restrict__ O, float* __restrict__ lse, int S, int H, float scale,
-                                                       int nqt, AttnDrop dr) {
+                                                       int nqt, AttnDrop dr, int d) {
     constexpr int LD = D + 1, NB = (D + 31) / 32;
+    const int w = RAG ? d : D;
     __shared__ float Ks[ATTN_TILE * LD], Vs[ATTN_TILE * LD];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 31, hi = lane >> 5;
     const int qt = blockIdx.x % nqt, bh = blockIdx.x / nqt, h = bh % H, b = bh / H;
@@ -74,15 +81,15 @@ __global__ __launch_bounds__(128) void attn_fwd_kernel(const float* __restrict__
     const bool qok = q < S;
     const size_t row0 = (size_t)b * S;
     float qf[D / 2];
-    load_frag<D>(Q, ldq, row0 + (qok ? q : 0), h * D, qok, hi, nullptr, scale, qf);
+    load_frag<D, RAG>(Q, ldq, row0 + (qok ? q : 0), h * w, qok, hi, nullptr, scale, qf, d);
     f32x16 o[NB];
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) o[nb] = zero16();
     float m = -INFINITY, l = 0.f;
     for (int k0 = 0; k0 < S; k0 += ATTN_TILE) {
         __syncthreads();
-        load_rows<D>(K, ldk, row0, k0, ATTN_TILE, S, h * D, 1.f, Ks);
-        load_rows<D>(V, ldv, row0, k0, ATTN_TILE, S, h * D, 1.f, Vs);
+        load_rows<D, RAG>(K, ldk, row0, k0, ATTN_TILE, S, h * w, 1.f, Ks, d);
+        load_rows<D, RAG>(V, ldv, row0, k0, ATTN_TILE, S, h * w, 1.f, Vs, d);
         __syncthreads();
         for (int kb = 0; kb < 2 && k0 + kb * 32 < S; ++kb) {
             f32x16 s = logits<D>(Ks, kb * 32 + li, hi, qf);
@@ -96,17 +103,18 @@ __global__ __launch_bounds__(128) void attn_fwd_kernel(const float* __restrict__
             accum_t<D, true>(o, Vs + kb * 32 * LD, s, li, hi, alpha);
         }
     }
-    store_t<D>(o, O, H * D, row0 + (qok ? q : 0), h * D, qok, hi, 1.f / l);
+    store_t<D, RAG>(o, O, H * w, row0 + (qok ? q : 0), h * w, qok, hi, 1.f / l, d);
     if (lse && qok && hi == 0) lse[(size_t)bh * S + q] = m + logf(l);
 }
 
 // dQ, and delta[b][h][q] = rowsum(dO * O) for the dK / dV kernel that follows.  Same tiling as the forward.
-template <int D, bool DROP>
+template <int D, bool DROP, bool RAG>
 __global__ __launch_bounds__(128) void attn_bwd_dq_kernel(const float* __restrict__ Q, const float* __restrict__ K, const float* __restrict__ V, int ldq,
                                                           int ldk, int ldv, const float* __restrict__ O, const float* __restrict__ dO,
                                                           const float* __restrict__ lse, float* __restrict__ dQ, int lddq, float* __restrict__ delta,
-                                                          int S, int H, float scale, int nqt, AttnDrop dr) {
+                                                          int S, int H, float scale, int nqt, AttnDrop dr, int d) {
     constexpr int LD = D + 1, NB = (D + 31) / 32;
+    const int w = RAG ? d : D;
     __shared__ float Ks[ATTN_TILE * LD], Vs[ATTN_TILE * LD];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 31, hi = lane >> 5;
     const int qt = blockIdx.x % nqt, bh = blockIdx.x / nqt, h = bh % H, b = bh / H;
@@ -114,9 +122,9 @@ __global__ __launch_bounds__(128) void attn_bwd_dq_kernel(const float* __restric
     const bool qok = q < S;
     const size_t row0 = (size_t)b * S, row = row0 + (qok ? q : 0);
     float qf[D / 2], dof[D / 2];
-    load_frag<D>(Q, ldq, row, h * D, qok, hi, nullptr, scale, qf);
-    load_frag<D>(dO, H * D, row, h * D, qok, hi, nullptr, 1.f, dof);
-    const float dl = delta_rowsum<D>(dof, O, H * D, row, h * D, qok, hi);
+    load_frag<D, RAG>(Q, ldq, row, h * w, qok, hi, nullptr, scale, qf, d);
+    load_frag<D, RAG>(dO, H * w, row, h * w, qok, hi, nullptr, 1.f, dof, d);
+    const float dl = delta_rowsum<D, RAG>(dof, O, H * w, row, h * w, qok, hi, d);
     if (qok && hi == 0) delta[(size_t)bh * S + q] = dl;
     const float lq = qok ? lse[(size_t)bh * S + q] : INFINITY;      // a row past S: p = exp(-inf) = 0
     f32x16 dq[NB];
@@ -124,8 +132,8 @@ __global__ __launch_bounds__(128) void attn_bwd_dq_kernel(const float* __restric
     for (int nb = 0; nb < NB; ++nb) dq[nb] = zero16();
     for (int k0 = 0; k0 < S; k0 += ATTN_TILE) {
         __syncthreads();
-        load_rows<D>(K, ldk, row0, k0, ATTN_TILE, S, h * D, 1.f, Ks);
-        load_rows<D>(V, ldv, row0, k0, ATTN_TILE, S, h * D, 1.f, Vs);
+        load_rows<D, RAG>(K, ldk, row0, k0, ATTN_TILE, S, h * w, 1.f, Ks, d);
+        load_rows<D, RAG>(V, ldv, row0, k0, ATTN_TILE, S, h * w, 1.f, Vs, d);
         __syncthreads();
         for (int kb = 0; kb < 2 && k0 + kb * 32 < S; ++kb) {
             f32x16 s = logits<D>(Ks, kb * 32 + li, hi, qf);
@@ -140,16 +148,17 @@ __global__ __launch_bounds__(128) void attn_bwd_dq_kernel(const float* __restric
             accum_t<D>(dq, Ks + kb * 32 * LD, s, li, hi);
         }
     }
-    store_t<D>(dq, dQ, lddq, row, h * D, qok, hi, scale);
+    store_t<D, RAG>(dq, dQ, lddq, row, h * w, qok, hi, scale, d);
 }
 
 // dK and dV: a workgroup owns 64 keys of one (batch, head) (32 per wave, K and V fragments in registers) and sweeps the query tiles
-template <int D, bool DROP>
+template <int D, bool DROP, bool RAG>
 __global__ __launch_bounds__(128) void attn_bwd_dkv_kernel(const float* __restrict__ Q, const float* __restrict__ K, const float* __restrict__ V, int ldq,
                                                            int ldk, int ldv, const float* __restrict__ dO, const float* __restrict__ lse,
                                                            const float* __restrict__ delta, float* __restrict__ dK, float* __restrict__ dV, int lddk,
-                                                           int lddv, int S, int H, float scale, int nkt, AttnDrop dr) {
+                                                           int lddv, int S, int H, float scale, int nkt, AttnDrop dr, int d) {
     constexpr int LD = D + 1, NB = (D + 31) / 32;
+    const int w = RAG ? d : D;
     __shared__ float Qs[ATTN_TILE * LD], Gs[ATTN_TILE * LD], ls[ATTN_TILE], ds_[ATTN_TILE];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 31, hi = lane >> 5;
     const int kt = blockIdx.x % nkt, bh = blockIdx.x / nkt, h = bh % H, b = bh / H;
@@ -157,15 +166,15 @@ __global__ __launch_bounds__(128) void attn_bwd_dkv_kernel(const float* __restri
     const bool kok = key < S;
     const size_t row0 = (size_t)b * S, row = row0 + (kok ? key : 0);
     float kf[D / 2], vf[D / 2];
-    load_frag<D>(K, ldk, row, h * D, kok, hi, nullptr, 1.f, kf);
-    load_frag<D>(V, ldv, row, h * D, kok, hi, nullptr, 1.f, vf);
+    load_frag<D, RAG>(K, ldk, row, h * w, kok, hi, nullptr, 1.f, kf, d);
+    load_frag<D, RAG>(V, ldv, row, h * w, kok, hi, nullptr, 1.f, vf, d);
     f32x16 dk[NB], dv[NB];
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) { dk[nb] = zero16(); dv[nb] = zero16(); }
     for (int q0 = 0; q0 < S; q0 += ATTN_TILE) {
         __syncthreads();
-        load_rows<D>(Q, ldq, row0, q0, ATTN_TILE, S, h * D, scale, Qs);
-        load_rows<D>(dO, H * D, row0, q0, ATTN_TILE, S, h * D, 1.f, Gs);
+        load_rows<D, RAG>(Q, ldq, row0, q0, ATTN_TILE, S, h * w, scale, Qs, d);
+        load_rows<D, RAG>(dO, H * w, row0, q0, ATTN_TILE, S, h * w, 1.f, Gs, d);
         load_lse_delta(lse, delta, (size_t)bh * S, q0, ATTN_TILE, S, ls, ds_);
         __syncthreads();
         for (int qb = 0; qb < 2 && q0 + qb * 32 < S; ++qb) {
@@ -218,8 +227,8 @@ __global__ __launch_bounds__(128) void attn_bwd_dkv_kernel(const float* __restri
             }
         }
     }
-    store_t<D>(dk, dK, lddk, row, h * D, kok, hi, 1.f);
-    store_t<D>(dv, dV, lddv, row, h * D, kok, hi, 1.f);
+    store_t<D, RAG>(dk, dK, lddk, row, h * w, kok, hi, 1.f, d);
+    store_t<D, RAG>(dv, dV, lddv, row, h * w, kok, hi, 1.f, d);
 }
 
 // ---- LayerNormalization over the last axis of [rows, C] (Keras: biased variance, eps inside the square root).  One wave per row, any C.
@@ -290,9 +299,11 @@ __global__ __launch_bounds__(256) void ln_bwd_fold_kernel(const float* __restric
 }
 inline int ln_blocks(int64_t rows) { const int64_t b = (rows + 15) / 16; return (int)(b < LN_MAX_BLOCKS ? b : LN_MAX_BLOCKS); }
 
-// launch `kern`<D_, drop> on `grid` workgroups (static LDS)
-#define AT_LAUNCH(D_, kern, drop, grid, st, ...) hipLaunchKernelGGL((kern<D_, drop>), dim3(grid), dim3(128), 0, st, __VA_ARGS__)
-#define AT_DISPATCH(kern, drop, d, grid, st, ...) ATTN_DISPATCH_D(d, AT_LAUNCH, kern, drop, grid, st, __VA_ARGS__)
+// launch `kern`<D_, drop, rag> on `grid` workgroups (static LDS)
+#define AT_LAUNCH(D_, kern, drop, rag, grid, st, ...) hipLaunchKernelGGL((kern<D_, drop, rag>), dim3(grid), dim3(128), 0, st, __VA_ARGS__)
+#define AT_DISPATCH(kern, drop, d, grid, st, ...) ATTN_DISPATCH_D(d, AT_LAUNCH, kern, drop, false, grid, st, __VA_ARGS__, d)
+// the ragged form: `kern`<8 ceil(d / 8), drop, true>
+#define ATW_DISPATCH(kern, drop, d, grid, st, ...) ATTN_DISPATCH_D(((d) + 7) & ~7, AT_LAUNCH, kern, drop, true, grid, st, __VA_ARGS__, d)
 
 inline bool rate_ok(float rate) { return rate >= 0.f && rate < 1.f; }      // (a NaN fails both)
 // the mask counter's last word (b H + h) S + n is 32 bits wide
@@ -301,29 +312,37 @@ inline AttnDrop at_drop(float rate, uint64_t seed, unsigned layer, unsigned step
     return AttnDrop{rate, 1.f / (1.f - rate), (unsigned)seed, (unsigned)(seed >> 32), layer, step};
 }
 
-// seld_attn_fwd (rate 0: the mask-free instantiations, whatever seed / layer / step) and seld_attn_drop_fwd
-int attn_fwd_impl(const float* Q, const float* K, const float* V, int ldq, int ldk, int ldv, float* O, float* lse, int B, int S, int H, int d,
+// seld_attn_fwd (rate 0: the mask-free instantiations, whatever seed / layer / step) and seld_attn_drop_fwd; any_d: seld_attnw_* — d in 1..64,
+// a multiple of 8 launches what seld_attn_* launches and any other d the ragged kernels
+int attn_fwd_impl(bool any_d, const float* Q, const float* K, const float* V, int ldq, int ldk, int ldv, float* O, float* lse, int B, int S, int H, int d,
                   float scale, float rate, uint64_t seed, unsigned layer, unsigned step, void* stream) {
-    if (!d_ok(d)) return SELD_ERR_UNSUPPORTED;
+    if (!(any_d ? dw_ok(d) : d_ok(d))) return SELD_ERR_UNSUPPORTED;
     if (!Q || !K || !V || !O || B < 1 || S < 1 || H < 1 || !ld_ok(ldq, H, d) || !ld_ok(ldk, H, d) || !ld_ok(ldv, H, d) || !rate_ok(rate))
         return SELD_ERR_INVALID;
     const int64_t grid = tile_grid(B, S, H);
     if (grid < 0) return SELD_ERR_UNSUPPORTED;
     const int nt = (int)(grid / B / H);
     const AttnDrop dr = at_drop(rate, seed, layer, step);
+    const bool rag = d % 8 != 0;
     if (rate > 0.f) {
         if (!ctr_ok(B, S, H)) return SELD_ERR_UNSUPPORTED;
-        AT_DISPATCH(attn_fwd_kernel, true, d, (unsigned)grid, (hipStream_t)stream, Q, K, V, ldq, ldk, ldv, O, lse, S, H, scale, nt, dr);
+        if (rag) {
+            ATW_DISPATCH(attn_fwd_kernel, true, d, (unsigned)grid, (hipStream_t)stream, Q, K, V, ldq, ldk, ldv, O, lse, S, H, scale, nt, dr);
+        } else {
+            AT_DISPATCH(attn_fwd_kernel, true, d, (unsigned)grid, (hipStream_t)stream, Q, K, V, ldq, ldk, ldv, O, lse, S, H, scale, nt, dr);
+        }
+    } else if (rag) {
+        ATW_DISPATCH(attn_fwd_kernel, false, d, (unsigned)grid, (hipStream_t)stream, Q, K, V, ldq, ldk, ldv, O, lse, S, H, scale, nt, dr);
     } else {
         AT_DISPATCH(attn_fwd_kernel, false, d, (unsigned)grid, (hipStream_t)stream, Q, K, V, ldq, ldk, ldv, O, lse, S, H, scale, nt, dr);
     }
     return ok();
 }
 
-int attn_bwd_impl(const float* Q, const float* K, const float* V, int ldq, int ldk, int ldv, const float* O, const float* dO, const float* lse,
+int attn_bwd_impl(bool any_d, const float* Q, const float* K, const float* V, int ldq, int ldk, int ldv, const float* O, const float* dO, const float* lse,
                   float* dQ, float* dK, float* dV, int lddq, int lddk, int lddv, float* scratch, int B, int S, int H, int d, float scale,
                   float rate, uint64_t seed, unsigned layer, unsigned step, void* stream) {
-    if (!d_ok(d)) return SELD_ERR_UNSUPPORTED;
+    if (!(any_d ? dw_ok(d) : d_ok(d))) return SELD_ERR_UNSUPPORTED;
     if (!Q || !K || !V || !O || !dO || !lse || !dQ || !dK || !dV || !scratch || B < 1 || S < 1 || H < 1 || !ld_ok(ldq, H, d) || !ld_ok(ldk, H, d) ||
         !ld_ok(ldv, H, d) || !ld_ok(lddq, H, d) || !ld_ok(lddk, H, d) || !ld_ok(lddv, H, d) || !rate_ok(rate))
         return SELD_ERR_INVALID;
@@ -331,12 +350,25 @@ int attn_bwd_impl(const float* Q, const float* K, const float* V, int ldq, int l
     if (grid < 0) return SELD_ERR_UNSUPPORTED;
     const int nt = (int)(grid / B / H);
     const AttnDrop dr = at_drop(rate, seed, layer, step);
+    const bool rag = d % 8 != 0;
     if (rate > 0.f) {
         if (!ctr_ok(B, S, H)) return SELD_ERR_UNSUPPORTED;
+        if (rag) {
+            ATW_DISPATCH(attn_bwd_dq_kernel, true, d, (unsigned)grid, (hipStream_t)stream, Q, K, V, ldq, ldk, ldv, O, dO, lse, dQ, lddq, scratch, S, H,
+                         scale, nt, dr);
+            ATW_DISPATCH(attn_bwd_dkv_kernel, true, d, (unsigned)grid, (hipStream_t)stream, Q, K, V, ldq, ldk, ldv, dO, lse, scratch, dK, dV, lddk, lddv, S,
+                         H, scale, nt, dr);
+            return ok();
+        }
         AT_DISPATCH(attn_bwd_dq_kernel, true, d, (unsigned)grid, (hipStream_t)stream, Q, K, V, ldq, ldk, ldv, O, dO, lse, dQ, lddq, scratch, S, H, scale,
                     nt, dr);
         AT_DISPATCH(attn_bwd_dkv_kernel, true, d, (unsigned)grid, (hipStream_t)stream, Q, K, V, ldq, ldk, ldv, dO, lse, scratch, dK, dV, lddk, lddv, S, H,
                     scale, nt, dr);
+    } else if (rag) {
+        ATW_DISPATCH(attn_bwd_dq_kernel, false, d, (unsigned)grid, (hipStream_t)stream, Q, K, V, ldq, ldk, ldv, O, dO, lse, dQ, lddq, scratch, S, H,
+                     scale, nt, dr);
+        ATW_DISPATCH(attn_bwd_dkv_kernel, false, d, (unsigned)grid, (hipStream_t)stream, Q, K, V, ldq, ldk, ldv, dO, lse, scratch, dK, dV, lddk, lddv, S,
+                     H, scale, nt, dr);
     } else {
         AT_DISPATCH(attn_bwd_dq_kernel, false, d, (unsigned)grid, (hipStream_t)stream, Q, K, V, ldq, ldk, ldv, O, dO, lse, dQ, lddq, scratch, S, H, scale,
                     nt, dr);
@@ -352,7 +384,7 @@ extern "C" {
 
 int seld_attn_fwd(const float* Q, const float* K, const float* V, int ldq, int ldk, int ldv, float* O, float* lse, int B, int S, int H, int d,
                   float scale, void* stream) {
-    return attn_fwd_impl(Q, K, V, ldq, ldk, ldv, O, lse, B, S, H, d, scale, 0.f, 0, 0, 0, stream);
+    return attn_fwd_impl(false, Q, K, V, ldq, ldk, ldv, O, lse, B, S, H, d, scale, 0.f, 0, 0, 0, stream);
 }
 
 /* floats of caller scratch seld_attn_bwd takes: delta[b][h][q] = rowsum(dO * O) */
@@ -364,19 +396,48 @@ int64_t seld_attn_bwd_scratch(int B, int S, int H, int d) {
 int seld_attn_bwd(const float* Q, const float* K, const float* V, int ldq, int ldk, int ldv, const float* O, const float* dO, const float* lse,
                   float* dQ, float* dK, float* dV, int lddq, int lddk, int lddv, float* scratch, int B, int S, int H, int d, float scale,
                   void* stream) {
-    return attn_bwd_impl(Q, K, V, ldq, ldk, ldv, O, dO, lse, dQ, dK, dV, lddq, lddk, lddv, scratch, B, S, H, d, scale, 0.f, 0, 0, 0, stream);
+    return attn_bwd_impl(false, Q, K, V, ldq, ldk, ldv, O, dO, lse, dQ, dK, dV, lddq, lddk, lddv, scratch, B, S, H, d, scale, 0.f, 0, 0, 0, stream);
 }
 
 /* the same with the probabilities dropped (header comment): rate 0 launches exactly what seld_attn_fwd / _bwd launch */
 int seld_attn_drop_fwd(const float* Q, const float* K, const float* V, int ldq, int ldk, int ldv, float* O, float* lse, int B, int S, int H, int d,
                        float scale, float rate, uint64_t seed, unsigned layer, unsigned step, void* stream) {
-    return attn_fwd_impl(Q, K, V, ldq, ldk, ldv, O, lse, B, S, H, d, scale, rate, seed, layer, step, stream);
+    return attn_fwd_impl(false, Q, K, V, ldq, ldk, ldv, O, lse, B, S, H, d, scale, rate, seed, layer, step, stream);
 }
 
 int seld_attn_drop_bwd(const float* Q, const float* K, const float* V, int ldq, int ldk, int ldv, const float* O, const float* dO, const float* lse,
                        float* dQ, float* dK, float* dV, int lddq, int lddk, int lddv, float* scratch, int B, int S, int H, int d, float scale,
                        float rate, uint64_t seed, unsigned layer, unsigned step, void* stream) {
-    return attn_bwd_impl(Q, K, V, ldq, ldk, ldv, O, dO, lse, dQ, dK, dV, lddq, lddk, lddv, scratch, B, S, H, d, scale, rate, seed, layer, step,
+    return attn_bwd_impl(false, Q, K, V, ldq, ldk, ldv, O, dO, lse, dQ, dK, dV, lddq, lddk, lddv, scratch, B, S, H, d, scale, rate, seed, layer, step,
+                         stream);
+}
+
+/* seld_attnw_*: the five entries above for any head width d in 1..64 (header comment of attn_tile.h); a multiple of 8 launches what they launch */
+int seld_attnw_fwd(const float* Q, const float* K, const float* V, int ldq, int ldk, int ldv, float* O, float* lse, int B, int S, int H, int d,
+                   float scale, void* stream) {
+    return attn_fwd_impl(true, Q, K, V, ldq, ldk, ldv, O, lse, B, S, H, d, scale, 0.f, 0, 0, 0, stream);
+}
+
+int64_t seld_attnw_bwd_scratch(int B, int S, int H, int d) {
+    if (!dw_ok(d) || B < 1 || S < 1 || H < 1 || (int64_t)H * d > 0x7fffffff || tile_grid(B, S, H) < 0) return -1;      // what seld_attnw_bwd refuses
+    return (int64_t)B * H * S;
+}
+
+int seld_attnw_bwd(const float* Q, const float* K, const float* V, int ldq, int ldk, int ldv, const float* O, const float* dO, const float* lse,
+                   float* dQ, float* dK, float* dV, int lddq, int lddk, int lddv, float* scratch, int B, int S, int H, int d, float scale,
+                   void* stream) {
+    return attn_bwd_impl(true, Q, K, V, ldq, ldk, ldv, O, dO, lse, dQ, dK, dV, lddq, lddk, lddv, scratch, B, S, H, d, scale, 0.f, 0, 0, 0, stream);
+}
+
+int seld_attnw_drop_fwd(const float* Q, const float* K, const float* V, int ldq, int ldk, int ldv, float* O, float* lse, int B, int S, int H, int d,
+                        float scale, float rate, uint64_t seed, unsigned layer, unsigned step, void* stream) {
+    return attn_fwd_impl(true, Q, K, V, ldq, ldk, ldv, O, lse, B, S, H, d, scale, rate, seed, layer, step, stream);
+}
+
+int seld_attnw_drop_bwd(const float* Q, const float* K, const float* V, int ldq, int ldk, int ldv, const float* O, const float* dO, const float* lse,
+                        float* dQ, float* dK, float* dV, int lddq, int lddk, int lddv, float* scratch, int B, int S, int H, int d, float scale,
+                        float rate, uint64_t seed, unsigned layer, unsigned step, void* stream) {
+    return attn_bwd_impl(true, Q, K, V, ldq, ldk, ldv, O, dO, lse, dQ, dK, dV, lddq, lddk, lddv, scratch, B, S, H, d, scale, rate, seed, layer, step,
                          stream);
 }
 

@@ -15,6 +15,12 @@
 // [key = row][dd = lane] reads are consecutive addresses.
 //
 // In every function: li = lane & 31, hi = lane >> 5; a workgroup is 128 threads (two waves of 32 rows each).
+//
+// Ragged head widths (RAG, seld_attnw_* of attention.hip): a head of d columns, d no multiple of 8, runs the D = 8 ceil(d / 8) instantiation with
+// the run-time d in the steps that touch global memory — load_frag and load_rows put zeros in columns dd >= d, store_t skips them, delta_rowsum
+// reads only real columns.  The LDS tiles, the fragments and every MFMA chain keep their D columns: a zero column adds exact zeros, so the values
+// are those of the D-wide kernel on zero-padded operands.  RAG is a template parameter (default off) for the reason BIAS is one below: the
+// instantiations without it keep their code, instruction for instruction.  Single dwords move, so nothing beyond 4-byte alignment is assumed.
 #pragma once
 #include "common.h"
 #include <math.h>
@@ -26,14 +32,14 @@ namespace attn_tile {
 __device__ __forceinline__ float xhalf(float v) { return __shfl_xor(v, 32, 64); }
 
 // the lane's fragment of row `row` (valid: ok) of a view: f[s] = (row[2 s + hi] + bias[2 s + hi]) * mul; bias may be NULL
-template <int D>
+template <int D, bool RAG = false>
 __device__ __forceinline__ void load_frag(const float* __restrict__ src, int ld, size_t row, int col0, bool ok, int hi, const float* __restrict__ bias,
-                                          float mul, float (&f)[D / 2]) {
+                                          float mul, float (&f)[D / 2], int d = D) {
     const float* p = src + row * (size_t)ld + col0 + hi;
 #pragma unroll
     for (int s = 0; s < D / 2; ++s) {
         float v = 0.f;
-        if (ok) {
+        if (ok && (!RAG || 2 * s + hi < d)) {
             v = p[2 * s];
             if (bias) v += bias[col0 + hi + 2 * s];
             v *= mul;
@@ -43,9 +49,9 @@ __device__ __forceinline__ void load_frag(const float* __restrict__ src, int ld,
 }
 
 // out^T[dd][lane's row] accumulators -> out[row][col0 + dd] * mul
-template <int D>
+template <int D, bool RAG = false>
 __device__ __forceinline__ void store_t(const f32x16 (&acc)[(D + 31) / 32], float* __restrict__ out, int ld, size_t row, int col0, bool ok, int hi,
-                                        float mul) {
+                                        float mul, int d = D) {
     if (!ok) return;
     float* p = out + row * (size_t)ld + col0;
 #pragma unroll
@@ -53,21 +59,21 @@ __device__ __forceinline__ void store_t(const f32x16 (&acc)[(D + 31) / 32], floa
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int dd = nb * 32 + mfma_row(r, hi);
-            if (dd < D) p[dd] = acc[nb][r] * mul;
+            if (dd < D && (!RAG || dd < d)) p[dd] = acc[nb][r] * mul;
         }
 }
 
 // rows r0 .. r0 + n - 1 of one head of a [B*S, ld] view (BIAS: + bias[col0 + dd]; then * mul, the query's 1 / sqrt(key_dim)) -> LDS [n][D + 1];
 // rows outside [0, S) as zeros.  Called through the two load_rows overloads below.  BIAS is a template parameter, not a NULL test: a run-time
 // `if (bias)` inside this loop changed the code of half the attention.hip kernels, this form leaves the loader's users as they were
-template <int D, bool BIAS>
+template <int D, bool BIAS, bool RAG>
 __device__ __forceinline__ void load_rows_impl(const float* __restrict__ src, int ld, size_t row0, int r0, int n, int S, int col0,
-                                               const float* __restrict__ bias, float mul, float* dst) {
+                                               const float* __restrict__ bias, float mul, float* dst, int d) {
     for (int e = threadIdx.x; e < n * D; e += 128) {
         const int rr = e / D, dd = e - rr * D;
         const int r = r0 + rr;
         float v = 0.f;
-        if (r >= 0 && r < S) {
+        if (r >= 0 && r < S && (!RAG || dd < d)) {
             v = src[(row0 + r) * (size_t)ld + col0 + dd];
             if constexpr (BIAS) v += bias[col0 + dd];
             v *= mul;
@@ -75,14 +81,15 @@ __device__ __forceinline__ void load_rows_impl(const float* __restrict__ src, in
         dst[rr * (D + 1) + dd] = v;
     }
 }
-template <int D>
-__device__ __forceinline__ void load_rows(const float* __restrict__ src, int ld, size_t row0, int r0, int n, int S, int col0, float mul, float* dst) {
-    load_rows_impl<D, false>(src, ld, row0, r0, n, S, col0, nullptr, mul, dst);
+template <int D, bool RAG = false>
+__device__ __forceinline__ void load_rows(const float* __restrict__ src, int ld, size_t row0, int r0, int n, int S, int col0, float mul, float* dst,
+                                          int d = D) {
+    load_rows_impl<D, false, RAG>(src, ld, row0, r0, n, S, col0, nullptr, mul, dst, d);
 }
-template <int D>      // with a bias (not NULL)
+template <int D, bool RAG = false>      // with a bias (not NULL)
 __device__ __forceinline__ void load_rows(const float* __restrict__ src, int ld, size_t row0, int r0, int n, int S, int col0,
-                                          const float* __restrict__ bias, float mul, float* dst) {
-    load_rows_impl<D, true>(src, ld, row0, r0, n, S, col0, bias, mul, dst);
+                                          const float* __restrict__ bias, float mul, float* dst, int d = D) {
+    load_rows_impl<D, true, RAG>(src, ld, row0, r0, n, S, col0, bias, mul, dst, d);
 }
 
 // lse / delta of queries q0 .. q0 + n - 1 of one (batch, head) (base = its first element) -> LDS; a row past S gets lse = inf: p = exp(-inf) = 0
@@ -151,12 +158,13 @@ __device__ __forceinline__ void accum_t(f32x16 (&acc)[(D + 31) / 32], const floa
 }
 
 // the dQ kernels' prologue: delta = rowsum(dO * O) of the lane's row (valid: ok) from its dO fragment; the caller writes it to the scratch
-template <int D>
-__device__ __forceinline__ float delta_rowsum(const float (&dof)[D / 2], const float* __restrict__ O, int ld, size_t row, int col0, bool ok, int hi) {
+template <int D, bool RAG = false>
+__device__ __forceinline__ float delta_rowsum(const float (&dof)[D / 2], const float* __restrict__ O, int ld, size_t row, int col0, bool ok, int hi,
+                                              int d = D) {
     const float* op = O + row * (size_t)ld + col0 + hi;
     float dl = 0.f;
 #pragma unroll
-    for (int s = 0; s < D / 2; ++s) dl += ok ? dof[s] * op[2 * s] : 0.f;
+    for (int s = 0; s < D / 2; ++s) dl += ok && (!RAG || 2 * s + hi < d) ? dof[s] * op[2 * s] : 0.f;
     return dl + xhalf(dl);
 }
 
@@ -171,6 +179,7 @@ __device__ __forceinline__ void prob_ds_q(f32x16& s, const f32x16& dp, int key0,
 
 // ---- host side: what the entry points of both files check, and the launch over the head width
 inline bool d_ok(int d) { return d >= 8 && d <= 64 && d % 8 == 0; }
+inline bool dw_ok(int d) { return d >= 1 && d <= 64; }      // seld_attnw_*: any width; d % 8 != 0 runs the RAG form at D = 8 ceil(d / 8)
 // a row stride covers the H * d columns of all heads; the product in 64 bits: H * d past INT_MAX fits no int stride (and the kernels' H * D stays an int)
 inline bool ld_ok(int ld, int H, int d) { return (int64_t)ld >= (int64_t)H * d; }
 // workgroups B * H * ceil(S / 64), or -1 where they do not fit a launch; every product in 64 bits and bounded before the next factor

@@ -99,7 +99,12 @@ def _dropout_rate(cfg: dict, who: str, dropout: bool = True) -> float:
     return r
 
 
-def _check_key_dim(key_dim) -> None:
+def _check_key_dim(key_dim, any_key_dim: bool = False) -> None:
+    """any_key_dim: any integer in 1..64 (seld_attnw_*); without it a multiple of 8 from 8 to 64 (seld_attn_*)"""
+    if any_key_dim:
+        if isinstance(key_dim, (bool, np.bool_)) or not isinstance(key_dim, (int, np.integer)) or not 1 <= int(key_dim) <= 64:
+            raise ValueError(f"key_dim {key_dim!r}: with any_key_dim the attention kernels take an integer from 1 to 64")
+        return
     dk = int(key_dim)
     if dk < 8 or dk > 64 or dk % 8:
         raise ValueError(f"key_dim {dk}: the attention kernels take a multiple of 8 from 8 to 64")
@@ -174,6 +179,7 @@ class _Rt:
         self.dropout_cur = 0
         self.dropout = False      # the blocks built on this runtime may draw (the owner accepted the library's draws: _dropout_rate)
         self.any_units = False    # the GRU blocks built on this runtime may have any width in 1..256 (seld_rnn_gruw_*: ConvTemporalNet search=True)
+        self.any_key_dim = False  # the transformer / conformer blocks built on it may have any key_dim in 1..64 (seld_attnw_*: likewise)
 
     def next_draws(self):
         """a model's training forward begins: new masks (Keras), backward or not"""
@@ -515,14 +521,20 @@ class LayerNorm:
 
 class _Attention:
     """What the three attention layers allocate alike on [B, S, D] with H heads of dk: q k v o do, the gradients dq dk_ dv, the softmax's lse,
-    the backward kernel's scratch (`scratch_fn(B, S, H, dk)` floats; negative: the kernels refuse this key_dim), the output and the scale."""
+    the backward kernel's scratch (`scratch_fn(B, S, H, dk)` floats; negative: the kernels refuse this key_dim), the output and the scale.
+    any_width: the layer's core is seld_attn_*, which on a runtime with any_key_dim has a form for every dk in 1..64 (seld_attnw_*)."""
+    any_width = False
 
     def __init__(self, rt: _Rt, name: str, B: int, S: int, D: int, n_head: int, key_dim: int, scratch_fn, drop: _Drop = None, site: int = 0):
         self.rt, self.name, self.S, self.D, self.H, self.dk = rt, name, int(S), int(D), int(n_head), int(key_dim)
         self.drop, self.site = drop, site      # the probabilities' Dropout (None: none)
+        self.wide = self.any_width and rt.any_key_dim and self.dk % 8 != 0      # a multiple of 8 keeps the calls of every other runtime
+        if self.wide:
+            scratch_fn = rt.lib.seld_attnw_bwd_scratch
         need = int(scratch_fn(B, self.S, self.H, self.dk))
         if need < 0:
-            raise ValueError(f"key_dim {key_dim!r}: the attention kernels take a multiple of 8 from 8 to 64")
+            raise ValueError(f"key_dim {key_dim!r}: the attention kernels take " +
+                             ("an integer from 1 to 64" if self.wide else "a multiple of 8 from 8 to 64"))
         R, HD = B * self.S, self.H * self.dk
         self.q, self.k, self.v, self.o, self.do = (rt.empty(R, HD) for _ in range(5))
         self.dq, self.dk_, self.dv = (rt.empty(R, HD) for _ in range(3))
@@ -532,30 +544,36 @@ class _Attention:
         self.scale = 1.0 / math.sqrt(float(self.dk))
 
     def _core_fwd(self, B, training):
-        """o = softmax(scale q k^T) v per head (seld_attn_fwd), the probabilities dropped where the block's Dropout draws (seld_attn_drop_fwd)"""
+        """o = softmax(scale q k^T) v per head (seld_attn_fwd), the probabilities dropped where the block's Dropout draws (seld_attn_drop_fwd);
+        a dk that is no multiple of 8 (`wide`): seld_attnw_fwd / seld_attnw_drop_fwd"""
         rt, HD = self.rt, self.H * self.dk
         args = (rt.p(self.q), rt.p(self.k), rt.p(self.v), HD, HD, HD, rt.p(self.o), rt.p(self.lse) if training else None, B, self.S, self.H, self.dk,
                 self.scale)
+        lib = rt.lib
         if self.drop is not None and self.drop.on:
-            rt.ck(rt.lib.seld_attn_drop_fwd(*args, self.drop.rate, rt.dropout_seed, self.drop.base + self.site, rt.dropout_cur, rt.st()))
+            fn = lib.seld_attnw_drop_fwd if self.wide else lib.seld_attn_drop_fwd
+            rt.ck(fn(*args, self.drop.rate, rt.dropout_seed, self.drop.base + self.site, rt.dropout_cur, rt.st()))
         else:
-            rt.ck(rt.lib.seld_attn_fwd(*args, rt.st()))
+            rt.ck((lib.seld_attnw_fwd if self.wide else lib.seld_attn_fwd)(*args, rt.st()))
 
     def _core_bwd(self, B):
-        """dq, dk_, dv from do (seld_attn_bwd / seld_attn_drop_bwd with the forward's masks)"""
+        """dq, dk_, dv from do (seld_attn_bwd / seld_attn_drop_bwd with the forward's masks; `wide`: seld_attnw_bwd / seld_attnw_drop_bwd)"""
         rt, HD = self.rt, self.H * self.dk
         args = (rt.p(self.q), rt.p(self.k), rt.p(self.v), HD, HD, HD, rt.p(self.o), rt.p(self.do), rt.p(self.lse), rt.p(self.dq), rt.p(self.dk_),
                 rt.p(self.dv), HD, HD, HD, rt.p(self.scratch), B, self.S, self.H, self.dk, self.scale)
+        lib = rt.lib
         if self.drop is not None and self.drop.on:
-            rt.ck(rt.lib.seld_attn_drop_bwd(*args, self.drop.rate, rt.dropout_seed, self.drop.base + self.site, rt.dropout_cur, rt.st()))
+            fn = lib.seld_attnw_drop_bwd if self.wide else lib.seld_attn_drop_bwd
+            rt.ck(fn(*args, self.drop.rate, rt.dropout_seed, self.drop.base + self.site, rt.dropout_cur, rt.st()))
         else:
-            rt.ck(rt.lib.seld_attn_bwd(*args, rt.st()))
+            rt.ck((lib.seld_attnw_bwd if self.wide else lib.seld_attn_bwd)(*args, rt.st()))
 
 
 class MultiHeadAttention(_Attention):
     """tf.keras.layers.MultiHeadAttention(n_head, key_dim, dropout)(x, x) on [B, S, D] (value_dim = key_dim, biases): three projections
     (one seld_m_gemm each: Keras' kernels [D, H, dk] are [D, H dk] row-major), the query scaled by 1 / sqrt(key_dim), seld_attn_fwd (in
     training with `drop`: seld_attn_drop_fwd), and the output projection [H dk, D]."""
+    any_width = True
 
     def __init__(self, rt: _Rt, name: str, B: int, S: int, D: int, n_head: int, key_dim: int, drop: _Drop = None, site: int = 0):
         super().__init__(rt, name, B, S, D, n_head, key_dim, rt.lib.seld_attn_bwd_scratch, drop, site)
@@ -693,8 +711,9 @@ class Stage:
 TRANSFORMER_KEYS = ("n_head", "key_dim", "ff_multiplier", "kernel_size")
 
 
-def check_transformer_config(cfg: dict, stage: bool = False, dropout: bool = False) -> None:
-    """the mandatory keys of reference modules.py:380-383 (and `depth`, modules.py:120); what has no kernel here is refused, not ignored"""
+def check_transformer_config(cfg: dict, stage: bool = False, dropout: bool = False, any_key_dim: bool = False) -> None:
+    """the mandatory keys of reference modules.py:380-383 (and `depth`, modules.py:120); what has no kernel here is refused, not ignored.
+    any_key_dim: key_dim may be any integer in 1..64 (seld_attnw_*), not only a multiple of 8"""
     for key in TRANSFORMER_KEYS + (("depth",) if stage else ()):
         if key not in cfg:
             raise ValueError(f"transformer_encoder_{'stage' if stage else 'block'}: missing {key!r}")
@@ -702,7 +721,7 @@ def check_transformer_config(cfg: dict, stage: bool = False, dropout: bool = Fal
     _dropout_rate(cfg, "transformer_encoder_block", dropout)
     if int(cfg["n_head"]) < 1 or int(cfg["kernel_size"]) < 1 or float(cfg["ff_multiplier"]) <= 0 or (stage and int(cfg["depth"]) < 1):
         raise ValueError("transformer_encoder_block: n_head, kernel_size, depth >= 1 and ff_multiplier > 0")
-    _check_key_dim(cfg["key_dim"])
+    _check_key_dim(cfg["key_dim"], any_key_dim)
 
 
 class TransformerEncoderBlock:
@@ -711,7 +730,7 @@ class TransformerEncoderBlock:
     the MultiHeadAttention drops its probabilities at the same rate.  The Dropouts draw in training only (_Drop: sites 0 - 3)."""
 
     def __init__(self, rt: _Rt, cfg: dict, S: int, D: int, prefix: str, B: int):
-        check_transformer_config(cfg, dropout=rt.dropout)
+        check_transformer_config(cfg, dropout=rt.dropout, any_key_dim=rt.any_key_dim)
         self.rt, self.S, self.D, self.B = rt, int(S), int(D), B
         self.F = int(cfg["ff_multiplier"] * self.D)
         if self.F < 1:
@@ -823,6 +842,7 @@ class _HeadMajorAttention(_Attention):
 class MultiHeadAttentionRef(_HeadMajorAttention):
     """The reference's layers.MultiHeadAttention_(n_head, key_dim, use_bias, dropout)([x, x, x]) (layers.py:102-287) on [B, S, D]: seld_attn_fwd /
     _bwd (in training with `drop`, the probabilities' Dropout of layers.py:253-257: seld_attn_drop_fwd / _bwd) between the shared projections."""
+    any_width = True
 
     def __init__(self, rt: _Rt, name: str, B: int, S: int, D: int, n_head: int, key_dim: int, use_bias: bool = True, drop: _Drop = None,
                  site: int = 0):
@@ -913,9 +933,9 @@ def basic_pos_encoding(S: int, D: int) -> np.ndarray:
     return np.stack([np.cos(arg), np.sin(arg)], -1).reshape(int(S), 2 * k).astype(np.float32)
 
 
-def check_conformer_config(cfg: dict, stage: bool = False, D=None, dropout: bool = False) -> None:
+def check_conformer_config(cfg: dict, stage: bool = False, D=None, dropout: bool = False, any_key_dim: bool = False) -> None:
     """what reference modules.py:410-430 reads (every key has a default there; `depth` is the stage's, modules.py:146); what has no kernel
-    here is refused, not ignored"""
+    here is refused, not ignored.  any_key_dim: key_dim may be any integer in 1..64 (seld_attnw_*), not only a multiple of 8"""
     who = f"conformer_encoder_{'stage' if stage else 'block'}"
     if stage and "depth" not in cfg:
         raise ValueError(f"{who}: missing 'depth'")
@@ -930,7 +950,7 @@ def check_conformer_config(cfg: dict, stage: bool = False, D=None, dropout: bool
     if int(cfg.get("n_head", 4)) < 1 or not 1 <= int(cfg.get("kernel_size", 32)) <= 64 or int(cfg.get("multiplier", 4)) < 1 or \
             (stage and int(cfg["depth"]) < 1):
         raise ValueError(f"{who}: n_head, multiplier, depth >= 1 and 1 <= kernel_size <= 64")
-    _check_key_dim(cfg.get("key_dim", 36))
+    _check_key_dim(cfg.get("key_dim", 36), any_key_dim)
 
 
 class ConformerEncoderBlock:
@@ -943,7 +963,7 @@ class ConformerEncoderBlock:
       out = LN(x + ffn_factor Dense(D)(act(Dense(multiplier D)(LN(x')))))       — the last residual adds to x, not x' (modules.py:495, 504)."""
 
     def __init__(self, rt: _Rt, cfg: dict, S: int, D: int, prefix: str, B: int):
-        check_conformer_config(cfg, D=D, dropout=rt.dropout)
+        check_conformer_config(cfg, D=D, dropout=rt.dropout, any_key_dim=rt.any_key_dim)
         self.rt, self.S, self.D, self.B = rt, int(S), int(D), B
         S, D = self.S, self.D
         self.F = int(cfg.get("multiplier", 4)) * D
@@ -1769,11 +1789,13 @@ assert tuple(SECOND_KINDS) == COMPOSED_SECOND + CONFORMER_SECOND + ATTENTION_SEC
 DROPOUT_KINDS = COMPOSED_SECOND + CONFORMER_SECOND + ATTENTION_SECOND + RNN_SECOND      # the SECOND kinds whose Dropouts can draw (_Drop): all
 
 
-def _check_second(kind: str, cfg: dict, D=None, dropout: bool = False, any_units: bool = False) -> None:
+def _check_second(kind: str, cfg: dict, D=None, dropout: bool = False, any_units: bool = False, any_key_dim: bool = False) -> None:
     _, check, _, stage, with_d = SECOND_KINDS[kind]
     kw = {"dropout": True} if dropout and kind in DROPOUT_KINDS else {}
     if any_units and check in (check_gru_config, check_rnn_config):
         kw["any_units"] = True
+    if any_key_dim and check in (check_transformer_config, check_conformer_config):
+        kw["any_key_dim"] = True
     check(cfg, stage, D, **kw) if with_d else check(cfg, stage, **kw)
 
 
@@ -1783,7 +1805,7 @@ def _build_second(kind: str, rt, cfg: dict, S: int, D: int, B: int, prefix=None,
     accepts the library's draws (_dropout_rate); a given rt carries its owner's choice"""
     block, _, pre, stage, _ = SECOND_KINDS[kind]
     dropout = bool(dropout) if rt is None else rt.dropout
-    _check_second(kind, cfg, D, dropout, rt is not None and rt.any_units)
+    _check_second(kind, cfg, D, dropout, rt is not None and rt.any_units, rt is not None and rt.any_key_dim)
     own = rt is None
     rt = rt or _Rt(torch.device("cuda", torch.cuda.current_device()))
     rt.dropout = dropout
@@ -2321,7 +2343,8 @@ class ConvTemporalNet(ComposedSeldNet):
     plan alone — variables and shapes without a device (nothing can be run).
 
     search=True (the architecture search, nas_seldnet): what its search spaces draw and the default refuses is built — a GRU kind of any
-    width in 1..256 (_Rt.any_units: seld_rnn_gruw_* at widths other than 128) and simple_dense_block's Dropout layers on the library's
+    width in 1..256 (_Rt.any_units: seld_rnn_gruw_* at widths other than 128), a transformer / conformer encoder kind of any key_dim in
+    1..64 (_Rt.any_key_dim: seld_attnw_* at key_dims that are no multiple of 8) and simple_dense_block's Dropout layers on the library's
     draws (DenseBlock dropout=True, as in VadArchNet).  What the default builds, it builds with the same calls: the same bits."""
 
     DENSE_KW: dict = {}      # what _build_3d passes to a DenseBlock beyond its place in the chain (search / VadArchNet: dropout; VadArchNet: flat)
@@ -2341,6 +2364,7 @@ class ConvTemporalNet(ComposedSeldNet):
         self.search = bool(search)
         if self.search:
             rt.any_units = True
+            rt.any_key_dim = True
             self.DENSE_KW = {"dropout": True}
         self.lib = rt.lib
         # ---- stem (layers.conv2d_bn + MaxPooling2D, models.py:62-64)

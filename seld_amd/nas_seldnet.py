@@ -2,9 +2,13 @@
 models.conv_temporal are drawn from a 2-D and a 1-D search space — the body's blocks and, from the 1-D space, a SED and a DOA head —
 rewritten into buildable ones, filtered by a complexity window, trained for one pass and recorded in a JSON file a later run resumes.
 Model, data, augmentation and metrics run on the device (modules.ConvTemporalNet with search=True: GRU stages of every width the space
-offers on seld_rnn_gruw_*, simple_dense_stage's Dropout on the library's draws); there is no CPU or PyTorch fallback.
+offers on seld_rnn_gruw_*, attention stages of every key_dim on seld_attnw_*, simple_dense_stage's Dropout on the library's draws); there
+is no CPU or PyTorch fallback.
 
   search_space_2d, search_space_1d        the reference's tables (nas_seldnet.py:37-77), value for value; the kinds it comments out stay out
+  search_space_1d_attention               the two 1-D kinds the reference carries commented out (nas_seldnet.py:59-64, 70-76), value for value:
+                                          transformer_encoder_stage and conformer_encoder_stage — the kinds the shipped SS5 model is made of;
+                                          --attention_stages searches {**search_space_1d, **search_space_1d_attention}
   conv_temporal_sampler(space_2d, space_1d, n_blocks, input_shape, default_config, config_postprocess_fn, constraint, rng, max_tries)
                                           config_sampler.py:23-89: n_2d blocks from the 2-D space, then 1-D ones, SED and DOA from the 1-D
                                           space, each argument drawn uniformly; n_2d is drawn anew every 10,000 rejected configurations
@@ -22,7 +26,10 @@ count of the plan's products, not the reference's stage_complexity formulas, so 
 architectures than it does there; input_shape carries the batch in front ([B, T, F, C]; a 3-entry shape gets B = 1) and main reads T, F,
 C off the data set where the reference hard-codes [300, 64, 7]; --label_window_size, --time_mask_size, --freq_mask_size (defaults 60, 24,
 16: the reference's constants) are arguments, and the masks' period is the whole clip where 100 does not divide it; max_tries; the
-history holds the mean loss and val_loss (the weighted sums) rather than Keras' per-output entries; --lr is a float."""
+history holds the mean loss and val_loss (the weighted sums) rather than Keras' per-output entries; --lr is a float; --attention_stages
+(above) — of what search_space_1d_attention offers, a conformer kernel_size above 64 (the depthwise kernels end there), pos_encoding 'rff'
+(its frequencies are drawn and stored nowhere) and 'basic' on an odd width (the reference's table does not broadcast) have no kernel: the
+plan raises ValueError and sample_constraint answers False, so such a draw is rejected and drawn again, never built as something else."""
 from __future__ import annotations
 
 import argparse
@@ -59,6 +66,24 @@ search_space_1d = {
         "units": list(UNITS),
         "dense_activation": ["relu"],
         "dropout_rate": [0., 0.2, 0.5],
+    },
+}
+KEY_DIMS = [2, 3, 4, 6, 8, 12, 16, 24, 32, 48]
+search_space_1d_attention = {
+    "transformer_encoder_stage": {
+        "depth": [1, 2, 3],
+        "n_head": [1, 2, 4, 8, 16],
+        "key_dim": list(KEY_DIMS),
+        "ff_multiplier": [0.25, 0.5, 1, 2, 4, 8],
+        "kernel_size": [1, 3, 5],
+    },
+    "conformer_encoder_stage": {
+        "depth": [1, 2, 3],
+        "key_dim": list(KEY_DIMS),
+        "n_head": [1, 2, 4, 8, 16],
+        "kernel_size": [4, 6, 8, 12, 16, 24, 32, 48, 64, 96, 128, 192, 256],
+        "multiplier": [1, 2, 4],
+        "pos_encoding": [None, "basic", "rff"],
     },
 }
 LOSS_WEIGHTS = (1.0, 1000.0)      # nas_seldnet.py:181
@@ -211,6 +236,8 @@ def get_parser():
     args.add_argument("--time_mask_size", type=int, default=24)
     args.add_argument("--freq_mask_size", type=int, default=16)
     args.add_argument("--seed", type=int, default=0)
+    args.add_argument("--attention_stages", action="store_true",
+                      help="also draw transformer_encoder_stage / conformer_encoder_stage (search_space_1d_attention)")
     return args
 
 
@@ -222,6 +249,7 @@ def main(argv=None) -> dict:
     if os.path.exists(name):      # resume past results; checked before anything touches the data or a device
         with open(name) as f:
             prev = json.load(f)
+        prev["train_config"].setdefault("attention_stages", False)      # a file from before the option existed
         if results["train_config"] != prev["train_config"]:
             raise ValueError("prev config has different train_config")
         results = prev
@@ -234,8 +262,9 @@ def main(argv=None) -> dict:
     default_config = {"n_classes": train_config.n_classes}
     constraint = sample_constraint(train_config.min_flops, train_config.max_flops)
     rng = np.random.default_rng([train_config.seed, start_idx])
+    space_1d = {**search_space_1d, **search_space_1d_attention} if train_config.attention_stages else search_space_1d
     for i in range(start_idx, train_config.n_samples):
-        model_config = conv_temporal_sampler(search_space_2d, search_space_1d, n_blocks=train_config.n_blocks, input_shape=input_shape,
+        model_config = conv_temporal_sampler(search_space_2d, space_1d, n_blocks=train_config.n_blocks, input_shape=input_shape,
                                              default_config=default_config, config_postprocess_fn=postprocess_fn, constraint=constraint, rng=rng)
         start = time.time()
         outputs = train_and_eval(train_config, model_config, input_shape, trainset, testset)
